@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- join throughput of the MI355X radix hash join on BASELINE.json's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one complete radixHashJoin of the synthetic workload with inputs already resident in
 HBM: partition R, partition S (2 passes of 8+8 radix bits by default, BASELINE config 3 as named), bucket
 build/probe, result pairs written to HBM, exact result count read back.  Rank 0 prints ONE JSON
-line.  `value` = (|R|+|S|) tuples joined per second, whole job (all ranks).
+line.  `value` = (|R|+|S|) tuples joined per second, whole job (all ranks); `ms_per_step` = wall time
+of one timed step.
+
+A plain run sets up, warms up, times --steps steps, verifies the last one and prints the line.  --full adds
+what takes runs of its own: the other BASELINE configs and the host-pointer legs (`other_configs`), the
+automatic radix plan (`auto_plan`), the CPU baseline (`cpu_baseline`) and, for N > 1, per-kernel device
+times from extra steps.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 
 N == 1 : 1B x 1B uniform uint64 PK/FK join (BASELINE.json configs[2], the configuration the metric's
          target is quoted on); every step's pair set is verified by (count, checksum) against the
@@ -447,6 +453,34 @@ def extras(eng, torch, dev, steps, which="all"):
     return res
 
 
+DUMP_SAMPLE_ROWS = 1 << 20     # --dump-outputs: about this many S rows of the result (16 MB as float64 pairs)
+DUMP_SEED = 7
+
+
+def dump_outputs(d, eng, torch, pairs, cnt, nglobal):
+    """--dump-outputs: what a caller of the timed join receives, comparable between builds (the order of the pairs in
+    the output buffer is not part of the contract, so nothing here depends on it):
+      match_count.npy    [count]                                   float64
+      pairs_checksum.npy [high 32 bits, low 32 bits] of the order-insensitive checksum of ALL pairs (rhj_pairs_checksum_dev)
+      pairs_sample.npy   [k, 2] {rowR, rowS} of every pair whose S rowID modulo stride equals off, sorted by (rowS, rowR);
+                         stride = ceil(|S| / DUMP_SAMPLE_ROWS), off fixed by DUMP_SEED: the same rows on every run"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    stride = max(1, -(-nglobal // DUMP_SAMPLE_ROWS))
+    off = int(np.random.default_rng(DUMP_SEED).integers(stride))
+    chunk = 1 << 26
+    parts = [np.empty((0, 2), dtype=np.int64)]
+    for a in range(0, cnt, chunk):                     # bounded temporaries: 64M pairs at a time
+        p = pairs[a:min(cnt, a + chunk)]
+        parts.append(p[torch.remainder(p[:, 1], stride) == off].cpu().numpy())
+    sample = np.concatenate(parts)
+    sample = sample[np.lexsort((sample[:, 0], sample[:, 1]))]
+    chk = eng.pairs_checksum(pairs, cnt)
+    np.save(os.path.join(d, "match_count.npy"), np.array([cnt], dtype=np.float64))
+    np.save(os.path.join(d, "pairs_checksum.npy"), np.array([chk >> 32, chk & 0xFFFFFFFF], dtype=np.float64))
+    np.save(os.path.join(d, "pairs_sample.npy"), sample.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -457,12 +491,18 @@ def main():
     ap.add_argument("--bits2", type=int, default=8)
     ap.add_argument("--passes", type=int, default=2, choices=[1, 2], help="1: single pass of --bits1 bits (BASELINE config 2)")
     ap.add_argument("--dist", choices=["uniform", "zipf"], default="uniform")
-    ap.add_argument("--cpu-sample", type=int, default=128_000_000, help="rows per side of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configs / end-to-end legs (N == 1)")
-    ap.add_argument("--extras", choices=["all", "small"], default="all", help="small: skip the 1B Zipf leg, 16M end-to-end")
+    ap.add_argument("--full", action="store_true", help="also run the other configs, the automatic plan, the CPU baseline "
+                                                         "and (N > 1) the per-kernel steps; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a fixed sample of the pairs)")
+    ap.add_argument("--cpu-sample", type=int, default=128_000_000, help="with --full: rows per side of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other BASELINE configs / end-to-end legs (N == 1)")
+    ap.add_argument("--extras", choices=["all", "small"], default="all", help="with --full: small skips the 1B Zipf leg, 16M end-to-end")
     ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-auto", action="store_true", help="skip the extra (untimed-for-value) run under the automatic radix plan")
+    ap.add_argument("--no-auto", action="store_true", help="with --full: skip the extra run under the automatic radix plan")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(sys.argv[1:], args.gpus))
@@ -500,7 +540,7 @@ def main():
     n = args.tuples
     nglobal = n * world
     opts = rhj.Opts(2, args.bits1, args.bits2) if args.passes == 2 else rhj.Opts(1, args.bits1, 0)
-    early = extras_host(eng, args.extras) if world == 1 and not args.no_extras else {}
+    early = extras_host(eng, args.extras) if world == 1 and args.full and not args.no_extras else {}
 
     # inputs resident in HBM, generated on device (SURVEY §8d generators; 16 B AoS tuples)
     R = torch.empty((n, 2), dtype=torch.int64, device=dev)
@@ -542,6 +582,7 @@ def main():
         cnt, res = step()
     barrier()
     dt = time.perf_counter() - t0
+    last = (cnt, res)                                  # what the last timed step computed (--dump-outputs)
     if world == 1:
         lt = eng.launch_timings()                      # every launch of the timed steps, in launch order
         for kind, ms in lt:
@@ -553,7 +594,7 @@ def main():
             for i, ms in enumerate(sc):
                 sc_pass[1 + (i & 1)][0] += ms
                 sc_pass[1 + (i & 1)][1] += 1
-    if world > 1:
+    if world > 1 and args.full:
         # per-kernel device time of the sharded path: `steps` MORE steps, outside the timed region (reading the HIP events of
         # an engine call synchronises after it, which the timed steps must not do)
         sj.collect_timings = True
@@ -565,6 +606,8 @@ def main():
             kt[k] = list(sj.kernel_ms.get(k, [0.0, 0]))
         barrier()
     eng.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, torch, last[1], last[0], nglobal)
 
     # verification of the last step (outside the timed region): exact count + order-insensitive checksum
     ok = True
@@ -588,7 +631,7 @@ def main():
 
     # N == 1 only, outside the timed region: the same workload under the engine's automatic radix plan
     auto = None
-    if world == 1 and not args.no_auto:
+    if world == 1 and args.full and not args.no_auto:
         from radixhashjoin_amd.binding import plan as rhj_plan
         ap_ = rhj_plan(n, n)
         if (ap_.passes, ap_.bits1, ap_.bits2) != (opts.passes, opts.bits1, opts.bits2):
@@ -676,7 +719,7 @@ def main():
                          "moved_bytes_per_launch": moved_per_tuple * tuples_per_launch,
                          "achieved_moved": moved, "frac_moved": moved / HBM_PEAK_GBS,
                          "partition_pass_GBps": (40.0 * npass_tuples / (part_ms * 1e-3) / 1e9) if part_ms else 0.0},
-            "kernel_ms_per_step": {k: v[0] / args.steps for k, v in kt.items()},
+            "kernel_ms_per_step": {k: v[0] / args.steps for k, v in kt.items()} if world == 1 or args.full else None,
         }
         line["kernel_GBps"] = {"join (48 B per tuple pair: 16 B per input tuple + 16 B per pair)":
                                48.0 * n / (kt["join"][0] / max(kt["join"][1], 1) * 1e-3) / 1e9 if kt["join"][0] else 0.0,
@@ -691,18 +734,19 @@ def main():
                                "local_plan": sj.stats.get("plan"), "rowid_mode": sj.stats.get("rowid_mode"), "backend": dist.get_backend(),
                                "ranks_seen": dist.get_world_size(), "ranks_in_all_reduce": ranks_counted,
                                "devices_visible": torch.cuda.device_count(),
-                               "kernel_ms_per_step_rank0": {k: v[0] / args.steps for k, v in kt.items()},
-                               "kernel_ms_note": "device time of rank 0's kernels, from extra steps outside the timed region"}
+                               "kernel_ms_per_step_rank0": {k: v[0] / args.steps for k, v in kt.items()} if args.full else None,
+                               "kernel_ms_note": "device time of rank 0's kernels, from extra steps outside the timed region"
+                                                 + ("" if args.full else " (run with --full)")}
         if auto is not None:
             line["auto_plan"] = auto
-        else:
+        elif world == 1 and args.full and not args.no_auto:
             line["auto_plan"] = "same as the named plan"
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             R = S = out = res = None                      # the headline inputs are done with: HBM back for the other configs
             eng.release_workspace()
             torch.cuda.empty_cache()
             line["other_configs"] = dict(early, **extras(eng, torch, dev, args.steps, args.extras))
-        if world == 1 and args.cpu_sample > 0:
+        if world == 1 and args.full and args.cpu_sample > 0:
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample)
             line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
         print(json.dumps(line), flush=True)

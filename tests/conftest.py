@@ -1,6 +1,11 @@
+import atexit
+import functools
 import json
 import os
+import re
+import shutil
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -65,7 +70,49 @@ def synthetic_golden():
 def small_joins():
     with open(os.path.join(GOLDEN, "small_joins.json")) as f:
         meta = json.load(f)["calls"]
-    return meta, np.load(os.path.join(GOLDEN, "small_joins.npz"))
+    return meta, load_npz_parts("small_joins")
+
+
+# A committed file stays within 1 MiB: larger fixtures are stored in parts, <name>.part0, <name>.part1, ... (byte ranges of
+# a relation file; disjoint sets of arrays of an .npz), and put back together here.
+PART = re.compile(r"(.+)\.part(\d+)(\.npz)?$")
+
+
+def load_npz_parts(stem):
+    """{array name: array} of tests/golden/<stem>.part<k>.npz"""
+    parts = sorted((int(m.group(2)), f) for f in os.listdir(GOLDEN) for m in [PART.match(f)]
+                   if m and m.group(1) == stem and m.group(3))
+    assert parts and [k for k, _ in parts] == list(range(len(parts))), stem
+    out = {}
+    for _, f in parts:
+        with np.load(os.path.join(GOLDEN, f)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def golden_workdir():
+    """working directory for the binaries that read the golden workloads (`small/rN`, `edge/eN` relative to it): a
+    temporary copy of tests/golden/small and tests/golden/edge with every relation file whole again, removed at exit"""
+    d = tempfile.mkdtemp(prefix="rhj_golden_")
+    atexit.register(shutil.rmtree, d, True)
+    for sub in ("small", "edge"):
+        src, dst = os.path.join(GOLDEN, sub), os.path.join(d, sub)
+        os.makedirs(dst)
+        parts = {}
+        for f in sorted(os.listdir(src)):
+            m = PART.match(f)
+            if m:
+                parts.setdefault(m.group(1), []).append((int(m.group(2)), f))
+            else:
+                shutil.copyfile(os.path.join(src, f), os.path.join(dst, f))
+        for name, ps in parts.items():
+            assert [k for k, _ in sorted(ps)] == list(range(len(ps))), name
+            with open(os.path.join(dst, name), "wb") as out:
+                for _, f in sorted(ps):
+                    with open(os.path.join(src, f), "rb") as part:
+                        out.write(part.read())
+    return d
 
 
 @pytest.fixture(scope="session")
@@ -92,6 +139,37 @@ def make_inputs(o, spec):
     if spec["S"] == "disjoint":
         return R, o.gen_S_disjoint(spec["nS"], spec["D"])
     raise ValueError(spec["S"])
+
+
+@pytest.fixture(scope="session")
+def reference_recorded():
+    """what the real reference returned for the inputs of test_oracle.py's *_vs_reference tests
+    (tests/golden/make_reference_recorded.py): checked everywhere, also where oracle/_ref is not built"""
+    with open(os.path.join(GOLDEN, "reference_recorded.json")) as f:
+        return json.load(f)
+
+
+def digest(a):
+    """sha256 of an array's bytes (reference_recorded.json stores digests, not the arrays)"""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+NEXT_PRIME_XS = list(range(0, 2000)) + [4095, 4096, 65535, 65536, 10**6, 10**6 + 3]
+HASH_RELATION_NS = [0, 1, 7, 8, 9, 1000, 100003]
+
+
+def random_join_trials(seed=7, trials=40):
+    """(R, S) of test_random_joins_vs_reference: sizes below 3000, join-value domains from 1 to 2^62"""
+    from oracle.pyoracle import TUPLE
+    rng = np.random.default_rng(seed)
+    for _ in range(trials):
+        nR, nS = int(rng.integers(0, 3000)), int(rng.integers(0, 3000))
+        dom = int(rng.choice([1, 3, 50, 1000, 1 << 20, 1 << 62]))
+        R = np.empty(nR, dtype=TUPLE); S = np.empty(nS, dtype=TUPLE)
+        R["key"] = rng.permutation(nR); S["key"] = rng.permutation(nS)
+        R["payload"] = rng.integers(0, dom, nR, dtype=np.uint64); S["payload"] = rng.integers(0, dom, nS, dtype=np.uint64)
+        yield R, S
 
 
 def small_call_arrays(npz, i):

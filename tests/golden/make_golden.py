@@ -14,7 +14,8 @@ Outputs (data only: inputs and expected outputs):
   small_joins.json   the 94 multiRadixHashJoin calls the reference makes while running
                      small/small.work (link-time tap, oracle/ref_tap.cpp): sizes, match count,
                      checksums of R, S and of the pair set
-  small_joins.npz    complete inputs/outputs for a size-bounded subset of those calls
+  small_joins.part<k>.npz   complete inputs/outputs for a size-bounded subset of those calls, whole calls per
+                     part, every part within 1 MB (tests/conftest.py load_npz_parts puts them together)
 """
 import argparse
 import json
@@ -152,8 +153,31 @@ def main():
         with open(os.path.join(HERE, "small_joins.json"), "w") as f:
             json.dump(dict(source="oracle/_ref/join_tap over reference small/small.init + small/small.work "
                                   "(stdout byte-identical to small/small.result)", calls=meta), f, indent=1)
-        np.savez_compressed(os.path.join(HERE, "small_joins.npz"), **full)
+        save_npz_parts("small_joins", full)
         print(len(calls), "calls,", len(chosen), "with full vectors; sum matches", sum(c[2] for c in calls))
+
+
+def save_npz_parts(stem, arrays, limit=1_000_000):
+    """arrays named call<i>__* -> <stem>.part0.npz, .part1.npz, ...: the calls dealt round-robin over as few parts as keep
+    every compressed part within `limit` bytes (a committed file stays within 1 MiB)"""
+    import io
+    import re
+    call = lambda k: int(re.match(r"call(\d+)__", k).group(1))       # noqa: E731
+    calls = sorted({call(k) for k in arrays})
+    for n in range(1, len(calls) + 1):
+        blobs = []
+        for g in (set(calls[j::n]) for j in range(n)):
+            b = io.BytesIO()
+            np.savez_compressed(b, **{k: v for k, v in arrays.items() if call(k) in g})
+            blobs.append(b.getvalue())
+        if max(len(b) for b in blobs) <= limit:
+            break
+    for f in os.listdir(HERE):
+        if re.fullmatch(re.escape(stem) + r"\.part\d+\.npz", f):
+            os.remove(os.path.join(HERE, f))
+    for j, b in enumerate(blobs):
+        with open(os.path.join(HERE, f"{stem}.part{j}.npz"), "wb") as f:
+            f.write(b)
 
 
 if __name__ == "__main__":

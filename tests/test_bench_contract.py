@@ -15,14 +15,14 @@ REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 def test_cli_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out.stdout
 
 
 @pytest.mark.gpu
 def test_reduced_run_prints_one_json_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--tuples", "4000000", "--cpu-sample", "200000", "--no-extras"], capture_output=True, text=True, timeout=600)
+                          "--tuples", "4000000", "--cpu-sample", "200000", "--no-extras", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -48,3 +48,42 @@ def test_reduced_run_prints_one_json_line():
     assert c["kind"] in ("reference", "port") and c["cpu_model"] and c["cores"] in (1, 8)
     if c["kind"] == "reference":                      # SURVEY §8d protocol: 8 threads and 1 thread, median of >= 3 runs each
         assert set(c["tuples_per_s"]) == {"8_threads", "1_threads"} and all(len(v) >= 3 for v in c["runs_s"].values())
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """a plain run times the headline only (nothing that --full adds), and --dump-outputs writes what the last timed step
+    computed: float arrays, within 64 MB, the same on every run, and the sampled pairs are the closed form's"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from bench import np_mix
+    n = 3_000_000
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--tuples", str(n), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        ls = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(ls) == 1
+        lines.append(json.loads(ls[0]))
+        files = sorted(os.listdir(d))
+        assert files == ["match_count.npy", "pairs_checksum.npy", "pairs_sample.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f: np.load(d / f) for f in files})
+    for d in lines:
+        for k in REQUIRED:
+            assert k in d, k
+        assert d["verified"] is True and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 2.0 * n / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for k in ("cpu_baseline", "other_configs", "auto_plan", "gpu_over_cpu"):
+            assert k not in d, k
+    a, b = dumps
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64)
+        assert np.array_equal(a[f], b[f]), f                   # same inputs, same outputs, whatever order the pairs came in
+    assert a["match_count.npy"].tolist() == [float(lines[0]["config"]["matches_last_step_rank0"])] == [float(n)]
+    s = a["pairs_sample.npy"].astype(np.uint64)
+    assert s.shape[1] == 2 and 0.5 * (1 << 20) < len(s) <= n and np.all(np.diff(s[:, 1].astype(np.int64)) > 0)
+    # uniform PK/FK generator: S row j joins R row mix(j ^ 42) % n (bench.host_inputs, rhj_generate_dev)
+    assert np.array_equal(s[:, 0], np_mix(s[:, 1] ^ np.uint64(42)) % np.uint64(n))

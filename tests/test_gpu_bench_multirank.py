@@ -31,7 +31,7 @@ def test_bench_multirank_gloo_rehearsal(ranks, dist_, tuples, tmp_path):
     env = dict(os.environ, RHJ_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
-           "--tuples", str(tuples), "--dist", dist_, "--cpu-sample", "0", "--no-extras"]
+           "--tuples", str(tuples), "--dist", dist_, "--cpu-sample", "0", "--no-extras", "--full"]
     err = open(tmp_path / "stderr.txt", "wb")
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=err, timeout=900)
     err.close()

@@ -14,6 +14,8 @@ import subprocess
 
 import pytest
 
+from conftest import golden_workdir
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -63,7 +65,7 @@ class ChildTimeout(Exception):
 
 def run_once(path, stdin, log, limit):
     env = dict(os.environ, RHJ_SEAM_LOG=str(log))
-    pr = subprocess.Popen([path], stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=GOLD, env=env)
+    pr = subprocess.Popen([path], stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=golden_workdir(), env=env)
     try:
         out, err = pr.communicate(input=stdin, timeout=limit)            # both pipes drained while the child runs
     except subprocess.TimeoutExpired:

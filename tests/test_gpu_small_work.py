@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from conftest import golden_workdir
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -20,7 +22,7 @@ def run_small(tmp_path, mode="host"):
     log = tmp_path / "joins.log"
     env = dict(os.environ, RHJ_JOIN_LOG=str(log), RHJ_QUERY_MODE=mode)
     stdin = open(os.path.join(GOLD, "small", "small.init"), "rb").read() + open(os.path.join(GOLD, "small", "small.work"), "rb").read()
-    out = subprocess.run([JOIN], input=stdin, cwd=GOLD, env=env, capture_output=True, timeout=600, check=True).stdout
+    out = subprocess.run([JOIN], input=stdin, cwd=golden_workdir(), env=env, capture_output=True, timeout=600, check=True).stdout
     return out, log
 
 
@@ -63,7 +65,7 @@ def test_edge_queries_match_the_reference(mode):
     edge = os.path.join(GOLD, "edge")
     stdin = open(os.path.join(edge, "edge.init"), "rb").read() + open(os.path.join(edge, "edge.work"), "rb").read()
     env = dict(os.environ, RHJ_QUERY_MODE=mode)
-    out = subprocess.run([JOIN], input=stdin, cwd=GOLD, env=env, capture_output=True, timeout=600, check=True).stdout
+    out = subprocess.run([JOIN], input=stdin, cwd=golden_workdir(), env=env, capture_output=True, timeout=600, check=True).stdout
     assert out == open(os.path.join(edge, "edge.result"), "rb").read()
 
 

@@ -4,6 +4,8 @@ semantics (radixhashjoin_amd/host/query_unit.cpp), and the build products exist.
 import os
 import subprocess
 
+from conftest import golden_workdir
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "radixhashjoin_amd", "host")
 
@@ -42,7 +44,7 @@ def test_join_cli_fails_loudly_without_gpu():
         pytest.skip("a GPU is present")
     gold = os.path.join(ROOT, "tests", "golden")
     stdin = open(os.path.join(gold, "small", "small.init"), "rb").read() + b"3 0|0.2=1.0|1.2\nF\n"
-    r = subprocess.run([os.path.join(HOST, "join_gpu")], input=stdin, cwd=gold, capture_output=True, timeout=120)
+    r = subprocess.run([os.path.join(HOST, "join_gpu")], input=stdin, cwd=golden_workdir(), capture_output=True, timeout=120)
     assert r.returncode != 0
     assert b"rhj_init failed" in r.stderr
 

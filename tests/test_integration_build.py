@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.environ.get("RHJ_REFERENCE", "/root/reference")
 TOOL = os.path.join(ROOT, "tools", "bind_reference.sh")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout absent")
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout absent")
 
 
 def _undefined_symbols(binary):
@@ -26,6 +26,7 @@ def _defined_symbols(binary):
     return out
 
 
+@needs_ref
 @pytest.mark.parametrize("option", ["A", "B"])
 def test_binding_compiles_and_links(tmp_path, option):
     out = tmp_path / f"opt{option}"
@@ -49,6 +50,7 @@ def test_binding_compiles_and_links(tmp_path, option):
         assert "JoinJob::run" in defined and "Result::join_buckets" in defined
 
 
+@needs_ref
 def test_seam_target_builds():
     """oracle/Makefile `bindings`: reference objects unchanged + a link-time seam on the mangled symbol"""
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "bindings"], capture_output=True, text=True)
@@ -61,6 +63,7 @@ def test_seam_target_builds():
     assert "Query::run_joins" in d
 
 
+@needs_ref
 def test_bound_binaries_carry_the_fixed_stop(tmp_path):
     """join_seam binds JobScheduler::stop next to the seam (the reference's racy body stays under another name, uncalled);
     Option B's copy of JobScheduler.cpp gets the two-line source edit and nothing else; and the start / stop loop over the

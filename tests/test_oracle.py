@@ -1,12 +1,13 @@
 """CPU suite: pins the oracle (oracle/rhj_oracle.c) against the reference's golden data.
    (1) known answers produced by the real reference (tests/golden/synthetic.json, tiny_vectors.npz)
    (2) the 94 multiRadixHashJoin calls of small.work (tests/golden/small_joins.*)
-   (3) the reference itself, when oracle/_ref is built (page-order byte equality)."""
+   (3) what the reference itself returns (page-order byte equality): recorded in tests/golden/reference_recorded.json,
+       and live as well where oracle/_ref is built."""
 import numpy as np
 import pytest
 
-from conftest import make_inputs, small_call_arrays
-from oracle.pyoracle import PAIR, TUPLE, sorted_pairs
+from conftest import HASH_RELATION_NS, NEXT_PRIME_XS, digest, make_inputs, random_join_trials, small_call_arrays
+from oracle.pyoracle import PAIR, TUPLE, Reference, ref_available, sorted_pairs
 
 CPU_CASES = ["pkfk_1k", "pkfk_1m", "pkfk_4m_x_1m", "pkfk_300k_x_3m", "dup_10k", "dup_100k_50k", "dup_2m_d64k",
              "alleq_300_500", "alleq_7000_9", "tinyR_1_1000", "tinyS_1000_1", "tiny_5_3", "lt_ranges_7_7", "one_one",
@@ -20,9 +21,14 @@ def test_next_prime_known_values(oracle):
         assert oracle.next_prime(x) == p
 
 
-def test_next_prime_vs_reference(oracle, reference):
-    for x in list(range(0, 2000)) + [4095, 4096, 65535, 65536, 10**6, 10**6 + 3]:
-        assert oracle.next_prime(x) == reference.next_prime(x)
+def test_next_prime_vs_reference(oracle, reference_recorded):
+    rec = reference_recorded["next_prime"]
+    assert [x for x, _ in rec] == NEXT_PRIME_XS
+    ref = Reference() if ref_available() else None               # the live reference too, where oracle/_ref is built
+    for x, p in rec:
+        assert oracle.next_prime(x) == p
+        if ref is not None:
+            assert ref.next_prime(x) == p
 
 
 def test_mix_known_value(oracle):
@@ -88,27 +94,34 @@ def test_hash_relation_is_stable_partition(oracle, n):
             assert np.all(np.diff(a["key"][d == v].astype(np.int64)) > 0)
 
 
-@pytest.mark.parametrize("n", [0, 1, 7, 8, 9, 1000, 100003])
-def test_hash_relation_vs_reference(oracle, reference, n):
+@pytest.mark.parametrize("n", HASH_RELATION_NS)
+def test_hash_relation_vs_reference(oracle, reference_recorded, n):
     R = oracle.gen_R(n, max(n // 3, 1))
     a, ha = oracle.hash_relation(R)
-    b, hb = reference.hash_relation(R)
-    c, hc = reference.single_partition(R)
-    assert np.array_equal(a, b) and np.array_equal(ha, hb) and np.array_equal(a, c) and np.array_equal(ha, hc)
+    rec = reference_recorded["hash_relation"][str(n)]            # what the reference returned for this R
+    assert [digest(a), digest(ha)] == rec["hash_relation"] == rec["single_partition"]
+    if ref_available():
+        ref = Reference()
+        b, hb = ref.hash_relation(R)
+        c, hc = ref.single_partition(R)
+        assert np.array_equal(a, b) and np.array_equal(ha, hb) and np.array_equal(a, c) and np.array_equal(ha, hc)
 
 
-def test_random_joins_vs_reference(oracle, reference):
-    rng = np.random.default_rng(7)
-    for trial in range(40):
-        nR, nS = int(rng.integers(0, 3000)), int(rng.integers(0, 3000))
-        dom = int(rng.choice([1, 3, 50, 1000, 1 << 20, 1 << 62]))
-        R = np.empty(nR, dtype=TUPLE); S = np.empty(nS, dtype=TUPLE)
-        R["key"] = rng.permutation(nR); S["key"] = rng.permutation(nS)
-        R["payload"] = rng.integers(0, dom, nR, dtype=np.uint64); S["payload"] = rng.integers(0, dom, nS, dtype=np.uint64)
+def test_random_joins_vs_reference(oracle, reference_recorded):
+    recs = reference_recorded["random_joins"]
+    assert len(recs) == 40
+    ref = Reference() if ref_available() else None               # the live reference too, where oracle/_ref is built
+    for (R, S), rec in zip(random_join_trials(), recs):
+        nR, nS = len(R), len(S)
+        assert (nR, nS) == (rec["nR"], rec["nS"])
         po = oracle.join(R, S)
-        pr, cnt, head_null, _ = reference.join(R, S)
-        assert np.array_equal(po, pr)
-        assert head_null == (cnt == 0)
+        # the reference's pairs, in its own page order (recorded as a digest)
+        assert len(po) == rec["count"] and digest(po) == rec["pairs_sha256"]
+        assert rec["head_null"] == (rec["count"] == 0)
+        if ref is not None:
+            pr, cnt, head_null, _ = ref.join(R, S)
+            assert np.array_equal(po, pr)
+            assert head_null == (cnt == 0)
         # brute force on the small ones: the pair multiset is what equality of join values gives
         if nR * nS <= 400_000:
             rr, ss = np.nonzero(R["payload"][:, None] == S["payload"][None, :])

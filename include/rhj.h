@@ -42,7 +42,8 @@ typedef enum {
     RHJ_E_NODEVICE = -2,   /* no usable HIP device */
     RHJ_E_HIP = -3,        /* a HIP call failed (rhj_last_error has hipGetErrorString) */
     RHJ_E_NOMEM = -4,      /* HBM or host allocation failed */
-    RHJ_E_OVERFLOW = -5    /* d_out too small: *out_count holds the exact size needed, pairs beyond capacity dropped */
+    RHJ_E_OVERFLOW = -5    /* d_out too small: *out_count holds the exact size needed, pairs beyond capacity dropped (slots
+                              [0, capacity) hold distinct pairs of the result; nothing at or past capacity is written) */
 } rhj_status;
 
 /* Radix plan.  The reference hard-codes one 8-bit pass (HASH_LSB, Result.cpp:5,91); here the
@@ -121,7 +122,7 @@ int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
  * without duplicates answers every probe tuple with one match); 0: the first relation wins such a tie.  Same pairs either way. */
 int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
 /* what the last join did: "last.narrow" (0 / 1 / 2, see above), "last.join_kernel" (0 one-table, 1 chunked, 2 / 3
- * compact table full / half size, 4 / 5 the same with 20 probe slots per thread, 6 / 7 the 12288- / 6144-entry geometries, 8 / 9 / 10 see "join.big_kernel", -1 none: direct small join or empty input), "last.pipelined" (the number
+ * compact table full / half size, 4 / 5 the same with 20 probe slots per thread, 6 / 7 the 12288- / 6144-entry geometries, 8 / 9 / 10 / 11 see "join.big_kernel", -1 none: direct small join or empty input), "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home; 0: the plain path),
  * "last.max_part_R" / "last.max_part_S" (tuples in the largest partition of each side the last partitioned join saw; 0 for
  * an unpartitioned one), "partition.mix" (0 / 1: what joins on this context do) */

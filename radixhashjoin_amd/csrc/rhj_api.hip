@@ -1594,6 +1594,14 @@ int rhj_reserve(rhj_ctx *ctx, uint64_t nR, uint64_t nS, const rhj_opts *opts)
     return RHJ_OK;
 }
 
+// a join with an empty input runs no kernel: "last.join_kernel" / "last.narrow" say so instead of describing the join before it
+static int join_nothing(rhj_ctx *ctx)
+{
+    ctx->last_join_kind = -1;
+    ctx->cur_narrow = 0;
+    return RHJ_OK;
+}
+
 int rhj_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                  const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count)
 {
@@ -1601,7 +1609,7 @@ int rhj_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tupl
     if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
     *out_count = 0;
     prof_reset(ctx);
-    if (nR == 0 || nS == 0) return RHJ_OK;            // nothing to schedule (Result.cpp:101 never fires)
+    if (nR == 0 || nS == 0) return join_nothing(ctx);  // nothing to schedule (Result.cpp:101 never fires)
     if (!d_R || !d_S) return fail(ctx, RHJ_E_INVALID, "null input relation");
     rhj_opts plan;
     if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
@@ -1932,7 +1940,7 @@ int rhj_join(rhj_ctx *ctx, const rhj_tuple *R, uint64_t nR, const rhj_tuple *S, 
     *out_count = 0;
     prof_reset(ctx);
     ctx->last_pipelined = 0;
-    if (nR == 0 || nS == 0) return RHJ_OK;
+    if (nR == 0 || nS == 0) return join_nothing(ctx);
     if (!R || !S) return fail(ctx, RHJ_E_INVALID, "null input relation");
     rhj_opts plan;
     if (resolve_plan(nR, nS, opts, &plan, false, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");

@@ -47,8 +47,13 @@ def rel(n, dom, skew, key0):
 
 def shape(R, S):
     """the same re-labelling of the join values on both sides: spread over 64 bits, aligned (multiples of 2^k: what raw-bit radix
-    digits choke on), or values whose MIXED form shares its low 16 bits (few, large partitions after rhj_mix64)"""
-    mode = int(rng.integers(0, 4))
+    digits choke on), values whose MIXED form shares its low 16 bits (few, large partitions after rhj_mix64), near misses (join
+    values one apart in Gray code have mixed forms that differ in ONE bit, rotated anywhere into the 64), or fold collisions
+    (mixed form key << 16 | 0xBEEF, groups of 2^16 join values with keys x ^ d * 0x100000001: one bucket per group, whatever the
+    geometry, under 16-bit plans)"""
+    mode = int(rng.integers(0, 6))
+    base = rng.integers(0, 1 << 63, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    rot = np.uint64(int(rng.integers(0, 64)))
     for t in (R, S):
         v = t["payload"]
         if mode == 1:
@@ -57,6 +62,13 @@ def shape(R, S):
             v = v << np.uint64(shape.k)
         elif mode == 3:
             v = rhj.unmix64((v << np.uint64(16)) | np.uint64(0xBEEF))
+        elif mode == 4:
+            g = v ^ (v >> np.uint64(1))
+            g = (g << rot) | (g >> ((np.uint64(64) - rot) & np.uint64(63))) if rot else g
+            v = rhj.unmix64(base ^ g)
+        elif mode == 5:
+            key = (base >> np.uint64(16)) ^ ((v & np.uint64(0xFFFF)) * np.uint64(0x100000001)) ^ ((v >> np.uint64(16)) << np.uint64(16))
+            v = rhj.unmix64(((key & np.uint64((1 << 48) - 1)) << np.uint64(16)) | np.uint64(0xBEEF))
         t["payload"] = v
 
 

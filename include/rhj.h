@@ -114,6 +114,12 @@ int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
  * intermediate of the two passes (2; the only level of 17-18-bit plans) are stored as {payload 8 B, rowID 4 B} while every
  * rowID is below 2^32 (a larger one is detected on the device -- by the first histogram kernel -- and THAT join repeats itself
  * in the 16-byte format; the next join tries the narrow format again);
+ * "partition.countfree": -1 automatic, 0 never, 1 whenever it applies, whatever the size: in a device-resident join whose two
+ * passes are narrow (level 2, at most 8 bits each, digits of rhj_mix64(payload)), pass 1 writes every (digit, unit) run into
+ * a fixed region instead of at exact cursors, so the histogram read of the 16-byte input is not needed; a relation with a run
+ * that does not fit its region (heavy skew) is partitioned again with exact cursors inside the same call, and that side of the
+ * context's joins then stays on the exact path for the next 2, 4, ... 32 eligible joins (setting the option re-arms);
+ * automatic: relations of more than 2^28 tuples (RHJ_COUNTFREE=0 / 1 in the environment: A/B aid);
  * "partition.mix": -1 automatic (= 1 unless RHJ_MIX=0 is in the environment), 1: joins take their radix digits from
  * rhj_mix64(payload), 0: from the raw payload (see rhj_opts);
  * "join.sniff": -1 automatic (= 1 unless RHJ_SNIFF=0), 1: a partitioned join samples the join values of both relations for
@@ -121,7 +127,8 @@ int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
  * fewer duplicates becomes the hash table (the reference builds on the smaller bucket, S on a tie: JobScheduler.cpp:187; a table
  * without duplicates answers every probe tuple with one match); 0: the first relation wins such a tie.  Same pairs either way. */
 int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
-/* what the last join did: "last.narrow" (0 / 1 / 2, see above), "last.join_kernel" (0 one-table, 1 chunked, 2 / 3
+/* what the last join did: "last.narrow" (0 / 1 / 2, see above), "last.countfree_R" / "last.countfree_S" (pass 1 of that side:
+ * 0 exact cursors, 1 count-free, 2 count-free tried and repeated with exact cursors), "last.join_kernel" (0 one-table, 1 chunked, 2 / 3
  * compact table full / half size, 4 / 5 the same with 20 probe slots per thread, 6 / 7 the 12288- / 6144-entry geometries, 8 / 9 / 10 / 11 see "join.big_kernel", -1 none: direct small join or empty input), "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home; 0: the plain path),
  * "last.max_part_R" / "last.max_part_S" (tuples in the largest partition of each side the last partitioned join saw; 0 for

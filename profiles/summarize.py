@@ -28,7 +28,7 @@ def short(name):
         return name[:40]
     k = m.group(1)
     t = re.search(re.escape(k) + r"<([^>]*)>", name)
-    if k == "k_scatter_wcn" and t:                       # input format: 16-byte tuples or narrow arrays
+    if k in ("k_scatter_wcn", "k_scatter_wcn_cf") and t:  # input format: 16-byte tuples or narrow arrays (_cf: count-free pass 1 / its pass 2)
         k += "<in_narrow=%s>" % t.group(1).strip()
     if k == "k_join_ct" and t:
         a = [x.strip() for x in t.group(1).split(",")]
@@ -88,7 +88,8 @@ if sc:
     sys.path.insert(0, ROOT)
     from bench import source_blobs                      # the kernel sources these counters were measured on
     def one(flag):
-        v = [x for k, x in pmc.items() if k.startswith("k_scatter_wcn<in_narrow=%s" % flag) and "hbm_bytes_per_launch" in x]
+        v = [x for k, x in pmc.items() if k.startswith(("k_scatter_wcn<in_narrow=%s" % flag, "k_scatter_wcn_cf<in_narrow=%s" % flag))
+             and "hbm_bytes_per_launch" in x]
         return v[0]["hbm_bytes_per_launch"] if len(v) == 1 else None
     json.dump({"tuples": int(m.group(1)) if m else None, "bits": [int(b.group(1)), int(b.group(2))] if b else None,
                "scatter_hbm_bytes_per_launch": per_launch,

@@ -277,7 +277,7 @@ class Engine:
         self._chk(self.lib.rhj_set_option(self.ctx, name.encode(), int(value)))
 
     def info(self, name):
-        """what the last join did ("last.narrow", "last.join_kernel"; include/rhj.h)"""
+        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.join_kernel"; include/rhj.h)"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
         return v.value

@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <functional>
 #include <cstdio>
@@ -236,6 +237,16 @@ struct rhj_ctx {
     // 2, 4, ... 32 eligible joins (a caller whose rowIDs are always wide pays one extra histogram per relation now and then)
     u32 narrow_fail_streak = 0, narrow_skip = 0;
     bool narrow_off_once = false;      // the repeat of a join that fell back
+    // count-free pass 1 (rhj.h "partition.countfree"), per side of a join (0 = first relation): a side whose pass 1
+    // met a run longer than its region is repeated with exact cursors inside the same call (the skip word's bit 2 << side), and
+    // the context leaves that side on the exact path for the next 2, 4, ... 32 eligible joins
+    int opt_countfree = -1;            // -1: automatic (RHJ_COUNTFREE env; from CF_AUTO_MIN_TUPLES on), 0: never, 1: whenever the case applies
+    u32 cf_fail_streak[2] = {0, 0}, cf_skip[2] = {0, 0};
+    bool cf_off_once[2] = {false, false};   // the repeat of a side that fell back
+    bool cf_keep_R = false;            // ... during which R's partition of the first attempt stands (only S overflowed)
+    u32 cf_over = 0;                   // the skip word as join_phase read it (bits 1, 2)
+    int last_cf[2] = {0, 0};           // "last.countfree_R/_S": 0 exact, 1 count-free, 2 tried and fell back
+    DevBuf cf_cnt1, cf_pre, cf_tot;
     // multi-GPU receiver (rhj_shard_partition / rhj_shard_join): the partitions carry sender tags
     int shard_nseg = 0, shard_mode[2] = {0, 0};
     bool shard_side_done[2] = {false, false};
@@ -677,10 +688,46 @@ struct FusedIn {
     const u64 *key_bases = nullptr;
 };
 
+// the pass-1 units and groups of a fused two-pass partition of one unsegmented relation
+void fused_units(u64 n, int b1, PassGeom &g1, u32 &units1, u32 &per, u32 &ngroups)
+{
+    static const u32 want_groups = (u32)env_u64("RHJ_GROUPS", 16, 1, 64);                          // tuning aid
+    // 1024 pass-1 units instead of 2048: every unit flushes a 2^(b1+b2)-bin table, and the scatter does not care
+    // ([measured] at 10^9 tuples: histogram 2.54 against 2.74 ms, scatter within noise)
+    g1 = make_geom(n, 1, 0, b1, PART_TARGET_UNITS / 2);
+    units1 = (u32)((n + g1.L - 1) / g1.L);
+    per = units1 ? (units1 + want_groups - 1) / want_groups : 1;
+    ngroups = units1 ? (units1 + per - 1) / per : 1;
+}
+
+// Count-free pass 1: the regions.  cap = the mean run of a unit, m = L / 2^b1, plus ten standard deviations of a hashed digit's
+// count (sqrt(m)), rounded up to whole 32-tuple lines: at the headline's L = 978,944 that is 4448 for a mean of 3824 (+16 %; the
+// largest of its 2 x 261,376 runs is 4116).  Small relations (L bottoms out at one tile) get regions far above 16 n bytes:
+// the intermediate buffer is sized from the regions, the margin is never cut.
+CfGeom cf_geometry(u64 n, int b1)
+{
+    PassGeom g1;
+    CfGeom c;
+    fused_units(n, b1, g1, c.U, c.per, c.ngroups);
+    const double m = (double)g1.L / (double)((u64)1 << b1);
+    c.cap = (u32)(((u64)(m + 10.0 * std::sqrt(m)) + 1 + 31) / 32 * 32);
+    c.slots = ((u64)c.U << b1) * c.cap;
+    return c;
+}
+size_t cf_tmp_bytes(const CfGeom &c) { return (size_t)c.slots * 12; }
+// the case it applies to: 16-byte input, narrow level 2, digits of mix64(payload), both passes of at most 8 bits
+bool cf_applies(u64 n, int b1, int b2, int narrow, int mix, bool segs)
+{
+    if (segs || narrow != 2 || mix != MIX_STORE || b1 > 8 || b2 > 8 || n == 0) return false;
+    const CfGeom c = cf_geometry(n, b1);
+    return c.per <= cf_per_max() && (double)c.slots * 12.0 < 1.0e12;
+}
+
 // mix (16-byte input only): MIX_STORE inside a join -- the histogram and pass 1 take their digits from mix64(payload) and pass 1
 // writes the mixed value, so that pass 2 and the bucket join work on it unchanged
+// cf_side >= 0: pass 1 runs without counts where cf_applies() (that side's bit of the skip word reports a run that did not fit)
 int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int b2, void *d_out, u64 *d_ps, int narrow = 0,
-                             int mix = MIX_NONE, const PartScratch *scratch = nullptr)
+                             int mix = MIX_NONE, const PartScratch *scratch = nullptr, int cf_side = -1)
 {
     // the scratch tables and the stream of this relation: the context's first set on its stream, or -- R and S of a mid-size
     // join partitioned side by side -- the second set on the auxiliary stream (partition_phase)
@@ -690,9 +737,7 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
            &x_ps_1 = *sc.ps_1, &x_part_tmp = *sc.part_tmp, &x_seg_rng = *sc.seg_rng;
     const hipStream_t st = sc.st;
     const bool segs = in.P != nullptr;
-    // 1024 pass-1 units instead of 2048: every unit flushes a 2^(b1+b2)-bin table, and the scatter does not care
-    // ([measured] at 10^9 tuples: histogram 2.54 against 2.74 ms, scatter within noise)
-    PassGeom g1 = make_geom(n, 1, 0, b1, PART_TARGET_UNITS / 2);
+    PassGeom g1 = make_geom(n, 1, 0, b1, PART_TARGET_UNITS / 2);           // (see fused_units)
     g1.mix = segs ? MIX_NONE : mix;
     static const u32 want_groups = (u32)env_u64("RHJ_GROUPS", 16, 1, 64);                          // tuning aid
     u32 units1, per, ngroups, groups_per_seg = 0;
@@ -713,12 +758,13 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
             segL[s_] = L ? L : (u64)PART_TILE;
         }
     } else {
-        units1 = (u32)((n + g1.L - 1) / g1.L);
-        per = units1 ? (units1 + want_groups - 1) / want_groups : 1;
-        ngroups = units1 ? (units1 + per - 1) / per : 1;
+        PassGeom same;
+        fused_units(n, b1, same, units1, per, ngroups);
     }
     const size_t nb1 = (size_t)1 << b1, nb2 = (size_t)1 << b2;
     const u32 units2 = (u32)(nb1 * ngroups);
+    const bool cf = cf_side >= 0 && cf_applies(n, b1, b2, narrow, mix, segs);
+    const CfGeom cg = cf ? cf_geometry(n, b1) : CfGeom();
     RHJCHK(ensure(ctx, x_seg0, 64));
     RHJCHK(ensure(ctx, x_unit_start, 16));
     RHJCHK(ensure(ctx, x_unit_hist, (size_t)(units1 + 1) * nb1 * 4));
@@ -727,9 +773,14 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
     RHJCHK(ensure(ctx, x_hist2, (size_t)units2 * nb2 * 4));
     RHJCHK(ensure(ctx, x_grp_rng, ((size_t)units2 + 1) * 8));
     RHJCHK(ensure(ctx, x_unit_start2, (nb1 + 1) * 4));
-    RHJCHK(ensure(ctx, x_part_tmp, (size_t)(n ? n : 1) * 16));
+    RHJCHK(ensure(ctx, x_part_tmp, cf && cf_tmp_bytes(cg) > (size_t)n * 16 ? cf_tmp_bytes(cg) : (size_t)(n ? n : 1) * 16));
     RHJCHK(ensure(ctx, x_ps_1, (nb1 + 1) * 8));
     if (segs) RHJCHK(ensure(ctx, x_seg_rng, ((size_t)units1 + 1) * 8));
+    if (cf) {
+        RHJCHK(ensure(ctx, ctx->cf_cnt1, (size_t)units1 * nb1 * 4));
+        RHJCHK(ensure(ctx, ctx->cf_pre, cf_pre_words(units2) * 4));
+        RHJCHK(ensure(ctx, ctx->cf_tot, (size_t)units2 * 4));
+    }
     u64 *seg0 = (u64 *)x_seg0.p;
     u32 *unit_start1 = (u32 *)x_unit_start.p;
     const u64 *rng1 = segs ? (const u64 *)x_seg_rng.p : nullptr;
@@ -740,7 +791,7 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
         Span s(ctx, RHJ_K_AUX);
         if (segs) launch_seg_units(st, (u32)in.nseg, in.seg_off, segL, groups_per_seg * per, (u64 *)x_seg_rng.p, seg0, unit_start1);
         else launch_init_single_segment(st, n, g1.L, seg0, unit_start1);          // seg0 = {0,n}, unit_start1 = {0, units1}
-        HIPCHK(ctx, hipMemsetAsync(x_hist2.p, 0, (size_t)units2 * nb2 * 4, st));
+        if (!cf) HIPCHK(ctx, hipMemsetAsync(x_hist2.p, 0, (size_t)units2 * nb2 * 4, st));
     }
     DupSniff sn;
     if (ctx->sniff_side >= 0) {                         // a join's relation: sample its join values for duplicates
@@ -750,6 +801,37 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
         ctx->sniff_n[side] = n;
         Span s(ctx, RHJ_K_AUX);
         HIPCHK(ctx, hipMemsetAsync(sn.tab, 0, (size_t)SNIFF_SLOTS * 4, st));
+    }
+    if (cf) {
+        // No histogram of the 16-byte input: pass 1 into fixed regions, the piece tables, pass 2's histogram over the narrow
+        // payloads, today's pass-2 scan and scatter.  d_ps and the contents of every final partition are the exact path's.
+        ctx->last_cf[cf_side] = 1;
+        const u32 *pre = (const u32 *)ctx->cf_pre.p;
+        {
+            Span s(ctx, RHJ_K_SCATTER);
+            launch_cf_pass1(st, in.aos, x_part_tmp.p, cg, g1, seg0, unit_start1, (u32 *)ctx->cf_cnt1.p, wide, 2u << cf_side, sn);
+        }
+        {
+            Span s(ctx, RHJ_K_AUX);
+            launch_cf_tables(st, cg, (u32)nb1, (const u32 *)ctx->cf_cnt1.p, (u32 *)ctx->cf_pre.p, (u32 *)ctx->cf_tot.p,
+                             (u64 *)x_ps_1.p, (u32 *)x_unit_start2.p, wide);
+        }
+        {
+            Span s(ctx, RHJ_K_HIST);
+            launch_cf_hist2(st, x_part_tmp.p, cg, (u32)nb1, b1, b2, pre, (u32 *)x_hist2.p, wide);
+        }
+        PassGeom g2;
+        g2.n = n; g2.L = 0; g2.nseg = (u32)nb1; g2.max_units = units2; g2.shift = b1; g2.bits = b2;
+        {
+            Span s(ctx, RHJ_K_SCAN);
+            launch_scan_units(st, g2, (const u64 *)x_ps_1.p, (const u32 *)x_unit_start2.p, (const u32 *)x_hist2.p,
+                              (u64 *)x_unit_base.p, d_ps, nullptr);
+        }
+        {
+            Span s(ctx, RHJ_K_SCATTER);
+            launch_cf_pass2(st, x_part_tmp.p, d_out, n, cg, (u32)nb1, b1, b2, (const u64 *)x_unit_base.p, pre, wide);
+        }
+        return check_launch(ctx, "count-free two-pass partition");
     }
     {
         Span s(ctx, RHJ_K_HIST);                        // (16-byte input: also reports a rowID that does not fit the narrow format)
@@ -801,11 +883,11 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
 }
 
 int partition_relation_fused(rhj_ctx *ctx, const void *d_in, u64 n, int b1, int b2, void *d_out, u64 *d_ps, int narrow = 0,
-                             int mix = MIX_NONE, const PartScratch *scratch = nullptr)
+                             int mix = MIX_NONE, const PartScratch *scratch = nullptr, int cf_side = -1)
 {
     FusedIn in;
     in.aos = d_in;
-    return partition_relation_fused(ctx, in, n, b1, b2, d_out, d_ps, narrow, mix, scratch);
+    return partition_relation_fused(ctx, in, n, b1, b2, d_out, d_ps, narrow, mix, scratch, cf_side);
 }
 
 // Two narrow passes with SEPARATE histograms (plans of 17-18 bits: 2^(b1+b2) packed counters do not fit the LDS, so the
@@ -972,6 +1054,13 @@ bool is_direct(const rhj_ctx *ctx, u64 nparts, u64 nR, u64 nS)
            (nR < nS ? nS : nR) <= DIRECT_MAX_PROBE;
 }
 
+// "partition.countfree" as it stands: the option, else RHJ_COUNTFREE=0 / 1 in the environment (A/B aid), else -1 (automatic)
+int cf_want(const rhj_ctx *ctx)
+{
+    static const int env = getenv("RHJ_COUNTFREE") ? (int)env_u64("RHJ_COUNTFREE", 0, 0, 1) : -1;
+    return ctx->opt_countfree >= 0 ? ctx->opt_countfree : env;
+}
+
 // R and S of a fused two-pass plan side by side on two streams: device-resident joins (nothing to upload in between) of at
 // most 2^28 tuples per side (the second pass-1 intermediate costs 16 B per tuple of S), not while profiling (spans are timed
 // on one stream).  RHJ_TWO_STREAMS=0 switches it off.
@@ -979,10 +1068,25 @@ bool two_streams_ok(const rhj_ctx *ctx, u64 nR, u64 nS, const rhj_opts &plan, st
 {
     static const bool on = env_u64("RHJ_TWO_STREAMS", 1, 0, 1) != 0;
     if (!on || ctx->prof.on || (before_S && *before_S)) return false;
+    // forced count-free pass 1, or the repeat of a side that overflowed: the one-stream path carries both
+    if (cf_want(ctx) == 1 || ctx->cf_keep_R || ctx->cf_off_once[0] || ctx->cf_off_once[1]) return false;
     if (plan.passes != 2 || !fused_two_pass_ok(plan.bits1, plan.bits2)) return false;
     if (ctx->cur_narrow && !narrow_fused_plan(plan)) return false;
     const u64 hi = nR > nS ? nR : nS, lo = nR > nS ? nS : nR;
     return lo > 0 && hi <= ((u64)1 << 28);
+}
+
+// Count-free pass 1 for this side of this join?  (Only the one-stream path of partition_phase asks: the two-stream mid-size
+// path, the pipelined host path and the multi-GPU receiver keep exact cursors.)  Returns the side, or -1.
+constexpr u64 CF_AUTO_MIN_TUPLES = (u64)1 << 28;       // automatic mode: the larger relation has more tuples than this
+int cf_side_for(rhj_ctx *ctx, int side, u64 nR, u64 nS, const rhj_opts &plan, int mix)
+{
+    const int want = cf_want(ctx);
+    if (want == 0 || ctx->cf_off_once[side] || ctx->cur_narrow != 2 || !narrow_fused_plan(plan)) return -1;
+    if (!cf_applies(side ? nS : nR, plan.bits1, plan.bits2, ctx->cur_narrow, mix, false)) return -1;
+    if (want < 0 && (nR > nS ? nR : nS) <= CF_AUTO_MIN_TUPLES) return -1;
+    if (ctx->cf_skip[side] > 0) { ctx->cf_skip[side]--; return -1; }          // backing off after a fall-back of this side
+    return side;
 }
 
 // Partition phase of a join: leaves ctx->cur_* describing partitioned R and S.
@@ -1007,6 +1111,9 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
     ctx->last.bits2 = plan.bits2;
     ctx->counters_clean = false;
     ctx->cur_narrow = narrow_level(ctx, nR, nS, plan);
+    const bool keep_R = ctx->cf_keep_R;
+    if (!keep_R && !ctx->cf_off_once[0]) ctx->last_cf[0] = 0;
+    if (!ctx->cf_off_once[1]) ctx->last_cf[1] = 0;
     if (ctx->cur_narrow) {
         RHJCHK(ensure(ctx, ctx->narrow_flag, 64));
         Span s(ctx, RHJ_K_AUX);
@@ -1072,11 +1179,15 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
             const bool sniff = sniff_on(ctx);
             if (sniff) RHJCHK(ensure(ctx, ctx->sniff_tab, (size_t)2 * SNIFF_SLOTS * 4));
             ctx->sniff_side = sniff ? 0 : -1;
-            int prc = partition_relation_fused(ctx, d_R, nR, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p, ctx->cur_narrow, mix);
+            int prc = RHJ_OK;
+            if (!keep_R)                                        // (the repeat after an overflow of S alone: R stands, samples included)
+                prc = partition_relation_fused(ctx, d_R, nR, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p, ctx->cur_narrow, mix,
+                                               nullptr, cf_side_for(ctx, 0, nR, nS, plan, mix));
             if (prc == RHJ_OK) prc = s_ready();
             ctx->sniff_side = sniff ? 1 : -1;
             if (prc == RHJ_OK)
-                prc = partition_relation_fused(ctx, d_S, nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p, ctx->cur_narrow, mix);
+                prc = partition_relation_fused(ctx, d_S, nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p, ctx->cur_narrow, mix,
+                                               nullptr, cf_side_for(ctx, 1, nR, nS, plan, mix));
             ctx->sniff_side = -1;
             RHJCHK(prc);
             ctx->sniff_ready = sniff;
@@ -1171,7 +1282,8 @@ int join_phase_on(rhj_ctx *ctx, const void *d_Rp, const u64 *d_psR, u64 nR, cons
     HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
     if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (wide_rowid) return RHJ_RETRY_WIDE;                       // a rowID did not fit 32 bits: nothing of this run is valid
+    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
+    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
     *out_count = host[0];
     ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
     ctx->last_max_part[0] = direct ? 0 : host[2];
@@ -1325,6 +1437,28 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
     if (rc != RHJ_OK) { ctx->counters_clean = false; return rc; }
     const bool tried_narrow = ctx->cur_narrow != 0;
     rc = join_phase(ctx, d_out, cap, out_count);
+    // A side whose count-free pass 1 overflowed is partitioned again with exact cursors (k_hist2d_units), inside this call.  R's
+    // partition stands when only S overflowed; after an overflow of R the kernels of S returned at once, so S runs again (count-free
+    // as before: at most two repeats).
+    for (int attempt = 0; rc == RHJ_RETRY_CF && attempt < 2; attempt++) {
+        const u32 over = ctx->cf_over;
+        for (int side = 0; side < 2; side++)
+            if (over & (2u << side)) {
+                ctx->cf_off_once[side] = true;
+                ctx->last_cf[side] = 2;
+                ctx->cf_fail_streak[side]++;
+                ctx->cf_skip[side] = ctx->cf_fail_streak[side] > 4 ? 32u : 1u << ctx->cf_fail_streak[side];
+            }
+        ctx->cf_keep_R = !(over & 2u);
+        rc = partition_phase(ctx, d_R, nR, d_S, nS, plan);
+        ctx->cf_keep_R = false;
+        if (rc == RHJ_OK) rc = join_phase(ctx, d_out, cap, out_count);
+    }
+    ctx->cf_off_once[0] = ctx->cf_off_once[1] = false;
+    if (rc == RHJ_RETRY_CF) return fail(ctx, RHJ_E_HIP, "count-free partition: overflow flag after the exact repeat");
+    if (rc == RHJ_OK)
+        for (int side = 0; side < 2; side++) if (ctx->last_cf[side] == 1) ctx->cf_fail_streak[side] = 0;
+    if (rc != RHJ_OK && rc != RHJ_RETRY_WIDE) { ctx->counters_clean = false; return rc; }
     if (rc != RHJ_RETRY_WIDE) {
         if (rc == RHJ_OK && !ctx->narrow_off_once) narrow_note_done(ctx, plan, tried_narrow);   // (off_once: the repeat of a join that fell back)
         return rc;
@@ -1444,7 +1578,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->counters, &ctx->out_pairs, &ctx->small_out, &ctx->hist_tmp, &ctx->scan_tmp, &ctx->hist2,
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
-                     &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
+                     &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
                      &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1]};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
@@ -1508,6 +1642,11 @@ int rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value)
         return RHJ_OK;
     }
     if (n == "partition.mix" && value >= -1 && value <= 1) { ctx->opt_mix = (int)value; return RHJ_OK; }
+    if (n == "partition.countfree" && value >= -1 && value <= 1) {
+        ctx->opt_countfree = (int)value;
+        for (int side = 0; side < 2; side++) ctx->cf_fail_streak[side] = ctx->cf_skip[side] = 0;
+        return RHJ_OK;
+    }
     if (n == "join.fused" && value >= -1 && value <= 1) { ctx->opt_fused = (int)value; return RHJ_OK; }
     if (n == "join.sniff" && value >= -1 && value <= 1) { ctx->opt_sniff = (int)value; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_set_option: unknown option or value: " + n);
@@ -1518,6 +1657,8 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (!ctx || !name || !value) return fail(ctx, RHJ_E_INVALID, "rhj_get_info: null argument");
     const std::string n(name);
     if (n == "last.narrow") { *value = ctx->cur_narrow; return RHJ_OK; }
+    if (n == "last.countfree_R") { *value = ctx->last_cf[0]; return RHJ_OK; }
+    if (n == "last.countfree_S") { *value = ctx->last_cf[1]; return RHJ_OK; }
     if (n == "last.join_kernel") { *value = ctx->last_join_kind; return RHJ_OK; }
     if (n == "last.pipelined") { *value = ctx->last_pipelined; return RHJ_OK; }
     if (n == "last.max_part_R") { *value = (int64_t)ctx->last_max_part[0]; return RHJ_OK; }
@@ -1591,6 +1732,19 @@ int rhj_reserve(rhj_ctx *ctx, uint64_t nR, uint64_t nS, const rhj_opts *opts)
         RHJCHK(ensure(ctx, ctx->part_S, (size_t)(nS ? nS : 1) * 16));
     }
     if (plan.passes == 2) RHJCHK(ensure(ctx, ctx->part_tmp, (size_t)((nR > nS ? nR : nS) + 1) * 16));
+    if (plan.passes == 2 && narrow_fused_plan(plan) && ctx->opt_countfree != 0) {       // count-free pass 1: regions and small tables
+        for (int side = 0; side < 2; side++) {
+            const u64 n = side ? nS : nR;
+            if (!cf_applies(n, plan.bits1, plan.bits2, 2, MIX_STORE, false)) continue;
+            if (ctx->opt_countfree < 0 && (nR > nS ? nR : nS) <= CF_AUTO_MIN_TUPLES) continue;
+            const CfGeom c = cf_geometry(n, plan.bits1);
+            const size_t nb1 = (size_t)1 << plan.bits1, units2 = nb1 * c.ngroups;
+            RHJCHK(ensure(ctx, ctx->part_tmp, cf_tmp_bytes(c)));
+            RHJCHK(ensure(ctx, ctx->cf_cnt1, (size_t)c.U * nb1 * 4));
+            RHJCHK(ensure(ctx, ctx->cf_pre, cf_pre_words((u32)units2) * 4));
+            RHJCHK(ensure(ctx, ctx->cf_tot, units2 * 4));
+        }
+    }
     return RHJ_OK;
 }
 
@@ -2379,6 +2533,22 @@ ShardTables shard_tables(rhj_ctx *ctx, int side)
 }
 
 }  // namespace
+
+// Test aid, not part of rhj.h: the partitions of side (0 R, 1 S) as the last two-pass narrow rhj_join_dev left them -- payloads
+// (n u64), rowIDs (n u32) and the 2^(bits1 + bits2) + 1 boundaries -- copied to host arrays of the caller.
+extern "C" int rhj_debug_read_partitions(rhj_ctx *ctx, int side, uint64_t *payloads, uint32_t *rowids, uint64_t *bounds)
+{
+    RHJCHK(use_device(ctx));
+    if (side < 0 || side > 1 || !payloads || !rowids || !bounds || ctx->cur_narrow == 0 || ctx->cur_nparts < 2)
+        return fail(ctx, RHJ_E_INVALID, "rhj_debug_read_partitions: no narrow partitions to read");
+    const u64 n = side ? ctx->cur_nS : ctx->cur_nR;
+    const unsigned char *part = (const unsigned char *)(side ? ctx->cur_S : ctx->cur_R);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(payloads, part, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(rowids, part + narrow_k_offset(n), (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(bounds, side ? ctx->cur_psS : ctx->cur_psR, (size_t)(ctx->cur_nparts + 1) * 8, hipMemcpyDeviceToHost));
+    return RHJ_OK;
+}
 
 uint64_t rhj_narrow_key_offset(uint64_t n) { return narrow_k_offset(n); }
 uint64_t rhj_narrow_bytes(uint64_t n) { return (narrow_k_offset(n) + n * 4 + 255) & ~(uint64_t)255; }

@@ -169,6 +169,7 @@ void launch_scatter_ranges(hipStream_t st, const void *d_in, void *d_out, u32 nu
 // narrow intermediate format (k_scatter_wcn): payloads (u64) at offset 0 of a buffer of >= 16 n bytes, rowIDs (u32) here
 inline size_t narrow_k_offset(u64 n) { return ((size_t)n * 8 + 255) & ~(size_t)255; }
 constexpr int RHJ_RETRY_WIDE = 1000;                    // internal: join_phase saw the narrow-format overflow flag
+constexpr int RHJ_RETRY_CF = 1001;                      // internal: ... or a count-free pass 1's overflow bit (2 << side)
 constexpr u64 NARROW_MIN_TUPLES = 1024;                 // 12 n + 256 <= 16 n
 constexpr u64 NARROW_AUTO_MIN_TUPLES = 8000000;         // automatic choice: larger side at least this ([measured] 4M: 0.45 ms
                                                         // either way; 16M ... 256M: 5-8 % faster narrow; 10^9: 19 %)
@@ -188,6 +189,21 @@ void launch_scatter_units_narrow_peer(hipStream_t st, const void *d_in, const Pa
 void launch_scatter_ranges_narrow(hipStream_t st, const void *d_in, bool in_narrow, void *d_out, u64 n, u32 nunits, int shift,
                                   int bits, const u64 *d_unit_base, const u64 *d_rng, u32 *d_overflow, u32 tag_groups = 0,
                                   u32 tag_div = 0, const u32 *d_inK = nullptr);   // d_inK: narrow input whose rowID array is not at narrow_k_offset(n)
+// Count-free pass 1 of a fused 8+8 narrow partition (k_scatter_wcn_cf): U pass-1 units of g.L tuples, `per` of them
+// per group; region (d, u) of the intermediate arrays = slots [(d * U + u) * cap, + cap); slots = nb1 * U * cap; payloads (u64) at
+// offset 0 of the intermediate buffer, rowIDs (u32) at slots * 8.  d_flag: the join's skip word (bit 0: a wide rowID); `bit` is
+// OR-ed into it when a run does not fit its region.  Tables: cnt1 [U][nb1] u32, pre cf_pre_words(units2) u32, unit_tot [units2] u32.
+struct CfGeom { u32 U = 0, per = 0, ngroups = 0, cap = 0; u64 slots = 0; };
+u32 cf_per_max();                                       // pieces per pass-2 unit the kernels handle (64)
+size_t cf_pre_words(u32 units2);
+void launch_cf_pass1(hipStream_t st, const void *d_in, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
+                     const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff);
+void launch_cf_tables(hipStream_t st, const CfGeom &c, u32 nb1, const u32 *d_cnt1, u32 *d_pre, u32 *d_unit_tot, u64 *d_ps_1,
+                      u32 *d_unit_start2, const u32 *d_flag);
+void launch_cf_hist2(hipStream_t st, const void *d_tmp, const CfGeom &c, u32 nb1, int b1, int b2, const u32 *d_pre, u32 *d_hist2,
+                     const u32 *d_flag);
+void launch_cf_pass2(hipStream_t st, const void *d_tmp, void *d_out, u64 n, const CfGeom &c, u32 nb1, int b1, int b2,
+                     const u64 *d_unit_base, const u32 *d_pre, u32 *d_flag);
 const char *launch_attr_error();                       // text of the first refused hipFuncSetAttribute, or null
 void launch_scatter_ranges_n2a(hipStream_t st, const void *d_in, void *d_out, u64 n, u32 nunits, int shift, int bits,
                                const u64 *d_unit_base, const u64 *d_rng, const u64 *d_key_bases, u32 tag_groups, u32 tag_div,

@@ -1302,15 +1302,34 @@ struct WnPeer {
     u32 *K[SEG_MAX];             // rowID arrays of the ranks
 };
 
-template <bool IN_NARROW, int GR_ = WN_GR, int TPT_ = WN_TPT, int THREADS_ = WN_THREADS, bool PEER = false>
-__global__ void __launch_bounds__(THREADS_)
-k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32 *__restrict__ inK,
+// Count-free pass 1 (fused 8+8 plans, 16-byte input, MIX_STORE).  CF == 1, pass 1: unit u writes digit d into
+// its own region [(d * U + u) * cap, + cap) of the intermediate arrays -- no start cursors, hence no histogram of the 16-byte
+// input -- and leaves the run lengths in cnt1[u][d]; cap is a multiple of GR, so every region starts on a line of its own.  A
+// run that would pass cap ends the unit before anything of that tile is stored and raises `bit` in the skip word (*overflow,
+// the word every later kernel of the join tests): the host repeats that relation with exact cursors.  The duplicate sampling
+// of k_hist2d_units moves here.  CF == 2, pass 2: pass-2 unit (d, g) reads the `per` pieces that group g of pass-1 units left
+// in bucket d, at stride cap, as ONE dense sequence of tuples (slot t -> piece by a binary search of the exclusive prefix
+// pre[unit][0 .. CF_PRE), kept in LDS); cursors, carry lines and stores are those of the exact path.  Pass 2 visits the same
+// tuples per pass-2 unit as the exact path does, so the final boundaries are identical and every final partition holds the
+// same multiset of {h, rowID} (the order inside a partition is fixed on neither path: a tile's ranks come from LDS atomics).
+constexpr u32 CF_PER_MAX = 64, CF_PRE = CF_PER_MAX + 1;
+struct WnFree {
+    u32 U = 0, cap = 0, per = 0, ngroups = 0, bit = 0;
+    u32 *cnt1 = nullptr;             // CF == 1: [U][nbins] run lengths (written)
+    const u32 *pre = nullptr;        // CF == 2: [units2][CF_PRE] exclusive prefix of the piece lengths, padded with the total
+    DupSniff sn;                     // CF == 1
+};
+
+template <bool IN_NARROW, int GR_, int TPT_, int THREADS_, bool PEER, int CF>
+__device__ __forceinline__ void
+dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32 *__restrict__ inK,
               u64 *__restrict__ outP, u32 *__restrict__ outK, const u64 *__restrict__ seg_start,
               const u32 *__restrict__ unit_start, u32 nseg, u64 L, int shift, int bits,
               const u64 *__restrict__ unit_base, const u64 *__restrict__ unit_rng, u32 n_rng_units,
-              u32 *__restrict__ overflow, u64 key_base, WnTag tag, int mix, WnPeer peer)
+              u32 *__restrict__ overflow, u64 key_base, WnTag tag, int mix, const WnPeer &peer, const WnFree &fr)
 {
     static_assert(!PEER || !IN_NARROW, "the peer split reads the rank's own 16-byte shard");
+    static_assert(CF == 0 || (!PEER && CF == (IN_NARROW ? 2 : 1)), "count-free: pass 1 reads 16-byte tuples, pass 2 narrow pieces");
     // a rowID that does not fit 32 bits has been seen (by the histogram kernel or by an earlier workgroup of this pass):
     // the join is going to repeat itself in the 16-byte format, nothing written from here on will be read
     if (overflow != nullptr && __builtin_nontemporal_load(overflow) != 0) return;
@@ -1333,10 +1352,19 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
     u32 *own = wsc + THREADS / 64;                                           // PEER: owner rank of every digit
     u64 **pP = reinterpret_cast<u64 **>((reinterpret_cast<uintptr_t>(own + (PEER ? nbins : 0)) + 7) & ~(uintptr_t)7);   // PEER: the ranks' arrays
     u32 **pK = reinterpret_cast<u32 **>(pP + (PEER ? SEG_MAX : 0));
+    u32 *pre = own;                                                          // CF == 2: CF_PRE words
 
     const u32 u = blockIdx.x;
     u64 beg, end;
-    if (unit_rng != nullptr) {
+    u64 ubase = 0;                                                           // CF == 2: first slot of the unit's first region
+    if constexpr (CF == 2) {
+        if (u >= n_rng_units) return;
+        if (threadIdx.x < CF_PRE) pre[threadIdx.x] = fr.pre[(u64)u * CF_PRE + threadIdx.x];
+        __syncthreads();
+        beg = 0;
+        end = pre[CF_PER_MAX];
+        ubase = ((u64)(u / fr.ngroups) * fr.U + (u64)(u % fr.ngroups) * fr.per) * fr.cap;
+    } else if (unit_rng != nullptr) {
         if (u >= n_rng_units) return;
         beg = unit_rng[u];
         end = unit_rng[u + 1];
@@ -1359,11 +1387,14 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
     auto dstK = [&](u32 d) -> u32 * { if constexpr (PEER) return pK[own[d]]; else return outK; };
 
     for (u32 b = tid; b < nbins; b += THREADS) {
-        const u64 g = unit_base[(u64)u * nbins + b] + (PEER ? peer.delta[b] : 0ull);
+        u64 g;
+        if constexpr (CF == 1) g = ((u64)b * fr.U + u) * fr.cap;
+        else g = unit_base[(u64)u * nbins + b] + (PEER ? peer.delta[b] : 0ull);
         gnext[b] = g;
         LO[b] = (u32)(g & GM);
         cnt[b] = 0;
     }
+    if (CF == 1 && tid == 0) mtot[1] = 0;                                    // a run of this unit would pass its region
     __syncthreads();
 
     u32 ovf = 0;                                                             // any rowID >= 2^32 seen (16-byte input only)
@@ -1372,11 +1403,18 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
 #pragma unroll
         for (int k = 0; k < TPT; k++) {                                      // unconditional loads (see dev_scatter_wc)
             const u32 i0 = k * THREADS + tid, i = i0 < last ? i0 : last;
-            if constexpr (IN_NARROW) { pay[k] = inP[tb + i]; key[k] = inK[tb + i]; }
+            if constexpr (CF == 2) {                                         // slot -> (piece, offset): pre[lo] <= t < pre[lo + 1]
+                const u32 t = (u32)tb + i;
+                u32 lo = 0;
+#pragma unroll
+                for (u32 s_ = CF_PER_MAX / 2; s_ > 0; s_ >>= 1) if (pre[lo + s_] <= t) lo += s_;
+                const u64 a = ubase + (u64)lo * fr.cap + (t - pre[lo]);
+                pay[k] = inP[a]; key[k] = inK[a];
+            } else if constexpr (IN_NARROW) { pay[k] = inP[tb + i]; key[k] = inK[tb + i]; }
             else { const Tup v = in[tb + i]; pay[k] = v.payload; key[k] = v.key - key_base; }
         }
     };
-    auto process = [&](u64 (&pay)[TPT], KeyT (&key)[TPT], u64 tb, auto full_tag) {
+    auto process = [&](u64 (&pay)[TPT], KeyT (&key)[TPT], u64 tb, auto full_tag) -> bool {     // true (CF == 1 only): the unit gives up
         constexpr bool FULL = decltype(full_tag)::value;
         const u32 ntile = FULL ? (u32)TILE : (u32)(end - tb);
         u32 rk[TPT], dg[TPT];
@@ -1393,6 +1431,7 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
             if (FULL || i < ntile) {
                 rk[k] = atomicAdd(&cnt[dg[k]], 1u);
                 if constexpr (!IN_NARROW) ovf |= (u32)(key[k] >> 32);
+                if constexpr (CF == 1) { if (fr.sn.tab != nullptr) sniff_sample(fr.sn, pay[k]); }      // (mixed: MIX_STORE)
             }
         }
         __syncthreads();                                                     // B1: counts complete
@@ -1404,6 +1443,7 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
                 c = cnt[b];
                 g0 = gnext[b]; e = g0 + c; a = (g0 + GM) & ~GM;
                 m = (e >= a) ? (u32)(e - a) : 0u;
+                if constexpr (CF == 1) { if (e > ((u64)b * fr.U + u + 1) * fr.cap) mtot[1] = 1; }
             }
             const u32 inc = wave_incl_scan(m, lane);
             if (lane == 63) wsc[wave] = inc;
@@ -1424,6 +1464,7 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
             }
         }
         __syncthreads();                                                     // S2: plan visible
+        if constexpr (CF == 1) { if (mtot[1]) return true; }                 // (nothing of this tile has been stored)
 #pragma unroll
         for (int k = 0; k < TPT; k++) {
             const u32 i = k * THREADS + tid;
@@ -1472,24 +1513,37 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
                 }
             }
         }
+        return false;
     };
 
     u64 pa[TPT], pb[TPT];
     KeyT ka[TPT], kb[TPT];
     u64 cur = beg;
+    bool gave_up = false;
     if (cur < end) load_tile(pa, ka, cur);
     while (cur < end) {
         u64 nxt = cur + TILE;                                                // (prefetch on every path: see dev_scatter_wc)
         load_tile(pb, kb, nxt < end ? nxt : cur);
-        if (nxt <= end) process(pa, ka, cur, std::true_type{}); else process(pa, ka, cur, std::false_type{});
+        gave_up = (nxt <= end) ? process(pa, ka, cur, std::true_type{}) : process(pa, ka, cur, std::false_type{});
+        if (CF == 1 && gave_up) break;
         cur = nxt;
         if (cur >= end) break;
         nxt = cur + TILE;
         load_tile(pa, ka, nxt < end ? nxt : cur);
-        if (nxt <= end) process(pb, kb, cur, std::true_type{}); else process(pb, kb, cur, std::false_type{});
+        gave_up = (nxt <= end) ? process(pb, kb, cur, std::true_type{}) : process(pb, kb, cur, std::false_type{});
+        if (CF == 1 && gave_up) break;
         cur = nxt;
     }
+    if constexpr (CF == 1) {
+        if (gave_up) {                                                       // (uniform: every thread read the same LDS word)
+            if (tid == 0) atomicOr(overflow, fr.bit);
+            return;
+        }
+    }
     __syncthreads();
+    if constexpr (CF == 1) {
+        for (u32 b = tid; b < nbins; b += THREADS) fr.cnt1[(u64)u * nbins + b] = (u32)(gnext[b] - ((u64)b * fr.U + u) * fr.cap);
+    }
     // unit end: the still incomplete line of every digit (shared with the next unit's first line)
     for (u32 q = tid; q < nbins * GR; q += THREADS) {
         const u32 d = q / GR, j = q % GR;
@@ -1503,6 +1557,99 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
     if constexpr (!IN_NARROW) {
         if (__ballot(ovf != 0) != 0 && lane == 0) atomicOr(overflow, 1u);
     }
+}
+
+template <bool IN_NARROW, int GR_ = WN_GR, int TPT_ = WN_TPT, int THREADS_ = WN_THREADS, bool PEER = false>
+__global__ void __launch_bounds__(THREADS_)
+k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32 *__restrict__ inK,
+              u64 *__restrict__ outP, u32 *__restrict__ outK, const u64 *__restrict__ seg_start,
+              const u32 *__restrict__ unit_start, u32 nseg, u64 L, int shift, int bits,
+              const u64 *__restrict__ unit_base, const u64 *__restrict__ unit_rng, u32 n_rng_units,
+              u32 *__restrict__ overflow, u64 key_base, WnTag tag, int mix, WnPeer peer)
+{
+    dev_scatter_wcn<IN_NARROW, GR_, TPT_, THREADS_, PEER, 0>(in, inP, inK, outP, outK, seg_start, unit_start, nseg, L, shift, bits,
+                                                             unit_base, unit_rng, n_rng_units, overflow, key_base, tag, mix, peer, WnFree());
+}
+
+// the count-free forms: pass 1 (16-byte input, single segment {0, n} cut into units of L) and pass 2 (pieces)
+template <bool IN_NARROW>
+__global__ void __launch_bounds__(WN_THREADS)
+k_scatter_wcn_cf(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32 *__restrict__ inK, u64 *__restrict__ outP,
+                 u32 *__restrict__ outK, const u64 *__restrict__ seg_start, const u32 *__restrict__ unit_start, u64 L, int shift,
+                 int bits, const u64 *__restrict__ unit_base, u32 nunits, u32 *__restrict__ overflow, int mix, WnFree fr)
+{
+    dev_scatter_wcn<IN_NARROW, WN_GR, WN_TPT, WN_THREADS, false, IN_NARROW ? 2 : 1>(in, inP, inK, outP, outK, seg_start, unit_start, 1u, L,
+                                                                                    shift, bits, unit_base, nullptr, nunits, overflow, (u64)0,
+                                                                                    WnTag{1u, 1u, 0u}, mix, WnPeer{}, fr);
+}
+
+// Between the passes of a count-free partition.  k_cf_pieces: one wavefront per pass-2 unit (d, g) turns the lengths of its
+// <= 64 pieces, cnt1[g * per + j][d], into their exclusive prefix (entries from `per` on hold the unit's total) and the total.
+__global__ void __launch_bounds__(256)
+k_cf_pieces(const u32 *__restrict__ cnt1, u32 U, u32 nb1, u32 per, u32 ngroups, u32 *__restrict__ pre, u32 *__restrict__ unit_tot,
+            const u32 *__restrict__ skip)
+{
+    if (__builtin_nontemporal_load(skip) != 0) return;
+    const u32 unit = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (unit >= nb1 * ngroups) return;
+    const u32 d = unit / ngroups, u1 = (unit % ngroups) * per + lane;
+    const u32 len = (lane < per && u1 < U) ? cnt1[(u64)u1 * nb1 + d] : 0u;
+    const u32 inc = wave_incl_scan(len, (int)lane);
+    pre[(u64)unit * CF_PRE + lane] = inc - len;
+    if (lane == 63) { pre[(u64)unit * CF_PRE + 64] = inc; unit_tot[unit] = inc; }
+}
+
+// k_cf_bounds: the logical boundaries of the pass-1 buckets (what the exact path's pass-1 scan leaves in ps_1: the segment
+// starts of the pass-2 scan) from the unit totals, and unit_start2[d] = d * ngroups.  One workgroup, nb1 <= 256.
+__global__ void __launch_bounds__(256)
+k_cf_bounds(const u32 *__restrict__ unit_tot, u32 nb1, u32 ngroups, u64 *__restrict__ ps_1, u32 *__restrict__ unit_start2,
+            const u32 *__restrict__ skip)
+{
+    __shared__ u32 wsum[4];
+    const u32 d = threadIdx.x;
+    // (written whatever the skip word says: the pass-2 scan has no skip test and takes its loop bounds from this table)
+    if (d < nb1) unit_start2[d] = d * ngroups;
+    if (d == 0) unit_start2[nb1] = nb1 * ngroups;
+    if (__builtin_nontemporal_load(skip) != 0) return;
+    u32 v = 0, total;
+    if (d < nb1) for (u32 g = 0; g < ngroups; g++) v += unit_tot[d * ngroups + g];
+    const u32 ex = block_excl_scan<256>(v, wsum, total);
+    if (d < nb1) ps_1[d] = ex;
+    if (d == 0) ps_1[nb1] = total;
+}
+
+// k_hist_pieces_n: the histogram of pass 2 over the pieces of a count-free pass 1 -- k_hist_units_n's read (payloads only,
+// eight loads in flight per lane), one workgroup per pass-2 unit, every wavefront streaming whole pieces.
+__global__ void __launch_bounds__(PART_THREADS)
+k_hist_pieces_n(const u64 *__restrict__ inP, const u32 *__restrict__ pre_all, WnFree fr, int shift, int bits,
+                u32 *__restrict__ unit_hist, const u32 *__restrict__ skip)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (__builtin_nontemporal_load(skip) != 0) return;
+    u32 *cnt = reinterpret_cast<u32 *>(smem);
+    const u32 nbins = 1u << bits, mask = nbins - 1, u = blockIdx.x;
+    u32 *pre = cnt + nbins;
+    for (u32 b = threadIdx.x; b < nbins; b += PART_THREADS) cnt[b] = 0;
+    if (threadIdx.x < CF_PRE) pre[threadIdx.x] = pre_all[(u64)u * CF_PRE + threadIdx.x];
+    __syncthreads();
+    const u64 ubase = ((u64)(u / fr.ngroups) * fr.U + (u64)(u % fr.ngroups) * fr.per) * fr.cap;
+    const u32 lane = threadIdx.x & 63;
+    for (u32 j = threadIdx.x >> 6; j < fr.per; j += PART_THREADS / 64) {
+        const u64 *p = inP + ubase + (u64)j * fr.cap;
+        const u32 len = pre[j + 1] - pre[j];
+        u32 i = lane;
+        for (; i + 7u * 64u < len; i += 8u * 64u) {
+            u64 v[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[k] = p[i + k * 64];
+#pragma unroll
+            for (int k = 0; k < 8; k++) atomicAdd(&cnt[(u32)(v[k] >> shift) & mask], 1u);
+        }
+        for (; i < len; i += 64) atomicAdd(&cnt[(u32)(p[i] >> shift) & mask], 1u);
+    }
+    __syncthreads();
+    u32 *out = unit_hist + (u64)u * nbins;
+    for (u32 b = threadIdx.x; b < nbins; b += PART_THREADS) out[b] = cnt[b];
 }
 
 // Contract check of the public stage call rhj_bucket_join before it routes to the compact-table kernel, which compares
@@ -2845,6 +2992,8 @@ static void allow_big_lds()
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<false>, wn_lds_bytes(WN_MAX_BITS));
     SET_LDS(k_scatter_wcn<true>, wn_lds_bytes(WN_MAX_BITS));
+    SET_LDS(k_scatter_wcn_cf<false>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
+    SET_LDS(k_scatter_wcn_cf<true>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
     SET_LDS((k_scatter_wcn<false, WN_GR, WN_TPT, WN_THREADS, true>), wn_lds_bytes(WN_MAX_BITS, WN_GR, WN_TPT, WN_THREADS, true));
     SET_LDS((k_scatter_wcn<false, WN9_GR, WN9_TPT, WN9_THREADS>), wn_lds_bytes(WN9_MAX_BITS, WN9_GR, WN9_TPT, WN9_THREADS));
     SET_LDS((k_scatter_wcn<true, WN9_GR, WN9_TPT, WN9_THREADS>), wn_lds_bytes(WN9_MAX_BITS, WN9_GR, WN9_TPT, WN9_THREADS));
@@ -3173,6 +3322,48 @@ void launch_scatter_ranges_narrow(hipStream_t st, const void *d_in, bool in_narr
                            (u64)0, shift, bits, d_unit_base, d_rng, nunits, d_overflow, (u64)0, tag, 0, WnPeer{});
 }
 int tag_bits() { return (int)TAG_BITS; }
+
+// ---- count-free pass 1 --------------------------------------------------------------------------------------
+u32 cf_per_max() { return CF_PER_MAX; }
+size_t cf_pre_words(u32 units2) { return (size_t)units2 * CF_PRE; }
+static WnFree cf_make(const CfGeom &c, u32 bit, u32 *cnt1, const u32 *pre, const DupSniff &sn)
+{
+    WnFree fr;
+    fr.U = c.U; fr.cap = c.cap; fr.per = c.per; fr.ngroups = c.ngroups; fr.bit = bit; fr.cnt1 = cnt1; fr.pre = pre; fr.sn = sn;
+    return fr;
+}
+void launch_cf_pass1(hipStream_t st, const void *d_in, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
+                     const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff)
+{
+    if (c.U == 0) return;
+    allow_big_lds();
+    hipLaunchKernelGGL(k_scatter_wcn_cf<false>, dim3(c.U), dim3(WN_THREADS), wn_lds_bytes(g.bits) + CF_PRE * 4, st, (const Tup *)d_in,
+                       (const u64 *)nullptr, (const u32 *)nullptr, (u64 *)d_tmp, (u32 *)((unsigned char *)d_tmp + c.slots * 8),
+                       d_seg_start, d_unit_start, g.L, g.shift, g.bits, (const u64 *)nullptr, c.U, d_flag, g.mix,
+                       cf_make(c, bit, d_cnt1, nullptr, sniff));
+}
+void launch_cf_tables(hipStream_t st, const CfGeom &c, u32 nb1, const u32 *d_cnt1, u32 *d_pre, u32 *d_unit_tot, u64 *d_ps_1,
+                      u32 *d_unit_start2, const u32 *d_flag)
+{
+    const u32 units2 = nb1 * c.ngroups;
+    hipLaunchKernelGGL(k_cf_pieces, dim3((units2 + 3) / 4), dim3(256), 0, st, d_cnt1, c.U, nb1, c.per, c.ngroups, d_pre, d_unit_tot, d_flag);
+    hipLaunchKernelGGL(k_cf_bounds, dim3(1), dim3(256), 0, st, (const u32 *)d_unit_tot, nb1, c.ngroups, d_ps_1, d_unit_start2, d_flag);
+}
+void launch_cf_hist2(hipStream_t st, const void *d_tmp, const CfGeom &c, u32 nb1, int b1, int b2, const u32 *d_pre, u32 *d_hist2,
+                     const u32 *d_flag)
+{
+    hipLaunchKernelGGL(k_hist_pieces_n, dim3(nb1 * c.ngroups), dim3(PART_THREADS), ((size_t)4 << b2) + CF_PRE * 4, st, (const u64 *)d_tmp,
+                       d_pre, cf_make(c, 0, nullptr, d_pre, DupSniff()), b1, b2, d_hist2, d_flag);
+}
+void launch_cf_pass2(hipStream_t st, const void *d_tmp, void *d_out, u64 n, const CfGeom &c, u32 nb1, int b1, int b2,
+                     const u64 *d_unit_base, const u32 *d_pre, u32 *d_flag)
+{
+    allow_big_lds();
+    hipLaunchKernelGGL(k_scatter_wcn_cf<true>, dim3(nb1 * c.ngroups), dim3(WN_THREADS), wn_lds_bytes(b2) + CF_PRE * 4, st, (const Tup *)nullptr,
+                       (const u64 *)d_tmp, (const u32 *)((const unsigned char *)d_tmp + c.slots * 8), (u64 *)d_out,
+                       (u32 *)((unsigned char *)d_out + narrow_k_offset(n)), (const u64 *)nullptr, (const u32 *)nullptr, (u64)0, b1, b2,
+                       d_unit_base, nb1 * c.ngroups, d_flag, 0, cf_make(c, 0, nullptr, d_pre, DupSniff()));
+}
 
 void launch_check_radix(hipStream_t st, const void *d_R, const u64 *d_startR, const void *d_S, const u64 *d_startS, u64 nparts,
                         int radix_bits, u64 *d_bad)

@@ -224,6 +224,12 @@ void launch_pass_pair(hipStream_t st, const PassPairHost &h, int, int, int phase
     u64 *z = h.zero8;
     if (phase == 0 && z) fake_enqueue(st, [=] { memset(z, 0, 64); });      // (the first launch clears the join counters)
 }
+u32 cf_per_max() { return 64; }
+size_t cf_pre_words(u32 units2) { return (size_t)units2 * 65; }
+void launch_cf_pass1(hipStream_t, const void *, void *, const CfGeom &, const PassGeom &, const u64 *, const u32 *, u32 *, u32 *, u32, const DupSniff &) {}
+void launch_cf_tables(hipStream_t, const CfGeom &, u32, const u32 *, u32 *, u32 *, u64 *, u32 *, const u32 *) {}
+void launch_cf_hist2(hipStream_t, const void *, const CfGeom &, u32, int, int, const u32 *, u32 *, const u32 *) {}
+void launch_cf_pass2(hipStream_t, const void *, void *, u64, const CfGeom &, u32, int, int, const u64 *, const u32 *, u32 *) {}
 void launch_hist2d_units(hipStream_t, const void *, bool, u64, u64, u32, int, int, u32, u32, u32 *, u32 *, u64, u32 *, const u64 *, int, const DupSniff &) {}
 void launch_seg_units(hipStream_t, u32, const u64 *, const u64 *, u32, u64 *, u64 *, u32 *) {}
 void launch_make_group_ranges(hipStream_t, const u64 *, u32, u32, u32, u64, u64 *, u32 *) {}

@@ -1,11 +1,13 @@
 // tools/copybench.hip -- which 16 B/lane copy shapes reach the HBM copy ceiling on MI355X (development aid).
 //   hipcc --offload-arch=gfx950 -O3 -o gpurun_out/copybench tools/copybench.hip && gpurun_out/copybench [GiB]
+//   ... copybench pieces: the read patterns of a count-free pass 1's output
 // Shapes: the scatter kernel's (one contiguous region per workgroup, 32 KiB tiles, next tile prefetched)
 // against tile-interleaved and grid-stride copies, with and without nontemporal hints.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 #include <algorithm>
 
@@ -208,6 +210,121 @@ __global__ void __launch_bounds__(THREADS) k_aos_to_soa(const Tup *__restrict__ 
     }
 }
 
+// ---- count-free pass 1: what reading its output costs ------------------------------------
+// Pass 1 without counts leaves bucket d's tuples as one piece per pass-1 unit u, in region (d * U + u) * cap of the
+// payload / rowID arrays; a pass-2 unit (d, g) then reads PER consecutive pieces at stride cap instead of one run.
+// len(d, u) = mean - spread/2 + (a hash of the region) % spread: not line-aligned, as the real pieces.
+__host__ __device__ __forceinline__ u32 piece_len(u32 region, u32 mean, u32 spread)
+{
+    return mean - spread / 2 + (u32)(((u64)region * 0x9E3779B97F4A7C15ull) >> 40) % spread;
+}
+__global__ void k_fill_hash(u64 *__restrict__ p, u64 n)       // digits spread over all counters, as hashed join values are
+{
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        u64 z = (i + 1) * 0x9E3779B97F4A7C15ull; z ^= z >> 29; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 32;
+        p[i] = z;
+    }
+}
+constexpr int PC_PER = 64;              // pieces per pass-2 unit (pass-1 units per group)
+
+// (a) the pass-2 histogram: 8 B per tuple.  PIECES: every wavefront streams whole pieces (piece j of the unit goes to
+// wavefront j % waves), eight loads in flight per lane; else the unit's tuples are ONE run (today's k_hist_units_n shape).
+template <int THREADS, bool PIECES>
+__global__ void __launch_bounds__(THREADS) k_hist_pieces(const u64 *__restrict__ inP, u32 cap, u32 mean, u32 spread, int shift,
+                                                         u32 *__restrict__ hist)
+{
+    __shared__ u32 cnt[256];
+    __shared__ u32 pre[PC_PER + 1];
+    const u32 unit = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 256) cnt[tid] = 0;
+    if (tid == 0) { u32 s = 0; for (int j = 0; j < PC_PER; j++) { pre[j] = s; s += piece_len(unit * PC_PER + j, mean, spread); } pre[PC_PER] = s; }
+    __syncthreads();
+    const u64 ubase = (u64)unit * PC_PER * cap;
+    if (PIECES) {
+        for (u32 j = wave; j < PC_PER; j += THREADS / 64) {
+            const u64 *p = inP + ubase + (u64)j * cap;
+            const u32 len = pre[j + 1] - pre[j];
+            u32 i = lane;
+            for (; i + 7u * 64u < len; i += 8u * 64u) {
+                u64 v[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) v[k] = p[i + k * 64];
+#pragma unroll
+                for (int k = 0; k < 8; k++) atomicAdd(&cnt[(u32)(v[k] >> shift) & 255u], 1u);
+            }
+            for (; i < len; i += 64) atomicAdd(&cnt[(u32)(p[i] >> shift) & 255u], 1u);
+        }
+    } else {
+        const u64 *p = inP + ubase;
+        const u32 len = pre[PC_PER];
+        u32 i = tid;
+        for (; i + 7u * THREADS < len; i += 8u * THREADS) {
+            u64 v[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[k] = p[i + k * THREADS];
+#pragma unroll
+            for (int k = 0; k < 8; k++) atomicAdd(&cnt[(u32)(v[k] >> shift) & 255u], 1u);
+        }
+        for (; i < len; i += THREADS) atomicAdd(&cnt[(u32)(p[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 256) hist[(u64)unit * 256 + tid] = cnt[tid];
+}
+
+// (b) pass 2's byte mix: 8 + 4 B read per tuple in dense 4096-tuple tiles (slot t of the unit -> piece by a binary search of
+// the prefix in LDS, next tile prefetched), 8 + 4 B written as 256 streams of 32-tuple lines per workgroup (k_stream_lines).
+template <int THREADS, int TPT, bool PIECES>
+__global__ void __launch_bounds__(THREADS) k_pass2_pieces(const u64 *__restrict__ inP, const u32 *__restrict__ inK, u64 *__restrict__ outP,
+                                                          u32 *__restrict__ outK, u32 cap, u32 mean, u32 spread, u32 cpud)
+{
+    constexpr u32 TILE = THREADS * TPT, GR = 32;
+    __shared__ u32 pre[PC_PER + 1];
+    const u32 unit = blockIdx.x, tid = threadIdx.x, G = gridDim.x;
+    if (tid == 0) { u32 s = 0; for (int j = 0; j < PC_PER; j++) { pre[j] = s; s += piece_len(unit * PC_PER + j, mean, spread); } pre[PC_PER] = s; }
+    __syncthreads();
+    const u32 total = pre[PC_PER];
+    const u64 ubase = (u64)unit * PC_PER * cap, cpd = (u64)G * cpud;
+    auto addr = [&](u32 t) -> u64 {
+        if (!PIECES) return ubase + t;
+        u32 lo = 0;
+#pragma unroll
+        for (u32 s = PC_PER / 2; s > 0; s >>= 1) if (pre[lo + s] <= t) lo += s;
+        return ubase + (u64)lo * cap + (t - pre[lo]);
+    };
+    auto load = [&](u64 (&p)[TPT], u32 (&kk)[TPT], u32 tb) {
+#pragma unroll
+        for (int k = 0; k < TPT; k++) {
+            u32 t = tb + k * THREADS + tid; t = t < total ? t : total - 1;
+            const u64 a = addr(t); p[k] = inP[a]; kk[k] = inK[a];
+        }
+    };
+    auto store = [&](u64 (&p)[TPT], u32 (&kk)[TPT], u32 tb) {
+#pragma unroll
+        for (int k = 0; k < TPT; k++) {
+            const u32 it = k * THREADS + tid;
+            if (tb + it < total) {
+                const u64 cg = (u64)(tb / TILE) * (TILE / GR) + it / GR;
+                const u64 o = ((cg & 255) * cpd + (u64)unit * cpud + (cg >> 8)) * GR + it % GR;
+                __builtin_nontemporal_store(p[k], &outP[o]); __builtin_nontemporal_store(kk[k], &outK[o]);
+            }
+        }
+    };
+    u64 pa[TPT], pb[TPT]; u32 ka[TPT], kb[TPT];
+    u32 cur = 0;
+    load(pa, ka, cur);
+    while (cur < total) {
+        u32 nxt = cur + TILE;
+        load(pb, kb, nxt < total ? nxt : cur);
+        store(pa, ka, cur);
+        cur = nxt; if (cur >= total) break;
+        nxt = cur + TILE;
+        load(pa, ka, nxt < total ? nxt : cur);
+        store(pb, kb, cur);
+        cur = nxt;
+    }
+}
+
+
 template <typename F> static double time_ms(F f, int reps = 5)
 {
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
@@ -221,8 +338,42 @@ template <typename F> static double time_ms(F f, int reps = 5)
     return ms[ms.size() / 2];
 }
 
+// copybench pieces: the two read patterns of a count-free pass 1's output at 10^9 tuples (256 buckets x 1024 pass-1 units,
+// mean piece 3824 tuples in regions of cap = 4448), each against its contiguous form, plus the 16-byte read they replace.
+static int run_pieces()
+{
+    const u32 nb1 = 256, U = 1024, mean = 3824, spread = 257, cap = 4448, units2 = nb1 * U / PC_PER;
+    const u64 regions = (u64)nb1 * U, slots = regions * cap;
+    u64 ntup = 0; u32 lmax = 0;
+    for (u32 r = 0; r < regions; r++) { const u32 l = piece_len(r, mean, spread); ntup += l; lmax = l > lmax ? l : lmax; }
+    if (lmax > cap) { fprintf(stderr, "piece above cap\n"); return 1; }
+    const u32 cpud = ((u32)PC_PER * lmax / 32 + 1 + 255) / 256;                  // 32-tuple chunks per (unit, stream)
+    const u64 out_slots = 256ull * units2 * cpud * 32;                           // one past the largest index written
+    u64 *inP, *outP; u32 *inK, *outK, *hist; Tup *aos; u64 *sink;
+    CK(hipMalloc(&inP, slots * 8)); CK(hipMalloc(&inK, slots * 4)); CK(hipMalloc(&outP, out_slots * 8)); CK(hipMalloc(&outK, out_slots * 4));
+    CK(hipMalloc(&hist, (size_t)units2 * 256 * 4)); CK(hipMalloc(&aos, ntup * 16)); CK(hipMalloc(&sink, 8));
+    hipLaunchKernelGGL(k_fill_hash, dim3(4096), dim3(256), 0, 0, inP, slots); CK(hipDeviceSynchronize()); CK(hipMemset(inK, 1, slots * 4)); CK(hipMemset(aos, 1, ntup * 16)); CK(hipMemset(sink, 0, 8));
+    printf("# %llu tuples in %llu pieces (mean %u, max %u, cap %u); times scaled to 10^9 tuples\n", (unsigned long long)ntup,
+           (unsigned long long)regions, mean, lmax, cap);
+    auto rep = [&](const char *name, double ms) { printf("%-74s %8.3f ms\n", name, ms * 1e9 / (double)ntup); fflush(stdout); };
+    for (int round = 0; round < 2; round++) {
+        {
+            const int G = 1024; const u64 L = ((ntup + G - 1) / G + 2047) / 2048 * 2048;
+            rep("16 B AoS read T=512 tpt=4 contiguous G=1024 (the histogram's)",
+                time_ms([&] { hipLaunchKernelGGL((k_read<512, 4, 0>), dim3(G), dim3(512), 0, 0, aos, sink, ntup, L); }));
+        }
+        rep("(a) 8 B hist, one run per unit, T=512", time_ms([&] { hipLaunchKernelGGL((k_hist_pieces<512, false>), dim3(units2), dim3(512), 0, 0, inP, cap, mean, spread, 8, hist); }));
+        rep("(a) 8 B hist, 64 pieces at stride cap, wavefront per piece, T=512", time_ms([&] { hipLaunchKernelGGL((k_hist_pieces<512, true>), dim3(units2), dim3(512), 0, 0, inP, cap, mean, spread, 8, hist); }));
+        rep("(a) 8 B hist, 64 pieces at stride cap, wavefront per piece, T=1024", time_ms([&] { hipLaunchKernelGGL((k_hist_pieces<1024, true>), dim3(units2), dim3(1024), 0, 0, inP, cap, mean, spread, 8, hist); }));
+        rep("(b) 12 + 12 B, one run per unit, T=1024 lds=150K", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, false>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud); }));
+        rep("(b) 12 + 12 B, 64 pieces at stride cap, dense tiles, T=1024 lds=150K", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, true>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud); }));
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "pieces")) return run_pieces();
     const double gib = argc > 1 ? atof(argv[1]) : 14.9;
     const u64 n = (u64)(gib * (1ull << 30) / 16) / 8192 * 8192;
     Tup *in, *out; u64 *sink;

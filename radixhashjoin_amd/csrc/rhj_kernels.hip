@@ -1312,7 +1312,12 @@ struct WnPeer {
 // pre[unit][0 .. CF_PRE), kept in LDS); cursors, carry lines and stores are those of the exact path.  Pass 2 visits the same
 // tuples per pass-2 unit as the exact path does, so the final boundaries are identical and every final partition holds the
 // same multiset of {h, rowID} (the order inside a partition is fixed on neither path: a tile's ranks come from LDS atomics).
-constexpr u32 CF_PER_MAX = 64, CF_PRE = CF_PER_MAX + 1;
+// The payload array between the two count-free passes is private to them and k_hist_pieces_n, and laid out in WORD PLANES: inside
+// every 256-byte block of 32 slots the 32 low words of h come first, then the 32 high words (slot a: word cf_w(a) and CF_HI words
+// further).  Pass 2's digit lies in the low word (bits1 + bits2 <= 16), so its histogram reads every other 128-byte line.
+constexpr u32 CF_PER_MAX = 64, CF_PRE = CF_PER_MAX + 1, CF_HI = 32;
+static_assert(WN_GR == 32, "a carry line of the count-free pass 1 is one block of word planes");
+__device__ __forceinline__ u64 cf_w(u64 a) { return ((a >> 5) << 6) | (a & 31); }
 struct WnFree {
     u32 U = 0, cap = 0, per = 0, ngroups = 0, bit = 0;
     u32 *cnt1 = nullptr;             // CF == 1: [U][nbins] run lengths (written)
@@ -1385,6 +1390,13 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
     // where digit d's tuples are written: the one output relation, or the arrays of the rank that owns class d
     auto dstP = [&](u32 d) -> u64 * { if constexpr (PEER) return pP[own[d]]; else return outP; };
     auto dstK = [&](u32 d) -> u32 * { if constexpr (PEER) return pK[own[d]]; else return outK; };
+    auto storeP = [&](u32 d, u64 o, u64 v) {                                 // payload of slot o (CF == 1: as two words, see cf_w)
+        if constexpr (CF == 1) {
+            u32 *W = reinterpret_cast<u32 *>(outP) + cf_w(o);
+            __builtin_nontemporal_store((u32)v, W);
+            __builtin_nontemporal_store((u32)(v >> 32), W + CF_HI);
+        } else __builtin_nontemporal_store(v, &dstP(d)[o]);
+    };
 
     for (u32 b = tid; b < nbins; b += THREADS) {
         u64 g;
@@ -1409,7 +1421,8 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
 #pragma unroll
                 for (u32 s_ = CF_PER_MAX / 2; s_ > 0; s_ >>= 1) if (pre[lo + s_] <= t) lo += s_;
                 const u64 a = ubase + (u64)lo * fr.cap + (t - pre[lo]);
-                pay[k] = inP[a]; key[k] = inK[a];
+                const u32 *W = reinterpret_cast<const u32 *>(inP) + cf_w(a);
+                pay[k] = W[0] | (u64)W[CF_HI] << 32; key[k] = inK[a];
             } else if constexpr (IN_NARROW) { pay[k] = inP[tb + i]; key[k] = inK[tb + i]; }
             else { const Tup v = in[tb + i]; pay[k] = v.payload; key[k] = v.key - key_base; }
         }
@@ -1482,7 +1495,7 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
             const u64 x = LB[d];
             if (x != ~0ull && j >= (u32)(x & GM)) {
                 const u64 o = (x & ~GM) + j;
-                __builtin_nontemporal_store(sp[TILE + q], &dstP(d)[o]);
+                storeP(d, o, sp[TILE + q]);
                 __builtin_nontemporal_store(sk[TILE + q], &dstK(d)[o]);
             }
         }
@@ -1494,7 +1507,7 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
             if (i < mt) {
                 const u64 v = sp[i];
                 const u32 d = (u32)(v >> shift) & mask;
-                if (i < T[d]) { const u64 o = A[d] + i; __builtin_nontemporal_store(v, &dstP(d)[o]); __builtin_nontemporal_store(sk[i], &dstK(d)[o]); }      // whole lines [a, b)
+                if (i < T[d]) { const u64 o = A[d] + i; storeP(d, o, v); __builtin_nontemporal_store(sk[i], &dstK(d)[o]); }      // whole lines [a, b)
                 else keep |= 1u << k;                                                       // tail [b, e): carried on
             }
         }
@@ -1550,7 +1563,7 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
         const u64 g = gnext[d];
         if (j >= LO[d] && j < (u32)(g & GM)) {
             const u64 o = (g & ~GM) + j;
-            __builtin_nontemporal_store(sp[TILE + q], &dstP(d)[o]);
+            storeP(d, o, sp[TILE + q]);
             __builtin_nontemporal_store(sk[TILE + q], &dstK(d)[o]);
         }
     }
@@ -1618,10 +1631,12 @@ k_cf_bounds(const u32 *__restrict__ unit_tot, u32 nb1, u32 ngroups, u64 *__restr
     if (d == 0) ps_1[nb1] = total;
 }
 
-// k_hist_pieces_n: the histogram of pass 2 over the pieces of a count-free pass 1 -- k_hist_units_n's read (payloads only,
-// eight loads in flight per lane), one workgroup per pass-2 unit, every wavefront streaming whole pieces.
+// k_hist_pieces_n: the histogram of pass 2 over the pieces of a count-free pass 1, one workgroup per pass-2 unit, every wavefront
+// streaming whole pieces.  It reads the low-word lines only (cf_w: the first 128 bytes of every 256-byte block, 4 bytes per tuple):
+// a piece starts on a block boundary, so 8 lanes cover a line with 16-byte loads and a wavefront 8 blocks = 256 tuples per load,
+// eight loads in flight per lane (clamped to the piece's last block; the tuple index masks what lies beyond the piece).
 __global__ void __launch_bounds__(PART_THREADS)
-k_hist_pieces_n(const u64 *__restrict__ inP, const u32 *__restrict__ pre_all, WnFree fr, int shift, int bits,
+k_hist_pieces_n(const u32 *__restrict__ W, const u32 *__restrict__ pre_all, WnFree fr, int shift, int bits,
                 u32 *__restrict__ unit_hist, const u32 *__restrict__ skip)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1633,19 +1648,26 @@ k_hist_pieces_n(const u64 *__restrict__ inP, const u32 *__restrict__ pre_all, Wn
     if (threadIdx.x < CF_PRE) pre[threadIdx.x] = pre_all[(u64)u * CF_PRE + threadIdx.x];
     __syncthreads();
     const u64 ubase = ((u64)(u / fr.ngroups) * fr.U + (u64)(u % fr.ngroups) * fr.per) * fr.cap;
-    const u32 lane = threadIdx.x & 63;
+    const u32 lane = threadIdx.x & 63, sub = lane >> 3, off = (lane & 7) * 4;
     for (u32 j = threadIdx.x >> 6; j < fr.per; j += PART_THREADS / 64) {
-        const u64 *p = inP + ubase + (u64)j * fr.cap;
-        const u32 len = pre[j + 1] - pre[j];
-        u32 i = lane;
-        for (; i + 7u * 64u < len; i += 8u * 64u) {
-            u64 v[8];
+        const u32 *p = W + cf_w(ubase + (u64)j * fr.cap) + off;            // (a region starts on a block: cap is a multiple of 32)
+        const u32 len = pre[j + 1] - pre[j], nblk = (len + 31) / 32;         // len <= cap: a longer run raised the skip word
+        for (u32 b0 = 0; b0 < nblk; b0 += 64) {
+            uint4 v[8];
 #pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = p[i + k * 64];
+            for (int k = 0; k < 8; k++) {
+                const u32 b = b0 + k * 8 + sub;
+                v[k] = *reinterpret_cast<const uint4 *>(p + (u64)(b < nblk ? b : nblk - 1) * (2 * CF_HI));
+            }
 #pragma unroll
-            for (int k = 0; k < 8; k++) atomicAdd(&cnt[(u32)(v[k] >> shift) & mask], 1u);
+            for (int k = 0; k < 8; k++) {
+                const u32 t = (b0 + k * 8 + sub) * 32 + off;                 // first of the lane's four tuples
+                if (t + 0 < len) atomicAdd(&cnt[(v[k].x >> shift) & mask], 1u);
+                if (t + 1 < len) atomicAdd(&cnt[(v[k].y >> shift) & mask], 1u);
+                if (t + 2 < len) atomicAdd(&cnt[(v[k].z >> shift) & mask], 1u);
+                if (t + 3 < len) atomicAdd(&cnt[(v[k].w >> shift) & mask], 1u);
+            }
         }
-        for (; i < len; i += 64) atomicAdd(&cnt[(u32)(p[i] >> shift) & mask], 1u);
     }
     __syncthreads();
     u32 *out = unit_hist + (u64)u * nbins;
@@ -3352,7 +3374,7 @@ void launch_cf_tables(hipStream_t st, const CfGeom &c, u32 nb1, const u32 *d_cnt
 void launch_cf_hist2(hipStream_t st, const void *d_tmp, const CfGeom &c, u32 nb1, int b1, int b2, const u32 *d_pre, u32 *d_hist2,
                      const u32 *d_flag)
 {
-    hipLaunchKernelGGL(k_hist_pieces_n, dim3(nb1 * c.ngroups), dim3(PART_THREADS), ((size_t)4 << b2) + CF_PRE * 4, st, (const u64 *)d_tmp,
+    hipLaunchKernelGGL(k_hist_pieces_n, dim3(nb1 * c.ngroups), dim3(PART_THREADS), ((size_t)4 << b2) + CF_PRE * 4, st, (const u32 *)d_tmp,
                        d_pre, cf_make(c, 0, nullptr, d_pre, DupSniff()), b1, b2, d_hist2, d_flag);
 }
 void launch_cf_pass2(hipStream_t st, const void *d_tmp, void *d_out, u64 n, const CfGeom &c, u32 nb1, int b1, int b2,

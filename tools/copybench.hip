@@ -1,6 +1,7 @@
 // tools/copybench.hip -- which 16 B/lane copy shapes reach the HBM copy ceiling on MI355X (development aid).
 //   hipcc --offload-arch=gfx950 -O3 -o gpurun_out/copybench tools/copybench.hip && gpurun_out/copybench [GiB]
 //   ... copybench pieces: the read patterns of a count-free pass 1's output
+//   ... copybench planes: word-plane layouts of its payload array
 // Shapes: the scatter kernel's (one contiguous region per workgroup, 32 KiB tiles, next tile prefetched)
 // against tile-interleaved and grid-stride copies, with and without nontemporal hints.
 #include <hip/hip_runtime.h>
@@ -273,9 +274,9 @@ __global__ void __launch_bounds__(THREADS) k_hist_pieces(const u64 *__restrict__
 
 // (b) pass 2's byte mix: 8 + 4 B read per tuple in dense 4096-tuple tiles (slot t of the unit -> piece by a binary search of
 // the prefix in LDS, next tile prefetched), 8 + 4 B written as 256 streams of 32-tuple lines per workgroup (k_stream_lines).
-template <int THREADS, int TPT, bool PIECES>
+template <int THREADS, int TPT, bool PIECES, int LAYOUT = 0>
 __global__ void __launch_bounds__(THREADS) k_pass2_pieces(const u64 *__restrict__ inP, const u32 *__restrict__ inK, u64 *__restrict__ outP,
-                                                          u32 *__restrict__ outK, u32 cap, u32 mean, u32 spread, u32 cpud)
+                                                          u32 *__restrict__ outK, u32 cap, u32 mean, u32 spread, u32 cpud, u64 plane)
 {
     constexpr u32 TILE = THREADS * TPT, GR = 32;
     __shared__ u32 pre[PC_PER + 1];
@@ -295,7 +296,13 @@ __global__ void __launch_bounds__(THREADS) k_pass2_pieces(const u64 *__restrict_
 #pragma unroll
         for (int k = 0; k < TPT; k++) {
             u32 t = tb + k * THREADS + tid; t = t < total ? t : total - 1;
-            const u64 a = addr(t); p[k] = inP[a]; kk[k] = inK[a];
+            const u64 a = addr(t);
+            if (LAYOUT != 0) {                                               // (word planes: see k_hist_planes; 1 blocked, 2 separate)
+                const u32 *W = reinterpret_cast<const u32 *>(inP);
+                const u64 w = LAYOUT == 1 ? (((a >> 5) << 6) | (a & 31)) : a;
+                p[k] = W[w] | (u64)W[w + (LAYOUT == 1 ? 32 : plane)] << 32;
+            } else p[k] = inP[a];
+            kk[k] = inK[a];
         }
     };
     auto store = [&](u64 (&p)[TPT], u32 (&kk)[TPT], u32 tb) {
@@ -324,6 +331,81 @@ __global__ void __launch_bounds__(THREADS) k_pass2_pieces(const u64 *__restrict_
     }
 }
 
+
+// ---- word planes for the count-free payload array -------------------------------------------
+// The pass-2 digit lies in the low 32-bit word of a payload, so the histogram needs 4 of the 8 bytes.  BLOCKED: inside every
+// 256-byte block of 32 slots the 32 low words come first, then the 32 high words: slot a -> word w(a) = ((a >> 5) << 6) | (a & 31),
+// high word at w(a) + 32; the histogram reads every other 128-byte line.  Else a separate, dense array of low words.
+// 16-byte loads: 8 lanes cover a line, a wavefront 256 tuples per load, eight loads in flight (clamped to the piece's last block).
+template <int THREADS, bool BLOCKED>
+__global__ void __launch_bounds__(THREADS) k_hist_planes(const u32 *__restrict__ W, u32 cap, u32 mean, u32 spread, int shift,
+                                                         u32 *__restrict__ hist)
+{
+    __shared__ u32 cnt[256];
+    __shared__ u32 pre[PC_PER + 1];
+    const u32 unit = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 256) cnt[tid] = 0;
+    if (tid == 0) { u32 s = 0; for (int j = 0; j < PC_PER; j++) { pre[j] = s; s += piece_len(unit * PC_PER + j, mean, spread); } pre[PC_PER] = s; }
+    __syncthreads();
+    const u64 ubase = (u64)unit * PC_PER * cap;
+    const u32 sub = lane >> 3, off = (lane & 7) * 4;
+    for (u32 j = wave; j < PC_PER; j += THREADS / 64) {
+        const u32 *p = W + (ubase + (u64)j * cap) * (BLOCKED ? 2 : 1);
+        const u32 len = pre[j + 1] - pre[j], nblk = (len + 31) / 32;
+        for (u32 b0 = 0; b0 < nblk; b0 += 64) {
+            uint4 v[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                u32 b = b0 + k * 8 + sub; b = b < nblk ? b : nblk - 1;
+                v[k] = *reinterpret_cast<const uint4 *>(p + (u64)b * (BLOCKED ? 64 : 32) + off);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const u32 t = (b0 + k * 8 + sub) * 32 + off;                 // (beyond the clamp: t >= len)
+                if (t + 0 < len) atomicAdd(&cnt[(v[k].x >> shift) & 255u], 1u);
+                if (t + 1 < len) atomicAdd(&cnt[(v[k].y >> shift) & 255u], 1u);
+                if (t + 2 < len) atomicAdd(&cnt[(v[k].z >> shift) & 255u], 1u);
+                if (t + 3 < len) atomicAdd(&cnt[(v[k].w >> shift) & 255u], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < 256) hist[(u64)unit * 256 + tid] = cnt[tid];
+}
+
+// pass 1's write pattern (k_stream_lines, narrow, 32-tuple chunks, nontemporal).  LAYOUT 0: 256 + 128 bytes into two arrays
+// (today's), 1: the same bytes with the payload words in blocked planes, 2: 128 + 128 + 128 bytes into three arrays.
+template <int THREADS, int TPT, int LAYOUT>
+__global__ void __launch_bounds__(THREADS) k_stream_planes(const Tup *__restrict__ in, u64 *__restrict__ outP, u32 *__restrict__ outK,
+                                                           u64 plane, u64 n, u64 L)
+{
+    constexpr u64 TILE = (u64)THREADS * TPT, GR = 32;
+    const u32 u = blockIdx.x, tid = threadIdx.x, G = gridDim.x;
+    const u64 beg = (u64)u * L, end = beg + L < n ? beg + L : n;
+    const u64 cpud = (L / GR + 255) / 256, cpd = (u64)G * cpud;
+    u32 *W = reinterpret_cast<u32 *>(outP);
+    u64 j = 0;
+    for (u64 tb = beg; tb < end; tb += TILE, j++) {
+        Tup t[TPT];
+#pragma unroll
+        for (int k = 0; k < TPT; k++) { const u64 i = tb + (u64)k * THREADS + tid; if (i < end) t[k] = in[i]; }
+#pragma unroll
+        for (int k = 0; k < TPT; k++) {
+            const u32 it = k * THREADS + tid;
+            if (tb + it < end) {
+                const u64 cg = j * (TILE / GR) + it / GR;
+                const u64 o = ((cg & 255) * cpd + (u64)u * cpud + (cg >> 8)) * GR + it % GR;
+                const u64 v = t[k].payload;
+                if (LAYOUT == 0) __builtin_nontemporal_store(v, &outP[o]);
+                else {
+                    const u64 w = LAYOUT == 1 ? (((o >> 5) << 6) | (o & 31)) : o, hi = LAYOUT == 1 ? 32 : plane;
+                    __builtin_nontemporal_store((u32)v, &W[w]); __builtin_nontemporal_store((u32)(v >> 32), &W[w + hi]);
+                }
+                __builtin_nontemporal_store((u32)t[k].key, &outK[o]);
+            }
+        }
+    }
+}
 
 template <typename F> static double time_ms(F f, int reps = 5)
 {
@@ -365,14 +447,54 @@ static int run_pieces()
         rep("(a) 8 B hist, one run per unit, T=512", time_ms([&] { hipLaunchKernelGGL((k_hist_pieces<512, false>), dim3(units2), dim3(512), 0, 0, inP, cap, mean, spread, 8, hist); }));
         rep("(a) 8 B hist, 64 pieces at stride cap, wavefront per piece, T=512", time_ms([&] { hipLaunchKernelGGL((k_hist_pieces<512, true>), dim3(units2), dim3(512), 0, 0, inP, cap, mean, spread, 8, hist); }));
         rep("(a) 8 B hist, 64 pieces at stride cap, wavefront per piece, T=1024", time_ms([&] { hipLaunchKernelGGL((k_hist_pieces<1024, true>), dim3(units2), dim3(1024), 0, 0, inP, cap, mean, spread, 8, hist); }));
-        rep("(b) 12 + 12 B, one run per unit, T=1024 lds=150K", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, false>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud); }));
-        rep("(b) 12 + 12 B, 64 pieces at stride cap, dense tiles, T=1024 lds=150K", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, true>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud); }));
+        rep("(b) 12 + 12 B, one run per unit, T=1024 lds=150K", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, false>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud, (u64)0); }));
+        rep("(b) 12 + 12 B, 64 pieces at stride cap, dense tiles, T=1024 lds=150K", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, true>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud, (u64)0); }));
+    }
+    return 0;
+}
+
+// copybench planes: the same geometry as `pieces`; what the word-plane layouts of the count-free payload array cost and save.
+// Each line stands against the `pieces` figure it would replace (printed first in every round).
+static int run_planes()
+{
+    const u32 nb1 = 256, U = 1024, mean = 3824, spread = 257, cap = 4448, units2 = nb1 * U / PC_PER;
+    const u64 regions = (u64)nb1 * U, slots = regions * cap;
+    u64 ntup = 0; u32 lmax = 0;
+    for (u32 r = 0; r < regions; r++) { const u32 l = piece_len(r, mean, spread); ntup += l; lmax = l > lmax ? l : lmax; }
+    if (lmax > cap || cap % 32) { fprintf(stderr, "piece above cap\n"); return 1; }
+    const u32 cpud = ((u32)PC_PER * lmax / 32 + 1 + 255) / 256;
+    const u64 out_slots = 256ull * units2 * cpud * 32;
+    const int G1 = 1024;                                                          // pass 1: 1024 units, 256 streams each
+    const u64 n1 = ntup - (32ull << 20), L1 = ((n1 + G1 - 1) / G1 + 4095) / 4096 * 4096;
+    const u64 top1 = 256ull * G1 * ((L1 / 32 + 255) / 256) * 32;                  // one past the largest index pass 1's pattern writes
+    if (top1 > out_slots) { fprintf(stderr, "stream test would overrun: %llu > %llu\n", (unsigned long long)top1, (unsigned long long)out_slots); return 1; }
+    u64 *inP, *outP; u32 *inK, *outK, *hist; Tup *aos;
+    CK(hipMalloc(&inP, slots * 8)); CK(hipMalloc(&inK, slots * 4)); CK(hipMalloc(&outP, out_slots * 8)); CK(hipMalloc(&outK, out_slots * 4));
+    CK(hipMalloc(&hist, (size_t)units2 * 256 * 4)); CK(hipMalloc(&aos, ntup * 16));
+    hipLaunchKernelGGL(k_fill_hash, dim3(4096), dim3(256), 0, 0, inP, slots); CK(hipDeviceSynchronize()); CK(hipMemset(inK, 1, slots * 4)); CK(hipMemset(aos, 1, ntup * 16));
+    printf("# %llu tuples in %llu pieces (mean %u, max %u, cap %u); times scaled to 10^9 tuples\n", (unsigned long long)ntup,
+           (unsigned long long)regions, mean, lmax, cap);
+    auto rep = [&](const char *name, double ms, u64 n) { printf("%-78s %8.3f ms\n", name, ms * 1e9 / (double)n); fflush(stdout); };
+    const u32 *W = reinterpret_cast<const u32 *>(inP);
+    for (int round = 0; round < 3; round++) {
+        rep("pieces (a) 8 B hist, wavefront per piece, T=512 (today)", time_ms([&] { hipLaunchKernelGGL((k_hist_pieces<512, true>), dim3(units2), dim3(512), 0, 0, inP, cap, mean, spread, 8, hist); }), ntup);
+        rep("(a) 4 B hist, blocked planes (every other line), 16 B loads, T=512", time_ms([&] { hipLaunchKernelGGL((k_hist_planes<512, true>), dim3(units2), dim3(512), 0, 0, W, cap, mean, spread, 8, hist); }), ntup);
+        rep("(a) 4 B hist, blocked planes (every other line), 16 B loads, T=1024", time_ms([&] { hipLaunchKernelGGL((k_hist_planes<1024, true>), dim3(units2), dim3(1024), 0, 0, W, cap, mean, spread, 8, hist); }), ntup);
+        rep("(b) 4 B hist, separate low-word array (dense), 16 B loads, T=512", time_ms([&] { hipLaunchKernelGGL((k_hist_planes<512, false>), dim3(units2), dim3(512), 0, 0, W, cap, mean, spread, 8, hist); }), ntup);
+        rep("(b) 4 B hist, separate low-word array (dense), 16 B loads, T=1024", time_ms([&] { hipLaunchKernelGGL((k_hist_planes<1024, false>), dim3(units2), dim3(1024), 0, 0, W, cap, mean, spread, 8, hist); }), ntup);
+        rep("pass-1 writes, 256 streams/WG of 256 + 128 B, T=1024 lds=150K (today)", time_ms([&] { hipLaunchKernelGGL((k_stream_planes<1024, 4, 0>), dim3(G1), dim3(1024), 150 << 10, 0, aos, outP, outK, (u64)0, n1, L1); }), n1);
+        rep("    the same bytes, payload words in blocked planes", time_ms([&] { hipLaunchKernelGGL((k_stream_planes<1024, 4, 1>), dim3(G1), dim3(1024), 150 << 10, 0, aos, outP, outK, (u64)0, n1, L1); }), n1);
+        rep("(c) pass-1 writes, 256 streams/WG of 128 + 128 + 128 B into three arrays", time_ms([&] { hipLaunchKernelGGL((k_stream_planes<1024, 4, 2>), dim3(G1), dim3(1024), 150 << 10, 0, aos, outP, outK, out_slots, n1, L1); }), n1);
+        rep("pieces (b) 12 + 12 B, 64 pieces at stride cap, dense tiles, T=1024 lds=150K (today)", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, true>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud, (u64)0); }), ntup);
+        rep("(d) the same, payloads read through the blocked index", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, true, 1>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud, (u64)0); }), ntup);
+        rep("(d) the same, payloads read from two separate word arrays", time_ms([&] { hipLaunchKernelGGL((k_pass2_pieces<1024, 4, true, 2>), dim3(units2), dim3(1024), 150 << 10, 0, inP, inK, outP, outK, cap, mean, spread, cpud, slots); }), ntup);
     }
     return 0;
 }
 
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "planes")) return run_planes();
     if (argc > 1 && !strcmp(argv[1], "pieces")) return run_pieces();
     const double gib = argc > 1 ? atof(argv[1]) : 14.9;
     const u64 n = (u64)(gib * (1ull << 30) / 16) / 8192 * 8192;

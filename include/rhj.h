@@ -108,8 +108,8 @@ int  rhj_set_stream(rhj_ctx *ctx, void *hip_stream);
 int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
 /* tuning / test knobs; results never depend on them.  "join.big_tables": -1 (default) choose the bucket-join kernel by
  * the average build partition, 0 always the one-table kernel, 1 always an oversized-partition kernel;
- * "join.big_kernel": -1 automatic, 1 the chunked 16-byte-entry kernel, 2 / 3 the compact-table kernel at full / half size
- * where the plan allows, 4 / 5 the same with 20 instead of 16 probe slots per thread (narrow partitions; else 2 / 3), 6 / 7 the 12288-entry geometry and its half-size form (6144 entries), 8 the full-size table with half the buckets (17920 entries in 8192 buckets instead of 16352 in 16384), 9 the 6144-entry geometry skipping the slot rows a partition leaves empty, 10 the same with 13-bit arrival indices (keys of up to 51 bits: what plans of 13-15 radix bits take by themselves for partitions of 2-5 K tuples), 11 a 4096-entry table with 12-bit arrival indices (plans of 12 bits);
+ * "join.big_kernel": -1 automatic, else the bucket-join kernel to use where the plan allows it (the numbers of "last.join_kernel";
+ * 4 / 5 over 16-byte partitions run as 8 / 3);
  * "partition.narrow": -1 automatic, 0 never, 1 / 2: inside a join with a two-pass plan, partitions (1) and the
  * intermediate of the two passes (2; the only level of 17-18-bit plans) are stored as {payload 8 B, rowID 4 B} while every
  * rowID is below 2^32 (a larger one is detected on the device -- by the first histogram kernel -- and THAT join repeats itself
@@ -128,8 +128,13 @@ int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
  * without duplicates answers every probe tuple with one match); 0: the first relation wins such a tie.  Same pairs either way. */
 int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
 /* what the last join did: "last.narrow" (0 / 1 / 2, see above), "last.countfree_R" / "last.countfree_S" (pass 1 of that side:
- * 0 exact cursors, 1 count-free, 2 count-free tried and repeated with exact cursors), "last.join_kernel" (0 one-table, 1 chunked, 2 / 3
- * compact table full / half size, 4 / 5 the same with 20 probe slots per thread, 6 / 7 the 12288- / 6144-entry geometries, 8 / 9 / 10 / 11 see "join.big_kernel", -1 none: direct small join or empty input), "last.pipelined" (the number
+ * 0 exact cursors, 1 count-free, 2 count-free tried and repeated with exact cursors), "last.join_kernel" (-1 none: direct small join or empty
+ * input; 0 the one-table kernel; 1 the chunked 16-byte-entry kernel; 2 ... 11 the compact-table kernel, one number per geometry:
+ * 2 / 3 full / half size, 4 / 5 the same with 20 instead of 16 probe slots per thread (narrow partitions only), 6 / 7 the middle
+ * geometry and its half-size form, 8 the full-size table with half the buckets, 9 the half-size middle geometry skipping the slot
+ * rows a partition leaves empty, 10 the same with 13-bit arrival indices (keys of up to 51 bits: what plans of 13-15 radix bits take
+ * by themselves for partitions of 2-5 K tuples), 11 a smaller table with 12-bit arrival indices (plans of 12 bits); the sizes are
+ * the rows of JOIN_GEOM in radixhashjoin_amd/csrc/rhj_internal.h), "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home; 0: the plain path),
  * "last.max_part_R" / "last.max_part_S" (tuples in the largest partition of each side the last partitioned join saw; 0 for
  * an unpartitioned one), "partition.mix" (0 / 1: what joins on this context do) */

@@ -477,7 +477,7 @@ int ilog2_ceil(u64 x)
 // Reference: one fixed 8-bit pass (Result.cpp:5,91).  Here: the fewest radix bits such that the
 // average build-side partition fills at most 15/16 of one LDS hash table (BJ_CHUNK), in <= 2 passes.
 // device_resident: the inputs are in HBM already (rhj_join_dev); else the host-pointer call, whose small path is one launch
-// largest average partition (tuples, either side) the 6144-entry kernel with 13-bit arrival indices is chosen for
+// largest average partition (tuples, either side) JK_CT_G13 is chosen for
 u64 g13_upto()
 {
     // 15/16 of its table: the row guards stop paying beyond CT_GUARDED_UPTO, but half as many partitions still do ([measured, wall
@@ -488,7 +488,7 @@ u64 g13_upto()
 
 bool default_join_kernels(const rhj_ctx *ctx) { return ctx->opt_big_kernel < 0 && ctx->opt_big_tables < 0; }
 
-// ct13_ok: the join may pick the 6144-entry compact-table kernel for plans of 13-15 bits (default kernel choice, not the
+// ct13_ok: the join may pick the JK_CT_G13 compact-table kernel for plans of 13-15 bits (default kernel choice, not the
 // multi-GPU receiver): the plan then leaves partitions of up to CT_GUARDED_UPTO tuples
 int resolve_plan(u64 nR, u64 nS, const rhj_opts *in, rhj_opts *out, bool device_resident = false, bool ct13_ok = true)
 {
@@ -510,7 +510,7 @@ int resolve_plan(u64 nR, u64 nS, const rhj_opts *in, rhj_opts *out, bool device_
             if (nb > (u64)BJ_CHUNK && !direct) bits = ilog2_ceil((nb + fit - 1) / fit);
             if (bits == 0) o.passes = 0;
             else if (bits <= 9) { o.passes = 1; o.bits1 = bits; }
-            // Up to two and a half 8448-tuple chunks per partition after ONE 9-bit pass (three launches; the chunked
+            // Up to two and a half JK_BKT_BIG chunks per partition after ONE 9-bit pass (three launches; the chunked
             // 16-byte-entry kernel joins): a two-pass plan costs ~27 launches, 0.2 ms of fixed latency that such a join does
             // not have to spare.  [measured, round 4, wall ms one pass / two] 8.5M 0.43 / 0.50 . 10M 0.51 / 0.54 . 12M 0.61 / 0.59
             else if (nb <= (u64)512 * 5 * join_table_tuples(JK_BKT_BIG) * 15 / 32) { o.passes = 1; o.bits1 = 9; }
@@ -518,7 +518,7 @@ int resolve_plan(u64 nR, u64 nS, const rhj_opts *in, rhj_opts *out, bool device_
                 // Two passes.  Up to 16 bits both histograms come from ONE read of the input (k_hist2d_units); a 17- or
                 // 18-bit plan re-reads each relation once more just to count (10.7 instead of 5.4 ms per 10^9-tuple join).
                 // Partitions that 16 bits leave larger than one 16-byte-entry table go to the compact-table bucket join
-                // (one 17920-entry table, both sides read once), which costs less than that extra read: measured at
+                // (one JK_CT_13 table, both sides read once), which costs less than that extra read: measured at
                 // 10^9 x 10^9, 8+8 bits 43 ms against 49 ms for 9+9.  Beyond 1.1 * 10^9 tuples per side a 16-bit partition
                 // no longer fits ONE compact table (chunks: probe payloads streamed again per chunk) and 9+9 bits (the
                 // widest line-aligned write-combining scatter) takes over: 2.2 * 10^9 x 2.2 * 10^9, 121.6 against 125.3 ms.
@@ -526,8 +526,8 @@ int resolve_plan(u64 nR, u64 nS, const rhj_opts *in, rhj_opts *out, bool device_
                 // 20 slots per thread), 18 (9+9) beyond; both run in the narrow format with 16-tuple carry lines in their 9-bit passes (k_scatter_wcn
                 // <GR = 16>) and a second, 8 B/tuple histogram read of the narrow intermediate.
                 if (bits > 16) bits = nb <= (u64)65536 * 16800 ? 16 : nb <= (u64)131072 * 16800 ? 17 : 18;
-                // One bit fewer where that leaves partitions for the 6144-entry compact-table kernel (k_join_ct<.., KB = 13>, plans
-                // of 13-15 bits, average partitions of up to 15/16 of its 6144 entries on both sides): half as many partitions,
+                // One bit fewer where that leaves partitions for the JK_CT_G13 compact-table kernel (k_join_ct<.., KB = 13>, plans
+                // of 13-15 bits, average partitions of up to 15/16 of its table on both sides): half as many partitions,
                 // tasks and histogram rows.  [measured, one box, wall ms, bits as above -> one fewer] 34M 1.538 -> 1.431 . 40M 1.722 ->
                 // 1.579 . 66M 2.814 -> 2.538 . 83M 3.397 -> 2.971 . 135M 5.692 -> 5.091 . 165M 6.729 -> 6.084
                 static const bool ct13_env = env_u64("RHJ_CT13", 1, 0, 1) != 0;
@@ -964,56 +964,50 @@ int partition_relation(rhj_ctx *ctx, const void *d_in, u64 n, int passes, int b1
 }
 
 // Which bucket-join kernel a partitioned join runs (JoinKernel).
-// Average build partition larger than one 4224-tuple table (an explicit plan with too few bits, or more than 2^30
-// tuples): the compact-table kernel when the plan removed enough payload bits for 48-bit keys, else 8448-tuple
+// Average build partition larger than one JK_BKT table (an explicit plan with too few bits, or more than 2^30
+// tuples): the compact-table kernel when the plan removed enough payload bits for 48-bit keys, else JK_BKT_BIG
 // chunks.  The compact-table kernel keeps a task's probe rowIDs in registers, so a task is at most that many tuples.
 // allow13: plans of 13-15 bits may take the compact-table kernel with 13-bit arrival indices (keys of up to 51 bits) for
 // average partitions of 2-5 K tuples (not the multi-GPU receiver, whose sender tags the one-table kernel resolves).
 int choose_join_kind(const rhj_ctx *ctx, u64 nR, u64 nS, u64 nparts, int radix_bits, bool narrow = false, bool allow13 = true)
 {
-    const u64 nbuild = nR < nS ? nR : nS;
+    const u64 nbuild = nR < nS ? nR : nS, nprobe = nR < nS ? nS : nR, ab = nbuild / nparts, ap = nprobe / nparts;   // (nparts >= 1: every caller)
+    // the average partition fits kind k's table AND its probe tasks (a partition cut into two tasks builds its table twice)
+    auto fits = [&](int k) { return ab <= (u64)join_table_tuples(k) * 15 / 16 && ap <= (u64)join_probe_split(k) * 15 / 16; };
     if (radix_bits < join_ct_min_radix_bits(JK_CT) && radix_bits >= join_ct_min_radix_bits(JK_CT_Q12) && allow13 &&
         (ctx->opt_big_kernel < 0 || ctx->opt_big_kernel == JK_CT_Q12) && (radix_bits == join_ct_min_radix_bits(JK_CT_Q12) || ctx->opt_big_kernel == JK_CT_Q12)) {
-        // plans of exactly 12 bits (and a forced kernel 11 from 12 bits on): the 4096-entry table with 12-bit arrival indices
+        // plans of exactly 12 bits (and a forced kernel 11 from 12 bits on): JK_CT_Q12's table with 12-bit arrival indices
         static const bool on12 = env_u64("RHJ_CT13", 1, 0, 1) != 0;
-        const u64 np12 = nR < nS ? nS : nR, ab12 = nbuild / nparts, ap12 = np12 / nparts;
-        const bool fits12 = ab12 <= (u64)join_table_tuples(JK_CT_Q12) * 15 / 16 && ap12 <= (u64)join_probe_split(JK_CT_Q12) * 15 / 16;
         if ((ctx->opt_big_kernel == JK_CT_Q12 && ctx->opt_big_tables == 1) ||
-            (on12 && ctx->opt_big_tables < 0 && ab12 > (u64)CT_GUARDED_FROM && fits12))
+            (on12 && ctx->opt_big_tables < 0 && ab > (u64)CT_GUARDED_FROM && fits(JK_CT_Q12)))
             return JK_CT_Q12;
     }
     if (radix_bits < join_ct_min_radix_bits(JK_CT) && radix_bits >= join_ct_min_radix_bits(JK_CT_G13) && allow13 &&
         (ctx->opt_big_kernel < 0 || ctx->opt_big_kernel == JK_CT_G13)) {
         static const bool on = env_u64("RHJ_CT13", 1, 0, 1) != 0;              // tuning aid: 0 = the one-table kernel as before
-        const u64 nprobe13 = nR < nS ? nS : nR, ab13 = nbuild / nparts, ap13 = nprobe13 / nparts;
-        const bool fits13 = ab13 <= (u64)join_table_tuples(JK_CT_G13) * 15 / 16 && ap13 <= (u64)join_probe_split(JK_CT_G13) * 15 / 16 &&
-                            ab13 <= g13_upto() && ap13 <= g13_upto();
         if ((ctx->opt_big_kernel == JK_CT_G13 && ctx->opt_big_tables == 1) ||
-            (on && ctx->opt_big_tables < 0 && ab13 > (u64)CT_GUARDED_FROM && fits13))
+            (on && ctx->opt_big_tables < 0 && ab > (u64)CT_GUARDED_FROM && fits(JK_CT_G13) && ab <= g13_upto() && ap <= g13_upto()))
             return JK_CT_G13;
     }
-    // ... and from half a table on when the plan allows the compact-table kernel: its 6144-entry geometry with row guards
+    // ... and from half a table on when the plan allows the compact-table kernel: its JK_CT_HALF_MID_G geometry (row guards)
     // handles a tuple in two thirds of the one-table kernel's time ([measured] 1.5 - 2.7 * 10^8 tuples under 16 bits)
     const bool ct_ok = radix_bits >= join_ct_min_radix_bits(JK_CT) && ctx->opt_big_kernel != JK_BKT_BIG;
     const u64 big_from = ct_ok ? (u64)CT_GUARDED_FROM : (u64)BJ_CHUNK;
-    if (!(ctx->opt_big_tables == 1 || (ctx->opt_big_tables < 0 && nbuild / nparts > big_from))) return JK_BKT;
+    if (!(ctx->opt_big_tables == 1 || (ctx->opt_big_tables < 0 && ab > big_from))) return JK_BKT;
     if (radix_bits < join_ct_min_radix_bits(JK_CT) || ctx->opt_big_kernel == JK_BKT_BIG) return JK_BKT_BIG;
     if (jk_is_ct(ctx->opt_big_kernel) && !jk_ct_narrow_only(ctx->opt_big_kernel)) return ctx->opt_big_kernel;
     if (ctx->opt_big_kernel == JK_CT_WIDE) return narrow ? JK_CT_WIDE : JK_CT_13;
     if (ctx->opt_big_kernel == JK_CT_HALF_WIDE) return narrow ? JK_CT_HALF_WIDE : JK_CT_HALF;
-    // the compact-table kernel at half size (two workgroups per CU) while the average partition fits its table
-    // AND its 8192-tuple probe tasks (a partition cut into two tasks builds its table twice)
-    const u64 nprobe = nR < nS ? nS : nR, ab = nbuild / nparts, ap = nprobe / nparts;
-    auto fits = [&](int k) { return ab <= (u64)join_table_tuples(k) * 15 / 16 && ap <= (u64)join_probe_split(k) * 15 / 16; };
-    // 12 + 12 slot rows, 6144 entries: partitions of up to 5.76 K tuples; with row guards while two or more rows stay empty
+    // the compact-table kernel at half size (two workgroups per CU) while the average partition fits
+    // JK_CT_HALF_MID: partitions of up to 5.76 K tuples; with row guards while two or more rows stay empty
     if (fits(JK_CT_HALF_MID)) return ab <= (u64)CT_GUARDED_UPTO && ap <= (u64)CT_GUARDED_UPTO ? JK_CT_HALF_MID_G : JK_CT_HALF_MID;
     if (fits(JK_CT_HALF)) return JK_CT_HALF;
     // 20 probe slots per thread (narrow partitions only) before a partition's probe side is cut into two tasks that build the
     // table twice: [measured] 2.2 * 10^9 x 2.2 * 10^9, join kernel 32.5 ms with two 16-slot tasks per partition
     if (narrow && fits(JK_CT_HALF_WIDE)) return JK_CT_HALF_WIDE;
     if (fits(JK_CT_MID)) return JK_CT_MID;           // 12 + 12 slot rows instead of 18 + 16 for partitions of up to 11.5 K tuples
-    if (fits(JK_CT)) return JK_CT;                   // 16352 entries in 16384 buckets (up to 1.005 * 10^9 tuples under 16 bits)
-    if (fits(JK_CT_13)) return JK_CT_13;             // 17920 entries in 8192 buckets
+    if (fits(JK_CT)) return JK_CT;                   // (up to 1.005 * 10^9 tuples under 16 bits)
+    if (fits(JK_CT_13)) return JK_CT_13;             // the larger table in half the buckets
     if (narrow && fits(JK_CT_WIDE)) return JK_CT_WIDE;
     return JK_CT_13;
 }

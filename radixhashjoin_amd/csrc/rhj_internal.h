@@ -26,7 +26,7 @@ constexpr int BJ_TILE = BJ_THREADS * BJ_EPT;      // 4096
 constexpr int BJ_FIT = BJ_CHUNK * 15 / 16;        // plan: average build partition <= 3960 tuples
 constexpr u32 BJ_MAX_PROBE_SPLIT = 1u << 24;      // probe tuples per join task at most (a caller's larger probe_split is clamped: same pairs, more tasks)
 // under a plan of >= 16 bits, average build partitions of CT_GUARDED_FROM ... CT_GUARDED_UPTO tuples go to the compact-table
-// kernel's 6144-entry geometry with row guards (k_join_ct<.., GUARD>): 4 ... 10 of its 12 slot rows in use
+// kernel's JK_CT_HALF_MID_G geometry (row guards, k_join_ct<.., GUARD>): 4 ... 10 of its 12 slot rows in use
 constexpr int CT_GUARDED_FROM = 2048, CT_GUARDED_UPTO = 5120;
 // small joins run unpartitioned in one launch (k_join_bkt DIRECT): every 4096-tuple probe tile re-builds the table chunks
 constexpr u64 DIRECT_MAX_BUILD = 12ull * BJ_CHUNK; // build side of at most 12 table chunks ...
@@ -63,6 +63,11 @@ struct PassGeom {
 // rhj_bucket_join) keep raw bits: their bucket order is documented.  MIX_DIGIT: digit of the mixed value, tuple written
 // as it came (rhj_shard_split16: the multi-GPU owner split of 16-byte tuples, joined by rhj_join_dev on the receiver).
 constexpr int MIX_NONE = 0, MIX_STORE = 1, MIX_DIGIT = 2;
+// multi-GPU: a receiver tells SEG_MAX segments (= senders = ranks) apart; the sender number travels in the low TAG_BITS payload bits
+constexpr int SEG_MAX = 16;
+constexpr u32 TAG_BITS = 4, TAG_MAX = 1u << TAG_BITS;   // sender tags in the low payload bits: <= 16 ranks (== SEG_MAX)
+constexpr int seg_max() { return SEG_MAX; }
+constexpr int tag_bits() { return (int)TAG_BITS; }
 
 // launchers (all asynchronous on `st`)
 void launch_init_single_segment(hipStream_t st, u64 n, u64 L, u64 *d_seg_start, u32 *d_unit_start);
@@ -113,7 +118,7 @@ struct BatchJoinDesc {
     u64 host_cap;
 };
 void launch_join_batch(hipStream_t st, const BatchJoinDesc *d_batch, u32 njoins, u32 max_blocks);
-u32 join_direct_tile();
+constexpr u32 join_direct_tile() { return (u32)BJ_TILE; }    // probe tuples per workgroup of a direct join
 void launch_checksum(hipStream_t st, const void *d_pairs, u64 n, u64 *d_sum);
 void launch_generate(hipStream_t st, int kind, void *d_out, u64 n, u64 row0, u64 D, u64 seed, double theta);
 void launch_expected_pkfk(hipStream_t st, const void *d_S, u64 n, u64 *d_sum);
@@ -139,20 +144,88 @@ u32 *fuse_join_ticket(void *d_ctl);
 // sniff: sample the join values for duplicates (DupSniff; the counters live in the control block)
 void launch_fused_pass(hipStream_t st, const PassPairHost &h, int bits, int phase, int parity, void *d_ctl, u32 probe_split, u32 max_tasks,
                        u32 table_tuples, JoinTask *d_tasks, u64 *d_counters, u64 *host_pub, bool sniff = false);
-constexpr int PASS_PAIR_MAX_BITS = 9;            // the write-combining scatter's range
-bool fused_two_pass_ok(int b1, int b2);
-// bucket-join kernels: JK_BKT partitions that fit one 4224-tuple table (two workgroups per CU); JK_BKT_BIG 8448-tuple
-// chunks, probe side re-read per chunk (any radix plan); JK_CT compact 8-byte entries, both sides read once
-// (plans that remove >= 16 payload bits)
+constexpr int WC_MAX_BITS = 9;                   // the write-combining scatters' range (k_scatter_wc*)
+constexpr int PASS_PAIR_MAX_BITS = WC_MAX_BITS;
+constexpr bool fused_two_pass_ok(int b1, int b2) { return b1 >= 1 && b2 >= 1 && b1 <= WC_MAX_BITS && b2 <= WC_MAX_BITS && b1 + b2 <= 16; }
+
+// ---- the bucket-join kernels: one row of JOIN_GEOM per JoinKernel ------------------------------------------------------------
+// k_join_bkt (JK_BKT, JK_BKT_BIG): 16-byte table entries, any radix plan.  k_join_ct (JK_CT ... JK_LAST): compact 8-byte entries
+// {key | arrival index of the build tuple}, both sides read once, for plans that remove at least key_index_bits payload bits.
+// The launchers, the LDS attributes and the host plan all read this table; nothing else states a geometry.
 enum JoinKernel { JK_BKT = 0, JK_BKT_BIG = 1, JK_CT = 2, JK_CT_HALF = 3, JK_CT_WIDE = 4, JK_CT_HALF_WIDE = 5, JK_CT_MID = 6, JK_CT_HALF_MID = 7, JK_CT_13 = 8,
                   JK_CT_HALF_MID_G = 9, JK_CT_G13 = 10, JK_CT_Q12 = 11, JK_LAST = JK_CT_Q12 };
-inline bool jk_is_ct(int k) { return k >= JK_CT && k <= JK_LAST; }                           // a compact-table geometry (48-bit keys: needs >= 16 radix bits)
-inline bool jk_ct_narrow_only(int k) { return k == JK_CT_WIDE || k == JK_CT_HALF_WIDE; }    // 20 probe slots: {payload, rowID} partitions only
-// _WIDE: 20 probe slots per thread (narrow format only); _MID: a 12288-entry table and 12 slots per thread (partitions of 8.4 - 11.5 K);
-// _HALF_MID: the same at half size, 6144 entries, 512 threads, two workgroups per CU (partitions of 4.2 - 5.8 K)
-u32 join_probe_split(int kind);      // probe tuples per task the kernel holds at most (0: no limit of its own)
-u32 join_table_tuples(int kind);     // build tuples per LDS table
-int join_ct_min_radix_bits(int kind = JK_CT);   // 16: keys of 48 bits beside a 16-bit arrival index; JK_CT_G13: 13 (51 + 13 bits); JK_CT_Q12: 12
+struct JoinGeom {
+    int threads, chunk, bucket_bits, ept;   // workgroup size; build tuples per LDS table; log2 of its hash buckets; probe slots per thread
+    bool guard;                             // k_join_ct GUARD: skip the slot rows a partition leaves empty
+    int key_index_bits;                     // k_join_ct KB: bits of the arrival index in a table entry; 0: a k_join_bkt geometry
+    bool narrow_only;                       // instantiated for {payload, rowID} partitions only
+};
+constexpr int CT_PT = 4;                    // k_join_ct: probe slots per tile of the register ring
+constexpr JoinGeom JOIN_GEOM[JK_LAST + 1] = {
+    // JK_BKT: partitions that fit one table; two workgroups per CU
+    {BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, false, 0, false},
+    // JK_BKT_BIG: one workgroup per CU (152 KiB LDS); the build side in chunks, the probe side re-read per chunk
+    {1024, 8448, 12, 4, false, 0, false},
+    // JK_CT: the full-size compact table (see k_join_ct)
+    {1024, 16352, 14, 16, false, 16, false},
+    // JK_CT_HALF: the same kernel at half size, for partitions of up to 8960 build tuples (3 ... 5.5 * 10^8 tuples under a 16-bit plan):
+    // 512 threads, 80 KiB LDS -> TWO workgroups per CU, which overlap each other's memory and LDS phases; the per-thread
+    // register picture (18 build slots, 16 probe slots, 128 VGPRs) is unchanged.  The kernel's cost per task does not shrink
+    // with the partition (every slot row is walked), so the full-size geometry is 2-3x too expensive there (measured at
+    // 3 * 10^8: 8.9 ms against 5.1 ms for the chunked 16-byte-entry kernel).
+    // (8960 entries in 4096 buckets until round 3: the probe tasks of 8192 tuples bound the partition size anyway, and twice
+    // the buckets are worth more than the last 800 entries)
+    {512, 8160, 13, 16, false, 16, false},
+    // JK_CT_WIDE, JK_CT_HALF_WIDE: ... and with 20 probe slots per thread instead of 16 (narrow format only; 12 spilled VGPRs):
+    // partitions whose probe side is just beyond one 16-slot task (2.2 * 10^9 tuples under 17 or 18 bits: 16.8 K / 8.4 K per
+    // partition) would otherwise be cut into two tasks that both build the whole table.  Full size: the table of JK_CT_13.
+    {1024, 17920, 13, 20, false, 16, true},
+    {512, 8960, 12, 20, false, 16, true},                     // the 20-slot form keeps the larger table
+    // JK_CT_MID: ... and a middle geometry: 12288 entries, 12 build and 12 probe slots per thread (1024 threads, one workgroup per CU).  The
+    // kernel's cost per task follows its slot rows, not the partition: partitions of 8.4 - 11.5 K tuples (5.5 - 7.5 * 10^8 tuples under
+    // 16 bits, 1.1 - 1.5 * 10^9 under 17) paid for 18 + 16 rows in the full-size geometry ([measured] join kernel 8.5 -> 6.6 ms at
+    // 6 * 10^8, 17.6 -> 14.1 at 1.5 * 10^9; 16 + 16 rows for the 15.3 K-tuple partitions of 10^9 tuples: 10.09 -> 10.02, not kept).
+    {1024, 12288, 14, 12, false, 16, false},
+    // JK_CT_HALF_MID: ... and at half size (512 threads, two workgroups per CU): 4.2 - 5.8 K-tuple partitions
+    {512, 6144, 13, 12, false, 16, false},
+    // JK_CT_13 (the full-size geometry of rounds 2 and 3 until the bucket count was doubled): 17920 entries, 8192 buckets.  For
+    // partitions of 15.3 - 16.8 K build tuples (1.005 - 1.1 * 10^9 tuples under 16 bits), which the 16352-entry table would
+    // build in two chunks; the 20-slot kernel (probe side beyond 16 K) keeps this table too.
+    {1024, 17920, 13, 16, false, 16, false},
+    // JK_CT_HALF_MID_G: the 6144-entry geometry with row guards, for average build partitions of CT_GUARDED_FROM ... CT_GUARDED_UPTO
+    {512, 6144, 13, 12, true, 16, false},
+    // JK_CT_G13: the 6144-entry geometry with row guards and 13-bit arrival indices: keys of up to 51 bits, i.e. plans of 13-15
+    // radix bits (1.6 * 10^7 ... 1.3 * 10^8 tuples per side), whose 2-4 K-tuple partitions the one-table kernel served until round 4
+    {512, 6144, 13, 12, true, 13, false},
+    // JK_CT_Q12: a 4096-entry table with 12-bit arrival indices (keys of up to 52 bits) in 4096 buckets, 8 + 8 slot rows per thread, row
+    // guards, 41 KiB of LDS: plans of exactly 12 bits (8.4 * 10^6 ... 1.6 * 10^7 tuples per side, partitions of 2-3.8 K tuples)
+    {512, 4096, 12, 8, true, 12, false},
+};
+constexpr bool jk_is_ct(int k) { return k >= JK_CT && k <= JK_LAST; }                         // a compact-table geometry
+constexpr const JoinGeom &join_geom(int kind) { return JOIN_GEOM[kind >= 0 && kind <= JK_LAST ? kind : JK_BKT]; }
+constexpr bool jk_ct_narrow_only(int k) { return join_geom(k).narrow_only; }
+// probe tuples per task the kernel holds at most: a compact-table task keeps its probe rowIDs in registers (0: no limit of its own)
+constexpr u32 join_probe_split(int kind) { return jk_is_ct(kind) ? (u32)(join_geom(kind).threads * join_geom(kind).ept) : 0u; }
+constexpr u32 join_table_tuples(int kind) { return (u32)join_geom(kind).chunk; }             // build tuples per LDS table
+// radix bits a plan must remove for the key to fit beside the arrival index: 16 (48-bit keys); JK_CT_G13: 13; JK_CT_Q12: 12
+constexpr int join_ct_min_radix_bits(int kind = JK_CT) { return join_geom(jk_is_ct(kind) ? kind : JK_CT).key_index_bits; }
+// dynamic LDS of a launch.  k_join_bkt: keys + rowIDs, bucket offsets, scan scratch, sender bases.  k_join_ct: entries, packed
+// 16-bit bucket counts, scan scratch (>= 128 B behind the table: a compare round may read 15 entries past a bucket's end)
+constexpr size_t join_lds_bytes(const JoinGeom &g)
+{
+    return g.key_index_bits == 0
+               ? (size_t)g.chunk * 16 + ((size_t)(1 << g.bucket_bits) + 4) * 4 + 64 * 4 + (size_t)(g.threads / 64) * 4 + 16 + 2 * TAG_MAX * 8
+               : (size_t)g.chunk * 8 + ((size_t)(1 << g.bucket_bits) / 2 + 2 + 2 * (g.threads / 64)) * 4 + 24 + (g.threads < 1024 ? 64 : 0);
+}
+constexpr bool join_geom_ok(int k)
+{
+    const JoinGeom &g = JOIN_GEOM[k];
+    return join_lds_bytes(g) <= 160 * 1024 &&                                             // what one workgroup can have
+           (!jk_is_ct(k) ? g.key_index_bits == 0 && !g.guard && !g.narrow_only
+                         : g.chunk <= 1 << g.key_index_bits && g.ept % CT_PT == 0 && (1 << g.bucket_bits) % (2 * g.threads) == 0) &&
+           (k == 0 || join_geom_ok(k - 1));
+}
+static_assert(join_geom_ok(JK_LAST), "a JOIN_GEOM row breaks what its kernel needs");
 // in_narrow: d_in is a payload array (u64).  key_base / d_wide (16-byte input): d_wide (may be null) is OR-ed with 1 when some
 // rowID - key_base does not fit 32 bits.  d_unit_rng (may be null): explicit pass-1 units (launch_seg_units).
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,
@@ -160,8 +233,6 @@ void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n
                          const u64 *d_unit_rng, int mix = 0, const DupSniff &sniff = DupSniff());
 void launch_seg_units(hipStream_t st, u32 nseg, const u64 *seg_off, const u64 *seg_L, u32 units_per_seg, u64 *d_unit_rng,
                       u64 *d_seg_start, u32 *d_unit_start);
-int seg_max();                                             // segments (= ranks) a receiver can tell apart: 16
-int tag_bits();                                            // low payload bits that carry the sender number at the receiver
 void launch_make_group_ranges(hipStream_t st, const u64 *d_unit_base1, u32 nb1, u32 units_per_group, u32 ngroups, u64 n,
                               u64 *d_rng, u32 *d_unit_start2);
 void launch_scatter_ranges(hipStream_t st, const void *d_in, void *d_out, u32 nunits, int shift, int bits,
@@ -173,8 +244,9 @@ constexpr int RHJ_RETRY_CF = 1001;                      // internal: ... or a co
 constexpr u64 NARROW_MIN_TUPLES = 1024;                 // 12 n + 256 <= 16 n
 constexpr u64 NARROW_AUTO_MIN_TUPLES = 8000000;         // automatic choice: larger side at least this ([measured] 4M: 0.45 ms
                                                         // either way; 16M ... 256M: 5-8 % faster narrow; 10^9: 19 %)
-bool narrow_pass_ok(int bits);                          // the 32-tuple-line geometry: <= 8 bits
-bool narrow_pass9_ok(int bits);                         // ... or the 16-tuple-line geometry: <= 9 bits
+constexpr int WN_MAX_BITS = 8, WN9_MAX_BITS = 9;
+constexpr bool narrow_pass_ok(int bits) { return bits >= 1 && bits <= WN_MAX_BITS; }     // the 32-tuple-line geometry
+constexpr bool narrow_pass9_ok(int bits) { return bits >= 1 && bits <= WN9_MAX_BITS; }   // ... or the 16-tuple-line geometry
 void launch_hist_units_narrow(hipStream_t st, const void *d_inP, const PassGeom &g, const u64 *d_seg_start,
                               const u32 *d_unit_start, u32 *d_unit_hist);
 void launch_scatter_units_narrow_any(hipStream_t st, const void *d_in, const u32 *d_inK, void *d_outP, u32 *d_outK, const PassGeom &g,
@@ -194,8 +266,9 @@ void launch_scatter_ranges_narrow(hipStream_t st, const void *d_in, bool in_narr
 // offset 0 of the intermediate buffer, rowIDs (u32) at slots * 8.  d_flag: the join's skip word (bit 0: a wide rowID); `bit` is
 // OR-ed into it when a run does not fit its region.  Tables: cnt1 [U][nb1] u32, pre cf_pre_words(units2) u32, unit_tot [units2] u32.
 struct CfGeom { u32 U = 0, per = 0, ngroups = 0, cap = 0; u64 slots = 0; };
-u32 cf_per_max();                                       // pieces per pass-2 unit the kernels handle (64)
-size_t cf_pre_words(u32 units2);
+constexpr u32 CF_PER_MAX = 64, CF_PRE = CF_PER_MAX + 1;  // pieces per pass-2 unit the kernels handle; words of a unit's prefix table
+constexpr u32 cf_per_max() { return CF_PER_MAX; }
+constexpr size_t cf_pre_words(u32 units2) { return (size_t)units2 * CF_PRE; }
 void launch_cf_pass1(hipStream_t st, const void *d_in, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
                      const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff);
 void launch_cf_tables(hipStream_t st, const CfGeom &c, u32 nb1, const u32 *d_cnt1, u32 *d_pre, u32 *d_unit_tot, u64 *d_ps_1,

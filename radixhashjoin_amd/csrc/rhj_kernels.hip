@@ -11,8 +11,9 @@
 // k_join_bkt             JoinJob::run, join_buckets,  JobScheduler.cpp:186-192,
 //                        add_result / addAll          Result.cpp:43-76, 21-35      HBM read+write (16 B/tuple + 16 B/pair)
 //                        (partitions that fit one 16 B/entry LDS table; DIRECT: small unpartitioned joins, no task list)
-// k_join_ct              the same for partitions of 2 K ... 17.9 K build tuples under plans that remove >= 16 payload
-//                        bits: 8 B entries, both sides read once; six table geometries         vector ALU + LDS latency
+// k_join_ct              the same for partitions of 2 K ... 17.9 K build tuples under plans that remove >= 12 payload
+//                        bits: 8 B entries, both sides read once; one instantiation per compact-table row of
+//                        JOIN_GEOM (rhj_internal.h) and tuple format                           vector ALU + LDS latency
 // k_*2                   the one-pass kernels with grid.y = relation: R and S of a join through the same launches
 // k_scatter_wcn          the same scatter writing the narrow {payload 8 B, rowID 4 B} format inside a join: 32-tuple carry lines for
 //                        <= 8-bit passes, 16-tuple lines for 9-bit passes (17-18-bit plans)                HBM read+write (28 / 24 B/tuple)
@@ -117,7 +118,6 @@ __global__ void k_init_single_segment(u64 n, u64 L, u64 *seg_start, u32 *unit_st
 // Pass-1 units of a relation that arrived in SEGMENTS (multi-GPU receiver: segment s = the tuples sender s sent): every
 // segment is cut into the same number of units (units past a short segment's end are empty), so unit u belongs to segment
 // u / units_per_seg and no unit straddles two senders.  Also writes the one-segment tables {0, n}, {0, units}.
-constexpr int SEG_MAX = 16;
 struct SegPlan { u32 nseg, units_per_seg; u64 off[SEG_MAX + 1]; u64 L[SEG_MAX]; };
 
 __global__ void __launch_bounds__(256) k_seg_units(SegPlan sp, u64 *__restrict__ unit_rng, u64 *__restrict__ seg_start,
@@ -818,11 +818,9 @@ k_scatter_units_pipe(const Tup *__restrict__ in, Tup *__restrict__ out, const u6
 // ------------------------------------------------------------------------------------------------
 // (multi-GPU receiver) pass-2 unit u holds tuples of sender (u % ngroups) / div; see k_scatter_wcn
 struct WnTag { u32 ngroups, div, bits; };   // bits == 0: no tagging
-constexpr u32 TAG_BITS = 4, TAG_MAX = 1u << TAG_BITS;   // sender tags in the low payload bits: <= 16 ranks (== SEG_MAX)
 constexpr int FUSE_STRIDE64_FWD = 16;                                       // (= FUSE_STRIDE64, defined with the fused kernels below)
 constexpr int WC_THREADS = 1024, WC_TPT = 4;                                // geometry for 9-bit passes (tile = THREADS * WC_TPT)
 constexpr int WC_THREADS_SMALL = 512;                                       // <= 8 bits: two workgroups per CU
-constexpr int WC_MAX_BITS = 9;
 
 // IN_NARROW (multi-GPU receiver, last pass in front of the compact-table join): the input is a narrow relation whose rowIDs are
 // local to the sender's shard; unit u holds tuples of ONE sender (see WnTag) and the 16-byte tuples written carry the GLOBAL
@@ -1279,9 +1277,9 @@ __global__ void __launch_bounds__(THREADS) k_scatter_fused2(PassPair a, int shif
 // Two geometries: <GR = 32, 1024 threads x 4> for passes of <= 8 bits (above), and <GR = 16, 896 threads x 4> for 9-bit passes
 // (plans of 17-18 bits, beyond 1.1 * 10^9 tuples per side): 512 carry lines of 16 tuples (one payload line + half a rowID line:
 // 0.125 lines per tuple, what the 16-byte scatter pays) = 96 KiB + a 3584-slot stage = 158 KiB of LDS.
-constexpr int WN_THREADS = 1024, WN_TPT = 4, WN_GR = 32, WN_MAX_BITS = 8;
-constexpr int WN9_THREADS = 896, WN9_TPT = 4, WN9_GR = 16, WN9_MAX_BITS = 9;   // 14 wavefronts x 4 tuples: a 3584-slot stage is
-                                                                                // what 160 KiB leave beside 512 x 16-tuple carry lines
+constexpr int WN_THREADS = 1024, WN_TPT = 4, WN_GR = 32;
+constexpr int WN9_THREADS = 896, WN9_TPT = 4, WN9_GR = 16;   // 14 wavefronts x 4 tuples: a 3584-slot stage is
+                                                              // what 160 KiB leave beside 512 x 16-tuple carry lines
 
 // key_base (16-byte input): the rowID stored is key - key_base (a shard of a range-sharded relation sends rowIDs local to
 //   the shard; the receiver adds the sender's base again in the join, see WnTag).
@@ -1315,7 +1313,7 @@ struct WnPeer {
 // The payload array between the two count-free passes is private to them and k_hist_pieces_n, and laid out in WORD PLANES: inside
 // every 256-byte block of 32 slots the 32 low words of h come first, then the 32 high words (slot a: word cf_w(a) and CF_HI words
 // further).  Pass 2's digit lies in the low word (bits1 + bits2 <= 16), so its histogram reads every other 128-byte line.
-constexpr u32 CF_PER_MAX = 64, CF_PRE = CF_PER_MAX + 1, CF_HI = 32;
+constexpr u32 CF_HI = 32;
 static_assert(WN_GR == 32, "a carry line of the count-free pass 1 is one block of word planes");
 __device__ __forceinline__ u64 cf_w(u64 a) { return ((a >> 5) << 6) | (a & 31); }
 struct WnFree {
@@ -1855,11 +1853,11 @@ __device__ __forceinline__ u32 bj_bucket(u64 v, int radix_bits)
     return (((u32)x ^ (u32)(x >> 32)) * 0x9E3779B1u) >> (32 - BBITS);
 }
 
-// Two geometries of the same kernel:
-//   <512, 4224, 11, 8>   two workgroups per CU (76 KiB LDS each): partitions that fit one table (the planned case)
-//   <1024, 8448, 12, 4>  one workgroup per CU (152 KiB LDS): used when the AVERAGE build partition exceeds 4224 tuples
-//                        (explicit plans such as 8+8 bits at 10^9 tuples): half as many build chunks, so half as
-//                        many re-probes of the probe side
+// Two geometries of the same kernel (JOIN_GEOM in rhj_internal.h):
+//   JK_BKT      two workgroups per CU (76 KiB LDS each): partitions that fit one table (the planned case)
+//   JK_BKT_BIG  one workgroup per CU (152 KiB LDS): used when the AVERAGE build partition exceeds one JK_BKT table
+//               (explicit plans such as 8+8 bits at 10^9 tuples): half as many build chunks, so half as
+//               many re-probes of the probe side
 // DIRECT: no task list -- the inputs are ONE unpartitioned pair of relations and workgroup b probes tuples
 // [b * dsplit, (b+1) * dsplit) of the probe side against the whole build side (small joins: the launch sequence
 // k_part_max / k_make_tasks / task-list read would cost more than the join itself).
@@ -2290,13 +2288,13 @@ k_join_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
 // addAll), organised so that BOTH sides are read from HBM exactly once and every tuple is inserted / probed once:
 //
 //   * inside a partition all payloads share their low radix_bits bits, so (payload >> radix_bits) < 2^48 decides
-//     equality: a table entry is 8 bytes, {48-bit key | 16-bit arrival index of the build tuple}.  16352 entries +
-//     16384 bucket offsets fill the 160 KiB LDS of one workgroup per CU: the whole 15.3 K-tuple build side is ONE
-//     table (k_join_bkt needs two 8448-tuple chunks and re-reads the probe side per chunk: 64 GB moved for 48 GB
+//     equality: a table entry is 8 bytes, {48-bit key | 16-bit arrival index of the build tuple}.  JK_CT's entries and
+//     bucket offsets fill the 160 KiB LDS of one workgroup per CU: the whole 15.3 K-tuple build side is ONE
+//     table (k_join_bkt needs two JK_BKT_BIG chunks and re-reads the probe side per chunk: 64 GB moved for 48 GB
 //     algorithmic, 2.0 TB/s, round 1).  The bucket count is what the probe phase pays for: a wavefront walks its 256
 //     buckets of a tile in lock step, so a tile costs as many compare rounds as its LONGEST bucket has entries --
 //     7 with 8192 buckets of 1.9 entries on average, 4.6 with 16384 of 0.93 ([measured] 10^9 x 10^9: join kernel
-//     10.1 -> 9.3 ms for 1568 table entries fewer; 17920 entries in 8192 buckets remain as JK_CT_13).
+//     10.1 -> 9.3 ms for 1568 table entries fewer; the larger table in 8192 buckets remains as JK_CT_13).
 //   * the probe side streams through a 3-tile register ring; a probe tuple leaves in registers its rowID and its
 //     matches as {first table position of its bucket, bit mask of the matching entries} (the register file, 512 KiB
 //     per CU, is the largest memory there is: it holds a whole 16 K-tuple probe task).  1024 threads x 128 VGPRs:
@@ -2314,41 +2312,13 @@ k_join_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
 //     mask: such (wavefront, tile)s go through a generic loop that re-reads the slot's probe tuple, scans long buckets
 //     with all 64 lanes, reserves its own output range and fetches build rowIDs from the partition in L2/HBM by the
 //     16-bit arrival index every entry carries -- correct for any input, off the fast path's registers.
-// Bucket counts are 16-bit halves of 32-bit LDS words (ds_add_rtn on the word; a half cannot carry: <= 17920 per
-// workgroup), so 16384 buckets cost 32 KiB.  They lie at LDS offset 0 (their byte offset is their address), the table
+// Bucket counts are 16-bit halves of 32-bit LDS words (ds_add_rtn on the word; a half cannot carry: at most one table's entries per
+// workgroup), so JK_CT's buckets cost 32 KiB.  They lie at LDS offset 0 (their byte offset is their address), the table
 // behind them, the scan scratch last (a compare round may read 15 entries past a bucket's end: never past the allocation).
 // ------------------------------------------------------------------------------------------------
-constexpr int CT_THREADS = 1024, CT_CHUNK = 16352, CT_BUCKET_BITS = 14, CT_EPT = 16, CT_PT = 4, CT_DEPTH = 3;
-// JK_CT_13 (the full-size geometry of rounds 2 and 3 until the bucket count was doubled): 17920 entries, 8192 buckets.  For
-// partitions of 15.3 - 16.8 K build tuples (1.005 - 1.1 * 10^9 tuples under 16 bits), which the 16352-entry table would
-// build in two chunks; the 20-slot kernel (probe side beyond 16 K) keeps this table too.
-constexpr int CT13_CHUNK = 17920, CT13_BUCKET_BITS = 13;
-// the same kernel at half size, for partitions of up to 8960 build tuples (3 ... 5.5 * 10^8 tuples under a 16-bit plan):
-// 512 threads, 80 KiB LDS -> TWO workgroups per CU, which overlap each other's memory and LDS phases; the per-thread
-// register picture (18 build slots, 16 probe slots, 128 VGPRs) is unchanged.  The kernel's cost per task does not shrink
-// with the partition (every slot row is walked), so the full-size geometry is 2-3x too expensive there (measured at
-// 3 * 10^8: 8.9 ms against 5.1 ms for the chunked 16-byte-entry kernel).
-constexpr int CTH_THREADS = 512, CTH_CHUNK = 8160, CTH_BUCKET_BITS = 13;      // (8960 entries in 4096 buckets until round 3: the probe tasks
-// of 8192 tuples bound the partition size anyway, and twice the buckets are worth more than the last 800 entries)
-constexpr int CTHW_CHUNK = 8960, CTHW_BUCKET_BITS = 12;                           // the 20-slot form keeps the larger table
-// ... and with 20 probe slots per thread instead of 16 (narrow format only; 12 spilled VGPRs): partitions whose probe side is
-// just beyond one 16-slot task (2.2 * 10^9 tuples under 17 or 18 bits: 16.8 K / 8.4 K per partition) would otherwise be cut into
-// two tasks that both build the whole table
-constexpr int CT_EPT_WIDE = 20;
-// ... and a middle geometry: 12288 entries, 12 build and 12 probe slots per thread (1024 threads, one workgroup per CU).  The
-// kernel's cost per task follows its slot rows, not the partition: partitions of 8.4 - 11.5 K tuples (5.5 - 7.5 * 10^8 tuples under
-// 16 bits, 1.1 - 1.5 * 10^9 under 17) paid for 18 + 16 rows in the full-size geometry ([measured] join kernel 8.5 -> 6.6 ms at
-// 6 * 10^8, 17.6 -> 14.1 at 1.5 * 10^9; 16 + 16 rows for the 15.3 K-tuple partitions of 10^9 tuples: 10.09 -> 10.02, not kept).
-constexpr int CTM_CHUNK = 12288, CTM_EPT = 12, CTM_BUCKET_BITS = 14, CTHM_BUCKET_BITS = 13;
-constexpr int CTHM_CHUNK = 6144;                    // ... and at half size (512 threads, two workgroups per CU): 4.2 - 5.8 K-tuple partitions
+// The geometries this kernel is instantiated with, what each is for and what it measured: JOIN_GEOM in rhj_internal.h.
+constexpr int CT_DEPTH = 3;
 constexpr u32 CT_NONE = 0xFFFFu;
-constexpr int CT_MIN_RADIX_BITS = 16;       // keys must fit 48 bits
-// JK_CT_G13: the 6144-entry geometry with row guards and 13-bit arrival indices: keys of up to 51 bits, i.e. plans of 13-15
-// radix bits (1.6 * 10^7 ... 1.3 * 10^8 tuples per side), whose 2-4 K-tuple partitions the one-table kernel served until round 4
-constexpr int CT13_KB = 13, CT13_MIN_RADIX_BITS = 64 - (64 - CT13_KB);
-// JK_CT_Q12: a 4096-entry table with 12-bit arrival indices (keys of up to 52 bits) in 4096 buckets, 8 + 8 slot rows per thread, row
-// guards, 41 KiB of LDS: plans of exactly 12 bits (8.4 * 10^6 ... 1.6 * 10^7 tuples per side, partitions of 2-3.8 K tuples)
-constexpr int CTQ_CHUNK = 4096, CTQ_BUCKET_BITS = 12, CTQ_EPT = 8, CTQ_KB = 12;
 constexpr u32 CT_MASK_BITS = 16;            // a probe records its matches as a bit mask over a bucket of at most this many entries
 
 // 32-bit Fibonacci hash of the folded key: one quarter-rate multiply instead of the four of a 64-bit product (the probe
@@ -2386,9 +2356,9 @@ constexpr int CT_NSTAMP = 16;
 // skip (optional): a device word that is non-zero when this join is going to be repeated in another format (a rowID did
 // not fit the narrow format): nothing to do then.
 // KB: bits of the arrival index in a table entry {key | index}: 16 by default (keys of 48 bits: plans that remove >= 16 payload bits);
-// 13 for the 6144-entry geometry under plans of 13-15 bits (keys of up to 51 bits: the partitions of 1.6 * 10^7 ... 1.3 * 10^8 tuples)
+// 13 for JK_CT_G13 under plans of 13-15 bits (keys of up to 51 bits: the partitions of 1.6 * 10^7 ... 1.3 * 10^8 tuples)
 template <int THREADS, int CHUNK, int BBITS, int EPT, bool STAMPS, bool NARROW, bool GUARD = false, int KB = 16>
-__global__ void __launch_bounds__(THREADS, THREADS * (CHUNK <= 8960 ? 2 : 1) / 256)   // wavefronts per SIMD: 2 (256 registers per lane) or 4 (128)
+__global__ void __launch_bounds__(THREADS, THREADS * (THREADS <= 512 ? 2 : 1) / 256)   // wavefronts per SIMD: 2 (256 registers per lane) or 4 (128); half size: two workgroups per CU
 k_join_ct(const RelView<NARROW> R, const RelView<NARROW> S, const JoinTask *__restrict__ tasks,
           const u32 *__restrict__ ntasks, int radix_bits, Pair *__restrict__ out, u64 out_capacity,
           u64 *__restrict__ out_count, u64 *__restrict__ stamps, u32 nstamp_wgs, const u32 *__restrict__ skip)
@@ -2445,7 +2415,7 @@ k_join_ct(const RelView<NARROW> R, const RelView<NARROW> S, const JoinTask *__re
     // Slot row k holds tuples [k * THREADS, (k + 1) * THREADS) of the chunk / task: whether a row is in use is the same for
     // every thread (a scalar compare and branch).  GUARD: rows beyond the partition are skipped, so a partition that fills
     // half the rows pays for half of them and one geometry serves a range of partition sizes at a cost that follows the
-    // partition ([measured] 6144-entry geometry, 2 * 10^8 tuples, 3 K-tuple partitions: join kernel 2.04 ms against 2.83
+    // partition ([measured] JK_CT_HALF_MID_G, 2 * 10^8 tuples, 3 K-tuple partitions: join kernel 2.04 ms against 2.83
     // unguarded and 2.58 for k_join_bkt).  The branches cost full partitions 10 % (they end the batches of loads and LDS
     // operations: 10^9 tuples 9.1 -> 10.2 ms), so kernels for full tables are instantiated without them.
 #define USED(k, n) (!GUARD || (u32)(k) * (u32)THREADS < (n))
@@ -2913,28 +2883,13 @@ static int wc_threads_for(int bits)
     if (force == 512 || force == 1024) return force;
     return bits <= 8 ? WC_THREADS_SMALL : WC_THREADS;
 }
-
-constexpr int BJ2_THREADS = 1024, BJ2_CHUNK = 8448, BJ2_BUCKET_BITS = 12, BJ2_EPT = 4;
-
-// probe tuples per task / build tuples per table of each join kernel (host plan)
-u32 join_probe_split(int kind)
+// The write-combining scatters exist in both workgroup sizes: f(std::integral_constant<int, THREADS>()) with the size a pass of
+// `bits` bits takes.  small_ok = false: 1024 threads whatever the tuning aid says.
+template <class F>
+static void with_wc_threads(int bits, bool small_ok, F &&f)
 {
-    return kind == JK_CT || kind == JK_CT_13 ? (u32)(CT_THREADS * CT_EPT) : kind == JK_CT_HALF ? (u32)(CTH_THREADS * CT_EPT) :
-           kind == JK_CT_WIDE ? (u32)(CT_THREADS * CT_EPT_WIDE) : kind == JK_CT_HALF_WIDE ? (u32)(CTH_THREADS * CT_EPT_WIDE) :
-           kind == JK_CT_MID ? (u32)(CT_THREADS * CTM_EPT) : kind == JK_CT_HALF_MID || kind == JK_CT_HALF_MID_G || kind == JK_CT_G13 ? (u32)(CTH_THREADS * CTM_EPT) :
-           kind == JK_CT_Q12 ? (u32)(CTH_THREADS * CTQ_EPT) : 0u;
-}
-u32 join_table_tuples(int kind)
-{
-    return kind == JK_CT ? (u32)CT_CHUNK : kind == JK_CT_13 || kind == JK_CT_WIDE ? (u32)CT13_CHUNK : kind == JK_CT_HALF ? (u32)CTH_CHUNK : kind == JK_CT_HALF_WIDE ? (u32)CTHW_CHUNK :
-           kind == JK_CT_MID ? (u32)CTM_CHUNK : kind == JK_CT_HALF_MID || kind == JK_CT_HALF_MID_G || kind == JK_CT_G13 ? (u32)CTHM_CHUNK : kind == JK_CT_Q12 ? (u32)CTQ_CHUNK :
-           kind == JK_BKT_BIG ? (u32)BJ2_CHUNK : (u32)BJ_CHUNK;
-}
-int join_ct_min_radix_bits(int kind) { return kind == JK_CT_G13 ? CT13_MIN_RADIX_BITS : kind == JK_CT_Q12 ? CTQ_KB : CT_MIN_RADIX_BITS; }
-
-static size_t bj_lds_bytes(int threads, int chunk, int bbits)
-{
-    return (size_t)chunk * 16 + ((size_t)(1 << bbits) + 4) * 4 + 64 * 4 + (size_t)(threads / 64) * 4 + 16 + 2 * TAG_MAX * 8;
+    if (small_ok && wc_threads_for(bits) == WC_THREADS_SMALL) f(std::integral_constant<int, WC_THREADS_SMALL>());
+    else f(std::integral_constant<int, WC_THREADS>());
 }
 
 // Per device (a process may drive several GPUs through different contexts) and exactly once: contexts of
@@ -2945,11 +2900,6 @@ static int current_device_slot()
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     return dev;
-}
-
-static size_t ct_lds_bytes(int threads = CT_THREADS, int chunk = CT_CHUNK, int bbits = CT_BUCKET_BITS)
-{
-    return (size_t)chunk * 8 + ((size_t)(1 << bbits) / 2 + 2 + 2 * (threads / 64)) * 4 + 24 + (threads < 1024 ? 64 : 0);   // (>= 128 B behind the table)
 }
 
 // hipFuncSetAttribute results are kept: a refused LDS size would otherwise surface later as an anonymous launch failure.
@@ -2963,16 +2913,63 @@ const char *launch_attr_error()
     return g_attr_error.empty() ? nullptr : g_attr_error.c_str();
 }
 
-static void set_lds(const void *fn, size_t bytes, const char *name)
+static void set_lds(const void *fn, size_t bytes, const std::string &name)
 {
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) return;
     (void)hipGetLastError();
     std::lock_guard<std::mutex> lk(g_attr_mu);
     if (g_attr_error.empty())
-        g_attr_error = std::string("hipFuncSetAttribute(") + name + ", dynamic LDS " + std::to_string(bytes) + " B): " + hipGetErrorString(e);
+        g_attr_error = "hipFuncSetAttribute(" + name + ", dynamic LDS " + std::to_string(bytes) + " B): " + hipGetErrorString(e);
 }
 #define SET_LDS(fn, bytes) set_lds(reinterpret_cast<const void *>(&fn), (bytes), #fn)
+
+// ---- the join kernels by JOIN_GEOM row: the only place that spells out their geometry arguments ------------------------------
+template <int K, bool DIRECT, bool NARROW = false, bool TAGGED = false, bool BATCH = false>
+static constexpr auto bkt_kernel()
+{
+    constexpr JoinGeom G = JOIN_GEOM[K];
+    return &k_join_bkt<G.threads, G.chunk, G.bucket_bits, G.ept, DIRECT, NARROW, TAGGED, BATCH>;
+}
+template <int K, bool DIRECT, bool NARROW = false, bool TAGGED = false, bool BATCH = false>
+static void allow_bkt_lds()
+{
+    set_lds(reinterpret_cast<const void *>(bkt_kernel<K, DIRECT, NARROW, TAGGED, BATCH>()), join_lds_bytes(JOIN_GEOM[K]),
+            "k_join_bkt, kind " + std::to_string(K));
+}
+
+// compact-table kind K over narrow or 16-byte partitions: a narrow-only geometry has no 16-byte instantiation
+template <int K, bool NARROW> constexpr bool ct_exists = NARROW || !JOIN_GEOM[K].narrow_only;
+template <int K, bool NARROW, bool STAMPS = false>
+static constexpr auto ct_kernel()
+{
+    constexpr JoinGeom G = JOIN_GEOM[K];
+    return &k_join_ct<G.threads, G.chunk, G.bucket_bits, G.ept, STAMPS, NARROW, G.guard, G.key_index_bits>;
+}
+template <int K, bool NARROW, bool STAMPS = false>
+static void allow_ct_lds()
+{
+    if constexpr (ct_exists<K, NARROW>)
+        set_lds(reinterpret_cast<const void *>(ct_kernel<K, NARROW, STAMPS>()), join_lds_bytes(JOIN_GEOM[K]),
+                "k_join_ct, kind " + std::to_string(K) + (NARROW ? ", narrow" : ", 16-byte tuples"));
+}
+template <int K, bool NARROW, bool STAMPS = false>
+static void launch_ct(hipStream_t st, u32 grid, RelView<NARROW> R, RelView<NARROW> S, const JoinTask *d_tasks, const u32 *d_ntasks,
+                      int radix_bits, Pair *out, u64 out_capacity, u64 *d_out_count, const u32 *d_skip, u64 *d_stamps = nullptr,
+                      u32 nstamp_wgs = 0)
+{
+    static_assert(ct_exists<K, NARROW>, "a narrow-only geometry has no kernel over 16-byte tuples");
+    constexpr JoinGeom G = JOIN_GEOM[K];
+    hipLaunchKernelGGL((ct_kernel<K, NARROW, STAMPS>()), dim3(grid), dim3(G.threads), join_lds_bytes(G), st, R, S, d_tasks, d_ntasks,
+                       radix_bits, out, out_capacity, d_out_count, d_stamps, nstamp_wgs, d_skip);
+}
+// f(std::integral_constant<int, K>()) for the compact-table kind K == kind, or for every one of them (kind < 0)
+template <int K = JK_CT, class F>
+static void for_ct_kind(int kind, F &&f)
+{
+    if (kind == K || kind < 0) f(std::integral_constant<int, K>());
+    if constexpr (K < JK_LAST) for_ct_kind<K + 1>(kind, f);
+}
 
 static void allow_big_lds()
 {
@@ -2985,31 +2982,17 @@ static void allow_big_lds()
     SET_LDS(k_scatter_wc2<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_fused2<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_fused2<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
-    SET_LDS((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, false>), bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS));
-    SET_LDS((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, true>), bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS));
-    SET_LDS((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, true, false, false, true>), bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS));
-    SET_LDS((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, false, true>), bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS));
-    SET_LDS((k_join_bkt<BJ2_THREADS, BJ2_CHUNK, BJ2_BUCKET_BITS, BJ2_EPT, false>), bj_lds_bytes(BJ2_THREADS, BJ2_CHUNK, BJ2_BUCKET_BITS));
-    SET_LDS((k_join_ct<CT_THREADS, CT_CHUNK, CT_BUCKET_BITS, CT_EPT, false, false>), ct_lds_bytes());
-    SET_LDS((k_join_ct<CTH_THREADS, CTH_CHUNK, CTH_BUCKET_BITS, CT_EPT, false, false>), ct_lds_bytes(CTH_THREADS, CTH_CHUNK, CTH_BUCKET_BITS));
-    SET_LDS((k_join_ct<CT_THREADS, CT_CHUNK, CT_BUCKET_BITS, CT_EPT, true, false>), ct_lds_bytes());
-    SET_LDS((k_join_ct<CT_THREADS, CT_CHUNK, CT_BUCKET_BITS, CT_EPT, false, true>), ct_lds_bytes());
-    SET_LDS((k_join_ct<CTH_THREADS, CTH_CHUNK, CTH_BUCKET_BITS, CT_EPT, false, true>), ct_lds_bytes(CTH_THREADS, CTH_CHUNK, CTH_BUCKET_BITS));
-    SET_LDS((k_join_ct<CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS, CT_EPT_WIDE, false, true>), ct_lds_bytes(CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS));
-    SET_LDS((k_join_ct<CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS, CT_EPT, false, true>), ct_lds_bytes(CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS));
-    SET_LDS((k_join_ct<CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS, CT_EPT, false, false>), ct_lds_bytes(CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS));
-    SET_LDS((k_join_ct<CT_THREADS, CTM_CHUNK, CTM_BUCKET_BITS, CTM_EPT, false, true>), ct_lds_bytes(CT_THREADS, CTM_CHUNK, CTM_BUCKET_BITS));
-    SET_LDS((k_join_ct<CT_THREADS, CTM_CHUNK, CTM_BUCKET_BITS, CTM_EPT, false, false>), ct_lds_bytes(CT_THREADS, CTM_CHUNK, CTM_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, true>), ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, false>), ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, true, true>), ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, false, true>), ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, true, true, CT13_KB>), ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTQ_CHUNK, CTQ_BUCKET_BITS, CTQ_EPT, false, true, true, CTQ_KB>), ct_lds_bytes(CTH_THREADS, CTQ_CHUNK, CTQ_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTQ_CHUNK, CTQ_BUCKET_BITS, CTQ_EPT, false, false, true, CTQ_KB>), ct_lds_bytes(CTH_THREADS, CTQ_CHUNK, CTQ_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, false, true, CT13_KB>), ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS));
-    SET_LDS((k_join_ct<CTH_THREADS, CTHW_CHUNK, CTHW_BUCKET_BITS, CT_EPT_WIDE, false, true>), ct_lds_bytes(CTH_THREADS, CTHW_CHUNK, CTHW_BUCKET_BITS));
-    SET_LDS((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, false, true, true>), bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS));
+    allow_bkt_lds<JK_BKT, false>();                                          // task list, 16-byte partitions
+    allow_bkt_lds<JK_BKT, true>();                                           // direct
+    allow_bkt_lds<JK_BKT, true, false, false, true>();                       // direct, batched
+    allow_bkt_lds<JK_BKT, false, true>();                                    // narrow partitions
+    allow_bkt_lds<JK_BKT, false, true, true>();                              // ... with sender tags
+    allow_bkt_lds<JK_BKT_BIG, false>();
+    for_ct_kind(-1, [](auto k) {
+        allow_ct_lds<decltype(k)::value, true>();
+        allow_ct_lds<decltype(k)::value, false>();
+    });
+    allow_ct_lds<JK_CT, false, true>();                                      // the stamps aid
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<false>, wn_lds_bytes(WN_MAX_BITS));
@@ -3048,13 +3031,20 @@ void launch_hist_units_narrow(hipStream_t st, const void *d_inP, const PassGeom 
                        d_seg_start, d_unit_start, g.nseg, g.L, g.shift, g.bits, d_unit_hist);
 }
 
+// slices of the three-kernel scan over the units of one segment: about sqrt(units), 8 ... SCAN_SLICES
+static u32 scan_slices(u32 units)
+{
+    u32 nsl = 8;
+    while (nsl < SCAN_SLICES && nsl * nsl < units) nsl++;
+    return nsl;
+}
+
 void launch_scan_units(hipStream_t st, const PassGeom &g, const u64 *d_seg_start, const u32 *d_unit_start,
                        const u32 *d_unit_hist, u64 *d_unit_base, u64 *d_part_start, u64 *d_scan_tmp)
 {
     const size_t nbins = (size_t)1 << g.bits;
     if (g.nseg == 1 && g.max_units > 2 * SCAN_SLICES && d_scan_tmp != nullptr) {
-        u32 nsl = 8;
-        while (nsl < SCAN_SLICES && nsl * nsl < g.max_units) nsl++;
+        const u32 nsl = scan_slices(g.max_units);
         hipLaunchKernelGGL(k_scan1_partial, dim3(nsl), dim3(1024), 0, st, d_unit_start, g.bits, d_unit_hist, d_scan_tmp);
         hipLaunchKernelGGL(k_scan1_mid, dim3(1), dim3(1024), 0, st, g.bits, nsl, d_scan_tmp, d_part_start, g.n);
         hipLaunchKernelGGL(k_scan1_final, dim3(nsl), dim3(1024), 0, st, d_unit_start, g.bits, d_unit_hist,
@@ -3072,14 +3062,11 @@ void launch_scatter_units(hipStream_t st, const void *d_in, void *d_out, const P
     if (g.max_units == 0) return;
     allow_big_lds();
     if (g.bits <= WC_MAX_BITS) {
-        if (wc_threads_for(g.bits) == WC_THREADS_SMALL)
-            hipLaunchKernelGGL(k_scatter_wc<WC_THREADS_SMALL>, dim3(g.max_units), dim3(WC_THREADS_SMALL),
-                               wc_lds_bytes(g.bits, WC_THREADS_SMALL), st, (const Tup *)d_in, (Tup *)d_out, d_seg_start,
-                               d_unit_start, g.nseg, g.L, g.shift, g.bits, d_unit_base, (const u64 *)nullptr, 0u, g.mix);
-        else
-            hipLaunchKernelGGL(k_scatter_wc<WC_THREADS>, dim3(g.max_units), dim3(WC_THREADS), wc_lds_bytes(g.bits, WC_THREADS),
-                               st, (const Tup *)d_in, (Tup *)d_out, d_seg_start, d_unit_start, g.nseg, g.L, g.shift, g.bits,
-                               d_unit_base, (const u64 *)nullptr, 0u, g.mix);
+        with_wc_threads(g.bits, true, [&](auto threads) {
+            constexpr int T = decltype(threads)::value;
+            hipLaunchKernelGGL(k_scatter_wc<T>, dim3(g.max_units), dim3(T), wc_lds_bytes(g.bits, T), st, (const Tup *)d_in, (Tup *)d_out,
+                               d_seg_start, d_unit_start, g.nseg, g.L, g.shift, g.bits, d_unit_base, (const u64 *)nullptr, 0u, g.mix);
+        });
         return;
     }
     // 10-bit pass: carry lines (2^10 x 128 B) do not fit LDS beside a tile -> tile-sort form
@@ -3088,20 +3075,25 @@ void launch_scatter_units(hipStream_t st, const void *d_in, void *d_out, const P
                        d_unit_base, g.mix);
 }
 
+static PassPair make_pass_pair(const PassPairHost &h)
+{
+    PassPair a;
+    a.mix = h.mix;
+    for (int i = 0; i < 2; i++) {
+        const PassSide &x = h.side[i];
+        a.r[i] = PassRel{(const Tup *)x.in, (Tup *)x.out, x.seg_start, x.unit_start, x.unit_hist, x.unit_base, x.part_start,
+                         x.scan_tmp, x.g.n, x.g.L, x.g.max_units};
+    }
+    return a;
+}
+
 // One partition pass over BOTH relations of a join, each kernel launched once (grid.y = relation).  bits <= WC_MAX_BITS.
 // phase: 0 unit tables, 1 histogram, 2 scan, 3 scatter (separate calls so that the host can time them per kind).
 void launch_pass_pair(hipStream_t st, const PassPairHost &h, int shift, int bits, int phase)
 {
     allow_big_lds();
-    PassPair a;
-    a.mix = h.mix;
-    u32 mu = 0;
-    for (int i = 0; i < 2; i++) {
-        const PassSide &x = h.side[i];
-        a.r[i] = PassRel{(const Tup *)x.in, (Tup *)x.out, x.seg_start, x.unit_start, x.unit_hist, x.unit_base, x.part_start,
-                         x.scan_tmp, x.g.n, x.g.L, x.g.max_units};
-        mu = x.g.max_units > mu ? x.g.max_units : mu;
-    }
+    const PassPair a = make_pass_pair(h);
+    const u32 mu = h.side[0].g.max_units > h.side[1].g.max_units ? h.side[0].g.max_units : h.side[1].g.max_units;
     if (mu == 0) return;
     if (phase == 0) {
         hipLaunchKernelGGL(k_init_single_segment2, dim3(2), dim3(64), 0, st, a, h.zero8);
@@ -3109,8 +3101,7 @@ void launch_pass_pair(hipStream_t st, const PassPairHost &h, int shift, int bits
         hipLaunchKernelGGL(k_hist_units2, dim3(mu, 2), dim3(PART_THREADS), ((size_t)4 << bits), st, a, shift, bits);
     } else if (phase == 2) {
         if (mu > 2 * SCAN_SLICES) {
-            u32 nsl = 8;
-            while (nsl < SCAN_SLICES && nsl * nsl < mu) nsl++;
+            const u32 nsl = scan_slices(mu);
             hipLaunchKernelGGL(k_scan1_partial2, dim3(nsl, 2), dim3(1024), 0, st, a, bits);
             hipLaunchKernelGGL(k_scan1_mid2, dim3(2), dim3(1024), 0, st, a, bits, nsl);
             hipLaunchKernelGGL(k_scan1_final2, dim3(nsl, 2), dim3(1024), 0, st, a, bits);
@@ -3118,11 +3109,11 @@ void launch_pass_pair(hipStream_t st, const PassPairHost &h, int shift, int bits
             const size_t nbins = (size_t)1 << bits, G = 1024 / nbins;
             hipLaunchKernelGGL(k_scan_units2, dim3(2), dim3(1024), G * nbins * 8, st, a, bits);
         }
-    } else if (wc_threads_for(bits) == WC_THREADS_SMALL) {
-        hipLaunchKernelGGL(k_scatter_wc2<WC_THREADS_SMALL>, dim3(mu, 2), dim3(WC_THREADS_SMALL), wc_lds_bytes(bits, WC_THREADS_SMALL),
-                           st, a, shift, bits);
     } else {
-        hipLaunchKernelGGL(k_scatter_wc2<WC_THREADS>, dim3(mu, 2), dim3(WC_THREADS), wc_lds_bytes(bits, WC_THREADS), st, a, shift, bits);
+        with_wc_threads(bits, true, [&](auto threads) {
+            constexpr int T = decltype(threads)::value;
+            hipLaunchKernelGGL(k_scatter_wc2<T>, dim3(mu, 2), dim3(T), wc_lds_bytes(bits, T), st, a, shift, bits);
+        });
     }
 }
 
@@ -3138,14 +3129,11 @@ void launch_fused_pass(hipStream_t st, const PassPairHost &h, int bits, int phas
                        u32 table_tuples, JoinTask *d_tasks, u64 *d_counters, u64 *host_pub, bool sniff)
 {
     allow_big_lds();
-    PassPair a;
-    a.mix = h.mix;
+    const PassPair a = make_pass_pair(h);
     u32 mu = 0;
     for (int i = 0; i < 2; i++) {
-        const PassSide &x = h.side[i];
-        a.r[i] = PassRel{(const Tup *)x.in, (Tup *)x.out, x.seg_start, x.unit_start, x.unit_hist, x.unit_base, x.part_start,
-                         x.scan_tmp, x.g.n, x.g.L, x.g.max_units};
-        const u32 units = (u32)((x.g.n + x.g.L - 1) / x.g.L);
+        const PassGeom &g = h.side[i].g;
+        const u32 units = (u32)((g.n + g.L - 1) / g.L);
         mu = units > mu ? units : mu;
     }
     if (mu == 0) mu = 1;                                                     // (both relations empty: the ticket logic still runs)
@@ -3179,15 +3167,15 @@ void launch_fused_pass(hipStream_t st, const PassPairHost &h, int bits, int phas
     const FuseTasks ft{probe_split, max_tasks, table_tuples, k, d_tasks, d_counters, host_pub, build_tie_shift(), sv};
     if (phase == 0) {
         hipLaunchKernelGGL(k_hist_fused2, dim3((mu + k - 1) / k, 2), dim3(PART_THREADS), ((size_t)8 << bits), st, a, 0, bits, fc, ft);
-    } else if (wc_threads_for(bits) == WC_THREADS_SMALL && bits <= 8) {
-        hipLaunchKernelGGL(k_scatter_fused2<WC_THREADS_SMALL>, dim3(mu + 1, 2), dim3(WC_THREADS_SMALL), wc_lds_bytes(bits, WC_THREADS_SMALL),
-                           st, a, 0, bits, fc, ft);
     } else {
-        hipLaunchKernelGGL(k_scatter_fused2<WC_THREADS>, dim3(mu + 1, 2), dim3(WC_THREADS), wc_lds_bytes(bits, WC_THREADS), st, a, 0, bits, fc, ft);
+        // (k_scatter_fused2 works with one digit per thread and its 512-thread form is written for passes of <= 8 bits, so a 9-bit
+        // pass takes 1024 threads even where RHJ_WC_THREADS=512 asks the other scatters for the small form)
+        with_wc_threads(bits, bits <= 8, [&](auto threads) {
+            constexpr int T = decltype(threads)::value;
+            hipLaunchKernelGGL(k_scatter_fused2<T>, dim3(mu + 1, 2), dim3(T), wc_lds_bytes(bits, T), st, a, 0, bits, fc, ft);
+        });
     }
 }
-
-bool fused_two_pass_ok(int b1, int b2) { return b1 >= 1 && b2 >= 1 && b1 <= WC_MAX_BITS && b2 <= WC_MAX_BITS && b1 + b2 <= 16; }
 
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,
                          u32 units_per_group, u32 ngroups, u32 *d_hist1, u32 *d_hist2, u64 key_base, u32 *d_wide,
@@ -3220,7 +3208,6 @@ void launch_seg_units(hipStream_t st, u32 nseg, const u64 *seg_off, const u64 *s
     const u32 total = nseg * units_per_seg + 1;
     hipLaunchKernelGGL(k_seg_units, dim3((total + 255) / 256), dim3(256), 0, st, sp, d_unit_rng, d_seg_start, d_unit_start);
 }
-int seg_max() { return SEG_MAX; }
 
 void launch_make_group_ranges(hipStream_t st, const u64 *d_unit_base1, u32 nb1, u32 units_per_group, u32 ngroups, u64 n,
                               u64 *d_rng, u32 *d_unit_start2)
@@ -3235,14 +3222,11 @@ void launch_scatter_ranges(hipStream_t st, const void *d_in, void *d_out, u32 nu
 {
     if (nunits == 0) return;
     allow_big_lds();
-    if (wc_threads_for(bits) == WC_THREADS_SMALL)
-        hipLaunchKernelGGL(k_scatter_wc<WC_THREADS_SMALL>, dim3(nunits), dim3(WC_THREADS_SMALL), wc_lds_bytes(bits, WC_THREADS_SMALL),
-                           st, (const Tup *)d_in, (Tup *)d_out, (const u64 *)nullptr, (const u32 *)nullptr, 0u, (u64)0, shift,
-                           bits, d_unit_base, d_rng, nunits, 0);
-    else
-        hipLaunchKernelGGL(k_scatter_wc<WC_THREADS>, dim3(nunits), dim3(WC_THREADS), wc_lds_bytes(bits, WC_THREADS), st,
-                           (const Tup *)d_in, (Tup *)d_out, (const u64 *)nullptr, (const u32 *)nullptr, 0u, (u64)0, shift, bits,
-                           d_unit_base, d_rng, nunits, 0);
+    with_wc_threads(bits, true, [&](auto threads) {
+        constexpr int T = decltype(threads)::value;
+        hipLaunchKernelGGL(k_scatter_wc<T>, dim3(nunits), dim3(T), wc_lds_bytes(bits, T), st, (const Tup *)d_in, (Tup *)d_out,
+                           (const u64 *)nullptr, (const u32 *)nullptr, 0u, (u64)0, shift, bits, d_unit_base, d_rng, nunits, 0);
+    });
 }
 
 // last pass of the multi-GPU receiver in front of the compact-table join: narrow in (rowIDs at narrow_k_offset(n)), 16-byte
@@ -3256,29 +3240,59 @@ void launch_scatter_ranges_n2a(hipStream_t st, const void *d_in, void *d_out, u6
     const u64 *iP = (const u64 *)d_in;
     const u32 *iK = (const u32 *)((const unsigned char *)d_in + narrow_k_offset(n));
     const WnTag tag{tag_groups, tag_div, 0u};
-    if (wc_threads_for(bits) == WC_THREADS_SMALL)
-        hipLaunchKernelGGL(k_scatter_wc_n<WC_THREADS_SMALL>, dim3(nunits), dim3(WC_THREADS_SMALL), wc_lds_bytes(bits, WC_THREADS_SMALL),
-                           st, iP, iK, (Tup *)d_out, shift, bits, d_unit_base, d_rng, nunits, d_key_bases, tag, d_skip);
-    else
-        hipLaunchKernelGGL(k_scatter_wc_n<WC_THREADS>, dim3(nunits), dim3(WC_THREADS), wc_lds_bytes(bits, WC_THREADS), st, iP, iK,
-                           (Tup *)d_out, shift, bits, d_unit_base, d_rng, nunits, d_key_bases, tag, d_skip);
+    with_wc_threads(bits, true, [&](auto threads) {
+        constexpr int T = decltype(threads)::value;
+        hipLaunchKernelGGL(k_scatter_wc_n<T>, dim3(nunits), dim3(T), wc_lds_bytes(bits, T), st, iP, iK, (Tup *)d_out, shift, bits,
+                           d_unit_base, d_rng, nunits, d_key_bases, tag, d_skip);
+    });
 }
 
 // Narrow-format scatters (k_scatter_wcn).  A narrow relation of n tuples lives in one buffer of >= 16 n bytes: payloads
 // (u64) at offset 0, rowIDs (u32) at narrow_k_offset(n).
-bool narrow_pass_ok(int bits) { return bits >= 1 && bits <= WN_MAX_BITS; }
-bool narrow_pass9_ok(int bits) { return bits >= 1 && bits <= WN9_MAX_BITS; }
+
+// What differs between the launches of k_scatter_wcn.  Units are either the segments cut into units of L tuples (seg_start,
+// unit_start, nseg, L) or explicit ranges [rng[u], rng[u+1]).
+struct WcnLaunch {
+    const void *in;                     // 16-byte tuples, or the payloads of a narrow input ...
+    const u32 *inK;                     // ... with these rowIDs
+    u64 *outP;
+    u32 *outK;
+    u32 units;
+    int shift, bits;
+    const u64 *unit_base;
+    u32 *overflow;
+    const u64 *seg_start = nullptr, *rng = nullptr;
+    const u32 *unit_start = nullptr;
+    u32 nseg = 0;
+    u64 L = 0, key_base = 0;
+    WnTag tag{1u, 1u, 0u};
+    int mix = 0;
+    WnPeer peer{};
+    void segments(const PassGeom &g, const u64 *d_seg_start, const u32 *d_unit_start)
+    {
+        seg_start = d_seg_start; unit_start = d_unit_start; nseg = g.nseg; L = g.L; mix = g.mix;
+    }
+};
+template <bool IN_NARROW, int GR = WN_GR, int TPT = WN_TPT, int THREADS = WN_THREADS, bool PEER = false>
+static void launch_wcn(hipStream_t st, const WcnLaunch &a)
+{
+    if (a.units == 0) return;
+    allow_big_lds();
+    hipLaunchKernelGGL((k_scatter_wcn<IN_NARROW, GR, TPT, THREADS, PEER>), dim3(a.units), dim3(THREADS),
+                       wn_lds_bytes(a.bits, GR, TPT, THREADS, PEER), st, (const Tup *)(IN_NARROW ? nullptr : a.in),
+                       (const u64 *)(IN_NARROW ? a.in : nullptr), a.inK, a.outP, a.outK, a.seg_start, a.unit_start, a.nseg, a.L, a.shift,
+                       a.bits, a.unit_base, a.rng, a.rng ? a.units : 0u, a.overflow, a.key_base, a.tag, a.mix, a.peer);
+}
 
 void launch_scatter_units_narrow(hipStream_t st, const void *d_in, void *d_out, u64 n, const PassGeom &g,
                                  const u64 *d_seg_start, const u32 *d_unit_start, const u64 *d_unit_base, u32 *d_overflow,
                                  u64 key_base)
 {
-    if (g.max_units == 0) return;
-    allow_big_lds();
-    hipLaunchKernelGGL(k_scatter_wcn<false>, dim3(g.max_units), dim3(WN_THREADS), wn_lds_bytes(g.bits), st, (const Tup *)d_in,
-                       (const u64 *)nullptr, (const u32 *)nullptr, (u64 *)d_out,
-                       (u32 *)((unsigned char *)d_out + narrow_k_offset(n)), d_seg_start, d_unit_start, g.nseg, g.L, g.shift,
-                       g.bits, d_unit_base, (const u64 *)nullptr, 0u, d_overflow, key_base, WnTag{1u, 1u, 0u}, g.mix, WnPeer{});
+    WcnLaunch a{d_in, nullptr, (u64 *)d_out, (u32 *)((unsigned char *)d_out + narrow_k_offset(n)), g.max_units, g.shift, g.bits,
+                d_unit_base, d_overflow};
+    a.segments(g, d_seg_start, d_unit_start);
+    a.key_base = key_base;
+    launch_wcn<false>(st, a);
 }
 
 // the multi-GPU sender's class split straight into the owners' receive arrays (k_scatter_wcn<.., PEER>): d_delta / d_owner:
@@ -3288,16 +3302,14 @@ void launch_scatter_units_narrow_peer(hipStream_t st, const void *d_in, const Pa
                                       const u64 *d_delta, const unsigned char *d_owner, void *const *peersP, void *const *peersK,
                                       int nranks)
 {
-    if (g.max_units == 0) return;
-    allow_big_lds();
-    WnPeer peer{};
-    peer.delta = d_delta;
-    peer.owner = d_owner;
-    for (int i = 0; i < nranks && i < SEG_MAX; i++) { peer.P[i] = (u64 *)peersP[i]; peer.K[i] = (u32 *)peersK[i]; }
-    hipLaunchKernelGGL((k_scatter_wcn<false, WN_GR, WN_TPT, WN_THREADS, true>), dim3(g.max_units), dim3(WN_THREADS),
-                       wn_lds_bytes(g.bits, WN_GR, WN_TPT, WN_THREADS, true), st, (const Tup *)d_in, (const u64 *)nullptr,
-                       (const u32 *)nullptr, (u64 *)nullptr, (u32 *)nullptr, d_seg_start, d_unit_start, g.nseg, g.L, g.shift, g.bits,
-                       d_unit_base, (const u64 *)nullptr, 0u, d_overflow, key_base, WnTag{1u, 1u, 0u}, g.mix, peer);
+    if (g.max_units == 0) return;                                            // (before peersP / peersK are read)
+    WcnLaunch a{d_in, nullptr, nullptr, nullptr, g.max_units, g.shift, g.bits, d_unit_base, d_overflow};
+    a.segments(g, d_seg_start, d_unit_start);
+    a.key_base = key_base;
+    a.peer.delta = d_delta;
+    a.peer.owner = d_owner;
+    for (int i = 0; i < nranks && i < SEG_MAX; i++) { a.peer.P[i] = (u64 *)peersP[i]; a.peer.K[i] = (u32 *)peersK[i]; }
+    launch_wcn<false, WN_GR, WN_TPT, WN_THREADS, true>(st, a);
 }
 
 // One narrow-output pass over segments cut into units (run_pass form): 16-byte or narrow input, <= 8 bits (32-tuple lines)
@@ -3305,21 +3317,16 @@ void launch_scatter_units_narrow_peer(hipStream_t st, const void *d_in, const Pa
 void launch_scatter_units_narrow_any(hipStream_t st, const void *d_in, const u32 *d_inK, void *d_outP, u32 *d_outK, const PassGeom &g,
                                      const u64 *d_seg_start, const u32 *d_unit_start, const u64 *d_unit_base, u32 *d_overflow)
 {
-    if (g.max_units == 0) return;
-    allow_big_lds();
+    WcnLaunch a{d_in, d_inK, (u64 *)d_outP, d_outK, g.max_units, g.shift, g.bits, d_unit_base, d_overflow};
+    a.segments(g, d_seg_start, d_unit_start);
     const bool in_narrow = d_inK != nullptr;
-    const WnTag notag{1u, 1u, 0u};
-#define WCN_ARGS (const Tup *)(in_narrow ? nullptr : d_in), (const u64 *)(in_narrow ? d_in : nullptr), d_inK, (u64 *)d_outP, d_outK,    \
-                 d_seg_start, d_unit_start, g.nseg, g.L, g.shift, g.bits, d_unit_base, (const u64 *)nullptr, 0u, d_overflow, (u64)0, notag, g.mix, WnPeer{}
     if (g.bits <= WN_MAX_BITS) {
-        if (in_narrow) hipLaunchKernelGGL(k_scatter_wcn<true>, dim3(g.max_units), dim3(WN_THREADS), wn_lds_bytes(g.bits), st, WCN_ARGS);
-        else hipLaunchKernelGGL(k_scatter_wcn<false>, dim3(g.max_units), dim3(WN_THREADS), wn_lds_bytes(g.bits), st, WCN_ARGS);
+        if (in_narrow) launch_wcn<true>(st, a);
+        else launch_wcn<false>(st, a);
     } else {
-        const size_t lds = wn_lds_bytes(g.bits, WN9_GR, WN9_TPT, WN9_THREADS);
-        if (in_narrow) hipLaunchKernelGGL((k_scatter_wcn<true, WN9_GR, WN9_TPT, WN9_THREADS>), dim3(g.max_units), dim3(WN9_THREADS), lds, st, WCN_ARGS);
-        else hipLaunchKernelGGL((k_scatter_wcn<false, WN9_GR, WN9_TPT, WN9_THREADS>), dim3(g.max_units), dim3(WN9_THREADS), lds, st, WCN_ARGS);
+        if (in_narrow) launch_wcn<true, WN9_GR, WN9_TPT, WN9_THREADS>(st, a);
+        else launch_wcn<false, WN9_GR, WN9_TPT, WN9_THREADS>(st, a);
     }
-#undef WCN_ARGS
 }
 
 // explicit unit ranges [d_rng[u], d_rng[u+1]); tag_groups / tag_div != 0: the low TAG_BITS bits of every payload written are
@@ -3328,26 +3335,16 @@ void launch_scatter_ranges_narrow(hipStream_t st, const void *d_in, bool in_narr
                                   int bits, const u64 *d_unit_base, const u64 *d_rng, u32 *d_overflow, u32 tag_groups,
                                   u32 tag_div, const u32 *d_inK)
 {
-    if (nunits == 0) return;
-    allow_big_lds();
-    u64 *oP = (u64 *)d_out;
-    u32 *oK = (u32 *)((unsigned char *)d_out + narrow_k_offset(n));
-    const WnTag tag = tag_div ? WnTag{tag_groups, tag_div, TAG_BITS} : WnTag{1u, 1u, 0u};
-    if (in_narrow)
-        hipLaunchKernelGGL(k_scatter_wcn<true>, dim3(nunits), dim3(WN_THREADS), wn_lds_bytes(bits), st, (const Tup *)nullptr,
-                           (const u64 *)d_in, d_inK ? d_inK : (const u32 *)((const unsigned char *)d_in + narrow_k_offset(n)), oP, oK,
-                           (const u64 *)nullptr, (const u32 *)nullptr, 0u, (u64)0, shift, bits, d_unit_base, d_rng, nunits,
-                           d_overflow, (u64)0, tag, 0, WnPeer{});
-    else
-        hipLaunchKernelGGL(k_scatter_wcn<false>, dim3(nunits), dim3(WN_THREADS), wn_lds_bytes(bits), st, (const Tup *)d_in,
-                           (const u64 *)nullptr, (const u32 *)nullptr, oP, oK, (const u64 *)nullptr, (const u32 *)nullptr, 0u,
-                           (u64)0, shift, bits, d_unit_base, d_rng, nunits, d_overflow, (u64)0, tag, 0, WnPeer{});
+    if (in_narrow && !d_inK) d_inK = (const u32 *)((const unsigned char *)d_in + narrow_k_offset(n));
+    WcnLaunch a{d_in, in_narrow ? d_inK : nullptr, (u64 *)d_out, (u32 *)((unsigned char *)d_out + narrow_k_offset(n)), nunits, shift, bits,
+                d_unit_base, d_overflow};
+    a.rng = d_rng;
+    if (tag_div) a.tag = WnTag{tag_groups, tag_div, TAG_BITS};
+    if (in_narrow) launch_wcn<true>(st, a);
+    else launch_wcn<false>(st, a);
 }
-int tag_bits() { return (int)TAG_BITS; }
 
 // ---- count-free pass 1 --------------------------------------------------------------------------------------
-u32 cf_per_max() { return CF_PER_MAX; }
-size_t cf_pre_words(u32 units2) { return (size_t)units2 * CF_PRE; }
 static WnFree cf_make(const CfGeom &c, u32 bit, u32 *cnt1, const u32 *pre, const DupSniff &sn)
 {
     WnFree fr;
@@ -3426,106 +3423,45 @@ void launch_join(hipStream_t st, const void *d_R, const u64 *d_startR, const voi
 {
     if (grid == 0) return;
     allow_big_lds();
-    DirectJoin pub{};                                                        // (JK_BKT / JK_BKT_BIG over 16-byte tuples only)
-    pub.host_count = host_pub;
-    pub.done = d_done;
+    Pair *o = (Pair *)d_out;
+    const JoinGeom &G = join_geom(kind);
+    const bool narrow = d_RK != nullptr;                                     // narrow partitions (k_scatter_wcn): d_R, d_S are payload arrays
+    if (narrow && kind == JK_BKT) {
+        // sender tags: the one-table kernel only (the host sees to it)
+        const auto fn = d_tag_base != nullptr ? bkt_kernel<JK_BKT, false, true, true>() : bkt_kernel<JK_BKT, false, true, false>();
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(G.threads), join_lds_bytes(G), st, RelView<true>{(const u64 *)d_R, d_RK},
+                           RelView<true>{(const u64 *)d_S, d_SK}, d_tasks, d_ntasks, radix_bits, o, out_capacity, d_out_count, DirectJoin{},
+                           d_tag_base, d_skip, (const BatchJoinDesc *)nullptr);
+        return;
+    }
+    if (!narrow && (kind == JK_BKT || kind == JK_BKT_BIG)) {
+        DirectJoin pub{};
+        pub.host_count = host_pub;
+        pub.done = d_done;
+        const auto fn = kind == JK_BKT ? bkt_kernel<JK_BKT, false>() : bkt_kernel<JK_BKT_BIG, false>();
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(G.threads), join_lds_bytes(G), st, RelView<false>{(const Tup *)d_R},
+                           RelView<false>{(const Tup *)d_S}, d_tasks, d_ntasks, radix_bits, o, out_capacity, d_out_count, pub,
+                           (const u64 *)nullptr, (const u32 *)nullptr, (const BatchJoinDesc *)nullptr);
+        return;
+    }
+    // What is left is a compact-table launch.  The host never asks for the chunked kernel over narrow partitions, for a narrow-only
+    // geometry over 16-byte tuples or for a kind outside the table; such a request has always run JK_CT, and still does:
+    if (!jk_is_ct(kind) || (!narrow && jk_ct_narrow_only(kind))) kind = JK_CT;
+    if (narrow) {
+        for_ct_kind(kind, [&](auto k) {
+            launch_ct<decltype(k)::value, true>(st, grid, {(const u64 *)d_R, d_RK}, {(const u64 *)d_S, d_SK}, d_tasks, d_ntasks, radix_bits, o,
+                                                out_capacity, d_out_count, d_skip);
+        });
+        return;
+    }
     const RelView<false> vR{(const Tup *)d_R}, vS{(const Tup *)d_S};
-    if (d_RK != nullptr) {                                                   // narrow partitions (k_scatter_wcn): d_R, d_S are payload arrays
-        const RelView<true> nR{(const u64 *)d_R, d_RK}, nS{(const u64 *)d_S, d_SK};
-        Pair *o = (Pair *)d_out;
-#define LAUNCH_BKT_N(TG) hipLaunchKernelGGL((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, false, true, TG>), dim3(grid), \
-            dim3(BJ_THREADS), bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS), st, nR, nS, d_tasks, d_ntasks, radix_bits, o,       \
-            out_capacity, d_out_count, DirectJoin{}, d_tag_base, d_skip)
-#define LAUNCH_CT_N(T, C, B, E) hipLaunchKernelGGL((k_join_ct<T, C, B, E, false, true>), dim3(grid), dim3(T),                        \
-            ct_lds_bytes(T, C, B), st, nR, nS, d_tasks, d_ntasks, radix_bits, o, out_capacity, d_out_count, (u64 *)nullptr, 0u, d_skip)
-        const bool tg = d_tag_base != nullptr;                              // sender tags: the one-table kernel only (the host sees to it)
-        if (kind == JK_BKT) { if (tg) LAUNCH_BKT_N(true); else LAUNCH_BKT_N(false); }
-        else if (kind == JK_CT_HALF) LAUNCH_CT_N(CTH_THREADS, CTH_CHUNK, CTH_BUCKET_BITS, CT_EPT);
-        else if (kind == JK_CT_HALF_WIDE) LAUNCH_CT_N(CTH_THREADS, CTHW_CHUNK, CTHW_BUCKET_BITS, CT_EPT_WIDE);
-        else if (kind == JK_CT_WIDE) LAUNCH_CT_N(CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS, CT_EPT_WIDE);
-        else if (kind == JK_CT_13) LAUNCH_CT_N(CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS, CT_EPT);
-        else if (kind == JK_CT_MID) LAUNCH_CT_N(CT_THREADS, CTM_CHUNK, CTM_BUCKET_BITS, CTM_EPT);
-        else if (kind == JK_CT_HALF_MID) LAUNCH_CT_N(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT);
-        else if (kind == JK_CT_Q12)
-            hipLaunchKernelGGL((k_join_ct<CTH_THREADS, CTQ_CHUNK, CTQ_BUCKET_BITS, CTQ_EPT, false, true, true, CTQ_KB>), dim3(grid), dim3(CTH_THREADS),
-                               ct_lds_bytes(CTH_THREADS, CTQ_CHUNK, CTQ_BUCKET_BITS), st, nR, nS, d_tasks, d_ntasks, radix_bits, o, out_capacity,
-                               d_out_count, (u64 *)nullptr, 0u, d_skip);
-        else if (kind == JK_CT_G13)
-            hipLaunchKernelGGL((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, true, true, CT13_KB>), dim3(grid), dim3(CTH_THREADS),
-                               ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS), st, nR, nS, d_tasks, d_ntasks, radix_bits, o, out_capacity,
-                               d_out_count, (u64 *)nullptr, 0u, d_skip);
-        else if (kind == JK_CT_HALF_MID_G)
-            hipLaunchKernelGGL((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, true, true>), dim3(grid), dim3(CTH_THREADS),
-                               ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS), st, nR, nS, d_tasks, d_ntasks, radix_bits, o, out_capacity,
-                               d_out_count, (u64 *)nullptr, 0u, d_skip);
-        else LAUNCH_CT_N(CT_THREADS, CT_CHUNK, CT_BUCKET_BITS, CT_EPT);     // JK_CT (the host never asks for another kind here)
-#undef LAUNCH_BKT_N
-#undef LAUNCH_CT_N
-        return;
-    }
-    if (kind == JK_BKT) {
-        hipLaunchKernelGGL((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, false>), dim3(grid), dim3(BJ_THREADS),
-                           bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS), st, vR, vS,
-                           d_tasks, d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, pub);
-        return;
-    }
-    if (kind == JK_BKT_BIG) {
-        hipLaunchKernelGGL((k_join_bkt<BJ2_THREADS, BJ2_CHUNK, BJ2_BUCKET_BITS, BJ2_EPT, false>), dim3(grid), dim3(BJ2_THREADS),
-                           bj_lds_bytes(BJ2_THREADS, BJ2_CHUNK, BJ2_BUCKET_BITS), st, vR, vS,
-                           d_tasks, d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, pub);
-        return;
-    }
-    if (kind == JK_CT_HALF_MID) {
-        hipLaunchKernelGGL((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, false>), dim3(grid), dim3(CTH_THREADS),
-                           ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS), st, vR, vS, d_tasks,
-                           d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, (u64 *)nullptr, 0u, (const u32 *)nullptr);
-        return;
-    }
-    if (kind == JK_CT_Q12) {
-        hipLaunchKernelGGL((k_join_ct<CTH_THREADS, CTQ_CHUNK, CTQ_BUCKET_BITS, CTQ_EPT, false, false, true, CTQ_KB>), dim3(grid), dim3(CTH_THREADS),
-                           ct_lds_bytes(CTH_THREADS, CTQ_CHUNK, CTQ_BUCKET_BITS), st, vR, vS, d_tasks,
-                           d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, (u64 *)nullptr, 0u, (const u32 *)nullptr);
-        return;
-    }
-    if (kind == JK_CT_G13) {
-        hipLaunchKernelGGL((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, false, true, CT13_KB>), dim3(grid), dim3(CTH_THREADS),
-                           ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS), st, vR, vS, d_tasks,
-                           d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, (u64 *)nullptr, 0u, (const u32 *)nullptr);
-        return;
-    }
-    if (kind == JK_CT_HALF_MID_G) {
-        hipLaunchKernelGGL((k_join_ct<CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS, CTM_EPT, false, false, true>), dim3(grid), dim3(CTH_THREADS),
-                           ct_lds_bytes(CTH_THREADS, CTHM_CHUNK, CTHM_BUCKET_BITS), st, vR, vS, d_tasks,
-                           d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, (u64 *)nullptr, 0u, (const u32 *)nullptr);
-        return;
-    }
-    if (kind == JK_CT_MID) {
-        hipLaunchKernelGGL((k_join_ct<CT_THREADS, CTM_CHUNK, CTM_BUCKET_BITS, CTM_EPT, false, false>), dim3(grid), dim3(CT_THREADS),
-                           ct_lds_bytes(CT_THREADS, CTM_CHUNK, CTM_BUCKET_BITS), st, vR, vS, d_tasks,
-                           d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, (u64 *)nullptr, 0u, (const u32 *)nullptr);
-        return;
-    }
-    if (kind == JK_CT_13) {
-        hipLaunchKernelGGL((k_join_ct<CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS, CT_EPT, false, false>), dim3(grid), dim3(CT_THREADS),
-                           ct_lds_bytes(CT_THREADS, CT13_CHUNK, CT13_BUCKET_BITS), st, vR, vS, d_tasks,
-                           d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, (u64 *)nullptr, 0u, (const u32 *)nullptr);
-        return;
-    }
-    if (kind == JK_CT_HALF) {
-        hipLaunchKernelGGL((k_join_ct<CTH_THREADS, CTH_CHUNK, CTH_BUCKET_BITS, CT_EPT, false, false>), dim3(grid), dim3(CTH_THREADS),
-                           ct_lds_bytes(CTH_THREADS, CTH_CHUNK, CTH_BUCKET_BITS), st, vR, vS, d_tasks,
-                           d_ntasks, radix_bits, (Pair *)d_out, out_capacity, d_out_count, (u64 *)nullptr, 0u, (const u32 *)nullptr);
-        return;
-    }
     static const bool want_stamps = getenv("RHJ_CT_STAMPS") != nullptr;
     const u32 nw = grid < 4096 ? grid : 4096;
     u64 *d_st = nullptr;
-    if (want_stamps && hipMalloc(&d_st, (size_t)nw * CT_NSTAMP * 8) != hipSuccess) { (void)hipGetLastError(); d_st = nullptr; }
+    if (want_stamps && kind == JK_CT && hipMalloc(&d_st, (size_t)nw * CT_NSTAMP * 8) != hipSuccess) { (void)hipGetLastError(); d_st = nullptr; }
     if (d_st != nullptr) {                                                   // tuning aid: phase timeline of the first workgroups
         (void)hipMemsetAsync(d_st, 0, (size_t)nw * CT_NSTAMP * 8, st);
-        hipLaunchKernelGGL((k_join_ct<CT_THREADS, CT_CHUNK, CT_BUCKET_BITS, CT_EPT, true, false>), dim3(grid), dim3(CT_THREADS),
-                           ct_lds_bytes(), st, vR, vS, d_tasks, d_ntasks, radix_bits,
-                           (Pair *)d_out, out_capacity, d_out_count, d_st, nw, (const u32 *)nullptr);
+        launch_ct<JK_CT, false, true>(st, grid, vR, vS, d_tasks, d_ntasks, radix_bits, o, out_capacity, d_out_count, nullptr, d_st, nw);
         std::vector<u64> h((size_t)nw * CT_NSTAMP);
         (void)hipMemcpyAsync(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost, st);
         (void)hipStreamSynchronize(st);
@@ -3548,9 +3484,10 @@ void launch_join(hipStream_t st, const void *d_R, const u64 *d_startR, const voi
         }
         return;
     }
-    hipLaunchKernelGGL((k_join_ct<CT_THREADS, CT_CHUNK, CT_BUCKET_BITS, CT_EPT, false, false>), dim3(grid), dim3(CT_THREADS),
-                       ct_lds_bytes(), st, vR, vS, d_tasks, d_ntasks, radix_bits,
-                       (Pair *)d_out, out_capacity, d_out_count, (u64 *)nullptr, 0u, (const u32 *)nullptr);
+    for_ct_kind(kind, [&](auto k) {                                          // (a 16-byte join is never repeated in another format: no skip word)
+        constexpr int K = decltype(k)::value;                               // (kind is not narrow-only here: see above)
+        if constexpr (ct_exists<K, false>) launch_ct<K, false>(st, grid, vR, vS, d_tasks, d_ntasks, radix_bits, o, out_capacity, d_out_count, nullptr);
+    });
 }
 
 // Unpartitioned join of two small relations in ONE launch: build side = S when nR >= nS (JobScheduler.cpp:187).
@@ -3568,10 +3505,10 @@ void launch_join_direct(hipStream_t st, const void *d_R, u64 nR, const void *d_S
     dj.np = (u32)(dj.build_is_S ? nR : nS);
     dj.split = (u32)BJ_TILE;
     const u32 grid = (dj.np + dj.split - 1) / dj.split;
-    hipLaunchKernelGGL((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, true>), dim3(grid), dim3(BJ_THREADS),
-                       bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS), st, RelView<false>{(const Tup *)d_R},
-                       RelView<false>{(const Tup *)d_S}, (const JoinTask *)nullptr, (const u32 *)nullptr, 0, (Pair *)d_out,
-                       out_capacity, d_out_count, dj);
+    hipLaunchKernelGGL((bkt_kernel<JK_BKT, true>()), dim3(grid), dim3(BJ_THREADS), join_lds_bytes(JOIN_GEOM[JK_BKT]), st,
+                       RelView<false>{(const Tup *)d_R}, RelView<false>{(const Tup *)d_S}, (const JoinTask *)nullptr, (const u32 *)nullptr, 0,
+                       (Pair *)d_out, out_capacity, d_out_count, dj, (const u64 *)nullptr, (const u32 *)nullptr,
+                       (const BatchJoinDesc *)nullptr);
 }
 
 // up to 16 direct joins in one launch: d_batch = BatchJoinDesc[njoins] in HBM, max_blocks = the largest nblocks among them
@@ -3579,12 +3516,11 @@ void launch_join_batch(hipStream_t st, const BatchJoinDesc *d_batch, u32 njoins,
 {
     if (njoins == 0 || max_blocks == 0) return;
     allow_big_lds();
-    hipLaunchKernelGGL((k_join_bkt<BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS, BJ_EPT, true, false, false, true>), dim3(max_blocks, njoins),
-                       dim3(BJ_THREADS), bj_lds_bytes(BJ_THREADS, BJ_CHUNK, BJ_BUCKET_BITS), st, RelView<false>{nullptr},
-                       RelView<false>{nullptr}, (const JoinTask *)nullptr, (const u32 *)nullptr, 0, (Pair *)nullptr, (u64)0,
-                       (u64 *)nullptr, DirectJoin{}, (const u64 *)nullptr, (const u32 *)nullptr, d_batch);
+    hipLaunchKernelGGL((bkt_kernel<JK_BKT, true, false, false, true>()), dim3(max_blocks, njoins), dim3(BJ_THREADS),
+                       join_lds_bytes(JOIN_GEOM[JK_BKT]), st, RelView<false>{nullptr}, RelView<false>{nullptr}, (const JoinTask *)nullptr,
+                       (const u32 *)nullptr, 0, (Pair *)nullptr, (u64)0, (u64 *)nullptr, DirectJoin{}, (const u64 *)nullptr,
+                       (const u32 *)nullptr, d_batch);
 }
-u32 join_direct_tile() { return (u32)BJ_TILE; }
 
 static unsigned stream_grid(u64 n)
 {

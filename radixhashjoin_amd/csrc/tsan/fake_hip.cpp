@@ -149,14 +149,6 @@ hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.001f
 static const u64 FAKE_PAIRS = (u64)1 << 20;
 struct FPair { u64 r, s; };
 
-bool fused_two_pass_ok(int b1, int b2) { return b1 >= 1 && b2 >= 1 && b1 <= 9 && b2 <= 9 && b1 + b2 <= 16; }
-u32 join_probe_split(int kind) { return jk_is_ct(kind) ? 16384u : 0u; }
-u32 join_table_tuples(int kind) { return jk_is_ct(kind) ? 16352u : kind == JK_BKT_BIG ? 8448u : (u32)BJ_CHUNK; }
-int join_ct_min_radix_bits(int kind) { return kind == JK_CT_G13 ? 13 : kind == JK_CT_Q12 ? 12 : 16; }
-int seg_max() { return 16; }
-int tag_bits() { return 4; }
-bool narrow_pass_ok(int bits) { return bits >= 1 && bits <= 8; }
-bool narrow_pass9_ok(int bits) { return bits >= 1 && bits <= 9; }
 const char *launch_attr_error() { return nullptr; }
 size_t scan_tmp_bytes(int bits) { return (size_t)64 * ((size_t)8 << bits); }
 size_t part_lds_bytes(int) { return 0; }
@@ -214,7 +206,6 @@ void launch_join_batch(hipStream_t st, const BatchJoinDesc *d_batch, u32 njoins,
         }
     });
 }
-u32 join_direct_tile() { return 4096; }
 void launch_checksum(hipStream_t, const void *, u64, u64 *) {}
 void launch_generate(hipStream_t, int, void *, u64, u64, u64, u64, double) {}
 void launch_expected_pkfk(hipStream_t, const void *, u64, u64 *) {}
@@ -224,8 +215,6 @@ void launch_pass_pair(hipStream_t st, const PassPairHost &h, int, int, int phase
     u64 *z = h.zero8;
     if (phase == 0 && z) fake_enqueue(st, [=] { memset(z, 0, 64); });      // (the first launch clears the join counters)
 }
-u32 cf_per_max() { return 64; }
-size_t cf_pre_words(u32 units2) { return (size_t)units2 * 65; }
 void launch_cf_pass1(hipStream_t, const void *, void *, const CfGeom &, const PassGeom &, const u64 *, const u32 *, u32 *, u32 *, u32, const DupSniff &) {}
 void launch_cf_tables(hipStream_t, const CfGeom &, u32, const u32 *, u32 *, u32 *, u64 *, u32 *, const u32 *) {}
 void launch_cf_hist2(hipStream_t, const void *, const CfGeom &, u32, int, int, const u32 *, u32 *, const u32 *) {}

@@ -137,7 +137,10 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * the rows of JOIN_GEOM in radixhashjoin_amd/csrc/rhj_internal.h), "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home; 0: the plain path),
  * "last.max_part_R" / "last.max_part_S" (tuples in the largest partition of each side the last partitioned join saw; 0 for
- * an unpartitioned one), "partition.mix" (0 / 1: what joins on this context do) */
+ * an unpartitioned one), "last.cols_R" / "last.cols_S" (how the last join read that side: 0 it was not a columnar call -- every join
+ * and stage call other than rhj_join_cols_dev leaves 0, as does a columnar call with an empty side; 1 the partition kernels read the side's column(s) directly; 2 the side was first
+ * materialised as 16-byte tuples in the workspace; see rhj_join_cols_dev for which plans are direct),
+ * "partition.mix" (0 / 1: what joins on this context do) */
 int  rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value);
 int  rhj_get_timings(rhj_ctx *ctx, rhj_timings *out);
 /* the same per LAUNCH, in launch order: kinds[i] (rhj_kernel_kind) and ms[i] of the first min(*n, capacity) timed spans of the
@@ -178,6 +181,23 @@ int rhj_join_batch(rhj_ctx *ctx, uint32_t n, const rhj_join_desc *joins, void **
  * out_capacity is too small; call again with a larger buffer. */
 int rhj_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                  const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count);
+
+/* ---- rhj_join_dev with each relation given as COLUMNS in HBM: d_val?[i] = join value of tuple i, d_id?[i] = its rowID, or
+ * d_id? == NULL: rowID = i (a stored, unfiltered relation; a torch tensor of keys).  Same pair multiset, count-only mode,
+ * RHJ_E_OVERFLOW contract, plan / options / timings / "last.*" reporting as rhj_join_dev on the tuples {id[i] or i, val[i]}.
+ * The two sides are independent (one may carry ids, the other not).  A side with n == 0: count 0; a NULL value column with
+ * n > 0: RHJ_E_INVALID.  Inputs are neither modified nor retained.
+ * DIRECT plans ("last.cols_*" == 1): every two-pass plan of at most 8 + 8 bits that runs in a narrow format ("partition.narrow"
+ * level 1 or 2: automatically from 8 * 10^6 tuples on the larger side, rowIDs below 2^32) -- the first kernels of the partition
+ * (the two-pass histogram, pass 1 with exact cursors or count-free, on one stream or two) read the value column, 8 B per tuple,
+ * and the id column as a second 8-byte stream, or nothing at all for NULL ids; a side that is partitioned again after a
+ * count-free overflow is read from its columns again.  MATERIALISED ("last.cols_*" == 2): unpartitioned and direct joins,
+ * one-pass plans, two-pass plans in the 16-byte format, 17-18-bit plans, and the 16-byte repeat of a join that met a rowID
+ * >= 2^32: one linear kernel writes the side as 16-byte tuples into a grow-only workspace buffer (rhj_release_workspace frees
+ * it), only for the side and at the moment a path asks, and the join continues exactly as rhj_join_dev. */
+int rhj_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                      const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+                      const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:

@@ -6,6 +6,9 @@ The product is the C-ABI shared library ``librhj_hip.so`` (hand-written HIP kern
 only the thin ctypes binding used by tests, ``bench.py`` and the multi-GPU driver; there is NO
 CPU fallback: if the HIP library is missing or no GPU is present, construction of an
 :class:`Engine` raises.
+
+From torch: ``idx_R, idx_S = Engine(0).join_columns(keys_R, keys_S)`` joins two int64 key tensors on the engine's device
+(``rhj_join_cols_dev``: the relations as columns, rowID = index).
 """
 from .binding import (  # noqa: F401
     PAIR,

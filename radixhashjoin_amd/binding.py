@@ -74,6 +74,7 @@ SYMBOLS = {
     "rhj_join": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(Opts), _P(_vp), _P(_u64)]),
     "rhj_join_batch": (C.c_int, [_vp, C.c_uint32, _P(JoinDesc), _P(_vp), _P(_u64)]),
     "rhj_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -246,6 +247,8 @@ class Engine:
     def __init__(self, device=0):
         self.lib = load_library()
         self.ctx = None
+        self.device = device
+        self.bound_stream = None        # the caller's stream set_stream bound the context to (None: the context's own stream)
         c = _vp()
         rc = self.lib.rhj_init(device, C.byref(c))
         if rc != RHJ_OK:
@@ -270,14 +273,16 @@ class Engine:
 
     # ---- context ------------------------------------------------------------------------------
     def set_stream(self, raw_stream):
+        """rhj_set_stream: run on a caller-owned hipStream_t; None / 0: the context's own stream.  Synchronises the stream in use."""
         self._chk(self.lib.rhj_set_stream(self.ctx, raw_stream))
+        self.bound_stream = raw_stream or None
 
     def set_option(self, name, value):
         """tuning / test knobs of include/rhj.h (results never depend on them)"""
         self._chk(self.lib.rhj_set_option(self.ctx, name.encode(), int(value)))
 
     def info(self, name):
-        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.join_kernel"; include/rhj.h)"""
+        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel"; include/rhj.h)"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
         return v.value
@@ -388,6 +393,57 @@ class Engine:
                                    C.byref(opts) if opts is not None else None, _addr(d_out), capacity, C.byref(n))
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
+
+    def join_cols_dev(self, d_valR, d_idR, nR, d_valS, d_idS, nS, d_out=None, capacity=0, opts=None, allow_overflow=False):
+        """rhj_join_cols_dev: join_dev with each relation as columns in HBM (uint64 join values; uint64 rowIDs, or None: the
+        rowID of a tuple is its index)"""
+        n = _u64()
+        rc = self.lib.rhj_join_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), _addr(d_idS), nS,
+                                        C.byref(opts) if opts is not None else None, _addr(d_out), capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def join_columns(self, keys_R, keys_S):
+        """Equi-join of two key tensors: (idx_R, idx_S), int64 tensors with keys_R[idx_R[i]] == keys_S[idx_S[i]] for every i,
+        every matching index pair exactly once, in no particular order.  keys_R / keys_S: contiguous 1-D 64-bit integer torch
+        tensors on this engine's device, compared by bit pattern.  Count, allocate, join -- ordered behind the work torch has queued
+        on its current stream: on a stream of its own (torch.cuda.stream(s)) the engine runs on that stream for the length of the call;
+        torch's default stream has no handle to hand over (its raw value is 0, which rhj_set_stream reads as "the context's own
+        stream"), so there the call waits on the host for the stream first and runs on the stream the engine has.  Either way the
+        results are complete when it returns, and a stream bound earlier with set_stream is bound again."""
+        import torch
+        ints = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)
+        for name, k in (("keys_R", keys_R), ("keys_S", keys_S)):
+            if not isinstance(k, torch.Tensor) or k.dtype not in ints or k.dim() != 1:
+                raise ValueError(f"{name}: a 1-D torch tensor of 64-bit integers is needed")
+            if k.device.type != "cuda" or (k.device.index or 0) != self.device:
+                raise ValueError(f"{name}: the tensor must live on the engine's device (cuda:{self.device}), not {k.device}")
+            if not k.is_contiguous():
+                raise ValueError(f"{name}: the tensor must be contiguous")
+        dev = keys_R.device
+        nR, nS = keys_R.numel(), keys_S.numel()
+        with torch.cuda.device(dev):
+            torch_stream = torch.cuda.current_stream(dev)
+            cur, before = torch_stream.cuda_stream, self.bound_stream
+            if cur == 0:
+                torch_stream.synchronize()      # the keys are written, and no queued torch work still uses a block torch.empty may hand out
+            elif cur != before:
+                self.set_stream(cur)
+            try:
+                count = self.join_cols_dev(keys_R, None, nR, keys_S, None, nS) if nR and nS else 0
+                idx_R = torch.empty(count, dtype=torch.int64, device=dev)
+                idx_S = torch.empty(count, dtype=torch.int64, device=dev)
+                if count:
+                    pairs = torch.empty((count, 2), dtype=torch.int64, device=dev)
+                    got = self.join_cols_dev(keys_R, None, nR, keys_S, None, nS, pairs, count)
+                    assert got == count, (got, count)
+                    self.pairs_split(pairs, count, idx_R, idx_S)
+            finally:
+                if cur != 0 and cur != before:
+                    self.set_stream(before)     # (synchronises torch's stream first: the results are complete)
+                else:
+                    self.sync()
+        return idx_R, idx_S
 
     def histogram(self, d_rel, n, shift, bits, d_hist):
         self._chk(self.lib.rhj_histogram(self.ctx, _addr(d_rel), n, shift, bits, _addr(d_hist)))

@@ -247,6 +247,12 @@ struct rhj_ctx {
     u32 cf_over = 0;                   // the skip word as join_phase read it (bits 1, 2)
     int last_cf[2] = {0, 0};           // "last.countfree_R/_S": 0 exact, 1 count-free, 2 tried and fell back
     DevBuf cf_cnt1, cf_pre, cf_tot;
+    // rhj_join_cols_dev: the relations of the join in progress as columns (val == nullptr: a 16-byte call); the 16-byte copy of
+    // a side that a plan without a columnar first kernel asks for (converted on first use, once per call); "last.cols_R/_S"
+    ColsIn cols_in[2];
+    DevBuf cols_aos[2];
+    bool cols_aos_done[2] = {false, false};
+    int last_cols[2] = {0, 0};         // 0: not a columnar call, 1: the partition kernels read the columns, 2: converted first
     // multi-GPU receiver (rhj_shard_partition / rhj_shard_join): the partitions carry sender tags
     int shard_nseg = 0, shard_mode[2] = {0, 0};
     bool shard_side_done[2] = {false, false};
@@ -437,6 +443,7 @@ void prof_reset(rhj_ctx *ctx)
         ctx->prof.kinds.clear();
     }
     memset(&ctx->last, 0, sizeof(ctx->last));
+    ctx->last_cols[0] = ctx->last_cols[1] = 0;      // "last.cols_*": every join or stage call starts here; rhj_join_cols_dev sets them as it goes
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -657,7 +664,8 @@ int run_pass_pair(rhj_ctx *ctx, const void *d_R, u64 nR, void *outR, u64 *psR, c
 // Two passes with ONE histogram read (k_hist2d_units): used when both passes fit the write-combining scatter
 // and b1 + b2 <= 16.  Pass-2 units = pieces of each pass-1 bucket written by groups of pass-1 units.
 // narrow: 0 = 16-byte tuples throughout; 1 = pass 2 writes the narrow format (what the join kernel then reads); 2 = pass 1 too
-// Input: 16-byte tuples (in.aos), or -- the multi-GPU receiver -- narrow arrays that arrived in nseg sender segments
+// Input: 16-byte tuples (in.aos), the same relation as columns (in.cols: the histogram and pass 1 read them directly, narrow
+// level 1 or 2, exact cursors or count-free; everything behind pass 1 is unchanged), or -- the multi-GPU receiver -- narrow arrays that arrived in nseg sender segments
 // (in.P / in.K / in.seg_off; narrow is then 2): pass-1 units are cut at the segment boundaries and pass 2 writes the sender
 // number into the low payload bits (k_scatter_wcn's WnTag), which the join kernels resolve into global rowIDs.
 // the scratch tables one relation's fused two-pass partition works in, and the stream it runs on
@@ -678,6 +686,7 @@ PartScratch second_scratch(rhj_ctx *ctx)
 
 struct FusedIn {
     const void *aos = nullptr;
+    ColsIn cols;                       // ... or (cols.val != nullptr) the caller's relation as columns: rhj_join_cols_dev
     const u64 *P = nullptr;
     const u32 *K = nullptr;
     int nseg = 0;
@@ -736,7 +745,7 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
            &x_scan_tmp = *sc.scan_tmp, &x_hist2 = *sc.hist2, &x_grp_rng = *sc.grp_rng, &x_unit_start2 = *sc.unit_start2,
            &x_ps_1 = *sc.ps_1, &x_part_tmp = *sc.part_tmp, &x_seg_rng = *sc.seg_rng;
     const hipStream_t st = sc.st;
-    const bool segs = in.P != nullptr;
+    const bool segs = in.P != nullptr, cols = in.cols.val != nullptr;
     PassGeom g1 = make_geom(n, 1, 0, b1, PART_TARGET_UNITS / 2);           // (see fused_units)
     g1.mix = segs ? MIX_NONE : mix;
     static const u32 want_groups = (u32)env_u64("RHJ_GROUPS", 16, 1, 64);                          // tuning aid
@@ -809,7 +818,8 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
         const u32 *pre = (const u32 *)ctx->cf_pre.p;
         {
             Span s(ctx, RHJ_K_SCATTER);
-            launch_cf_pass1(st, in.aos, x_part_tmp.p, cg, g1, seg0, unit_start1, (u32 *)ctx->cf_cnt1.p, wide, 2u << cf_side, sn);
+            if (cols) launch_cf_pass1_cols(st, in.cols, x_part_tmp.p, cg, g1, seg0, unit_start1, (u32 *)ctx->cf_cnt1.p, wide, 2u << cf_side, sn);
+            else launch_cf_pass1(st, in.aos, x_part_tmp.p, cg, g1, seg0, unit_start1, (u32 *)ctx->cf_cnt1.p, wide, 2u << cf_side, sn);
         }
         {
             Span s(ctx, RHJ_K_AUX);
@@ -835,8 +845,12 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
     }
     {
         Span s(ctx, RHJ_K_HIST);                        // (16-byte input: also reports a rowID that does not fit the narrow format)
-        launch_hist2d_units(st, segs ? (const void *)in.P : in.aos, segs, n, g1.L, units1, b1, b2, per, ngroups,
-                            (u32 *)x_unit_hist.p, (u32 *)x_hist2.p, 0, wide, rng1, g1.mix, sn);
+        if (cols)
+            launch_hist2d_units_cols(st, in.cols, n, g1.L, units1, b1, b2, per, ngroups, (u32 *)x_unit_hist.p, (u32 *)x_hist2.p, wide,
+                                     g1.mix, sn);
+        else
+            launch_hist2d_units(st, segs ? (const void *)in.P : in.aos, segs, n, g1.L, units1, b1, b2, per, ngroups,
+                                (u32 *)x_unit_hist.p, (u32 *)x_hist2.p, 0, wide, rng1, g1.mix, sn);
     }
     {
         Span s(ctx, RHJ_K_SCAN);
@@ -848,6 +862,10 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
         if (segs)
             launch_scatter_ranges_narrow(st, in.P, true, x_part_tmp.p, n, units1, 0, b1, (const u64 *)x_unit_base.p,
                                          rng1, wide, 0, 0, in.K);
+        else if (cols && narrow == 2)
+            launch_scatter_units_narrow_cols(st, in.cols, x_part_tmp.p, n, g1, seg0, unit_start1, (const u64 *)x_unit_base.p, wide);
+        else if (cols)
+            launch_scatter_units_cols(st, in.cols, x_part_tmp.p, g1, seg0, unit_start1, (const u64 *)x_unit_base.p);
         else if (narrow == 2)
             launch_scatter_units_narrow(st, in.aos, x_part_tmp.p, n, g1, seg0, unit_start1, (const u64 *)x_unit_base.p,
                                         wide);
@@ -1083,6 +1101,35 @@ int cf_side_for(rhj_ctx *ctx, int side, u64 nR, u64 nS, const rhj_opts &plan, in
     return side;
 }
 
+// A relation of a columnar join (rhj_join_cols_dev; a 16-byte call passes through both unchanged).  fused_input: for
+// partition_relation_fused, whose first kernels read the columns themselves ("last.cols" 1).  cols_to_aos: for every other path --
+// d becomes the side's 16-byte copy in the workspace, converted by one linear kernel the first time the call asks ("last.cols" 2).
+FusedIn fused_input(rhj_ctx *ctx, int side, const void *d)
+{
+    FusedIn in;
+    in.aos = d;
+    if (!d && ctx->cols_in[side].val) { in.cols = ctx->cols_in[side]; ctx->last_cols[side] = 1; }   // (d != nullptr: converted already)
+    return in;
+}
+int cols_to_aos(rhj_ctx *ctx, int side, u64 n, const void *&d)
+{
+    if (!ctx->cols_in[side].val) return RHJ_OK;
+    ctx->last_cols[side] = 2;
+    if (!ctx->cols_aos_done[side]) {
+        RHJCHK(ensure(ctx, ctx->cols_aos[side], (size_t)(n ? n : 1) * 16));
+        Span s(ctx, RHJ_K_AUX);
+        launch_cols_to_tuples(ctx->stream, ctx->cols_in[side], n, ctx->cols_aos[side].p);
+        ctx->cols_aos_done[side] = true;
+    }
+    d = ctx->cols_aos[side].p;
+    return RHJ_OK;
+}
+int cols_to_aos(rhj_ctx *ctx, u64 nR, const void *&d_R, u64 nS, const void *&d_S)
+{
+    RHJCHK(cols_to_aos(ctx, 0, nR, d_R));
+    return cols_to_aos(ctx, 1, nS, d_S);
+}
+
 // Partition phase of a join: leaves ctx->cur_* describing partitioned R and S.
 // before_S (optional, consumed by the first call that gets it): invoked once, after the kernels that partition R have been
 // enqueued and before anything reads S -- rhj_join uploads S there, so that S crosses PCIe while R is being partitioned
@@ -1113,6 +1160,8 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
         Span s(ctx, RHJ_K_AUX);
         HIPCHK(ctx, hipMemsetAsync(ctx->narrow_flag.p, 0, 64, ctx->stream));
     }
+    // a columnar join: the fused two-pass path in a narrow format reads the columns; every other path takes 16-byte copies
+    if (!(plan.passes == 2 && ctx->cur_narrow && narrow_fused_plan(plan))) RHJCHK(cols_to_aos(ctx, nR, d_R, nS, d_S));
     if (plan.passes == 0) {
         RHJCHK(s_ready());
         RHJCHK(ensure(ctx, ctx->ps_R, 64));
@@ -1160,10 +1209,12 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
             HIPCHK(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->aux_ev[0], 0));
             const PartScratch s2 = second_scratch(ctx);
             ctx->sniff_side = sniff ? 0 : -1;
-            int prc = partition_relation_fused(ctx, d_R, nR, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p, ctx->cur_narrow, mix);
+            int prc = partition_relation_fused(ctx, fused_input(ctx, 0, d_R), nR, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p,
+                                               ctx->cur_narrow, mix);
             ctx->sniff_side = sniff ? 1 : -1;
             if (prc == RHJ_OK)
-                prc = partition_relation_fused(ctx, d_S, nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p, ctx->cur_narrow, mix, &s2);
+                prc = partition_relation_fused(ctx, fused_input(ctx, 1, d_S), nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p,
+                                               ctx->cur_narrow, mix, &s2);
             ctx->sniff_side = -1;
             RHJCHK(prc);
             ctx->sniff_ready = sniff;
@@ -1175,13 +1226,13 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
             ctx->sniff_side = sniff ? 0 : -1;
             int prc = RHJ_OK;
             if (!keep_R)                                        // (the repeat after an overflow of S alone: R stands, samples included)
-                prc = partition_relation_fused(ctx, d_R, nR, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p, ctx->cur_narrow, mix,
-                                               nullptr, cf_side_for(ctx, 0, nR, nS, plan, mix));
+                prc = partition_relation_fused(ctx, fused_input(ctx, 0, d_R), nR, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p,
+                                               ctx->cur_narrow, mix, nullptr, cf_side_for(ctx, 0, nR, nS, plan, mix));
             if (prc == RHJ_OK) prc = s_ready();
             ctx->sniff_side = sniff ? 1 : -1;
             if (prc == RHJ_OK)
-                prc = partition_relation_fused(ctx, d_S, nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p, ctx->cur_narrow, mix,
-                                               nullptr, cf_side_for(ctx, 1, nR, nS, plan, mix));
+                prc = partition_relation_fused(ctx, fused_input(ctx, 1, d_S), nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p,
+                                               ctx->cur_narrow, mix, nullptr, cf_side_for(ctx, 1, nR, nS, plan, mix));
             ctx->sniff_side = -1;
             RHJCHK(prc);
             ctx->sniff_ready = sniff;
@@ -1332,6 +1383,7 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
         f.swap(*before_S);
         RHJCHK(f());
     }
+    RHJCHK(cols_to_aos(ctx, nR, d_R, nS, d_S));              // (a columnar join: no columnar form of the one-pass kernels)
     ctx->cur_nR = nR;
     ctx->cur_nS = nS;
     ctx->last.passes = 1;
@@ -1572,7 +1624,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->counters, &ctx->out_pairs, &ctx->small_out, &ctx->hist_tmp, &ctx->scan_tmp, &ctx->hist2,
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
-                     &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
+                     &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
                      &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1]};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
@@ -1653,6 +1705,8 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.narrow") { *value = ctx->cur_narrow; return RHJ_OK; }
     if (n == "last.countfree_R") { *value = ctx->last_cf[0]; return RHJ_OK; }
     if (n == "last.countfree_S") { *value = ctx->last_cf[1]; return RHJ_OK; }
+    if (n == "last.cols_R") { *value = ctx->last_cols[0]; return RHJ_OK; }
+    if (n == "last.cols_S") { *value = ctx->last_cols[1]; return RHJ_OK; }
     if (n == "last.join_kernel") { *value = ctx->last_join_kind; return RHJ_OK; }
     if (n == "last.pipelined") { *value = ctx->last_pipelined; return RHJ_OK; }
     if (n == "last.max_part_R") { *value = (int64_t)ctx->last_max_part[0]; return RHJ_OK; }
@@ -1762,6 +1816,31 @@ int rhj_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tupl
     rhj_opts plan;
     if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
     RHJCHK(partition_and_join(ctx, d_R, nR, d_S, nS, plan, d_out, d_out ? out_capacity : 0, (u64 *)out_count));
+    if (d_out && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
+    return RHJ_OK;
+}
+
+// rhj_join_dev on relations given as columns.  The columns stay in the context for the length of the call: partition_phase and
+// the one-pass join hand them to the kernels that read columns (fused_input) or convert the side they need (cols_to_aos), also
+// when a join repeats itself (count-free overflow: columns again; wide rowID: the 16-byte copy).
+int rhj_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR, const uint64_t *d_valS,
+                      const uint64_t *d_idS, uint64_t nS, const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity,
+                      uint64_t *out_count)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
+    *out_count = 0;
+    prof_reset(ctx);
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    if (nR == 0 || nS == 0) return join_nothing(ctx);
+    rhj_opts plan;
+    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
+    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = partition_and_join(ctx, nullptr, nR, nullptr, nS, plan, d_out, d_out ? out_capacity : 0, (u64 *)out_count);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    RHJCHK(rc);
     if (d_out && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
     return RHJ_OK;
 }

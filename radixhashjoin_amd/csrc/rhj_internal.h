@@ -69,6 +69,9 @@ constexpr u32 TAG_BITS = 4, TAG_MAX = 1u << TAG_BITS;   // sender tags in the lo
 constexpr int seg_max() { return SEG_MAX; }
 constexpr int tag_bits() { return (int)TAG_BITS; }
 
+// a relation given as COLUMNS (rhj_join_cols_dev): val[i] = join value of tuple i, id[i] = its rowID, id == nullptr: rowID = i
+struct ColsIn { const u64 *val = nullptr, *id = nullptr; };
+
 // launchers (all asynchronous on `st`)
 void launch_init_single_segment(hipStream_t st, u64 n, u64 L, u64 *d_seg_start, u32 *d_unit_start);
 // DupSniff: which side of a join has duplicate join values -- asked of the data, by the histogram kernels that read every tuple
@@ -231,6 +234,16 @@ static_assert(join_geom_ok(JK_LAST), "a JOIN_GEOM row breaks what its kernel nee
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,
                          u32 units_per_group, u32 ngroups, u32 *d_hist1, u32 *d_hist2, u64 key_base, u32 *d_wide,
                          const u64 *d_unit_rng, int mix = 0, const DupSniff &sniff = DupSniff());
+// the kernels that may be the first to touch a caller's relation on the fused two-pass path, reading COLUMNS: the exact-cursor
+// histogram, pass 1 with a 16-byte (narrow level 1) or narrow (level 2) intermediate, the count-free pass 1; and the
+// conversion the other plans start with.  Same geometry, tables and outputs as the 16-byte forms they stand beside.
+void launch_hist2d_units_cols(hipStream_t st, const ColsIn &cols, u64 n, u64 L, u32 units, int b1, int b2, u32 units_per_group,
+                              u32 ngroups, u32 *d_hist1, u32 *d_hist2, u32 *d_wide, int mix, const DupSniff &sniff);
+void launch_scatter_units_cols(hipStream_t st, const ColsIn &cols, void *d_out, const PassGeom &g, const u64 *d_seg_start,
+                               const u32 *d_unit_start, const u64 *d_unit_base);
+void launch_scatter_units_narrow_cols(hipStream_t st, const ColsIn &cols, void *d_out, u64 n, const PassGeom &g, const u64 *d_seg_start,
+                                      const u32 *d_unit_start, const u64 *d_unit_base, u32 *d_overflow);
+void launch_cols_to_tuples(hipStream_t st, const ColsIn &cols, u64 n, void *d_out);
 void launch_seg_units(hipStream_t st, u32 nseg, const u64 *seg_off, const u64 *seg_L, u32 units_per_seg, u64 *d_unit_rng,
                       u64 *d_seg_start, u32 *d_unit_start);
 void launch_make_group_ranges(hipStream_t st, const u64 *d_unit_base1, u32 nb1, u32 units_per_group, u32 ngroups, u64 n,
@@ -271,6 +284,8 @@ constexpr u32 cf_per_max() { return CF_PER_MAX; }
 constexpr size_t cf_pre_words(u32 units2) { return (size_t)units2 * CF_PRE; }
 void launch_cf_pass1(hipStream_t st, const void *d_in, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
                      const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff);
+void launch_cf_pass1_cols(hipStream_t st, const ColsIn &cols, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
+                          const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff);
 void launch_cf_tables(hipStream_t st, const CfGeom &c, u32 nb1, const u32 *d_cnt1, u32 *d_pre, u32 *d_unit_tot, u64 *d_ps_1,
                       u32 *d_unit_start2, const u32 *d_flag);
 void launch_cf_hist2(hipStream_t st, const void *d_tmp, const CfGeom &c, u32 nb1, int b1, int b2, const u32 *d_pre, u32 *d_hist2,

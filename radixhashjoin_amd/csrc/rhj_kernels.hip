@@ -18,9 +18,12 @@
 // k_scatter_wcn          the same scatter writing the narrow {payload 8 B, rowID 4 B} format inside a join: 32-tuple carry lines for
 //                        <= 8-bit passes, 16-tuple lines for 9-bit passes (17-18-bit plans)                HBM read+write (28 / 24 B/tuple)
 // k_hist_units_n         HistogramJob::run over a narrow payload array (pass 2 of 17-18-bit plans)          HBM read (8 B/tuple)
+// k_*<IN_COLS / _ID>     k_hist2d_units, k_scatter_wc(_cols), k_scatter_wcn and the count-free pass 1 reading a caller's relation
+//                        as COLUMNS (rhj_join_cols_dev): join values 8 B/tuple, rowIDs a second 8 B stream or the index
+// k_cols_to_tuples       columns -> 16-byte tuples, for the plans whose first kernel has no columnar form   HBM read+write
 // multi-GPU receiver / sender (no reference counterpart: the reference is one process):
 // k_seg_units            pass-1 units cut at the sender segments of a received shard
-// k_hist2d_units<true>   the two-pass histogram over received payloads                                       HBM read (8 B/tuple)
+// k_hist2d_units<IN_NRW> the two-pass histogram over received payloads                                       HBM read (8 B/tuple)
 // k_scatter_wc_n         last pass in front of the compact-table join: narrow in, 16-byte tuples with global rowIDs out
 // k_join_bkt<..TAGGED>   the one-table join resolving {sender tag, shard-local rowID} into global rowIDs
 // k_check_radix          contract check of the public rhj_bucket_join (radix_bits must describe the partitions)
@@ -39,6 +42,16 @@ namespace {
 
 struct __align__(16) Tup { u64 key; u64 payload; };   // reference structs.h:33-36
 struct __align__(16) Pair { u64 r; u64 s; };          // reference Result.h:9-12
+
+// How a kernel that may be the FIRST to touch a relation reads it (a compile-time parameter: every form is its own code).
+//   IN_AOS      16-byte tuples {rowID, join value}: the reference's layout, every other entry point
+//   IN_NRW      the narrow arrays of an earlier pass or of a received shard: payloads (u64) + rowIDs (u32)
+//   IN_COLS     a column of join values (u64); the rowID of a tuple is its index -- no load for it (rhj_join_cols_dev, NULL ids)
+//   IN_COLS_ID  ... and a column of rowIDs (u64): two coalesced 8-byte streams
+// The columnar forms get the value column in the kernel's `inP` argument and the id column in its `in` argument (cols_ids).
+enum InForm : int { IN_AOS = 0, IN_NRW = 1, IN_COLS = 2, IN_COLS_ID = 3 };
+constexpr bool in_cols(InForm f) { return f == IN_COLS || f == IN_COLS_ID; }
+__device__ __forceinline__ const u64 *cols_ids(const Tup *in) { return reinterpret_cast<const u64 *>(in); }
 
 __device__ __forceinline__ u64 mix64(u64 z)
 {
@@ -362,12 +375,13 @@ __device__ __forceinline__ BuildRule sniff_rule(const SniffVerdict &sv, u32 *sh,
     return r;
 }
 
-template <bool IN_NARROW>
+template <InForm IN>
 __global__ void __launch_bounds__(H2_THREADS)
 k_hist2d_units(const Tup *__restrict__ in, const u64 *__restrict__ inP, u64 n, u64 L, int b1, int b2, u32 units_per_group,
                u32 ngroups, u32 *__restrict__ hist1, u32 *__restrict__ hist2, u64 key_base, u32 *__restrict__ wide,
                const u64 *__restrict__ unit_rng, int mix, DupSniff sn)
 {
+    constexpr bool IN_NARROW = IN == IN_NRW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const u32 nb1 = 1u << b1, nb2 = 1u << b2, nbin = nb1 * nb2;
     u32 *tab = reinterpret_cast<u32 *>(smem);                 // nbin / 2 words, two 16-bit counters each
@@ -400,7 +414,8 @@ k_hist2d_units(const Tup *__restrict__ in, const u64 *__restrict__ inP, u64 n, u
         }
     };
     u64 i = beg + tid;
-    if constexpr (IN_NARROW) {
+    if constexpr (IN_NARROW || IN == IN_COLS) {
+        // (IN_COLS: a value column whose rowIDs are the indices, below 2^32 -- the host takes this form for such relations only)
         for (; i + 7ull * H2_THREADS < end; i += 8ull * H2_THREADS) {        // 8 x 8 B loads in flight per lane
             u64 v[8];
 #pragma unroll
@@ -409,6 +424,19 @@ k_hist2d_units(const Tup *__restrict__ in, const u64 *__restrict__ inP, u64 n, u
             for (int k = 0; k < 8; k++) count(v[k]);
         }
         for (; i < end; i += H2_THREADS) count(inP[i]);
+    } else if constexpr (IN == IN_COLS_ID) {
+        // value column + id column: the same bytes per lane in flight as the 16-byte form, in two streams
+        const u64 *__restrict__ ids = cols_ids(in);
+        u32 hi = 0;
+        for (; i + 3ull * H2_THREADS < end; i += 4ull * H2_THREADS) {
+            u64 v[4], r[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) { v[k] = inP[i + (u64)k * H2_THREADS]; r[k] = ids[i + (u64)k * H2_THREADS]; }
+#pragma unroll
+            for (int k = 0; k < 4; k++) { count(v[k]); hi |= (u32)((r[k] - key_base) >> 32); }
+        }
+        for (; i < end; i += H2_THREADS) { count(inP[i]); hi |= (u32)((ids[i] - key_base) >> 32); }
+        if (wide != nullptr && __ballot(hi != 0) != 0 && lane == 0) atomicOr(wide, 1u);
     } else {
         // wide (optional): the narrow format is wanted downstream -- this kernel sees every rowID anyway, so a rowID that
         // does not fit 32 bits (after subtracting key_base) is reported here, before any scatter has run
@@ -825,7 +853,7 @@ constexpr int WC_THREADS_SMALL = 512;                                       // <
 // IN_NARROW (multi-GPU receiver, last pass in front of the compact-table join): the input is a narrow relation whose rowIDs are
 // local to the sender's shard; unit u holds tuples of ONE sender (see WnTag) and the 16-byte tuples written carry the GLOBAL
 // rowID key_add + rowID32 -- the compact-table kernels then run unchanged on what one GPU would have partitioned itself.
-template <int THREADS, bool IN_NARROW = false>
+template <int THREADS, InForm IN = IN_AOS>
 __device__ __forceinline__ void
 dev_scatter_wc(const Tup *__restrict__ in, Tup *__restrict__ out, const u64 *__restrict__ seg_start,
                const u32 *__restrict__ unit_start, u32 nseg, u64 L, int shift, int bits,
@@ -842,7 +870,9 @@ dev_scatter_wc(const Tup *__restrict__ in, Tup *__restrict__ out, const u64 *__r
     // mix (16-byte input only, see MIX_* in rhj_internal.h): MIX_STORE -- first pass inside a join: the payload becomes
     // mix64(payload) as it is loaded, and that is what is written; MIX_DIGIT -- the digit comes from mix64(payload), the tuple
     // is written as it came (the multi-GPU owner split of 16-byte tuples)
+    // IN_COLS / IN_COLS_ID (pass 1 of a join given as columns, 16-byte intermediate): inP = the value column, `in` = the id column
     constexpr int TILE = THREADS * WC_TPT;
+    constexpr bool IN_NARROW = IN == IN_NRW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const u32 nbins = 1u << bits, mask = nbins - 1;
     Tup *tile = reinterpret_cast<Tup *>(smem);                               // TILE * 16
@@ -886,6 +916,11 @@ dev_scatter_wc(const Tup *__restrict__ in, Tup *__restrict__ out, const u64 *__r
         for (int k = 0; k < WC_TPT; k++) {
             const u32 i = k * THREADS + tid;
             if constexpr (IN_NARROW) { const u64 j = beg + (i < last ? i : last); t[k].payload = inP[j]; t[k].key = key_add + inK[j]; }
+            else if constexpr (in_cols(IN)) {
+                const u64 j = beg + (i < last ? i : last);
+                t[k].payload = inP[j];
+                if constexpr (IN == IN_COLS_ID) t[k].key = cols_ids(in)[j]; else t[k].key = j;
+            }
             else t[k] = in[beg + (i < last ? i : last)];
         }
     };
@@ -905,12 +940,16 @@ dev_scatter_wc(const Tup *__restrict__ in, Tup *__restrict__ out, const u64 *__r
     // just prefetched -- before it touches the current one.
     auto load_tile = [&](Tup (&t)[WC_TPT], u64 tb) {
         const u32 last = ((end - tb < (u64)TILE) ? (u32)(end - tb) : (u32)TILE) - 1u;      // tb < end
-        const Tup *__restrict__ tp = in + tb;
 #pragma unroll
         for (int k = 0; k < WC_TPT; k++) {
             const u32 i = k * THREADS + tid;
             if constexpr (IN_NARROW) { const u64 j = tb + (i < last ? i : last); t[k].payload = inP[j]; t[k].key = key_add + inK[j]; }
-            else t[k] = tp[i < last ? i : last];
+            else if constexpr (in_cols(IN)) {
+                const u64 j = tb + (i < last ? i : last);
+                t[k].payload = inP[j];
+                if constexpr (IN == IN_COLS_ID) t[k].key = cols_ids(in)[j]; else t[k].key = j;
+            }
+            else { const Tup *__restrict__ tp = in + tb; t[k] = tp[i < last ? i : last]; }
         }
     };
     // FULL: the tile has TILE tuples (every tile of a unit but its last): no per-tuple range checks
@@ -1045,8 +1084,31 @@ k_scatter_wc_n(const u64 *__restrict__ inP, const u32 *__restrict__ inK, Tup *__
 {
     if (skip != nullptr && *skip != 0) return;
     const u64 add = key_bases[(blockIdx.x % tag.ngroups) / tag.div];
-    dev_scatter_wc<THREADS, true>(nullptr, out, nullptr, nullptr, 0u, 0, shift, bits, unit_base, unit_rng, n_rng_units, blockIdx.x,
+    dev_scatter_wc<THREADS, IN_NRW>(nullptr, out, nullptr, nullptr, 0u, 0, shift, bits, unit_base, unit_rng, n_rng_units, blockIdx.x,
                                   inP, inK, add);
+}
+
+// columns in (segments cut into units, the form of k_scatter_wc), 16-byte tuples out: pass 1 of a narrow level-1 join
+template <int THREADS, InForm IN>
+__global__ void __launch_bounds__(THREADS)
+k_scatter_wc_cols(const u64 *__restrict__ val, const u64 *__restrict__ ids, Tup *__restrict__ out, const u64 *__restrict__ seg_start,
+                  const u32 *__restrict__ unit_start, u32 nseg, u64 L, int shift, int bits, const u64 *__restrict__ unit_base, int mix)
+{
+    static_assert(in_cols(IN), "the columnar forms");
+    dev_scatter_wc<THREADS, IN>(reinterpret_cast<const Tup *>(ids), out, seg_start, unit_start, nseg, L, shift, bits, unit_base,
+                                (const u64 *)nullptr, 0u, blockIdx.x, val, nullptr, 0, mix);
+}
+
+// columns -> 16-byte tuples (linear; rhj_join_cols_dev on the plans that start with a kernel without a columnar form)
+__global__ void __launch_bounds__(256)
+k_cols_to_tuples(const u64 *__restrict__ val, const u64 *__restrict__ ids, u64 n, Tup *__restrict__ out)
+{
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+        Tup t;
+        t.key = ids != nullptr ? ids[i] : i;
+        t.payload = val[i];
+        out[i] = t;
+    }
 }
 
 template <int THREADS>
@@ -1323,7 +1385,7 @@ struct WnFree {
     DupSniff sn;                     // CF == 1
 };
 
-template <bool IN_NARROW, int GR_, int TPT_, int THREADS_, bool PEER, int CF>
+template <InForm IN, int GR_, int TPT_, int THREADS_, bool PEER, int CF>
 __device__ __forceinline__ void
 dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32 *__restrict__ inK,
               u64 *__restrict__ outP, u32 *__restrict__ outK, const u64 *__restrict__ seg_start,
@@ -1331,14 +1393,18 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
               const u64 *__restrict__ unit_base, const u64 *__restrict__ unit_rng, u32 n_rng_units,
               u32 *__restrict__ overflow, u64 key_base, WnTag tag, int mix, const WnPeer &peer, const WnFree &fr)
 {
-    static_assert(!PEER || !IN_NARROW, "the peer split reads the rank's own 16-byte shard");
-    static_assert(CF == 0 || (!PEER && CF == (IN_NARROW ? 2 : 1)), "count-free: pass 1 reads 16-byte tuples, pass 2 narrow pieces");
+    // IN_COLS / IN_COLS_ID: the caller's relation as columns (inP = join values, `in` = the id column; key_base is not applied).
+    // IN_COLS keeps the rowID -- the index, below 2^32 -- in 32 bits from the start and has nothing to report as wide.
+    constexpr bool IN_NARROW = IN == IN_NRW;
+    static_assert(!PEER || IN == IN_AOS, "the peer split reads the rank's own 16-byte shard");
+    static_assert(CF == 0 || (!PEER && CF == (IN_NARROW ? 2 : 1)), "count-free: pass 1 reads the caller's tuples, pass 2 narrow pieces");
     // a rowID that does not fit 32 bits has been seen (by the histogram kernel or by an earlier workgroup of this pass):
     // the join is going to repeat itself in the 16-byte format, nothing written from here on will be read
     if (overflow != nullptr && __builtin_nontemporal_load(overflow) != 0) return;
     constexpr int THREADS = THREADS_, TPT = TPT_, TILE = THREADS * TPT, GR = GR_;
     constexpr u64 GM = GR - 1;
-    using KeyT = typename std::conditional<IN_NARROW, u32, u64>::type;
+    using KeyT = typename std::conditional<IN_NARROW || IN == IN_COLS, u32, u64>::type;
+    constexpr bool WIDE_KEYS = sizeof(KeyT) == 8;                            // rowIDs arrive in 64 bits: one may not fit the format
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const u32 nbins = 1u << bits, mask = nbins - 1;
     u64 *sp = reinterpret_cast<u64 *>(smem);                                 // payloads: TILE staging slots, then nbins carry lines
@@ -1422,6 +1488,8 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
                 const u32 *W = reinterpret_cast<const u32 *>(inP) + cf_w(a);
                 pay[k] = W[0] | (u64)W[CF_HI] << 32; key[k] = inK[a];
             } else if constexpr (IN_NARROW) { pay[k] = inP[tb + i]; key[k] = inK[tb + i]; }
+            else if constexpr (IN == IN_COLS) { pay[k] = inP[tb + i]; key[k] = (u32)(tb + i); }
+            else if constexpr (IN == IN_COLS_ID) { pay[k] = inP[tb + i]; key[k] = cols_ids(in)[tb + i]; }
             else { const Tup v = in[tb + i]; pay[k] = v.payload; key[k] = v.key - key_base; }
         }
     };
@@ -1441,7 +1509,7 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
             dg[k] = (u32)(pay[k] >> shift) & mask;
             if (FULL || i < ntile) {
                 rk[k] = atomicAdd(&cnt[dg[k]], 1u);
-                if constexpr (!IN_NARROW) ovf |= (u32)(key[k] >> 32);
+                if constexpr (WIDE_KEYS) ovf |= (u32)(key[k] >> 32);
                 if constexpr (CF == 1) { if (fr.sn.tab != nullptr) sniff_sample(fr.sn, pay[k]); }      // (mixed: MIX_STORE)
             }
         }
@@ -1565,12 +1633,12 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
             __builtin_nontemporal_store(sk[TILE + q], &dstK(d)[o]);
         }
     }
-    if constexpr (!IN_NARROW) {
+    if constexpr (WIDE_KEYS) {
         if (__ballot(ovf != 0) != 0 && lane == 0) atomicOr(overflow, 1u);
     }
 }
 
-template <bool IN_NARROW, int GR_ = WN_GR, int TPT_ = WN_TPT, int THREADS_ = WN_THREADS, bool PEER = false>
+template <InForm IN, int GR_ = WN_GR, int TPT_ = WN_TPT, int THREADS_ = WN_THREADS, bool PEER = false>
 __global__ void __launch_bounds__(THREADS_)
 k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32 *__restrict__ inK,
               u64 *__restrict__ outP, u32 *__restrict__ outK, const u64 *__restrict__ seg_start,
@@ -1578,18 +1646,18 @@ k_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32
               const u64 *__restrict__ unit_base, const u64 *__restrict__ unit_rng, u32 n_rng_units,
               u32 *__restrict__ overflow, u64 key_base, WnTag tag, int mix, WnPeer peer)
 {
-    dev_scatter_wcn<IN_NARROW, GR_, TPT_, THREADS_, PEER, 0>(in, inP, inK, outP, outK, seg_start, unit_start, nseg, L, shift, bits,
+    dev_scatter_wcn<IN, GR_, TPT_, THREADS_, PEER, 0>(in, inP, inK, outP, outK, seg_start, unit_start, nseg, L, shift, bits,
                                                              unit_base, unit_rng, n_rng_units, overflow, key_base, tag, mix, peer, WnFree());
 }
 
-// the count-free forms: pass 1 (16-byte input, single segment {0, n} cut into units of L) and pass 2 (pieces)
-template <bool IN_NARROW>
+// the count-free forms: pass 1 (16-byte or columnar input, single segment {0, n} cut into units of L) and pass 2 (pieces)
+template <InForm IN>
 __global__ void __launch_bounds__(WN_THREADS)
 k_scatter_wcn_cf(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u32 *__restrict__ inK, u64 *__restrict__ outP,
                  u32 *__restrict__ outK, const u64 *__restrict__ seg_start, const u32 *__restrict__ unit_start, u64 L, int shift,
                  int bits, const u64 *__restrict__ unit_base, u32 nunits, u32 *__restrict__ overflow, int mix, WnFree fr)
 {
-    dev_scatter_wcn<IN_NARROW, WN_GR, WN_TPT, WN_THREADS, false, IN_NARROW ? 2 : 1>(in, inP, inK, outP, outK, seg_start, unit_start, 1u, L,
+    dev_scatter_wcn<IN, WN_GR, WN_TPT, WN_THREADS, false, IN == IN_NRW ? 2 : 1>(in, inP, inK, outP, outK, seg_start, unit_start, 1u, L,
                                                                                     shift, bits, unit_base, nullptr, nunits, overflow, (u64)0,
                                                                                     WnTag{1u, 1u, 0u}, mix, WnPeer{}, fr);
 }
@@ -2978,6 +3046,10 @@ static void allow_big_lds()
     SET_LDS(k_scatter_units_pipe, part_lds_bytes(PART_MAX_BITS));
     SET_LDS(k_scatter_wc<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
+    SET_LDS((k_scatter_wc_cols<WC_THREADS, IN_COLS>), wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
+    SET_LDS((k_scatter_wc_cols<WC_THREADS_SMALL, IN_COLS>), wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
+    SET_LDS((k_scatter_wc_cols<WC_THREADS, IN_COLS_ID>), wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
+    SET_LDS((k_scatter_wc_cols<WC_THREADS_SMALL, IN_COLS_ID>), wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wc2<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc2<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_fused2<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
@@ -2995,13 +3067,17 @@ static void allow_big_lds()
     allow_ct_lds<JK_CT, false, true>();                                      // the stamps aid
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
-    SET_LDS(k_scatter_wcn<false>, wn_lds_bytes(WN_MAX_BITS));
-    SET_LDS(k_scatter_wcn<true>, wn_lds_bytes(WN_MAX_BITS));
-    SET_LDS(k_scatter_wcn_cf<false>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
-    SET_LDS(k_scatter_wcn_cf<true>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
-    SET_LDS((k_scatter_wcn<false, WN_GR, WN_TPT, WN_THREADS, true>), wn_lds_bytes(WN_MAX_BITS, WN_GR, WN_TPT, WN_THREADS, true));
-    SET_LDS((k_scatter_wcn<false, WN9_GR, WN9_TPT, WN9_THREADS>), wn_lds_bytes(WN9_MAX_BITS, WN9_GR, WN9_TPT, WN9_THREADS));
-    SET_LDS((k_scatter_wcn<true, WN9_GR, WN9_TPT, WN9_THREADS>), wn_lds_bytes(WN9_MAX_BITS, WN9_GR, WN9_TPT, WN9_THREADS));
+    SET_LDS(k_scatter_wcn<IN_AOS>, wn_lds_bytes(WN_MAX_BITS));
+    SET_LDS(k_scatter_wcn<IN_NRW>, wn_lds_bytes(WN_MAX_BITS));
+    SET_LDS(k_scatter_wcn<IN_COLS>, wn_lds_bytes(WN_MAX_BITS));
+    SET_LDS(k_scatter_wcn<IN_COLS_ID>, wn_lds_bytes(WN_MAX_BITS));
+    SET_LDS(k_scatter_wcn_cf<IN_AOS>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
+    SET_LDS(k_scatter_wcn_cf<IN_COLS>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
+    SET_LDS(k_scatter_wcn_cf<IN_COLS_ID>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
+    SET_LDS(k_scatter_wcn_cf<IN_NRW>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
+    SET_LDS((k_scatter_wcn<IN_AOS, WN_GR, WN_TPT, WN_THREADS, true>), wn_lds_bytes(WN_MAX_BITS, WN_GR, WN_TPT, WN_THREADS, true));
+    SET_LDS((k_scatter_wcn<IN_AOS, WN9_GR, WN9_TPT, WN9_THREADS>), wn_lds_bytes(WN9_MAX_BITS, WN9_GR, WN9_TPT, WN9_THREADS));
+    SET_LDS((k_scatter_wcn<IN_NRW, WN9_GR, WN9_TPT, WN9_THREADS>), wn_lds_bytes(WN9_MAX_BITS, WN9_GR, WN9_TPT, WN9_THREADS));
     });
 }
 
@@ -3073,6 +3149,32 @@ void launch_scatter_units(hipStream_t st, const void *d_in, void *d_out, const P
     hipLaunchKernelGGL(k_scatter_units_pipe, dim3(g.max_units), dim3(PART_THREADS), part_lds_bytes(g.bits), st,
                        (const Tup *)d_in, (Tup *)d_out, d_seg_start, d_unit_start, g.nseg, g.L, g.shift, g.bits,
                        d_unit_base, g.mix);
+}
+
+// launch_scatter_units reading columns (passes of at most WC_MAX_BITS bits: pass 1 of a fused two-pass plan)
+void launch_scatter_units_cols(hipStream_t st, const ColsIn &cols, void *d_out, const PassGeom &g, const u64 *d_seg_start,
+                               const u32 *d_unit_start, const u64 *d_unit_base)
+{
+    if (g.max_units == 0) return;
+    allow_big_lds();
+    with_wc_threads(g.bits, true, [&](auto threads) {
+        constexpr int T = decltype(threads)::value;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(g.max_units), dim3(T), wc_lds_bytes(g.bits, T), st, cols.val, cols.id, (Tup *)d_out, d_seg_start,
+                               d_unit_start, g.nseg, g.L, g.shift, g.bits, d_unit_base, g.mix);
+        };
+        if (cols.id) go(k_scatter_wc_cols<T, IN_COLS_ID>);
+        else go(k_scatter_wc_cols<T, IN_COLS>);
+    });
+}
+
+// columns -> 16-byte tuples {id[i] or i, val[i]}: what the plans without a columnar first kernel continue on
+void launch_cols_to_tuples(hipStream_t st, const ColsIn &cols, u64 n, void *d_out)
+{
+    if (n == 0) return;
+    u64 g = (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(k_cols_to_tuples, dim3((unsigned)g), dim3(256), 0, st, cols.val, cols.id, n, (Tup *)d_out);
 }
 
 static PassPair make_pass_pair(const PassPairHost &h)
@@ -3177,23 +3279,44 @@ void launch_fused_pass(hipStream_t st, const PassPairHost &h, int bits, int phas
     }
 }
 
-void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,
-                         u32 units_per_group, u32 ngroups, u32 *d_hist1, u32 *d_hist2, u64 key_base, u32 *d_wide,
-                         const u64 *d_unit_rng, int mix, const DupSniff &sniff)
+static void hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, const ColsIn &cols, u64 n, u64 L, u32 units, int b1, int b2,
+                        u32 units_per_group, u32 ngroups, u32 *d_hist1, u32 *d_hist2, u64 key_base, u32 *d_wide,
+                        const u64 *d_unit_rng, int mix, const DupSniff &sniff)
 {
     static std::once_flag once[64];
     const size_t lds = ((size_t)1 << (b1 + b2)) * 2 + ((size_t)4 << b1);
     std::call_once(once[current_device_slot()], [] {
-        SET_LDS(k_hist2d_units<false>, ((size_t)1 << 16) * 2 + ((size_t)4 << WC_MAX_BITS));
-        SET_LDS(k_hist2d_units<true>, ((size_t)1 << 16) * 2 + ((size_t)4 << WC_MAX_BITS));
+        SET_LDS(k_hist2d_units<IN_AOS>, ((size_t)1 << 16) * 2 + ((size_t)4 << WC_MAX_BITS));
+        SET_LDS(k_hist2d_units<IN_NRW>, ((size_t)1 << 16) * 2 + ((size_t)4 << WC_MAX_BITS));
+        SET_LDS(k_hist2d_units<IN_COLS>, ((size_t)1 << 16) * 2 + ((size_t)4 << WC_MAX_BITS));
+        SET_LDS(k_hist2d_units<IN_COLS_ID>, ((size_t)1 << 16) * 2 + ((size_t)4 << WC_MAX_BITS));
     });
     if (units == 0) return;
-    if (in_narrow)
-        hipLaunchKernelGGL(k_hist2d_units<true>, dim3(units), dim3(H2_THREADS), lds, st, (const Tup *)nullptr, (const u64 *)d_in, n,
+    if (cols.val && cols.id)
+        hipLaunchKernelGGL(k_hist2d_units<IN_COLS_ID>, dim3(units), dim3(H2_THREADS), lds, st, (const Tup *)cols.id, cols.val, n,
+                           L, b1, b2, units_per_group, ngroups, d_hist1, d_hist2, key_base, d_wide, d_unit_rng, mix, sniff);
+    else if (cols.val)
+        hipLaunchKernelGGL(k_hist2d_units<IN_COLS>, dim3(units), dim3(H2_THREADS), lds, st, (const Tup *)nullptr, cols.val, n,
+                           L, b1, b2, units_per_group, ngroups, d_hist1, d_hist2, (u64)0, (u32 *)nullptr, d_unit_rng, mix, sniff);
+    else if (in_narrow)
+        hipLaunchKernelGGL(k_hist2d_units<IN_NRW>, dim3(units), dim3(H2_THREADS), lds, st, (const Tup *)nullptr, (const u64 *)d_in, n,
                            L, b1, b2, units_per_group, ngroups, d_hist1, d_hist2, (u64)0, (u32 *)nullptr, d_unit_rng, 0, sniff);
     else
-        hipLaunchKernelGGL(k_hist2d_units<false>, dim3(units), dim3(H2_THREADS), lds, st, (const Tup *)d_in, (const u64 *)nullptr, n,
+        hipLaunchKernelGGL(k_hist2d_units<IN_AOS>, dim3(units), dim3(H2_THREADS), lds, st, (const Tup *)d_in, (const u64 *)nullptr, n,
                            L, b1, b2, units_per_group, ngroups, d_hist1, d_hist2, key_base, d_wide, d_unit_rng, mix, sniff);
+}
+
+void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,
+                         u32 units_per_group, u32 ngroups, u32 *d_hist1, u32 *d_hist2, u64 key_base, u32 *d_wide,
+                         const u64 *d_unit_rng, int mix, const DupSniff &sniff)
+{
+    hist2d_units(st, d_in, in_narrow, ColsIn(), n, L, units, b1, b2, units_per_group, ngroups, d_hist1, d_hist2, key_base, d_wide,
+                 d_unit_rng, mix, sniff);
+}
+void launch_hist2d_units_cols(hipStream_t st, const ColsIn &cols, u64 n, u64 L, u32 units, int b1, int b2, u32 units_per_group,
+                              u32 ngroups, u32 *d_hist1, u32 *d_hist2, u32 *d_wide, int mix, const DupSniff &sniff)
+{
+    hist2d_units(st, nullptr, false, cols, n, L, units, b1, b2, units_per_group, ngroups, d_hist1, d_hist2, 0, d_wide, nullptr, mix, sniff);
 }
 
 // pass-1 units cut at segment boundaries (multi-GPU receiver); d_unit_rng gets nseg * units_per_seg + 1 entries
@@ -3268,19 +3391,20 @@ struct WcnLaunch {
     WnTag tag{1u, 1u, 0u};
     int mix = 0;
     WnPeer peer{};
+    const u64 *ids = nullptr;           // IN_COLS_ID: `in` is the value column, this the id column
     void segments(const PassGeom &g, const u64 *d_seg_start, const u32 *d_unit_start)
     {
         seg_start = d_seg_start; unit_start = d_unit_start; nseg = g.nseg; L = g.L; mix = g.mix;
     }
 };
-template <bool IN_NARROW, int GR = WN_GR, int TPT = WN_TPT, int THREADS = WN_THREADS, bool PEER = false>
+template <InForm IN, int GR = WN_GR, int TPT = WN_TPT, int THREADS = WN_THREADS, bool PEER = false>
 static void launch_wcn(hipStream_t st, const WcnLaunch &a)
 {
     if (a.units == 0) return;
     allow_big_lds();
-    hipLaunchKernelGGL((k_scatter_wcn<IN_NARROW, GR, TPT, THREADS, PEER>), dim3(a.units), dim3(THREADS),
-                       wn_lds_bytes(a.bits, GR, TPT, THREADS, PEER), st, (const Tup *)(IN_NARROW ? nullptr : a.in),
-                       (const u64 *)(IN_NARROW ? a.in : nullptr), a.inK, a.outP, a.outK, a.seg_start, a.unit_start, a.nseg, a.L, a.shift,
+    hipLaunchKernelGGL((k_scatter_wcn<IN, GR, TPT, THREADS, PEER>), dim3(a.units), dim3(THREADS),
+                       wn_lds_bytes(a.bits, GR, TPT, THREADS, PEER), st, (const Tup *)(IN == IN_AOS ? a.in : IN == IN_COLS_ID ? a.ids : nullptr),
+                       (const u64 *)(IN == IN_AOS ? nullptr : a.in), a.inK, a.outP, a.outK, a.seg_start, a.unit_start, a.nseg, a.L, a.shift,
                        a.bits, a.unit_base, a.rng, a.rng ? a.units : 0u, a.overflow, a.key_base, a.tag, a.mix, a.peer);
 }
 
@@ -3292,7 +3416,17 @@ void launch_scatter_units_narrow(hipStream_t st, const void *d_in, void *d_out, 
                 d_unit_base, d_overflow};
     a.segments(g, d_seg_start, d_unit_start);
     a.key_base = key_base;
-    launch_wcn<false>(st, a);
+    launch_wcn<IN_AOS>(st, a);
+}
+void launch_scatter_units_narrow_cols(hipStream_t st, const ColsIn &cols, void *d_out, u64 n, const PassGeom &g, const u64 *d_seg_start,
+                                      const u32 *d_unit_start, const u64 *d_unit_base, u32 *d_overflow)
+{
+    WcnLaunch a{cols.val, nullptr, (u64 *)d_out, (u32 *)((unsigned char *)d_out + narrow_k_offset(n)), g.max_units, g.shift, g.bits,
+                d_unit_base, d_overflow};
+    a.segments(g, d_seg_start, d_unit_start);
+    a.ids = cols.id;
+    if (cols.id) launch_wcn<IN_COLS_ID>(st, a);
+    else launch_wcn<IN_COLS>(st, a);
 }
 
 // the multi-GPU sender's class split straight into the owners' receive arrays (k_scatter_wcn<.., PEER>): d_delta / d_owner:
@@ -3309,7 +3443,7 @@ void launch_scatter_units_narrow_peer(hipStream_t st, const void *d_in, const Pa
     a.peer.delta = d_delta;
     a.peer.owner = d_owner;
     for (int i = 0; i < nranks && i < SEG_MAX; i++) { a.peer.P[i] = (u64 *)peersP[i]; a.peer.K[i] = (u32 *)peersK[i]; }
-    launch_wcn<false, WN_GR, WN_TPT, WN_THREADS, true>(st, a);
+    launch_wcn<IN_AOS, WN_GR, WN_TPT, WN_THREADS, true>(st, a);
 }
 
 // One narrow-output pass over segments cut into units (run_pass form): 16-byte or narrow input, <= 8 bits (32-tuple lines)
@@ -3321,11 +3455,11 @@ void launch_scatter_units_narrow_any(hipStream_t st, const void *d_in, const u32
     a.segments(g, d_seg_start, d_unit_start);
     const bool in_narrow = d_inK != nullptr;
     if (g.bits <= WN_MAX_BITS) {
-        if (in_narrow) launch_wcn<true>(st, a);
-        else launch_wcn<false>(st, a);
+        if (in_narrow) launch_wcn<IN_NRW>(st, a);
+        else launch_wcn<IN_AOS>(st, a);
     } else {
-        if (in_narrow) launch_wcn<true, WN9_GR, WN9_TPT, WN9_THREADS>(st, a);
-        else launch_wcn<false, WN9_GR, WN9_TPT, WN9_THREADS>(st, a);
+        if (in_narrow) launch_wcn<IN_NRW, WN9_GR, WN9_TPT, WN9_THREADS>(st, a);
+        else launch_wcn<IN_AOS, WN9_GR, WN9_TPT, WN9_THREADS>(st, a);
     }
 }
 
@@ -3340,8 +3474,8 @@ void launch_scatter_ranges_narrow(hipStream_t st, const void *d_in, bool in_narr
                 d_unit_base, d_overflow};
     a.rng = d_rng;
     if (tag_div) a.tag = WnTag{tag_groups, tag_div, TAG_BITS};
-    if (in_narrow) launch_wcn<true>(st, a);
-    else launch_wcn<false>(st, a);
+    if (in_narrow) launch_wcn<IN_NRW>(st, a);
+    else launch_wcn<IN_AOS>(st, a);
 }
 
 // ---- count-free pass 1 --------------------------------------------------------------------------------------
@@ -3351,15 +3485,27 @@ static WnFree cf_make(const CfGeom &c, u32 bit, u32 *cnt1, const u32 *pre, const
     fr.U = c.U; fr.cap = c.cap; fr.per = c.per; fr.ngroups = c.ngroups; fr.bit = bit; fr.cnt1 = cnt1; fr.pre = pre; fr.sn = sn;
     return fr;
 }
-void launch_cf_pass1(hipStream_t st, const void *d_in, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
+template <InForm IN>
+static void cf_pass1(hipStream_t st, const Tup *in, const u64 *inP, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
                      const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff)
 {
     if (c.U == 0) return;
     allow_big_lds();
-    hipLaunchKernelGGL(k_scatter_wcn_cf<false>, dim3(c.U), dim3(WN_THREADS), wn_lds_bytes(g.bits) + CF_PRE * 4, st, (const Tup *)d_in,
-                       (const u64 *)nullptr, (const u32 *)nullptr, (u64 *)d_tmp, (u32 *)((unsigned char *)d_tmp + c.slots * 8),
+    hipLaunchKernelGGL(k_scatter_wcn_cf<IN>, dim3(c.U), dim3(WN_THREADS), wn_lds_bytes(g.bits) + CF_PRE * 4, st, in,
+                       inP, (const u32 *)nullptr, (u64 *)d_tmp, (u32 *)((unsigned char *)d_tmp + c.slots * 8),
                        d_seg_start, d_unit_start, g.L, g.shift, g.bits, (const u64 *)nullptr, c.U, d_flag, g.mix,
                        cf_make(c, bit, d_cnt1, nullptr, sniff));
+}
+void launch_cf_pass1(hipStream_t st, const void *d_in, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
+                     const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff)
+{
+    cf_pass1<IN_AOS>(st, (const Tup *)d_in, nullptr, d_tmp, c, g, d_seg_start, d_unit_start, d_cnt1, d_flag, bit, sniff);
+}
+void launch_cf_pass1_cols(hipStream_t st, const ColsIn &cols, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
+                          const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff)
+{
+    if (cols.id) cf_pass1<IN_COLS_ID>(st, (const Tup *)cols.id, cols.val, d_tmp, c, g, d_seg_start, d_unit_start, d_cnt1, d_flag, bit, sniff);
+    else cf_pass1<IN_COLS>(st, nullptr, cols.val, d_tmp, c, g, d_seg_start, d_unit_start, d_cnt1, d_flag, bit, sniff);
 }
 void launch_cf_tables(hipStream_t st, const CfGeom &c, u32 nb1, const u32 *d_cnt1, u32 *d_pre, u32 *d_unit_tot, u64 *d_ps_1,
                       u32 *d_unit_start2, const u32 *d_flag)
@@ -3378,7 +3524,7 @@ void launch_cf_pass2(hipStream_t st, const void *d_tmp, void *d_out, u64 n, cons
                      const u64 *d_unit_base, const u32 *d_pre, u32 *d_flag)
 {
     allow_big_lds();
-    hipLaunchKernelGGL(k_scatter_wcn_cf<true>, dim3(nb1 * c.ngroups), dim3(WN_THREADS), wn_lds_bytes(b2) + CF_PRE * 4, st, (const Tup *)nullptr,
+    hipLaunchKernelGGL(k_scatter_wcn_cf<IN_NRW>, dim3(nb1 * c.ngroups), dim3(WN_THREADS), wn_lds_bytes(b2) + CF_PRE * 4, st, (const Tup *)nullptr,
                        (const u64 *)d_tmp, (const u32 *)((const unsigned char *)d_tmp + c.slots * 8), (u64 *)d_out,
                        (u32 *)((unsigned char *)d_out + narrow_k_offset(n)), (const u64 *)nullptr, (const u32 *)nullptr, (u64)0, b1, b2,
                        d_unit_base, nb1 * c.ngroups, d_flag, 0, cf_make(c, 0, nullptr, d_pre, DupSniff()));

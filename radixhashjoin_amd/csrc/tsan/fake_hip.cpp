@@ -220,6 +220,12 @@ void launch_cf_tables(hipStream_t, const CfGeom &, u32, const u32 *, u32 *, u32 
 void launch_cf_hist2(hipStream_t, const void *, const CfGeom &, u32, int, int, const u32 *, u32 *, const u32 *) {}
 void launch_cf_pass2(hipStream_t, const void *, void *, u64, const CfGeom &, u32, int, int, const u64 *, const u32 *, u32 *) {}
 void launch_hist2d_units(hipStream_t, const void *, bool, u64, u64, u32, int, int, u32, u32, u32 *, u32 *, u64, u32 *, const u64 *, int, const DupSniff &) {}
+void launch_hist2d_units_cols(hipStream_t, const ColsIn &, u64, u64, u32, int, int, u32, u32, u32 *, u32 *, u32 *, int, const DupSniff &) {}
+void launch_scatter_units_cols(hipStream_t, const ColsIn &, void *, const PassGeom &, const u64 *, const u32 *, const u64 *) {}
+void launch_scatter_units_narrow_cols(hipStream_t, const ColsIn &, void *, u64, const PassGeom &, const u64 *, const u32 *, const u64 *, u32 *) {}
+void launch_cols_to_tuples(hipStream_t, const ColsIn &, u64, void *) {}
+void launch_cf_pass1_cols(hipStream_t, const ColsIn &, void *, const CfGeom &, const PassGeom &, const u64 *, const u32 *, u32 *, u32 *, u32,
+                          const DupSniff &) {}
 void launch_seg_units(hipStream_t, u32, const u64 *, const u64 *, u32, u64 *, u64 *, u32 *) {}
 void launch_make_group_ranges(hipStream_t, const u64 *, u32, u32, u32, u64, u64 *, u32 *) {}
 void launch_scatter_ranges(hipStream_t, const void *, void *, u32, int, int, const u64 *, const u64 *) {}

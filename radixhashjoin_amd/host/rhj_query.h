@@ -73,7 +73,8 @@ struct Query {                                /* Query.h:34-59 */
     void read_projections();
     void execute(JobScheduler &js, std::vector<relList> &relations);
     /* the same query executed device-resident (rhj_query_dev.cpp): what execute() does unless
-       $RHJ_QUERY_MODE == "host" */
+       $RHJ_QUERY_MODE == "host"; $RHJ_QUERY_MODE == "cols": the join inputs are built as columns (the stored column itself
+       for an unfiltered alias) and joined by rhj_join_cols_dev instead of 16-byte tuples and rhj_join_dev */
     void execute_device(JobScheduler &js, std::vector<relList> &relations);
     bool run_filters(std::vector<relList> &relations,
                      std::unordered_map<uint64_t, std::unordered_set<uint64_t> > &filtered);
@@ -91,6 +92,9 @@ private:
     size_t pos_ = 0;
     void parse_all();
 };
+
+/* test hook of the "cols" mode: appends "cols <nR> <nS> <count>" to $RHJ_JOIN_LOG (one line per rhj_join_cols_dev call) */
+void log_cols_join(uint64_t nR, uint64_t nS, uint64_t count);
 
 /* intermediate.h:10-14 */
 void parse_table(join_info &join, relList &relation,

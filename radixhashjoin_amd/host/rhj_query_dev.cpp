@@ -5,10 +5,13 @@
 // gathers.  An alias that is already part of the intermediate enters a join POSITION-CARRYING
 // ({key = intermediate row, payload = value}): the pairs then name intermediate rows directly, which replaces
 // both the de-duplication of structs.cpp:238-241 and update_intermediate's matching (intermediate.cpp:52-87).
+// RHJ_QUERY_MODE=cols: the same execution with the join inputs as COLUMNS for rhj_join_cols_dev -- the stored column itself
+// (no kernel at all) for an alias without a row list, one 8-byte gather otherwise -- instead of 16-byte tuples.
 #include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "rhj_query.h"
@@ -77,6 +80,47 @@ DevArr join_pairs(rhj_ctx *ctx, const DevArr &R, uint64_t nR, const DevArr &S, u
         int rc = rhj_join_dev(ctx, (const rhj_tuple *)R.p, nR, (const rhj_tuple *)S.p, nS, nullptr, (rhj_pair *)out.p, cap, &count);
         if (rc == RHJ_OK) { out.n = count; return out; }
         if (rc != RHJ_E_OVERFLOW) die(ctx, "rhj_join_dev", rc);
+        cap = count;                                   // exact size is known now
+    }
+}
+
+bool cols_mode()
+{
+    static const bool on = getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "cols";
+    return on;
+}
+
+// one side of a columnar join: value column + id column (nullptr: the rowID is the position)
+struct ColSide {
+    const uint64_t *val = nullptr, *id = nullptr;
+    DevArr gathered;                                   // owns val when it had to be gathered
+};
+
+//   alias not in the intermediate, no row list   the stored column itself              ids: none (rowID = row)
+//   ... with a row list                          gather(col, rows)                     ids: the row list
+//   alias already in the intermediate            gather(col, inter[a])                 ids: none (position-carrying)
+ColSide col_side(rhj_ctx *ctx, const uint64_t *col, const DevArr &inter_a, const Rows &r, uint64_t n)
+{
+    ColSide s;
+    const bool in = !inter_a.empty();
+    if (!in && r.ptr() == nullptr) { s.val = col; return s; }
+    s.gathered = DevArr(ctx, n * 8);
+    OK(ctx, rhj_gather_u64(ctx, col, in ? inter_a.p : r.ptr(), n, s.gathered.p));
+    s.gathered.n = n;
+    s.val = s.gathered.p;
+    s.id = in ? nullptr : r.ptr();
+    return s;
+}
+
+DevArr join_pairs_cols(rhj_ctx *ctx, const ColSide &R, uint64_t nR, const ColSide &S, uint64_t nS, uint64_t &count)
+{
+    uint64_t cap = (nR > nS ? nR : nS) + 1024;
+    for (;;) {
+        DevArr out(ctx, cap * 16);
+        int rc = rhj_join_cols_dev(ctx, R.val, R.id, nR, S.val, S.id, nS, nullptr, (rhj_pair *)out.p, cap, &count);
+        log_cols_join(nR, nS, count);
+        if (rc == RHJ_OK) { out.n = count; return out; }
+        if (rc != RHJ_E_OVERFLOW) die(ctx, "rhj_join_cols_dev", rc);
         cap = count;                                   // exact size is known now
     }
 }
@@ -152,11 +196,17 @@ void Query::execute_device(JobScheduler &js, std::vector<relList> &relations)
         }
         // an equi-join through the hot path.  Side already in the intermediate: position-carrying input.
         const uint64_t nR = in1 ? T : rows[j.table1].n, nS = in2 ? T : rows[j.table2].n;
-        DevArr R(ctx, nR * 16), S(ctx, nS * 16);
-        OK(ctx, rhj_gather_tuples(ctx, c1, in1 ? inter[j.table1].p : rows[j.table1].ptr(), nR, in1 ? 1 : 0, (rhj_tuple *)R.p));
-        OK(ctx, rhj_gather_tuples(ctx, c2, in2 ? inter[j.table2].p : rows[j.table2].ptr(), nS, in2 ? 1 : 0, (rhj_tuple *)S.p));
         uint64_t m = 0;
-        DevArr pairs = join_pairs(ctx, R, nR, S, nS, m);                              // <-- rhj_join_dev
+        DevArr pairs;
+        if (cols_mode()) {
+            const ColSide R = col_side(ctx, c1, inter[j.table1], rows[j.table1], nR), S = col_side(ctx, c2, inter[j.table2], rows[j.table2], nS);
+            pairs = join_pairs_cols(ctx, R, nR, S, nS, m);                            // <-- rhj_join_cols_dev
+        } else {
+            DevArr R(ctx, nR * 16), S(ctx, nS * 16);
+            OK(ctx, rhj_gather_tuples(ctx, c1, in1 ? inter[j.table1].p : rows[j.table1].ptr(), nR, in1 ? 1 : 0, (rhj_tuple *)R.p));
+            OK(ctx, rhj_gather_tuples(ctx, c2, in2 ? inter[j.table2].p : rows[j.table2].ptr(), nS, in2 ? 1 : 0, (rhj_tuple *)S.p));
+            pairs = join_pairs(ctx, R, nR, S, nS, m);                                 // <-- rhj_join_dev
+        }
         if (m == 0) { filtered_out = true; return; }
         DevArr kr(ctx, m * 8), ks(ctx, m * 8);
         OK(ctx, rhj_pairs_split(ctx, (const rhj_pair *)pairs.p, m, kr.p, ks.p));

@@ -2873,7 +2873,10 @@ int rhj_shard_join(rhj_ctx *ctx, rhj_pair *d_out, uint64_t out_capacity, uint64_
     *out_count = 0;
     prof_reset(ctx);
     const u64 mR = ctx->shard_n[0], mS = ctx->shard_n[1];
-    if (mR == 0 || mS == 0) return RHJ_OK;
+    if (mR == 0 || mS == 0) {                              // an empty input: no kernel runs ("last.join_kernel" -1, rhj.h)
+        ctx->last_join_kind = -1;
+        return RHJ_OK;
+    }
     const int mode = ctx->shard_mode[0];
     const int tb = ctx->shard_plan.bits1 + ctx->shard_plan.bits2;
     const bool narrow = mode != RHJ_SHARD_GLOBAL16;

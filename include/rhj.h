@@ -134,7 +134,10 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * geometry and its half-size form, 8 the full-size table with half the buckets, 9 the half-size middle geometry skipping the slot
  * rows a partition leaves empty, 10 the same with 13-bit arrival indices (keys of up to 51 bits: what plans of 13-15 radix bits take
  * by themselves for partitions of 2-5 K tuples), 11 a smaller table with 12-bit arrival indices (plans of 12 bits); the sizes are
- * the rows of JOIN_GEOM in radixhashjoin_amd/csrc/rhj_internal.h), "last.pipelined" (the number
+ * the rows of JOIN_GEOM in radixhashjoin_amd/csrc/rhj_internal.h; 12 the semi / anti join kernel: rhj_semi_join_dev /
+ * rhj_semi_join_cols_dev, whatever the plan), "last.semi_tables" (the largest number of LDS tables any one task of the last
+ * semi / anti join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
+ * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home; 0: the plain path),
  * "last.max_part_R" / "last.max_part_S" (tuples in the largest partition of each side the last partitioned join saw; 0 for
  * an unpartitioned one), "last.cols_R" / "last.cols_S" (how the last join read that side: 0 it was not a columnar call -- every join
@@ -198,6 +201,31 @@ int rhj_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tupl
 int rhj_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
                       const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
                       const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count);
+
+/* ---- semi-join and anti-join: WHICH tuples of R have a partner in S at all (RHJ_SEMI: EXISTS, isin on key columns, semi-join
+ * reduction) or have none (RHJ_ANTI: NOT EXISTS; a left outer join is the inner join plus the anti-join's rows).  R as columns
+ * exactly as in rhj_join_cols_dev (d_idR == NULL: rowID = i); S is its value column alone: S has no id column, its rowIDs never
+ * reach the result.
+ * Output: d_out_ids receives the rowID (id[i], or i for a NULL id column; .key for tuples) of every tuple of R that qualifies, each
+ * tuple exactly ONCE whatever the multiplicity of its value in S (a value repeated 10^4 times on both sides: 10^4 ids, not the 10^8
+ * pairs of the inner join); two tuples of R with the same value are two tuples, and both are reported.  Order is unspecified.
+ * d_out_ids == NULL with out_capacity 0 counts only.  Returns RHJ_E_OVERFLOW (and the exact *out_count) when out_capacity is too
+ * small: slots [0, capacity) then hold distinct ids of the result, and nothing at or past capacity is written.
+ * nR == 0: count 0.  nS == 0: count 0 for RHJ_SEMI, all nR ids for RHJ_ANTI.  A NULL value column (relation) with n > 0, or a kind
+ * other than the two below: RHJ_E_INVALID.  Inputs are neither modified nor retained.
+ * Plan, options, timings, "last.narrow", "last.countfree_*" and "last.cols_*" as rhj_join_cols_dev / rhj_join_dev on the same sizes
+ * (same partition kernels, same repeats after a count-free overflow or a rowID >= 2^32 of R in a narrow format), except that a
+ * one-pass plan always runs as separate partition and join launches; "last.join_kernel" is 12, "last.semi_tables" see rhj_get_info.
+ * rhj_opts.probe_split above 32768 acts as 32768 (a task keeps one match bit per tuple of R in LDS). */
+#define RHJ_SEMI 0   /* R tuples whose join value occurs in S          */
+#define RHJ_ANTI 1   /* R tuples whose join value does not occur in S  */
+int rhj_semi_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *d_valS, uint64_t nS, int kind, const rhj_opts *opts,
+                           uint64_t *d_out_ids, uint64_t out_capacity, uint64_t *out_count);
+/* ... on 16-byte tuples (the .key of S's tuples is not looked at) */
+int rhj_semi_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                      int kind, const rhj_opts *opts,
+                      uint64_t *d_out_ids, uint64_t out_capacity, uint64_t *out_count);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:

@@ -8,15 +8,18 @@ CPU fallback: if the HIP library is missing or no GPU is present, construction o
 :class:`Engine` raises.
 
 From torch: ``idx_R, idx_S = Engine(0).join_columns(keys_R, keys_S)`` joins two int64 key tensors on the engine's device
-(``rhj_join_cols_dev``: the relations as columns, rowID = index).
+(``rhj_join_cols_dev``: the relations as columns, rowID = index); ``Engine(0).semi_join_columns(keys_R, keys_S, anti=False)``
+returns the indices of the keys of R that occur (``anti=True``: do not occur) in S (``rhj_semi_join_cols_dev``).
 """
 from .binding import (  # noqa: F401
+    ANTI,
     PAIR,
     TUPLE,
     DeviceBuffer,
     Engine,
     Opts,
     RhjError,
+    SEMI,
     Timings,
     lib_path,
     load_library,
@@ -24,5 +27,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI"]
 __version__ = "0.1.0"

@@ -1,4 +1,5 @@
 """ctypes binding of include/rhj.h (librhj_hip.so).  No compute happens in Python."""
+import contextlib
 import ctypes as C
 import os
 
@@ -75,6 +76,8 @@ SYMBOLS = {
     "rhj_join_batch": (C.c_int, [_vp, C.c_uint32, _P(JoinDesc), _P(_vp), _P(_u64)]),
     "rhj_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_semi_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_semi_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -171,6 +174,7 @@ def narrow_bytes(n):
     return load_library().rhj_narrow_bytes(n)
 
 
+SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
 
@@ -282,7 +286,8 @@ class Engine:
         self._chk(self.lib.rhj_set_option(self.ctx, name.encode(), int(value)))
 
     def info(self, name):
-        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel"; include/rhj.h)"""
+        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables";
+        include/rhj.h)"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
         return v.value
@@ -403,14 +408,31 @@ class Engine:
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
 
-    def join_columns(self, keys_R, keys_S):
-        """Equi-join of two key tensors: (idx_R, idx_S), int64 tensors with keys_R[idx_R[i]] == keys_S[idx_S[i]] for every i,
-        every matching index pair exactly once, in no particular order.  keys_R / keys_S: contiguous 1-D 64-bit integer torch
-        tensors on this engine's device, compared by bit pattern.  Count, allocate, join -- ordered behind the work torch has queued
-        on its current stream: on a stream of its own (torch.cuda.stream(s)) the engine runs on that stream for the length of the call;
-        torch's default stream has no handle to hand over (its raw value is 0, which rhj_set_stream reads as "the context's own
-        stream"), so there the call waits on the host for the stream first and runs on the stream the engine has.  Either way the
-        results are complete when it returns, and a stream bound earlier with set_stream is bound again."""
+    def semi_join_cols_dev(self, d_valR, d_idR, nR, d_valS, nS, kind, d_out=None, capacity=0, opts=None, allow_overflow=False):
+        """rhj_semi_join_cols_dev: the rowIDs of the R tuples whose join value occurs (kind SEMI) / does not occur (ANTI) in the
+        value column of S, each once; d_out: uint64[capacity] in HBM, or None to count"""
+        n = _u64()
+        rc = self.lib.rhj_semi_join_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), nS, kind,
+                                             C.byref(opts) if opts is not None else None, _addr(d_out), capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def semi_join_dev(self, d_R, nR, d_S, nS, kind, d_out=None, capacity=0, opts=None, allow_overflow=False):
+        """rhj_semi_join_dev: semi_join_cols_dev on 16-byte tuples (the rowIDs of S are not looked at)"""
+        n = _u64()
+        rc = self.lib.rhj_semi_join_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, kind,
+                                        C.byref(opts) if opts is not None else None, _addr(d_out), capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    @contextlib.contextmanager
+    def _on_torch_stream(self, keys_R, keys_S):
+        """What join_columns and semi_join_columns share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
+        engine's device (ValueError otherwise).  The body runs ordered behind the work torch has queued on its current stream: on a
+        stream of its own (torch.cuda.stream(s)) the engine runs on that stream for the length of the body; torch's default stream
+        has no handle to hand over (its raw value is 0, which rhj_set_stream reads as "the context's own stream"), so there the call
+        waits on the host for the stream first and runs on the stream the engine has.  Either way the results are complete when
+        the block is left, and a stream bound earlier with set_stream is bound again.  Yields the tensors' device."""
         import torch
         ints = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)
         for name, k in (("keys_R", keys_R), ("keys_S", keys_S)):
@@ -421,7 +443,6 @@ class Engine:
             if not k.is_contiguous():
                 raise ValueError(f"{name}: the tensor must be contiguous")
         dev = keys_R.device
-        nR, nS = keys_R.numel(), keys_S.numel()
         with torch.cuda.device(dev):
             torch_stream = torch.cuda.current_stream(dev)
             cur, before = torch_stream.cuda_stream, self.bound_stream
@@ -430,20 +451,47 @@ class Engine:
             elif cur != before:
                 self.set_stream(cur)
             try:
-                count = self.join_cols_dev(keys_R, None, nR, keys_S, None, nS) if nR and nS else 0
-                idx_R = torch.empty(count, dtype=torch.int64, device=dev)
-                idx_S = torch.empty(count, dtype=torch.int64, device=dev)
-                if count:
-                    pairs = torch.empty((count, 2), dtype=torch.int64, device=dev)
-                    got = self.join_cols_dev(keys_R, None, nR, keys_S, None, nS, pairs, count)
-                    assert got == count, (got, count)
-                    self.pairs_split(pairs, count, idx_R, idx_S)
+                yield dev
             finally:
                 if cur != 0 and cur != before:
                     self.set_stream(before)     # (synchronises torch's stream first: the results are complete)
                 else:
                     self.sync()
+
+    def join_columns(self, keys_R, keys_S):
+        """Equi-join of two key tensors: (idx_R, idx_S), int64 tensors with keys_R[idx_R[i]] == keys_S[idx_S[i]] for every i,
+        every matching index pair exactly once, in no particular order.  keys_R / keys_S: contiguous 1-D 64-bit integer torch
+        tensors on this engine's device, compared by bit pattern.  Count, allocate, join -- ordered behind the work torch has queued
+        on its current stream (see _on_torch_stream); the results are complete when it returns, and a stream bound earlier with
+        set_stream is bound again."""
+        import torch
+        with self._on_torch_stream(keys_R, keys_S) as dev:
+            nR, nS = keys_R.numel(), keys_S.numel()
+            count = self.join_cols_dev(keys_R, None, nR, keys_S, None, nS) if nR and nS else 0
+            idx_R = torch.empty(count, dtype=torch.int64, device=dev)
+            idx_S = torch.empty(count, dtype=torch.int64, device=dev)
+            if count:
+                pairs = torch.empty((count, 2), dtype=torch.int64, device=dev)
+                got = self.join_cols_dev(keys_R, None, nR, keys_S, None, nS, pairs, count)
+                assert got == count, (got, count)
+                self.pairs_split(pairs, count, idx_R, idx_S)
         return idx_R, idx_S
+
+    def semi_join_columns(self, keys_R, keys_S, anti=False):
+        """idx_R, an int64 tensor: every i for which keys_R[i] occurs in keys_S -- with anti=True, does NOT occur -- exactly once,
+        in no particular order, however often the key is repeated in keys_S (torch.isin as indices; EXISTS / NOT EXISTS).  Tensors,
+        streams and completion as join_columns.  Count, allocate, fill.  (A left outer join is join_columns plus the rows of
+        semi_join_columns(.., anti=True).)"""
+        import torch
+        kind = ANTI if anti else SEMI
+        with self._on_torch_stream(keys_R, keys_S) as dev:
+            nR, nS = keys_R.numel(), keys_S.numel()
+            count = self.semi_join_cols_dev(keys_R, None, nR, keys_S, nS, kind) if nR else 0
+            idx_R = torch.empty(count, dtype=torch.int64, device=dev)
+            if count:
+                got = self.semi_join_cols_dev(keys_R, None, nR, keys_S, nS, kind, idx_R, count)
+                assert got == count, (got, count)
+        return idx_R
 
     def histogram(self, d_rel, n, shift, bits, d_hist):
         self._chk(self.lib.rhj_histogram(self.ctx, _addr(d_rel), n, shift, bits, _addr(d_hist)))

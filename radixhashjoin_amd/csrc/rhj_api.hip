@@ -230,6 +230,7 @@ struct rhj_ctx {
     int last_join_kind = -1;
     int last_pipelined = 0;            // S chunks of the last rhj_join (0: not pipelined)
     u64 last_max_part[2] = {0, 0};     // largest partition of R / S the last task list saw (0: direct join)
+    int last_semi_tables = 0;          // "last.semi_tables": LDS tables the busiest task of the last semi / anti join built (0: another call)
     bool counters_clean = false;       // the 64-byte join counters are zero (cleared by the partition phase's first launch)
     int cur_narrow = 0;                // partitions are in the narrow {payload, rowID} format (k_scatter_wcn); 2: so was the intermediate
     DevBuf narrow_flag;                // u32: a rowID >= 2^32 met a narrow scatter -> the join re-runs in the 16-byte format
@@ -444,6 +445,7 @@ void prof_reset(rhj_ctx *ctx)
     }
     memset(&ctx->last, 0, sizeof(ctx->last));
     ctx->last_cols[0] = ctx->last_cols[1] = 0;      // "last.cols_*": every join or stage call starts here; rhj_join_cols_dev sets them as it goes
+    ctx->last_semi_tables = 0;                      // "last.semi_tables": ... and semi_phase this one
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -1348,6 +1350,67 @@ int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
                          ctx->cur_nparts, ctx->cur_radix_bits, ctx->cur_probe_split, d_out, cap, out_count, ctx->cur_narrow != 0);
 }
 
+// What a join reports once both sides are partitioned: the pairs (join_phase), or the rowIDs of the tuples of R with (RHJ_SEMI) or
+// without (RHJ_ANTI) a partner in S (semi_phase).
+enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI };
+
+// Semi / anti join phase on the partitions partition_phase left: k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
+// Reads the skip word behind its kernel and answers with the retry codes of join_phase_on.
+int semi_phase(rhj_ctx *ctx, JoinOutput what, void *d_out, u64 cap, u64 *out_count)
+{
+    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
+    const bool narrow = ctx->cur_narrow != 0;
+    u32 split = ctx->cur_probe_split;
+    if (split == 0 || split > SEMI_MAX_SPLIT) split = SEMI_MAX_SPLIT;        // a task's match bits: 4 KiB of LDS
+    const u64 max_tasks64 = nparts + nR / split + 1;
+    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
+    const u32 max_tasks = (u32)max_tasks64;
+    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
+    RHJCHK(ensure(ctx, ctx->counters, 64));
+    u64 *d_count = (u64 *)ctx->counters.p;
+    if (!ctx->counters_clean) {                        // (a paired partition pass has cleared them already)
+        Span s(ctx, RHJ_K_AUX);
+        HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+    }
+    ctx->counters_clean = false;
+    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
+        Span s(ctx, RHJ_K_AUX);
+        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+        launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+    }
+    ctx->last_join_kind = JK_SEMI;
+    ctx->sniff_ready = false;                          // (the samples of the partition phase are not asked)
+    {
+        Span s(ctx, RHJ_K_TASKS);
+        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, ctx->cur_psS, nparts, split, what == OUT_ANTI, (JoinTask *)ctx->tasks.p,
+                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
+    }
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        launch_semi_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
+                         ctx->cur_radix_bits, what == OUT_ANTI, (u64 *)d_out, d_out ? cap : 0, d_count, d_count + 7,
+                         narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
+                         narrow ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
+                         narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+    }
+    RHJCHK(check_launch(ctx, "semi join phase"));
+    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // count, ntasks, max |R_k|, max |S_k|, -, oversized table side, -, most tables of a task (if > 1)
+    u32 wide_rowid = 0;
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
+    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
+    *out_count = host[0];
+    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
+    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
+    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
+    ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
+    if (host[5])
+        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    return RHJ_OK;
+}
+
 // bookkeeping of the narrow-format back-off (rhj.h "partition.narrow"), shared by the plain and the pipelined host path
 void narrow_note_fallback(rhj_ctx *ctx)                  // a join met a rowID >= 2^32 in the narrow format
 {
@@ -1475,14 +1538,18 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
 
 // partition + join.  A run in the narrow format whose histogram kernel met a rowID >= 2^32 costs two histogram launches
 // (every later kernel of the run returns at once) and is repeated in the 16-byte format; the fall-back is per join.
+// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase (which always takes the unfused
+// path: the one-pass form has the pair join built into its launches).
 int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan, void *d_out,
-                       u64 cap, u64 *out_count, std::function<int()> *before_S = nullptr)
+                       u64 cap, u64 *out_count, std::function<int()> *before_S = nullptr, JoinOutput what = OUT_PAIRS)
 {
-    if (fused_one_pass_ok(ctx, nR, nS, plan)) return join_one_pass_fused(ctx, d_R, nR, d_S, nS, plan, d_out, cap, out_count, before_S);
+    if (what == OUT_PAIRS && fused_one_pass_ok(ctx, nR, nS, plan))
+        return join_one_pass_fused(ctx, d_R, nR, d_S, nS, plan, d_out, cap, out_count, before_S);
+    auto after_partition = [&]() { return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : semi_phase(ctx, what, d_out, cap, out_count); };
     int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S);
     if (rc != RHJ_OK) { ctx->counters_clean = false; return rc; }
     const bool tried_narrow = ctx->cur_narrow != 0;
-    rc = join_phase(ctx, d_out, cap, out_count);
+    rc = after_partition();
     // A side whose count-free pass 1 overflowed is partitioned again with exact cursors (k_hist2d_units), inside this call.  R's
     // partition stands when only S overflowed; after an overflow of R the kernels of S returned at once, so S runs again (count-free
     // as before: at most two repeats).
@@ -1498,7 +1565,7 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
         ctx->cf_keep_R = !(over & 2u);
         rc = partition_phase(ctx, d_R, nR, d_S, nS, plan);
         ctx->cf_keep_R = false;
-        if (rc == RHJ_OK) rc = join_phase(ctx, d_out, cap, out_count);
+        if (rc == RHJ_OK) rc = after_partition();
     }
     ctx->cf_off_once[0] = ctx->cf_off_once[1] = false;
     if (rc == RHJ_RETRY_CF) return fail(ctx, RHJ_E_HIP, "count-free partition: overflow flag after the exact repeat");
@@ -1514,7 +1581,7 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
     rc = partition_phase(ctx, d_R, nR, d_S, nS, plan);
     ctx->narrow_off_once = false;
     if (rc != RHJ_OK) { ctx->counters_clean = false; return rc; }
-    return join_phase(ctx, d_out, cap, out_count);
+    return after_partition();
 }
 
 // one relation under a resolved two-pass (or one-pass) plan; narrow: the level narrow_level() returned for the join
@@ -1711,6 +1778,7 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.pipelined") { *value = ctx->last_pipelined; return RHJ_OK; }
     if (n == "last.max_part_R") { *value = (int64_t)ctx->last_max_part[0]; return RHJ_OK; }
     if (n == "last.max_part_S") { *value = (int64_t)ctx->last_max_part[1]; return RHJ_OK; }
+    if (n == "last.semi_tables") { *value = ctx->last_semi_tables; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }
@@ -1843,6 +1911,71 @@ int rhj_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_id
     RHJCHK(rc);
     if (d_out && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
     return RHJ_OK;
+}
+
+// Semi / anti join: the partition phase and the repeat ladder of rhj_join_dev / rhj_join_cols_dev, then semi_phase.
+// d_R / d_S null: the relations are ctx->cols_in.  An empty S under RHJ_ANTI: every tuple of R, by the bucket kernel over empty
+// tables -- R unpartitioned, its one partition cut into tasks.
+static int semi_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, int kind, const rhj_opts *opts,
+                            uint64_t *d_out_ids, u64 out_capacity, uint64_t *out_count)
+{
+    if (nR == 0 || (nS == 0 && kind == RHJ_SEMI)) return join_nothing(ctx);
+    const u64 cap = d_out_ids ? out_capacity : 0;
+    if (nS == 0) {
+        ctx->cur_nR = nR;
+        ctx->cur_nS = 0;
+        ctx->cur_probe_split = 0;
+        ctx->cur_narrow = 0;
+        ctx->counters_clean = false;
+        ctx->last_cf[0] = ctx->last_cf[1] = 0;
+        RHJCHK(cols_to_aos(ctx, 0, nR, d_R));
+        RHJCHK(ensure(ctx, ctx->ps_R, 64));
+        RHJCHK(ensure(ctx, ctx->ps_S, 64));
+        ctx->cur_R = ctx->cur_S = d_R;                 // (no tuple of S is read)
+        ctx->cur_psR = (const u64 *)ctx->ps_R.p;
+        ctx->cur_psS = (const u64 *)ctx->ps_S.p;
+        ctx->cur_nparts = 1;
+        ctx->cur_radix_bits = 0;
+        const int rc = semi_phase(ctx, OUT_ANTI, d_out_ids, cap, (u64 *)out_count);
+        if (rc != RHJ_OK) return rc > 0 ? fail(ctx, RHJ_E_HIP, "semi join: a repeat was asked for without a partition phase") : rc;
+    } else {
+        rhj_opts plan;
+        if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+        RHJCHK(partition_and_join(ctx, d_R, nR, d_S, nS, plan, d_out_ids, cap, (u64 *)out_count, nullptr,
+                                  kind == RHJ_ANTI ? OUT_ANTI : OUT_SEMI));
+    }
+    if (d_out_ids && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
+    return RHJ_OK;
+}
+
+int rhj_semi_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, int kind,
+                      const rhj_opts *opts, uint64_t *d_out_ids, uint64_t out_capacity, uint64_t *out_count)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
+    *out_count = 0;
+    prof_reset(ctx);
+    if (kind != RHJ_SEMI && kind != RHJ_ANTI) return fail(ctx, RHJ_E_INVALID, "kind is neither RHJ_SEMI nor RHJ_ANTI");
+    if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return semi_join_common(ctx, d_R, nR, d_S, nS, kind, opts, d_out_ids, out_capacity, out_count);
+}
+
+int rhj_semi_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR, const uint64_t *d_valS,
+                           uint64_t nS, int kind, const rhj_opts *opts, uint64_t *d_out_ids, uint64_t out_capacity,
+                           uint64_t *out_count)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
+    *out_count = 0;
+    prof_reset(ctx);
+    if (kind != RHJ_SEMI && kind != RHJ_ANTI) return fail(ctx, RHJ_E_INVALID, "kind is neither RHJ_SEMI nor RHJ_ANTI");
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
+    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = nullptr;      // S has no id column: rowID = index, never reported
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = semi_join_common(ctx, nullptr, nR, nullptr, nS, kind, opts, d_out_ids, out_capacity, out_count);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
 }
 
 namespace {

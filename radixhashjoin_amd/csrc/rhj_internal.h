@@ -229,6 +229,30 @@ constexpr bool join_geom_ok(int k)
            (k == 0 || join_geom_ok(k - 1));
 }
 static_assert(join_geom_ok(JK_LAST), "a JOIN_GEOM row breaks what its kernel needs");
+// ---- the semi / anti join kernel (k_semi_bkt): one geometry -------------------------------------------------------
+// An open-addressed LDS table of 8-byte KEYS of S (no rowIDs), insert-if-absent, filled while S's partition streams through it in
+// tiles of SEMI_BUILD_TILE tuples and closed before a tile that could take it past SEMI_FILL distinct keys (9/16 of its slots: a
+// linear probe always meets an empty slot, and soon); a 4 KiB bitmap of match bits for the task's at most SEMI_MAX_SPLIT tuples of R.
+constexpr int JK_SEMI = JK_LAST + 1;              // "last.join_kernel" of a semi / anti join (12)
+constexpr int SEMI_THREADS = 512;                 // 8 wavefronts; 68.3 KiB of LDS: two workgroups per CU
+constexpr int SEMI_SLOT_BITS = 13;                // 8192 slots = 64 KiB
+constexpr u32 SEMI_FILL = 4608;                   // distinct keys a table takes at most
+constexpr int SEMI_BPT = 2;                       // tuples of S per thread per build tile
+constexpr u32 SEMI_BUILD_TILE = SEMI_THREADS * SEMI_BPT;
+constexpr int SEMI_EPT = 8;                       // tuples of R per thread per probe tile (4096)
+constexpr u32 SEMI_MAX_SPLIT = 32768;             // tuples of R per task at most: the match bits of a task
+constexpr size_t semi_lds_bytes() { return ((size_t)8 << SEMI_SLOT_BITS) + SEMI_MAX_SPLIT / 8 + 64 * 4 + 32; }
+static_assert(2 * semi_lds_bytes() <= 160 * 1024 && SEMI_FILL + SEMI_BUILD_TILE <= (1u << SEMI_SLOT_BITS) &&
+              SEMI_MAX_SPLIT % (SEMI_THREADS * SEMI_EPT) == 0 && SEMI_EPT * (SEMI_THREADS / 64) == 64, "k_semi_bkt's geometry");
+// task list of a semi / anti join: partition k gets ceil(|R_k| / split) tasks if |R_k| != 0 && (|S_k| != 0 || anti); the table side
+// is always S.  d_stats as launch_make_tasks (zeroed by the caller): largest partitions, [3] = an |S_k| >= 2^32.
+void launch_make_semi_tasks(hipStream_t st, const u64 *d_startR, const u64 *d_startS, u64 nparts, u32 split, int anti,
+                            JoinTask *d_tasks, u32 *d_ntasks, u32 max_tasks, u64 *d_stats);
+// d_out: u64 rowIDs of R (may be null: count only); d_max_tables: atomicMax of the tables a task built, by tasks that built
+// several; d_RK / d_SK: the rowID arrays of narrow partitions (both or neither); d_skip: as launch_join
+void launch_semi_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                      int radix_bits, int anti, u64 *d_out, u64 out_capacity, u64 *d_out_count, u64 *d_max_tables,
+                      const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
 // in_narrow: d_in is a payload array (u64).  key_base / d_wide (16-byte input): d_wide (may be null) is OR-ed with 1 when some
 // rowID - key_base does not fit 32 bits.  d_unit_rng (may be null): explicit pass-1 units (launch_seg_units).
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,

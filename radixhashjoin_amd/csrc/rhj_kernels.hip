@@ -1887,6 +1887,51 @@ k_make_tasks(const u64 *__restrict__ startR, const u64 *__restrict__ startS, u64
     }
 }
 
+// Task list of a semi / anti join (k_semi_bkt): the table side is always S's partition, the probe side always R's -- no sniff, no
+// skew rule.  Partition k gets ceil(|R_k| / split) tasks if |R_k| != 0 && (|S_k| != 0 || anti): an anti join reports the tuples of
+// R whose partition of S is empty, a semi join has nothing to report there.  stats as k_make_tasks (zero before): [0] / [1] the
+// largest partition of R / S, [3] an |S_k| >= 2^32, which a task cannot address.
+__global__ void __launch_bounds__(1024)
+k_make_semi_tasks(const u64 *__restrict__ startR, const u64 *__restrict__ startS, u64 nparts, u32 split, int anti,
+                  JoinTask *__restrict__ tasks, u32 *__restrict__ ntasks, u32 max_tasks, u64 *__restrict__ stats)
+{
+    __shared__ u32 wsum[16];
+    __shared__ u32 gbase;
+    const u64 k = (u64)blockIdx.x * 1024 + threadIdx.x;
+    u64 r0 = 0, nr = 0, s0 = 0, ns = 0;
+    if (k < nparts) { r0 = startR[k]; nr = startR[k + 1] - r0; s0 = startS[k]; ns = startS[k + 1] - s0; }
+    u64 mr = nr, ms = ns;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const u64 a = __shfl_down(mr, off, 64), b = __shfl_down(ms, off, 64);
+        mr = a > mr ? a : mr;
+        ms = b > ms ? b : ms;
+    }
+    if ((threadIdx.x & 63) == 0) { if (mr) atomicMax(&stats[0], mr); if (ms) atomicMax(&stats[1], ms); }
+    u32 nt = 0;
+    if (nr != 0 && (ns != 0 || anti)) {
+        nt = (u32)((nr + split - 1) / split);
+        if (ns >> 32) { nt = 0; atomicMax(&stats[3], ns); }                  // report instead of truncating (host: RHJ_E_INVALID)
+    }
+    u32 tot;
+    const u32 ex = block_excl_scan<1024>(nt, wsum, tot);
+    if (threadIdx.x == 0) gbase = tot ? atomicAdd(ntasks, tot) : 0u;
+    __syncthreads();
+    u32 slot = gbase + ex;
+    for (u32 j = 0; j < nt; j++, slot++) {
+        if (slot >= max_tasks) break;                  // cannot happen: max_tasks is an upper bound
+        JoinTask t;
+        t.pbeg = r0 + (u64)j * split;
+        const u64 rem = nr - (u64)j * split;
+        t.plen = (u32)(rem < split ? rem : split);
+        t.part = (u32)k;
+        t.bbeg = s0;
+        t.blen = (u32)ns;
+        t.build_is_S = 1;
+        tasks[slot] = t;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K4 (bucketized LDS table): bucket build + probe + result write.
 // JoinJob::run + Result::join_buckets (Result.cpp:43-76) + the page appends of add_result/addAll
@@ -2347,6 +2392,189 @@ k_join_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
             }
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Semi / anti join of one task: which tuples of R's range have a partner in S's partition at all.
+//   * the table holds KEYS of S only, open-addressed with linear probing, insert-if-absent by a 64-bit LDS compare-and-swap:
+//     a join value repeated 10^6 times in S occupies one slot, so the heavy values of a Zipf S never ask for a second table.
+//     The all-ones word marks an empty slot; a key of S that IS all ones sets a flag beside the table instead.
+//   * S's partition streams through in tiles of SEMI_BUILD_TILE tuples.  The count of distinct keys is read between two
+//     barriers after every tile -- the same number whatever the order of the inserts -- and a table closes before the tile that
+//     could take it past SEMI_FILL, so where a table ends does not depend on timing, and a probe always meets an empty slot.
+//     SEMI_FILL is 9/16 of the slots: a wavefront probes in lock step, so a slot row costs what its LONGEST probe costs, and
+//     the long probes of a fuller table cost more than the further table ([measured] DESIGN 4.12).
+//   * every table is probed by all tiles of the task's R range; a probe stops at its first hit.  The sweep of the LAST table
+//     emits: the one sweep there is when S's partition fits a table (or is empty: the anti join of a partition without S), and
+//     R is then read from HBM once.  Earlier sweeps leave a match bit per tuple in LDS (a wavefront owns the two words of its
+//     64 tuples of a slot row: plain stores); the last sweep probes only the tuples whose bit is still clear.
+//   * emit: per slot row a wavefront ballot + mbcnt prefix, one 64-lane scan over the (slot, wavefront) totals, one global
+//     atomicAdd per tile; 8-byte rowIDs dense in lane order, nothing at or past out_capacity, nothing at all when counting.
+// ------------------------------------------------------------------------------------------------
+constexpr u64 SEMI_EMPTY = ~0ull;
+constexpr int SEMI_PROBE_GROUP = 4;               // slot rows of a probe tile whose first table reads are issued together
+static_assert(SEMI_EPT % SEMI_PROBE_GROUP == 0, "whole groups");
+typedef u64 v2u64 __attribute__((ext_vector_type(2)));
+
+template <bool NARROW>
+__global__ void __launch_bounds__(SEMI_THREADS, 4)
+k_semi_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks,
+           int radix_bits, int anti, u64 *__restrict__ out, u64 out_capacity, u64 *__restrict__ out_count,
+           u64 *__restrict__ max_tables, const u32 *__restrict__ skip)
+{
+    if (skip != nullptr && *skip != 0) return;
+    if (blockIdx.x >= *ntasks) return;
+    constexpr int THREADS = SEMI_THREADS, NW = THREADS / 64, EPT = SEMI_EPT, TILE = THREADS * EPT;
+    constexpr u32 SLOTS = 1u << SEMI_SLOT_BITS;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64 *tab = reinterpret_cast<u64 *>(smem);                                // SLOTS keys
+    u32 *bm = reinterpret_cast<u32 *>(tab + SLOTS);                          // SEMI_MAX_SPLIT match bits
+    u32 *wtot = bm + SEMI_MAX_SPLIT / 32;                                    // 64: [slot][wave] totals of a tile
+    u32 *ctl = wtot + 64;                                                    // [0] distinct keys in the table, [1] S holds the all-ones key
+    u64 *gres = reinterpret_cast<u64 *>(ctl + 2);
+
+    const JoinTask task = tasks[blockIdx.x];
+    typedef typename RelView<NARROW>::Both Both;
+    const RelView<NARROW> Sv = S.at(task.bbeg);
+    const u32 ns = task.blen, np = task.plen;                                // np <= SEMI_MAX_SPLIT (the host clamps the split)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const typename RelView<NARROW>::Buf PB = R.at(task.pbeg).buf(0, np);
+    // (the match bits need no clearing: the first sweep of a task with several tables stores every word a later sweep reads)
+
+    // slots 2b, 2b + 1, 2b + 2, ... is a key's probe order: an insert takes the first empty slot in it, a probe reads it a pair
+    // (one 16-byte LDS read) at a time -- the key lies before the first empty slot or nowhere
+    const v2u64 *tab2 = reinterpret_cast<const v2u64 *>(tab);
+    auto probe_on = [&](u64 key, u32 b) -> bool {                            // ... from pair b on (key != SEMI_EMPTY)
+        for (;; b = (b + 1) & (SLOTS / 2 - 1)) {
+            const v2u64 e = tab2[b];
+            if (e.x == key || e.y == key) return true;
+            if (e.x == SEMI_EMPTY || e.y == SEMI_EMPTY) return false;
+        }
+    };
+    auto insert = [&](u64 key) -> bool {                                     // true: the key was not there
+        if (key == SEMI_EMPTY) { ctl[1] = 1; return false; }
+        for (u32 s = 2u * bj_bucket<SEMI_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            if (cur == key) return false;
+            if (cur != SEMI_EMPTY) continue;
+            const u64 old = atomicCAS((unsigned long long *)&tab[s], (unsigned long long)SEMI_EMPTY, (unsigned long long)key);
+            if (old == SEMI_EMPTY) return true;
+            if (old == key) return false;
+        }
+    };
+    auto rank_in = [&](unsigned long long m) -> u32 { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); };
+    auto load_keys = [&](u64 (&dst)[SEMI_BPT], u32 at) {                     // the tile of S that starts at tuple `at` (< ns)
+        const typename RelView<NARROW>::Buf SB = Sv.buf(at, ns - at < SEMI_BUILD_TILE ? ns - at : SEMI_BUILD_TILE);
+#pragma unroll
+        for (int k = 0; k < SEMI_BPT; k++) dst[k] = SB.payload((u32)k * THREADS, (u32)tid);
+    };
+
+    // the first tile of either side is in flight while the table is cleared; from then on the next tile of S is requested before
+    // the current one is inserted, the next tile of R before the current one is probed
+    u64 key[SEMI_BPT], key_next[SEMI_BPT];
+    if (ns != 0) load_keys(key, 0);
+    Both p[EPT], p_next[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; k++) p[k] = PB.both((u32)k * THREADS, (u32)tid);
+
+    u32 sdone = 0, ntab = 0;
+    bool last;
+    do {
+        // ---- build: the next whole tiles of S's partition -----------------------------------------
+        if (ns != 0) for (u32 i = tid; i < SLOTS; i += THREADS) tab[i] = SEMI_EMPTY;
+        if (tid == 0) { ctl[0] = 0; ctl[1] = 0; }
+        __syncthreads();
+        u32 filled = 0;
+        while (sdone < ns && filled + SEMI_BUILD_TILE <= SEMI_FILL) {
+            const u32 nt = ns - sdone < SEMI_BUILD_TILE ? ns - sdone : SEMI_BUILD_TILE;
+            const bool more = sdone + nt < ns;
+            if (more) load_keys(key_next, sdone + nt);
+#pragma unroll
+            for (int k = 0; k < SEMI_BPT; k++) {
+                const bool fresh = (u32)k * THREADS + tid < nt && insert(key[k]);
+                const unsigned long long m = __ballot(fresh);
+                if (lane == 0 && m) atomicAdd(&ctl[0], (u32)__popcll(m));
+            }
+            __syncthreads();
+            filled = ctl[0];
+            __syncthreads();                                                 // (everybody has read the count before the next tile adds to it)
+            sdone += nt;
+            if (more) {
+#pragma unroll
+                for (int k = 0; k < SEMI_BPT; k++) key[k] = key_next[k];     // (a table that closes here leaves them for the next one)
+            }
+        }
+        ntab++;
+        last = sdone >= ns;
+
+        // ---- probe: every tile of the task's R range ------------------------------------------------
+        for (u32 tb = 0; tb < np; tb += TILE) {
+            // the tile the next step starts with: the next of this sweep, or the first again for the next table's sweep
+            const u32 tn = tb + TILE < np ? tb + (u32)TILE : 0u;
+            const bool fetch = tn != tb && !(last && tn == 0);
+            if (fetch) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) p_next[k] = PB.both(tn + (u32)k * THREADS, (u32)tid);
+            }
+            u32 emit = 0;                                                    // bit k: this lane reports its tuple of slot row k
+            // The first pair of SEMI_PROBE_GROUP slot rows is read unconditionally and together (any pair index is inside the table):
+            // under SEMI_FILL most probes end there, and the LDS round trips of a group overlap; only the rest walk on alone.
+            v2u64 e0[SEMI_PROBE_GROUP];
+#pragma unroll
+            for (int k = 0; k < EPT; k++) {
+                if (k % SEMI_PROBE_GROUP == 0) {
+#pragma unroll
+                    for (int j = 0; j < SEMI_PROBE_GROUP; j++) e0[j] = tab2[bj_bucket<SEMI_SLOT_BITS - 1>(p[k + j].payload, radix_bits)];
+                }
+                const u32 i = tb + (u32)k * THREADS + tid;                   // < SEMI_MAX_SPLIT
+                bool hit = ntab > 1 && ((bm[i >> 5] >> (i & 31)) & 1u) != 0;
+                if (i < np && !hit && ns != 0) {                             // (ns == 0: the table was never cleared)
+                    const u64 key = p[k].payload;
+                    const v2u64 e = e0[k % SEMI_PROBE_GROUP];
+                    if (key == SEMI_EMPTY) hit = ctl[1] != 0;
+                    else if (e.x == key || e.y == key) hit = true;
+                    else if (e.x != SEMI_EMPTY && e.y != SEMI_EMPTY)
+                        hit = probe_on(key, (bj_bucket<SEMI_SLOT_BITS - 1>(key, radix_bits) + 1) & (SLOTS / 2 - 1));
+                }
+                if (last) {
+                    if (i < np && hit != (anti != 0)) emit |= 1u << k;
+                } else {
+                    const unsigned long long m = __ballot(hit);             // (bits set by earlier tables included)
+                    if (lane == 0) { bm[(i >> 5)] = (u32)m; bm[(i >> 5) + 1] = (u32)(m >> 32); }
+                }
+            }
+            if (last) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) {
+                    const unsigned long long m = __ballot((emit >> k) & 1u);
+                    if (lane == 0) wtot[k * NW + w] = (u32)__popcll(m);
+                }
+                __syncthreads();
+                const u32 mine = wtot[lane];                                 // every wavefront scans the 64 totals itself
+                const u32 inc64 = wave_incl_scan(mine, lane);
+                const u32 tile_total = __shfl(inc64, 63, 64);
+                if (tid == 0 && tile_total) *gres = atomicAdd((unsigned long long *)out_count, (unsigned long long)tile_total);
+                __syncthreads();
+                if (tile_total && out != nullptr) {
+                    const u64 g = *gres;
+                    const u32 wu = (u32)__builtin_amdgcn_readfirstlane(w);
+#pragma unroll
+                    for (int k = 0; k < EPT; k++) {
+                        const unsigned long long m = __ballot((emit >> k) & 1u);
+                        const u64 o = g + (u32)__builtin_amdgcn_readlane((int)(inc64 - mine), k * NW + wu) + rank_in(m);
+                        if (((emit >> k) & 1u) && o < out_capacity) out[o] = (u64)p[k].key;
+                    }
+                }
+                // wtot / gres are rewritten only after the next tile's first barrier: safe without another one
+            }
+            if (fetch) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) p[k] = p_next[k];
+            }
+        }
+        __syncthreads();                                                     // the table is cleared for the next tiles of S
+    } while (!last);
+    if (tid == 0 && ntab > 1) atomicMax((unsigned long long *)max_tables, (unsigned long long)ntab);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3065,6 +3293,8 @@ static void allow_big_lds()
         allow_ct_lds<decltype(k)::value, false>();
     });
     allow_ct_lds<JK_CT, false, true>();                                      // the stamps aid
+    SET_LDS(k_semi_bkt<true>, semi_lds_bytes());
+    SET_LDS(k_semi_bkt<false>, semi_lds_bytes());
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<IN_AOS>, wn_lds_bytes(WN_MAX_BITS));
@@ -3634,6 +3864,29 @@ void launch_join(hipStream_t st, const void *d_R, const u64 *d_startR, const voi
         constexpr int K = decltype(k)::value;                               // (kind is not narrow-only here: see above)
         if constexpr (ct_exists<K, false>) launch_ct<K, false>(st, grid, vR, vS, d_tasks, d_ntasks, radix_bits, o, out_capacity, d_out_count, nullptr);
     });
+}
+
+void launch_make_semi_tasks(hipStream_t st, const u64 *d_startR, const u64 *d_startS, u64 nparts, u32 split, int anti,
+                            JoinTask *d_tasks, u32 *d_ntasks, u32 max_tasks, u64 *d_stats)
+{
+    hipLaunchKernelGGL(k_make_semi_tasks, dim3((unsigned)((nparts + 1023) / 1024)), dim3(1024), 0, st, d_startR, d_startS, nparts,
+                       split, anti, d_tasks, d_ntasks, max_tasks, d_stats);
+}
+
+void launch_semi_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                      int radix_bits, int anti, u64 *d_out, u64 out_capacity, u64 *d_out_count, u64 *d_max_tables,
+                      const u32 *d_RK, const u32 *d_SK, const u32 *d_skip)
+{
+    if (grid == 0) return;
+    allow_big_lds();
+    if (d_RK != nullptr)                                                     // narrow partitions: d_R, d_S are payload arrays
+        hipLaunchKernelGGL(k_semi_bkt<true>, dim3(grid), dim3(SEMI_THREADS), semi_lds_bytes(), st, RelView<true>{(const u64 *)d_R, d_RK},
+                           RelView<true>{(const u64 *)d_S, d_SK}, d_tasks, d_ntasks, radix_bits, anti, d_out, out_capacity, d_out_count,
+                           d_max_tables, d_skip);
+    else
+        hipLaunchKernelGGL(k_semi_bkt<false>, dim3(grid), dim3(SEMI_THREADS), semi_lds_bytes(), st, RelView<false>{(const Tup *)d_R},
+                           RelView<false>{(const Tup *)d_S}, d_tasks, d_ntasks, radix_bits, anti, d_out, out_capacity, d_out_count,
+                           d_max_tables, d_skip);
 }
 
 // Unpartitioned join of two small relations in ONE launch: build side = S when nR >= nS (JobScheduler.cpp:187).

@@ -185,6 +185,20 @@ void launch_join(hipStream_t st, const void *, const u64 *, const void *, const 
         if (host_pub) for (int i = 0; i < 7; i++) host_pub[i] = d_out_count[i];      // (the last workgroup publishes the counters)
     });
 }
+void launch_make_semi_tasks(hipStream_t st, const u64 *, const u64 *, u64, u32, int, JoinTask *, u32 *d_ntasks, u32, u64 *)
+{
+    fake_enqueue(st, [=] { *d_ntasks = 1; });
+}
+void launch_semi_join(hipStream_t st, const void *, const void *, const JoinTask *, const u32 *, u32, int, int, u64 *d_out, u64 out_capacity,
+                      u64 *d_out_count, u64 *, const u32 *, const u32 *, const u32 *)
+{
+    fake_enqueue(st, [=] {
+        const u64 at = *d_out_count;
+        for (u64 i = at; i < at + FAKE_PAIRS; i++)
+            if (d_out && i < out_capacity) d_out[i] = i;
+        *d_out_count = at + FAKE_PAIRS;
+    });
+}
 int build_tie_shift() { return 4; }
 size_t fuse_ctl_bytes() { return 12352; }
 u32 *fuse_join_ticket(void *d_ctl) { return (u32 *)((unsigned char *)d_ctl + 12288) + 1; }

@@ -1,12 +1,14 @@
 // query_unit.cpp -- CPU-only unit checks of the query layer's host logic (no GPU call is made):
 // query text parser, the three update_intermediate cases against a brute-force restatement of
-// the reference's semantics (intermediate.cpp:52-87,146-183), Result page bookkeeping.
+// the reference's semantics (intermediate.cpp:52-87,146-183), Result page bookkeeping, the two forms of a same-alias
+// predicate (parse_table).
 // Exit code 0 = all checks passed.  Run by tests/test_host_logic.py.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <string>
+#include <unistd.h>
 #include <vector>
 
 #include "rhj_query.h"
@@ -101,6 +103,38 @@ int main()
         update_intermediate(got, res, j);
         Inter exp = brute(in, pairs, t1, t2);
         CHECK(rows_sorted(got) == rows_sorted(exp));
+    }
+    {   // parse_table: a.c0 = a.c1 is a row filter, on whichever representation the alias has at that point
+        char path[] = "/tmp/rhj_query_unit_XXXXXX";
+        const int fd = mkstemp(path);
+        CHECK(fd >= 0);
+        const uint64_t file[] = {6, 2, /* c0 */ 1, 2, 3, 4, 5, 6, /* c1 */ 1, 0, 3, 0, 0, 6};     // rows 0, 2, 5 pass
+        CHECK(write(fd, file, sizeof file) == (ssize_t)sizeof file);
+        close(fd);
+        relList rel(path);
+        unlink(path);
+        join_info same(1, 0, 1, 1);
+        // alias 1 not joined yet while aliases 0 and 2 hold columns of another length: its surviving rows shrink,
+        // no column is seeded and the other columns stay as they are
+        std::unordered_map<uint64_t, std::unordered_set<uint64_t> > filtered;
+        filtered[1] = {0, 1, 2, 3, 4};
+        Inter in(3);
+        in[0] = {7, 8, 9, 7, 8, 9, 7, 8, 9};
+        in[2] = {1, 1, 1, 2, 2, 2, 3, 3, 3};
+        const Inter before = in;
+        CHECK(parse_table(same, rel, filtered, in));
+        CHECK(in == before);
+        CHECK((filtered[1] == std::unordered_set<uint64_t>{0, 2}));
+        filtered[1] = {1, 3};
+        CHECK(!parse_table(same, rel, filtered, in) && in == before && filtered[1].empty());
+        // alias 1 joined: the intermediate rows whose rowID fails go, in every column
+        in[1] = {5, 1, 0, 0, 4, 2, 3, 5, 5};
+        CHECK(parse_table(same, rel, filtered, in));
+        CHECK((in[1] == std::vector<uint64_t>{5, 0, 0, 2, 5, 5}));
+        CHECK((in[0] == std::vector<uint64_t>{7, 9, 7, 9, 8, 9}) && (in[2] == std::vector<uint64_t>{1, 1, 2, 2, 3, 3}));
+        in[0] = {7, 8}; in[1] = {1, 4}; in[2] = {0, 0};
+        CHECK(!parse_table(same, rel, filtered, in) && in[1].empty());
+        rel.destroy();
     }
     if (failures) { fprintf(stderr, "%d checks failed\n", failures); return 1; }
     printf("query_unit: all checks passed\n");

@@ -209,14 +209,20 @@ bool Query::run_filters(vector<relList> &relations, FilteredRows &filtered)
 // ------------------------------------------------------------------------------------------------
 // intermediates
 // ------------------------------------------------------------------------------------------------
-// same-alias predicate a.c1 = a.c2 (intermediate.cpp:11-44): a row filter
-void parse_table(join_info &join, relList &relation, FilteredRows &filtered, vector<vector<uint64_t> > &intermediate)
+// same-alias predicate a.c1 = a.c2 (intermediate.cpp:11-44): a row filter.  Returns false when no row is left.
+// An alias that is not part of the intermediate yet loses rows of its `filtered` set and stays outside the intermediate:
+// a column seeded here would differ in length from the columns other aliases already hold, and the next join between
+// two "joined" aliases would index one by the positions of the other.
+bool parse_table(join_info &join, relList &relation, FilteredRows &filtered, vector<vector<uint64_t> > &intermediate)
 {
     const uint64_t *c1 = relation.values[join.column1], *c2 = relation.values[join.column2];
     vector<uint64_t> &col = intermediate[join.table1];
     if (col.empty()) {
-        for (uint64_t rowid : filtered.find(join.table1)->second) if (c1[rowid] == c2[rowid]) col.push_back(rowid);
-        return;
+        unordered_set<uint64_t> &rows = filtered.find(join.table1)->second;
+        for (auto it = rows.begin(); it != rows.end();) {
+            if (c1[*it] == c2[*it]) ++it; else it = rows.erase(it);
+        }
+        return !rows.empty();
     }
     // alias already joined: drop the intermediate ROWS that fail the predicate, in every column
     const size_t n = col.size();
@@ -228,6 +234,7 @@ void parse_table(join_info &join, relList &relation, FilteredRows &filtered, vec
         for (size_t e = 0; e < n; e++) if (ok[e]) k[w++] = k[e];
         k.resize(w);
     }
+    return !col.empty();
 }
 
 template <typename F> static void for_each_pair(const Result &res, F f)
@@ -319,8 +326,7 @@ void Query::run_joins(JobScheduler &js, vector<relList> &relations, FilteredRows
     vector<vector<uint64_t> > intermediate(table.size());
     for (join_info &j : join) {
         if (j.table1 == j.table2) {
-            parse_table(j, relations[table[j.table1]], filtered, intermediate);
-            if (intermediate[j.table1].empty()) { filtered_out = true; break; }
+            if (!parse_table(j, relations[table[j.table1]], filtered, intermediate)) { filtered_out = true; break; }
             continue;
         }
         relation relR, relS;
@@ -331,6 +337,9 @@ void Query::run_joins(JobScheduler &js, vector<relList> &relations, FilteredRows
         log_join(relR, relS, results);
         if (results.isEmpty()) { filtered_out = true; break; }
         update_intermediate(intermediate, results, j);
+        // a predicate between two joined aliases can leave no intermediate row although the join of their distinct rows
+        // found pairs: no row is NULL like any other empty step (and an emptied column would read as "not joined" below)
+        if (intermediate[j.table1].empty()) { filtered_out = true; break; }
     }
     js.barrier();
     if (filtered_out) return;
@@ -370,8 +379,7 @@ void Query::execute_batch(JobScheduler &js, vector<Query> &queries, vector<relLi
             // same-alias predicates are row filters on the host (parse_table): consume them until a real join comes up
             while (!s.done && s.next < s.q->join.size() && s.q->join[s.next].table1 == s.q->join[s.next].table2) {
                 join_info &j = s.q->join[s.next++];
-                parse_table(j, relations[s.q->table[j.table1]], s.filtered, s.intermediate);
-                if (s.intermediate[j.table1].empty()) { s.q->filtered_out = true; s.done = true; }
+                if (!parse_table(j, relations[s.q->table[j.table1]], s.filtered, s.intermediate)) { s.q->filtered_out = true; s.done = true; }
             }
             if (!s.done && s.next < s.q->join.size()) level.push_back(&s);
         }
@@ -394,6 +402,7 @@ void Query::execute_batch(JobScheduler &js, vector<Query> &queries, vector<relLi
             log_join(R[i], S[i], res[i]);
             if (res[i].isEmpty()) { s.q->filtered_out = true; s.done = true; continue; }
             update_intermediate(s.intermediate, res[i], s.q->join[s.next]);
+            if (s.intermediate[s.q->join[s.next].table1].empty()) { s.q->filtered_out = true; s.done = true; continue; }
             s.next++;
         }
     }

@@ -96,8 +96,8 @@ private:
 /* test hook of the "cols" mode: appends "cols <nR> <nS> <count>" to $RHJ_JOIN_LOG (one line per rhj_join_cols_dev call) */
 void log_cols_join(uint64_t nR, uint64_t nS, uint64_t count);
 
-/* intermediate.h:10-14 */
-void parse_table(join_info &join, relList &relation,
+/* intermediate.h:10-14.  parse_table: false when the same-alias predicate leaves no row */
+bool parse_table(join_info &join, relList &relation,
                  std::unordered_map<uint64_t, std::unordered_set<uint64_t> > &filtered,
                  std::vector<std::vector<uint64_t> > &intermediate);
 void update_intermediate(std::vector<std::vector<uint64_t> > &intermediate, const Result &results, join_info &join);

@@ -5,7 +5,8 @@ Query::run_joins the golden workload small.work never reaches (a projected alias
 joins, the a-b / c-d / b-c order, a predicate between two aliases already in the intermediate), and edge.result = what the
 REAL reference (oracle/_ref/join_ref, compiled from its own sources by oracle/Makefile) prints for them.
 Same-alias predicates (parse_table, intermediate.cpp:11-44) are NOT covered: the reference segfaults on them here
-(SURVEY §2 #7 documents the undefined behaviour), so that corner is parity-unpinned."""
+(SURVEY §2 #7 documents the undefined behaviour), so that corner has no parity fixture; tests/test_gpu_query_sql.py pins
+it to the SQL semantics (tests/sql_eval.py) in every executor mode instead."""
 import os
 import subprocess
 

@@ -135,8 +135,9 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * rows a partition leaves empty, 10 the same with 13-bit arrival indices (keys of up to 51 bits: what plans of 13-15 radix bits take
  * by themselves for partitions of 2-5 K tuples), 11 a smaller table with 12-bit arrival indices (plans of 12 bits); the sizes are
  * the rows of JOIN_GEOM in radixhashjoin_amd/csrc/rhj_internal.h; 12 the semi / anti join kernel: rhj_semi_join_dev /
- * rhj_semi_join_cols_dev, whatever the plan), "last.semi_tables" (the largest number of LDS tables any one task of the last
- * semi / anti join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
+ * rhj_semi_join_cols_dev, whatever the plan; 13 the aggregating join kernel: rhj_join_sum_dev / rhj_join_sum_cols_dev, whatever
+ * the plan), "last.semi_tables" (the largest number of LDS tables any one task of the last
+ * semi / anti join or aggregating join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home; 0: the plain path),
  * "last.max_part_R" / "last.max_part_S" (tuples in the largest partition of each side the last partitioned join saw; 0 for
@@ -226,6 +227,30 @@ int rhj_semi_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
 int rhj_semi_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                       int kind, const rhj_opts *opts,
                       uint64_t *d_out_ids, uint64_t out_capacity, uint64_t *out_count);
+
+/* ---- aggregating join: COUNT(*) and SUM(column of R) over R join S without producing the pairs (SELECT COUNT(*), SUM(r.x) FROM R JOIN
+ * S USING (key)).  For a join value repeated n times on both sides the pair set holds n^2 pairs; this call reads both relations once
+ * and keeps, beside every key of S in the join kernel's table, how often it occurs. */
+#define RHJ_SUM_MAX_COLS 4
+/* count = |R join S| and, for j < ncols, sums[j] = sum over the pairs of d_cols[j][rowR]  (mod 2^64), without producing the pairs:
+ * linear in nR + nS whatever the multiplicity of a join value.  R as columns exactly as rhj_join_cols_dev (d_idR == NULL: rowID = i);
+ * S is its value column alone.  d_cols: HOST array of ncols DEVICE columns, each col_rows uint64 long, indexed by R's rowID;
+ * a rowID >= col_rows is never dereferenced: RHJ_E_INVALID.  out_count / out_sums: HOST words; the call synchronises.
+ * ncols == 0 is a pure COUNT(*): d_cols, out_sums and col_rows are ignored.  RHJ_E_INVALID: ncols > RHJ_SUM_MAX_COLS, a NULL
+ * column (or NULL d_cols / out_sums) with ncols > 0, a NULL value column (relation) with n > 0, NULL out_count.  nR == 0 or nS == 0:
+ * count 0 and all sums 0, no launch.  The sums over columns of S's side are the same call with the sides exchanged.
+ * Plan, options, timings, "last.narrow", "last.countfree_*" and "last.cols_*" as rhj_join_cols_dev / rhj_join_dev on the same sizes
+ * (same partition kernels, same repeats after a count-free overflow or a rowID >= 2^32 of R in a narrow format; a repeat starts its
+ * sums from zero), except that a one-pass plan always runs as separate partition and join launches; "last.join_kernel" is 13,
+ * "last.semi_tables" see rhj_get_info.  rhj_opts.probe_split: values above 2^24 act as 2^24.  Results are bit-exact from run to
+ * run (integer addition does not depend on the order).  Inputs are neither modified nor retained. */
+int rhj_join_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                          const uint64_t *d_valS, uint64_t nS, const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows,
+                          const rhj_opts *opts, uint64_t *out_count, uint64_t *out_sums);
+/* ... on 16-byte tuples (rowR = .key; the .key of S's tuples is not looked at) */
+int rhj_join_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                     const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows,
+                     const rhj_opts *opts, uint64_t *out_count, uint64_t *out_sums);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:

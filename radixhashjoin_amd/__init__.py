@@ -9,7 +9,9 @@ CPU fallback: if the HIP library is missing or no GPU is present, construction o
 
 From torch: ``idx_R, idx_S = Engine(0).join_columns(keys_R, keys_S)`` joins two int64 key tensors on the engine's device
 (``rhj_join_cols_dev``: the relations as columns, rowID = index); ``Engine(0).semi_join_columns(keys_R, keys_S, anti=False)``
-returns the indices of the keys of R that occur (``anti=True``: do not occur) in S (``rhj_semi_join_cols_dev``).
+returns the indices of the keys of R that occur (``anti=True``: do not occur) in S (``rhj_semi_join_cols_dev``);
+``count, sums = Engine(0).join_sum_columns(keys_R, keys_S, weights)`` is COUNT(*) and SUM(weights[k][i]) over the join's pairs
+without the pairs (``rhj_join_sum_cols_dev``).
 """
 from .binding import (  # noqa: F401
     ANTI,
@@ -20,6 +22,7 @@ from .binding import (  # noqa: F401
     Opts,
     RhjError,
     SEMI,
+    SUM_MAX_COLS,
     Timings,
     lib_path,
     load_library,
@@ -27,5 +30,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "SUM_MAX_COLS"]
 __version__ = "0.1.0"

@@ -78,6 +78,8 @@ SYMBOLS = {
     "rhj_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_semi_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_semi_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_join_sum_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _P(_u64), _P(_u64)]),
+    "rhj_join_sum_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _P(_u64), _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -174,6 +176,7 @@ def narrow_bytes(n):
     return load_library().rhj_narrow_bytes(n)
 
 
+SUM_MAX_COLS = 4                                         # include/rhj.h RHJ_SUM_MAX_COLS: weight columns of a join_sum_* call
 SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
@@ -425,23 +428,48 @@ class Engine:
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
 
+    @staticmethod
+    def _sum_args(d_cols):
+        cols = (_vp * max(len(d_cols), 1))(*[_addr(c) for c in d_cols])
+        return cols, (_u64 * max(len(d_cols), 1))()
+
+    def join_sum_cols_dev(self, d_valR, d_idR, nR, d_valS, nS, d_cols=(), col_rows=0, opts=None):
+        """rhj_join_sum_cols_dev: (count, [sums]) -- |R join S| and, per column of d_cols (at most SUM_MAX_COLS device columns of
+        col_rows uint64, indexed by R's rowID), the sum of the column over the pairs mod 2^64, as Python ints; no pair is written"""
+        n = _u64()
+        cols, sums = self._sum_args(d_cols)
+        self._chk(self.lib.rhj_join_sum_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), nS, cols, len(d_cols),
+                                                 col_rows, C.byref(opts) if opts is not None else None, C.byref(n), sums))
+        return n.value, [int(sums[j]) for j in range(len(d_cols))]
+
+    def join_sum_dev(self, d_R, nR, d_S, nS, d_cols=(), col_rows=0, opts=None):
+        """rhj_join_sum_dev: join_sum_cols_dev on 16-byte tuples (rowR = .key; the rowIDs of S are not looked at)"""
+        n = _u64()
+        cols, sums = self._sum_args(d_cols)
+        self._chk(self.lib.rhj_join_sum_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, cols, len(d_cols), col_rows,
+                                            C.byref(opts) if opts is not None else None, C.byref(n), sums))
+        return n.value, [int(sums[j]) for j in range(len(d_cols))]
+
     @contextlib.contextmanager
-    def _on_torch_stream(self, keys_R, keys_S):
-        """What join_columns and semi_join_columns share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
-        engine's device (ValueError otherwise).  The body runs ordered behind the work torch has queued on its current stream: on a
+    def _on_torch_stream(self, keys_R, keys_S, weights=()):
+        """What join_columns, semi_join_columns and join_sum_columns share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
+        engine's device (ValueError otherwise); weights: tensors of the same kind, each as long as keys_R.  The body runs ordered behind the work torch has queued on its current stream: on a
         stream of its own (torch.cuda.stream(s)) the engine runs on that stream for the length of the body; torch's default stream
         has no handle to hand over (its raw value is 0, which rhj_set_stream reads as "the context's own stream"), so there the call
         waits on the host for the stream first and runs on the stream the engine has.  Either way the results are complete when
         the block is left, and a stream bound earlier with set_stream is bound again.  Yields the tensors' device."""
         import torch
         ints = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)
-        for name, k in (("keys_R", keys_R), ("keys_S", keys_S)):
+        for name, k in (("keys_R", keys_R), ("keys_S", keys_S)) + tuple((f"weights[{i}]", w) for i, w in enumerate(weights)):
             if not isinstance(k, torch.Tensor) or k.dtype not in ints or k.dim() != 1:
                 raise ValueError(f"{name}: a 1-D torch tensor of 64-bit integers is needed")
             if k.device.type != "cuda" or (k.device.index or 0) != self.device:
                 raise ValueError(f"{name}: the tensor must live on the engine's device (cuda:{self.device}), not {k.device}")
             if not k.is_contiguous():
                 raise ValueError(f"{name}: the tensor must be contiguous")
+        for i, w in enumerate(weights):
+            if w.numel() != keys_R.numel():
+                raise ValueError(f"weights[{i}]: {w.numel()} elements for {keys_R.numel()} keys of R")
         dev = keys_R.device
         with torch.cuda.device(dev):
             torch_stream = torch.cuda.current_stream(dev)
@@ -492,6 +520,19 @@ class Engine:
                 got = self.semi_join_cols_dev(keys_R, None, nR, keys_S, nS, kind, idx_R, count)
                 assert got == count, (got, count)
         return idx_R
+
+    def join_sum_columns(self, keys_R, keys_S, weights=()):
+        """(count, sums): count = the number of index pairs (i, j) with keys_R[i] == keys_S[j], sums[k] = the sum of weights[k][i]
+        over those pairs mod 2^64 (SELECT COUNT(*), SUM(r.x) FROM R JOIN S USING (key)), as Python ints in [0, 2^64) -- without the
+        pairs, in time linear in the inputs however often a key repeats.  weights: up to SUM_MAX_COLS contiguous 1-D 64-bit integer
+        tensors of len(keys_R) on the engine's device (int64 weights: read the sums as two's complement).  Tensors, streams and
+        completion as join_columns."""
+        weights = tuple(weights)
+        if len(weights) > SUM_MAX_COLS:
+            raise ValueError(f"at most {SUM_MAX_COLS} weight tensors per call, not {len(weights)}")
+        with self._on_torch_stream(keys_R, keys_S, weights):
+            nR, nS = keys_R.numel(), keys_S.numel()
+            return self.join_sum_cols_dev(keys_R, None, nR, keys_S, nS, weights, nR)
 
     def histogram(self, d_rel, n, shift, bits, d_hist):
         self._chk(self.lib.rhj_histogram(self.ctx, _addr(d_rel), n, shift, bits, _addr(d_hist)))

@@ -233,6 +233,11 @@ struct rhj_ctx {
     int last_semi_tables = 0;          // "last.semi_tables": LDS tables the busiest task of the last semi / anti join built (0: another call)
     bool counters_clean = false;       // the 64-byte join counters are zero (cleared by the partition phase's first launch)
     int cur_narrow = 0;                // partitions are in the narrow {payload, rowID} format (k_scatter_wcn); 2: so was the intermediate
+    DevBuf agg_out;                    // an aggregating join's words: [0] count, [1 .. 4] sums, [5] u32 a rowID >= col_rows was met
+    const u64 *agg_cols[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};   // ... its weight columns (device), for the length of the call
+    u32 agg_ncols = 0;
+    u64 agg_col_rows = 0;
+    u64 *agg_sums_out = nullptr;       // ... and where agg_phase leaves the ncols sums (host)
     DevBuf narrow_flag;                // u32: a rowID >= 2^32 met a narrow scatter -> the join re-runs in the 16-byte format
     // ... the next join tries the narrow format again; consecutive fall-backs make the context skip the attempt for the next
     // 2, 4, ... 32 eligible joins (a caller whose rowIDs are always wide pays one extra histogram per relation now and then)
@@ -1350,9 +1355,9 @@ int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
                          ctx->cur_nparts, ctx->cur_radix_bits, ctx->cur_probe_split, d_out, cap, out_count, ctx->cur_narrow != 0);
 }
 
-// What a join reports once both sides are partitioned: the pairs (join_phase), or the rowIDs of the tuples of R with (RHJ_SEMI) or
-// without (RHJ_ANTI) a partner in S (semi_phase).
-enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI };
+// What a join reports once both sides are partitioned: the pairs (join_phase), the rowIDs of the tuples of R with (RHJ_SEMI) or
+// without (RHJ_ANTI) a partner in S (semi_phase), or the pair count and sums over the pairs (agg_phase).
+enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2 };
 
 // Semi / anti join phase on the partitions partition_phase left: k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
 // Reads the skip word behind its kernel and answers with the retry codes of join_phase_on.
@@ -1408,6 +1413,73 @@ int semi_phase(rhj_ctx *ctx, JoinOutput what, void *d_out, u64 cap, u64 *out_cou
     ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
     if (host[5])
         return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    return RHJ_OK;
+}
+
+// Aggregating join phase on the partitions partition_phase left: k_make_semi_tasks (anti = 0) + k_agg_bkt over the
+// weight columns the entry point left in the context.  EVERY attempt zeroes the sums words and the guard flag before its kernel: a
+// repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes as semi_phase.
+int agg_phase(rhj_ctx *ctx, u64 *out_count)
+{
+    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
+    const bool narrow = ctx->cur_narrow != 0;
+    u32 split = ctx->cur_probe_split;
+    if (split == 0) split = 32768;
+    if (split > AGG_MAX_SPLIT) split = AGG_MAX_SPLIT;
+    const u64 max_tasks64 = nparts + nR / split + 1;
+    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
+    const u32 max_tasks = (u32)max_tasks64;
+    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
+    RHJCHK(ensure(ctx, ctx->counters, 64));
+    RHJCHK(ensure(ctx, ctx->agg_out, 64));
+    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
+    {
+        Span s(ctx, RHJ_K_AUX);
+        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));   // (a paired partition pass has cleared them already)
+        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
+    }
+    ctx->counters_clean = false;
+    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
+        Span s(ctx, RHJ_K_AUX);
+        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+        launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+    }
+    ctx->last_join_kind = JK_AGG;
+    ctx->sniff_ready = false;                          // (the samples of the partition phase are not asked)
+    {
+        Span s(ctx, RHJ_K_TASKS);
+        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, ctx->cur_psS, nparts, split, 0, (JoinTask *)ctx->tasks.p,
+                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
+    }
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        launch_agg_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
+                        ctx->cur_radix_bits, ctx->agg_cols, ctx->agg_ncols, ctx->agg_col_rows, d_agg, (u32 *)(d_agg + AGG_MAX_COLS + 1),
+                        d_count + 7,
+                        narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
+                        narrow ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
+                        narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+    }
+    RHJCHK(check_launch(ctx, "aggregating join phase"));
+    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, oversized table side, -, most tables of a task (if > 1)
+    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // count, sums, guard flag
+    u32 wide_rowid = 0;
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
+    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
+    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
+    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
+    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
+    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
+    ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
+    if (host[5])
+        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    if ((u32)agg[AGG_MAX_COLS + 1])
+        return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= col_rows: the weight columns have no such row");
+    *out_count = agg[0];
+    for (u32 j = 0; j < ctx->agg_ncols; j++) ctx->agg_sums_out[j] = agg[1 + j];
     return RHJ_OK;
 }
 
@@ -1538,14 +1610,16 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
 
 // partition + join.  A run in the narrow format whose histogram kernel met a rowID >= 2^32 costs two histogram launches
 // (every later kernel of the run returns at once) and is repeated in the 16-byte format; the fall-back is per join.
-// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase (which always takes the unfused
-// path: the one-pass form has the pair join built into its launches).
+// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase (which always take the
+// unfused path: the one-pass form has the pair join built into its launches).
 int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan, void *d_out,
                        u64 cap, u64 *out_count, std::function<int()> *before_S = nullptr, JoinOutput what = OUT_PAIRS)
 {
     if (what == OUT_PAIRS && fused_one_pass_ok(ctx, nR, nS, plan))
         return join_one_pass_fused(ctx, d_R, nR, d_S, nS, plan, d_out, cap, out_count, before_S);
-    auto after_partition = [&]() { return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : semi_phase(ctx, what, d_out, cap, out_count); };
+    auto after_partition = [&]() {
+        return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : what == OUT_SUMS ? agg_phase(ctx, out_count) : semi_phase(ctx, what, d_out, cap, out_count);
+    };
     int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S);
     if (rc != RHJ_OK) { ctx->counters_clean = false; return rc; }
     const bool tried_narrow = ctx->cur_narrow != 0;
@@ -1689,7 +1763,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->ps_1, &ctx->seg0, &ctx->unit_start, &ctx->unit_hist, &ctx->unit_base, &ctx->seg0_b,
                      &ctx->unit_start_b, &ctx->unit_hist_b, &ctx->unit_base_b, &ctx->scan_tmp_b, &ctx->tasks,
                      &ctx->counters, &ctx->out_pairs, &ctx->small_out, &ctx->hist_tmp, &ctx->scan_tmp, &ctx->hist2,
-                     &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->seg_rng, &ctx->tag_base,
+                     &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->agg_out, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
                      &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
                      &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1]};
@@ -1974,6 +2048,59 @@ int rhj_semi_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
     ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = nullptr;      // S has no id column: rowID = index, never reported
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
     const int rc = semi_join_common(ctx, nullptr, nR, nullptr, nS, kind, opts, d_out_ids, out_capacity, out_count);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// Aggregating join: the partition phase and the repeat ladder of rhj_join_dev / rhj_join_cols_dev, then agg_phase.
+// d_R / d_S null: the relations are ctx->cols_in.
+static int join_sum_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const uint64_t *const *d_cols, uint32_t ncols,
+                           uint64_t col_rows, const rhj_opts *opts, uint64_t *out_count, uint64_t *out_sums)
+{
+    if (ncols > RHJ_SUM_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncols is above RHJ_SUM_MAX_COLS");
+    if (ncols && (!d_cols || !out_sums)) return fail(ctx, RHJ_E_INVALID, "null weight column array or out_sums");
+    for (u32 j = 0; j < ncols; j++) {
+        if (!d_cols[j]) return fail(ctx, RHJ_E_INVALID, "null weight column");
+        out_sums[j] = 0;
+    }
+    if (nR == 0 || nS == 0) return join_nothing(ctx);
+    rhj_opts plan;
+    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) ctx->agg_cols[j] = j < ncols ? (const u64 *)d_cols[j] : nullptr;
+    ctx->agg_ncols = ncols;
+    ctx->agg_col_rows = ncols ? col_rows : ~0ull;
+    ctx->agg_sums_out = (u64 *)out_sums;
+    const int rc = partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_count, nullptr, OUT_SUMS);
+    ctx->agg_ncols = 0;
+    ctx->agg_sums_out = nullptr;
+    return rc;
+}
+
+int rhj_join_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                     const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows,
+                     const rhj_opts *opts, uint64_t *out_count, uint64_t *out_sums)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
+    *out_count = 0;
+    prof_reset(ctx);
+    if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return join_sum_common(ctx, d_R, nR, d_S, nS, d_cols, ncols, col_rows, opts, out_count, out_sums);
+}
+
+int rhj_join_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR, const uint64_t *d_valS, uint64_t nS,
+                          const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                          uint64_t *out_count, uint64_t *out_sums)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
+    *out_count = 0;
+    prof_reset(ctx);
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
+    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = nullptr;      // S has no id column: rowID = index, never looked at
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = join_sum_common(ctx, nullptr, nR, nullptr, nS, d_cols, ncols, col_rows, opts, out_count, out_sums);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

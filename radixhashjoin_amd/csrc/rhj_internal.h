@@ -253,6 +253,29 @@ void launch_make_semi_tasks(hipStream_t st, const u64 *d_startR, const u64 *d_st
 void launch_semi_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
                       int radix_bits, int anti, u64 *d_out, u64 out_capacity, u64 *d_out_count, u64 *d_max_tables,
                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
+// ---- the aggregating join kernel (k_agg_bkt): one geometry --------------------------------------------------------
+// k_semi_bkt's table of 8-byte keys of S with a 32-bit occurrence count beside every slot, in a parallel array: 8192 + 8192 = 96 KiB,
+// one workgroup of 1024 threads per CU -- four wavefronts per SIMD, and a 15 K-tuple partition of S in four tables where the
+// 4096-slot shape (48 KiB, workgroups of 512) would sweep R seven times.  No match bits: a task's R range is not bound by LDS.
+constexpr int JK_AGG = JK_SEMI + 1;               // "last.join_kernel" of an aggregating join (13)
+constexpr int AGG_MAX_COLS = 4;                   // sums per call (rhj.h RHJ_SUM_MAX_COLS)
+constexpr int AGG_THREADS = 1024;                 // 16 wavefronts
+constexpr int AGG_SLOT_BITS = 13;                 // 8192 slots: 64 KiB of keys + 32 KiB of counts
+constexpr u32 AGG_FILL = 4608;                    // distinct keys a table takes at most (9/16 of its slots, as SEMI_FILL)
+constexpr int AGG_BPT = 1;                        // tuples of S per thread per build tile
+constexpr u32 AGG_BUILD_TILE = AGG_THREADS * AGG_BPT;
+constexpr int AGG_EPT = 4;                        // tuples of R per thread per probe tile (4096)
+constexpr u32 AGG_MAX_SPLIT = BJ_MAX_PROBE_SPLIT; // tuples of R per task at most (rhj_opts.probe_split: values above 2^24 act as 2^24)
+constexpr size_t agg_lds_bytes() { return ((size_t)12 << AGG_SLOT_BITS) + 16; }
+static_assert(agg_lds_bytes() <= 160 * 1024 && AGG_FILL + AGG_BUILD_TILE <= (1u << AGG_SLOT_BITS) &&
+              (size_t)(AGG_THREADS / 64) * (AGG_MAX_COLS + 1) * 8 <= ((size_t)8 << AGG_SLOT_BITS) &&
+              (u64)AGG_MAX_SPLIT * 16 < (1ull << 31), "k_agg_bkt's geometry");
+// The task list is launch_make_semi_tasks with anti = 0.  d_cols: HOST array of ncols (<= AGG_MAX_COLS) device columns of col_rows words indexed by
+// R's rowID; d_sums: ncols + 1 words (zeroed by the caller), word 0 the count; d_bad: OR-ed with 1 when a rowID >= col_rows was
+// met (ncols != 0 only); the rest as launch_semi_join.
+void launch_agg_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                     int radix_bits, const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_sums, u32 *d_bad, u64 *d_max_tables,
+                     const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
 // in_narrow: d_in is a payload array (u64).  key_base / d_wide (16-byte input): d_wide (may be null) is OR-ed with 1 when some
 // rowID - key_base does not fit 32 bits.  d_unit_rng (may be null): explicit pass-1 units (launch_seg_units).
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,

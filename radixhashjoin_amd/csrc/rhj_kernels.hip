@@ -2578,6 +2578,174 @@ k_semi_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
 }
 
 // ------------------------------------------------------------------------------------------------
+// Aggregating join of one task: COUNT(*) and SUM(column of R) over R join S without the pairs.
+//   * k_semi_bkt's table -- keys of S, open-addressed, insert-if-absent by a 64-bit LDS compare-and-swap, the same tiles and the
+//     same close rule -- with a 32-bit occurrence count beside every slot: every tuple of S adds 1 to the slot its key occupies,
+//     whether it placed the key or found it (a table sees at most blen < 2^32 tuples).  The all-ones key counts in ctl[1].
+//   * a tuple of R with key k and rowID r meets c = count of k in this table (0: absent) and adds c to the thread's count and
+//     c * cols[j][r] to its sum j (mod 2^64).  Tables are ADDITIVE: a key of S whose tuples fall into several tables has its count
+//     split among them, every table is swept by all of the task's R range and adds its share -- no match bits, no last-table case,
+//     so the range is not bound by LDS.
+//   * cols[j][r] is read only where c != 0 and r < col_rows; a tuple with r >= col_rows adds nothing and raises *bad (the host
+//     answers RHJ_E_INVALID): a wild rowID never becomes an address.
+//   * end of task: wavefront shuffles, one LDS round, one 64-bit global atomicAdd per word into sums[0 .. ncols] (word 0: the
+//     count).  Integer addition mod 2^64 does not depend on the order: results are bit-exact from run to run.
+// ------------------------------------------------------------------------------------------------
+struct AggCols { const u64 *c[AGG_MAX_COLS]; };
+
+template <bool NARROW>
+__global__ void __launch_bounds__(AGG_THREADS, 4)
+k_agg_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks,
+          int radix_bits, AggCols cols, u32 ncols, u64 col_rows, u64 *__restrict__ sums, u32 *__restrict__ bad,
+          u64 *__restrict__ max_tables, const u32 *__restrict__ skip)
+{
+    if (skip != nullptr && *skip != 0) return;
+    if (blockIdx.x >= *ntasks) return;
+    constexpr int THREADS = AGG_THREADS, NW = THREADS / 64, EPT = AGG_EPT, TILE = THREADS * EPT;
+    constexpr u32 SLOTS = 1u << AGG_SLOT_BITS;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64 *tab = reinterpret_cast<u64 *>(smem);                                // SLOTS keys
+    u32 *cnt = reinterpret_cast<u32 *>(tab + SLOTS);                         // SLOTS counts, by slot
+    u32 *ctl = cnt + SLOTS;                                                  // [0] distinct keys in the table, [1] all-ones keys of S
+
+    const JoinTask task = tasks[blockIdx.x];
+    typedef typename RelView<NARROW>::Both Both;
+    const RelView<NARROW> Sv = S.at(task.bbeg);
+    const u32 ns = task.blen, np = task.plen;
+    if (ns == 0 || np == 0) return;                                          // (a task has both sides)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const typename RelView<NARROW>::Buf PB = R.at(task.pbeg).buf(0, np);
+
+    const v2u64 *tab2 = reinterpret_cast<const v2u64 *>(tab);
+    auto count_on = [&](u64 key, u32 b) -> u32 {                             // k_semi_bkt's paired walk from pair b on (key != SEMI_EMPTY)
+        for (;; b = (b + 1) & (SLOTS / 2 - 1)) {
+            const v2u64 e = tab2[b];
+            if (e.x == key) return cnt[2 * b];
+            if (e.y == key) return cnt[2 * b + 1];
+            if (e.x == SEMI_EMPTY || e.y == SEMI_EMPTY) return 0u;
+        }
+    };
+    auto insert = [&](u64 key) -> bool {                                     // true: the key was not there; counts the tuple either way
+        if (key == SEMI_EMPTY) { atomicAdd(&ctl[1], 1u); return false; }
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            bool fresh = false;
+            if (cur != key) {
+                if (cur != SEMI_EMPTY) continue;
+                const u64 old = atomicCAS((unsigned long long *)&tab[s], (unsigned long long)SEMI_EMPTY, (unsigned long long)key);
+                if (old == SEMI_EMPTY) fresh = true;
+                else if (old != key) continue;
+            }
+            atomicAdd(&cnt[s], 1u);
+            return fresh;
+        }
+    };
+    auto load_keys = [&](u64 (&dst)[AGG_BPT], u32 at) {                      // the tile of S that starts at tuple `at` (< ns)
+        const typename RelView<NARROW>::Buf SB = Sv.buf(at, ns - at < AGG_BUILD_TILE ? ns - at : AGG_BUILD_TILE);
+#pragma unroll
+        for (int k = 0; k < AGG_BPT; k++) dst[k] = SB.payload((u32)k * THREADS, (u32)tid);
+    };
+
+    u64 key[AGG_BPT], key_next[AGG_BPT];
+    load_keys(key, 0);
+    Both p[EPT], p_next[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; k++) p[k] = PB.both((u32)k * THREADS, (u32)tid);
+
+    u64 acc_count = 0, acc[AGG_MAX_COLS] = {0, 0, 0, 0};
+    bool wild = false;
+    u32 sdone = 0, ntab = 0;
+    bool last;
+    do {
+        // ---- build: the next whole tiles of S's partition (k_semi_bkt's close rule) --------------------
+        for (u32 i = tid; i < SLOTS; i += THREADS) { tab[i] = SEMI_EMPTY; cnt[i] = 0; }
+        if (tid == 0) { ctl[0] = 0; ctl[1] = 0; }
+        __syncthreads();
+        u32 filled = 0;
+        while (sdone < ns && filled + AGG_BUILD_TILE <= AGG_FILL) {
+            const u32 nt = ns - sdone < AGG_BUILD_TILE ? ns - sdone : AGG_BUILD_TILE;
+            const bool more = sdone + nt < ns;
+            if (more) load_keys(key_next, sdone + nt);
+#pragma unroll
+            for (int k = 0; k < AGG_BPT; k++) {
+                const bool fresh = (u32)k * THREADS + tid < nt && insert(key[k]);
+                const unsigned long long m = __ballot(fresh);
+                if (lane == 0 && m) atomicAdd(&ctl[0], (u32)__popcll(m));
+            }
+            __syncthreads();
+            filled = ctl[0];
+            __syncthreads();                                                 // (everybody has read the count before the next tile adds to it)
+            sdone += nt;
+            if (more) {
+#pragma unroll
+                for (int k = 0; k < AGG_BPT; k++) key[k] = key_next[k];
+            }
+        }
+        ntab++;
+        last = sdone >= ns;
+
+        // ---- probe: every tile of the task's R range adds this table's share -----------------------------
+        const u32 ones = ctl[1];
+        for (u32 tb = 0; tb < np; tb += TILE) {
+            const u32 tn = tb + TILE < np ? tb + (u32)TILE : 0u;
+            const bool fetch = tn != tb && !(last && tn == 0);
+            if (fetch) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) p_next[k] = PB.both(tn + (u32)k * THREADS, (u32)tid);
+            }
+            v2u64 e0[EPT];                                                   // the first pair of every slot row, read together
+#pragma unroll
+            for (int k = 0; k < EPT; k++) e0[k] = tab2[bj_bucket<AGG_SLOT_BITS - 1>(p[k].payload, radix_bits)];
+            u32 c[EPT];
+#pragma unroll
+            for (int k = 0; k < EPT; k++) {
+                const u32 i = tb + (u32)k * THREADS + tid;
+                c[k] = 0;
+                if (i < np) {
+                    const u64 key = p[k].payload;
+                    const u32 b = bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);
+                    const v2u64 e = e0[k];
+                    if (key == SEMI_EMPTY) c[k] = ones;
+                    else if (e.x == key) c[k] = cnt[2 * b];
+                    else if (e.y == key) c[k] = cnt[2 * b + 1];
+                    else if (e.x != SEMI_EMPTY && e.y != SEMI_EMPTY) c[k] = count_on(key, (b + 1) & (SLOTS / 2 - 1));
+                    if (ncols != 0 && (u64)p[k].key >= col_rows) { c[k] = 0; wild = true; }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < EPT; k++) {
+                acc_count += c[k];
+#pragma unroll
+                for (int j = 0; j < AGG_MAX_COLS; j++)
+                    if ((u32)j < ncols && c[k] != 0) acc[j] += (u64)c[k] * cols.c[j][(u64)p[k].key];
+            }
+            if (fetch) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) p[k] = p_next[k];
+            }
+        }
+        __syncthreads();                                                     // the table is cleared for the next tiles of S
+    } while (!last);
+
+    // ---- the task's words: wavefront, workgroup (the table's first bytes are free now), one global atomic each ----
+    if (__ballot(wild) && lane == 0) atomicOr(bad, 1u);
+    u64 v[AGG_MAX_COLS + 1] = {acc_count, acc[0], acc[1], acc[2], acc[3]};
+#pragma unroll
+    for (int j = 0; j <= AGG_MAX_COLS; j++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[j] += __shfl_down(v[j], off, 64);
+        if (lane == 0) tab[w * (AGG_MAX_COLS + 1) + j] = v[j];
+    }
+    __syncthreads();
+    if (tid <= (int)ncols) {
+        u64 t = 0;
+        for (int i = 0; i < NW; i++) t += tab[i * (AGG_MAX_COLS + 1) + tid];
+        if (t) atomicAdd((unsigned long long *)&sums[tid], (unsigned long long)t);
+    }
+    if (tid == 0 && ntab > 1) atomicMax((unsigned long long *)max_tables, (unsigned long long)ntab);
+}
+
+// ------------------------------------------------------------------------------------------------
 // K4 (compact-table form): bucket join for partitions whose build side does not fit a 16 B/tuple LDS table but
 // whose radix plan has removed >= 16 payload bits (BASELINE config 3: 8+8 bits at 10^9 tuples, 15.3 K-tuple
 // partitions).  Same job as k_join_bkt (JoinJob::run + Result::join_buckets, Result.cpp:43-76, + add_result /
@@ -3295,6 +3463,8 @@ static void allow_big_lds()
     allow_ct_lds<JK_CT, false, true>();                                      // the stamps aid
     SET_LDS(k_semi_bkt<true>, semi_lds_bytes());
     SET_LDS(k_semi_bkt<false>, semi_lds_bytes());
+    SET_LDS(k_agg_bkt<true>, agg_lds_bytes());
+    SET_LDS(k_agg_bkt<false>, agg_lds_bytes());
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<IN_AOS>, wn_lds_bytes(WN_MAX_BITS));
@@ -3886,6 +4056,24 @@ void launch_semi_join(hipStream_t st, const void *d_R, const void *d_S, const Jo
     else
         hipLaunchKernelGGL(k_semi_bkt<false>, dim3(grid), dim3(SEMI_THREADS), semi_lds_bytes(), st, RelView<false>{(const Tup *)d_R},
                            RelView<false>{(const Tup *)d_S}, d_tasks, d_ntasks, radix_bits, anti, d_out, out_capacity, d_out_count,
+                           d_max_tables, d_skip);
+}
+
+void launch_agg_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                     int radix_bits, const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_sums, u32 *d_bad, u64 *d_max_tables,
+                     const u32 *d_RK, const u32 *d_SK, const u32 *d_skip)
+{
+    if (grid == 0) return;
+    allow_big_lds();
+    AggCols cols;
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) cols.c[j] = j < ncols ? d_cols[j] : nullptr;
+    if (d_RK != nullptr)                                                     // narrow partitions: d_R, d_S are payload arrays
+        hipLaunchKernelGGL(k_agg_bkt<true>, dim3(grid), dim3(AGG_THREADS), agg_lds_bytes(), st, RelView<true>{(const u64 *)d_R, d_RK},
+                           RelView<true>{(const u64 *)d_S, d_SK}, d_tasks, d_ntasks, radix_bits, cols, ncols, col_rows, d_sums, d_bad,
+                           d_max_tables, d_skip);
+    else
+        hipLaunchKernelGGL(k_agg_bkt<false>, dim3(grid), dim3(AGG_THREADS), agg_lds_bytes(), st, RelView<false>{(const Tup *)d_R},
+                           RelView<false>{(const Tup *)d_S}, d_tasks, d_ntasks, radix_bits, cols, ncols, col_rows, d_sums, d_bad,
                            d_max_tables, d_skip);
 }
 

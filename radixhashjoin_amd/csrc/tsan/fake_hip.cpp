@@ -199,6 +199,11 @@ void launch_semi_join(hipStream_t st, const void *, const void *, const JoinTask
         *d_out_count = at + FAKE_PAIRS;
     });
 }
+void launch_agg_join(hipStream_t st, const void *, const void *, const JoinTask *, const u32 *, u32, int, const u64 *const *, u32 ncols, u64,
+                     u64 *d_sums, u32 *, u64 *, const u32 *, const u32 *, const u32 *)
+{
+    fake_enqueue(st, [=] { for (u32 j = 0; j <= ncols; j++) d_sums[j] += FAKE_PAIRS; });
+}
 int build_tie_shift() { return 4; }
 size_t fuse_ctl_bytes() { return 12352; }
 u32 *fuse_join_ticket(void *d_ctl) { return (u32 *)((unsigned char *)d_ctl + 12288) + 1; }

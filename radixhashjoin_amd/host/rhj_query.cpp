@@ -308,16 +308,16 @@ static void log_join(const relation &R, const relation &S, const Result &res)
     fclose(f);
 }
 
-// RHJ_QUERY_MODE=cols (rhj_query_dev.cpp): one line "cols <nR> <nS> <count>" per rhj_join_cols_dev call -- a test sees that
-// the columnar path ran (an unknown mode value silently runs the device path)
-void log_cols_join(uint64_t nR, uint64_t nS, uint64_t count)
+// RHJ_QUERY_MODE=cols / agg (rhj_query_dev.cpp): one line "cols <nR> <nS> <count>" per rhj_join_cols_dev call, "sum <nR> <nS> <count>"
+// per rhj_join_sum_cols_dev call -- a test sees that the path ran (an unknown mode value silently runs the device path)
+void log_cols_join(const char *what, uint64_t nR, uint64_t nS, uint64_t count)
 {
     const char *path = getenv("RHJ_JOIN_LOG");
     if (!path) return;
     std::lock_guard<std::mutex> lk(g_log_mu);
     FILE *f = fopen(path, "a");
     if (!f) return;
-    fprintf(f, "cols %llu %llu %llu\n", (unsigned long long)nR, (unsigned long long)nS, (unsigned long long)count);
+    fprintf(f, "%s %llu %llu %llu\n", what, (unsigned long long)nR, (unsigned long long)nS, (unsigned long long)count);
     fclose(f);
 }
 
@@ -420,7 +420,7 @@ void Query::execute_batch(JobScheduler &js, vector<Query> &queries, vector<relLi
 void Query::execute(JobScheduler &js, vector<relList> &relations)
 {
     // default: the whole query device-resident (rhj_query_dev.cpp; RHJ_QUERY_MODE=cols: with columnar join inputs,
-    // rhj_join_cols_dev); RHJ_QUERY_MODE=host keeps filters and
+    // rhj_join_cols_dev; RHJ_QUERY_MODE=agg: ... and the SUMs over the last join by rhj_join_sum_cols_dev); RHJ_QUERY_MODE=host keeps filters and
     // intermediates on the host and sends every equi-join through Result::multiRadixHashJoin with exactly the
     // join inputs the reference builds
     static const bool host_mode = getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "host";

@@ -74,7 +74,11 @@ struct Query {                                /* Query.h:34-59 */
     void execute(JobScheduler &js, std::vector<relList> &relations);
     /* the same query executed device-resident (rhj_query_dev.cpp): what execute() does unless
        $RHJ_QUERY_MODE == "host"; $RHJ_QUERY_MODE == "cols": the join inputs are built as columns (the stored column itself
-       for an unfiltered alias) and joined by rhj_join_cols_dev instead of 16-byte tuples and rhj_join_dev */
+       for an unfiltered alias) and joined by rhj_join_cols_dev instead of 16-byte tuples and rhj_join_dev;
+       $RHJ_QUERY_MODE == "agg": as "cols", and when the last predicate of the join list is an equi-join between a new alias and the
+       intermediate (or between two new aliases with nothing joined before) its pairs are never produced: the projections are grouped
+       by the side of that join their alias arrives on and summed by rhj_join_sum_cols_dev, one call per side and per
+       RHJ_SUM_MAX_COLS projections (count 0: the query is filtered out; an alias outside the final intermediate sums to 0) */
     void execute_device(JobScheduler &js, std::vector<relList> &relations);
     bool run_filters(std::vector<relList> &relations,
                      std::unordered_map<uint64_t, std::unordered_set<uint64_t> > &filtered);
@@ -93,8 +97,9 @@ private:
     void parse_all();
 };
 
-/* test hook of the "cols" mode: appends "cols <nR> <nS> <count>" to $RHJ_JOIN_LOG (one line per rhj_join_cols_dev call) */
-void log_cols_join(uint64_t nR, uint64_t nS, uint64_t count);
+/* test hook of the "cols" and "agg" modes: appends "<what> <nR> <nS> <count>" to $RHJ_JOIN_LOG -- what = "cols": one line per
+   rhj_join_cols_dev call; "sum": one per rhj_join_sum_cols_dev call */
+void log_cols_join(const char *what, uint64_t nR, uint64_t nS, uint64_t count);
 
 /* intermediate.h:10-14.  parse_table: false when the same-alias predicate leaves no row */
 bool parse_table(join_info &join, relList &relation,

@@ -7,6 +7,8 @@
 // both the de-duplication of structs.cpp:238-241 and update_intermediate's matching (intermediate.cpp:52-87).
 // RHJ_QUERY_MODE=cols: the same execution with the join inputs as COLUMNS for rhj_join_cols_dev -- the stored column itself
 // (no kernel at all) for an alias without a row list, one 8-byte gather otherwise -- instead of 16-byte tuples.
+// RHJ_QUERY_MODE=agg: as cols, except that a query whose LAST predicate is an equi-join through the hot path never produces that
+// join's pairs: its SUMs come from rhj_join_sum_cols_dev (sum_last_join below) instead of join + split + regather + rhj_sum_gather.
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -84,9 +86,15 @@ DevArr join_pairs(rhj_ctx *ctx, const DevArr &R, uint64_t nR, const DevArr &S, u
     }
 }
 
-bool cols_mode()
+bool agg_mode()
 {
-    static const bool on = getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "cols";
+    static const bool on = getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "agg";
+    return on;
+}
+
+bool cols_mode()                                       // (agg: columnar inputs for every join)
+{
+    static const bool on = agg_mode() || (getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "cols");
     return on;
 }
 
@@ -118,7 +126,7 @@ DevArr join_pairs_cols(rhj_ctx *ctx, const ColSide &R, uint64_t nR, const ColSid
     for (;;) {
         DevArr out(ctx, cap * 16);
         int rc = rhj_join_cols_dev(ctx, R.val, R.id, nR, S.val, S.id, nS, nullptr, (rhj_pair *)out.p, cap, &count);
-        log_cols_join(nR, nS, count);
+        log_cols_join("cols", nR, nS, count);
         if (rc == RHJ_OK) { out.n = count; return out; }
         if (rc != RHJ_E_OVERFLOW) die(ctx, "rhj_join_cols_dev", rc);
         cap = count;                                   // exact size is known now
@@ -135,6 +143,26 @@ void regather(rhj_ctx *ctx, std::vector<DevArr> &inter, const uint64_t *idx, uin
         next.n = m;
         col = std::move(next);
     }
+}
+
+// One projection of the last join in "agg" mode as a weight column indexed by the probe side's rowID: for a side that is the
+// intermediate (position-carrying, NULL ids) the projected column gathered through the alias' rows, T words; for a new alias the
+// stored column itself, indexed by the alias' rowIDs (its row list, or the position).
+struct Weight {
+    const uint64_t *col = nullptr;
+    DevArr gathered;
+};
+
+// |P join B| and the sums of `w` (at most RHJ_SUM_MAX_COLS columns of col_rows words) over its pairs, P the side the columns belong to
+uint64_t join_sums(rhj_ctx *ctx, const ColSide &P, uint64_t nP, const ColSide &B, uint64_t nB, const std::vector<Weight> &w,
+                   uint64_t col_rows, uint64_t *sums)
+{
+    const uint64_t *cols[RHJ_SUM_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t i = 0; i < w.size(); i++) cols[i] = w[i].col;
+    uint64_t count = 0;
+    OK(ctx, rhj_join_sum_cols_dev(ctx, P.val, P.id, nP, B.val, nB, cols, (uint32_t)w.size(), col_rows, nullptr, &count, sums));
+    log_cols_join("sum", nP, nB, count);
+    return count;
 }
 
 }  // namespace
@@ -198,6 +226,44 @@ void Query::execute_device(JobScheduler &js, std::vector<relList> &relations)
         const uint64_t nR = in1 ? T : rows[j.table1].n, nS = in2 ? T : rows[j.table2].n;
         uint64_t m = 0;
         DevArr pairs;
+        bool live = false;
+        for (const DevArr &c : inter) live = live || !c.empty();
+        if (agg_mode() && &j == &join.back() && (in1 || in2 || !live)) {
+            // The query ends here: the pairs would only be added up.  The final intermediate would hold the side that is already joined
+            // (every live alias) and the new alias, or the two new aliases; a projection belongs to the side its alias arrives on and is
+            // summed by a call with that side as R (the other side's call has the sides exchanged); any other alias sums to 0.
+            const ColSide side[2] = {col_side(ctx, c1, inter[j.table1], rows[j.table1], nR), col_side(ctx, c2, inter[j.table2], rows[j.table2], nS)};
+            const uint64_t n[2] = {nR, nS};
+            const bool in[2] = {in1, in2};
+            const size_t alias[2] = {j.table1, j.table2};
+            std::vector<size_t> on[2];
+            for (size_t i = 0; i < proj.size(); i++) {
+                proj[i].sum = 0;
+                for (int s = 0; s < 2; s++)
+                    if (in[s] ? !inter[proj[i].table].empty() : (size_t)proj[i].table == alias[s]) { on[s].push_back(i); break; }
+            }
+            if (on[0].empty() && on[1].empty()) m = join_sums(ctx, side[0], n[0], side[1], n[1], {}, 0, nullptr);   // COUNT(*) alone
+            bool none = false;                         // a call counted 0 pairs: every further call would
+            for (int s = 0; s < 2 && !none; s++)
+                for (size_t at = 0; at < on[s].size() && !none; at += RHJ_SUM_MAX_COLS) {
+                    const size_t nc = on[s].size() - at < RHJ_SUM_MAX_COLS ? on[s].size() - at : RHJ_SUM_MAX_COLS;
+                    std::vector<Weight> w(nc);
+                    for (size_t i = 0; i < nc; i++) {
+                        const proj_info &p = proj[on[s][at + i]];
+                        const uint64_t *col = device_column(ctx, relations[table[p.table]], p.column);
+                        if (!in[s]) { w[i].col = col; continue; }
+                        w[i].gathered = DevArr(ctx, T * 8);
+                        OK(ctx, rhj_gather_u64(ctx, col, inter[p.table].p, T, w[i].gathered.p));
+                        w[i].col = w[i].gathered.p;
+                    }
+                    uint64_t sums[RHJ_SUM_MAX_COLS] = {0, 0, 0, 0};
+                    m = join_sums(ctx, side[s], n[s], side[1 - s], n[1 - s], w, in[s] ? T : relations[table[alias[s]]].num_tuples, sums);
+                    none = m == 0;
+                    for (size_t i = 0; i < nc; i++) proj[on[s][at + i]].sum = sums[i];
+                }
+            if (m == 0) filtered_out = true;
+            return;
+        }
         if (cols_mode()) {
             const ColSide R = col_side(ctx, c1, inter[j.table1], rows[j.table1], nR), S = col_side(ctx, c2, inter[j.table2], rows[j.table2], nS);
             pairs = join_pairs_cols(ctx, R, nR, S, nS, m);                            // <-- rhj_join_cols_dev

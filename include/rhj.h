@@ -139,7 +139,9 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * the plan), "last.semi_tables" (the largest number of LDS tables any one task of the last
  * semi / anti join or aggregating join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
  * "last.pipelined" (the number
- * of S chunks the last rhj_join streamed through the device while finished pairs travelled home; 0: the plain path),
+ * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
+ * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
+ * than the optimistic page of max(nR, nS) + 1024 holds -- has taken too),
  * "last.max_part_R" / "last.max_part_S" (tuples in the largest partition of each side the last partitioned join saw; 0 for
  * an unpartitioned one), "last.cols_R" / "last.cols_S" (how the last join read that side: 0 it was not a columnar call -- every join
  * and stage call other than rhj_join_cols_dev leaves 0, as does a columnar call with an empty side; 1 the partition kernels read the side's column(s) directly; 2 the side was first

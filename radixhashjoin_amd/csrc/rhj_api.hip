@@ -2255,7 +2255,9 @@ int join_host_pipelined(rhj_ctx *ctx, const rhj_tuple *R, u64 nR, const rhj_tupl
     static const bool off = getenv("RHJ_NO_PIPELINE") != nullptr;                 // tuning aid: A/B against the plain path
     static const bool trace = getenv("RHJ_TRACE_JOIN") != nullptr;
     static const u64 max_chunks = env_u64("RHJ_PIPE_CHUNKS", 12, 2, PIPE_MAX_CHUNKS);   // tuning aid
-    static const u64 min_chunk = env_u64("RHJ_PIPE_MIN_CHUNK", PIPE_MIN_CHUNK, 1 << 16, 1 << 26);   // (tests: pipelining at small sizes)
+    // tests shrink the path with it (tests/pipeline_cases.py), but not below the 64 MiB result page under which PagePrefault
+    // starts nothing (no page: RHJ_NOT_PIPELINED below): max(nR, nS) + 1024 >= 4 194 304 whatever the chunk size
+    static const u64 min_chunk = env_u64("RHJ_PIPE_MIN_CHUNK", PIPE_MIN_CHUNK, 1 << 16, 1 << 26);
     int K = (int)(nS / min_chunk < max_chunks ? nS / min_chunk : max_chunks);
     if (off || plan.passes < 1 || nS < 4 * min_chunk || K < 2 || nR < min_chunk / 2) return RHJ_NOT_PIPELINED;
     const u64 chunk = ((nS + K - 1) / K + 4095) / 4096 * 4096;
@@ -2398,6 +2400,7 @@ int join_host_pipelined(rhj_ctx *ctx, const rhj_tuple *R, u64 nR, const rhj_tupl
         if (abandon && saw_wide) { narrow_note_fallback(ctx); return RHJ_NOT_PIPELINED_WIDE; }
         if (abandon) return RHJ_NOT_PIPELINED;
         narrow_note_done(ctx, plan, narrow != 0);
+        ctx->last_pipelined = K;                           // (every chunk went through: an empty result is no fall-back)
         *out_page = nullptr;                               // no match: head stays nullptr (Result::isEmpty)
         *out_count = 0;
         return RHJ_OK;

@@ -136,8 +136,9 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * by themselves for partitions of 2-5 K tuples), 11 a smaller table with 12-bit arrival indices (plans of 12 bits); the sizes are
  * the rows of JOIN_GEOM in radixhashjoin_amd/csrc/rhj_internal.h; 12 the semi / anti join kernel: rhj_semi_join_dev /
  * rhj_semi_join_cols_dev, whatever the plan; 13 the aggregating join kernel: rhj_join_sum_dev / rhj_join_sum_cols_dev, whatever
- * the plan), "last.semi_tables" (the largest number of LDS tables any one task of the last
- * semi / anti join or aggregating join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
+ * the plan; 14 the multiplicity join kernel: rhj_join_mult_dev / rhj_join_mult_cols_dev, whatever the plan),
+ * "last.semi_tables" (the largest number of LDS tables any one task of the last
+ * semi / anti join, aggregating join or multiplicity join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -253,6 +254,38 @@ int rhj_join_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *
 int rhj_join_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                      const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows,
                      const rhj_opts *opts, uint64_t *out_count, uint64_t *out_sums);
+
+/* ---- multiplicity join: for every row of R, how many tuples of S carry its join value -- or, with weights on S, the sum of their
+ * weights (SELECT r.id, SUM(s.w) FROM R JOIN S USING (key) GROUP BY r.id; the degree of every key; value_counts looked up per row).
+ * It is what rhj_join_sum_cols_dev adds up, returned per row, and the message of a sum over a tree-shaped query: a chain or star
+ * of joins is summed by at most 2 x (aliases - 1) such calls, linear in the inputs, with no pair set.
+ *
+ * for every tuple i of R:  d_out[rowR_i] += sum over the tuples j of S with valS[j] == valR[i] of w_j   (mod 2^64)
+ * w_j = d_wS[rowS_j], or 1 when d_wS == NULL.  rowR_i = d_idR[i] or i; rowS_j = d_idS[j] or j (id column NULL).
+ * Zeroing: the call zeroes all out_rows words of d_out itself, and does so again on every attempt.
+ * Accumulation: every tuple of R then ADDS its multiplicity to d_out[rowR]: two tuples of R with the same rowID accumulate, words
+ * that no tuple of R names stay 0.
+ * out_total: a HOST word that receives the sum of all multiplicities mod 2^64 -- |R join S| when unweighted, the number
+ * rhj_join_sum_cols_dev counts.  The call synchronises: d_out and *out_total are complete when it returns.
+ * Guards: a rowR >= out_rows is never stored to and a rowS >= wS_rows is never loaded from (weighted only; wS_rows is ignored when
+ * d_wS == NULL): either raises a flag word in HBM and the call returns RHJ_E_INVALID (d_out is then undefined, the context stays
+ * usable).  The flag is raised for every such tuple whose partition holds tuples of the other side -- always when it has a
+ * partner there.
+ * nR == 0 or nS == 0: d_out all zero, total 0, no join launch.  RHJ_E_INVALID: NULL d_out with out_rows > 0, NULL out_total, a
+ * NULL value column (relation) with n > 0.  Inputs are neither modified nor retained; d_out must not overlap them.
+ * Plan, options, timings, "last.narrow", "last.countfree_*" and "last.cols_*" as rhj_join_cols_dev / rhj_join_dev on the same sizes
+ * (same partition kernels, same repeats: a count-free overflow repeats with exact cursors, a rowID >= 2^32 of EITHER side in a
+ * narrow format repeats at 16 bytes -- S's rowIDs are read here --, and a repeat starts from a zeroed d_out), except that a
+ * one-pass plan always runs as separate partition and join launches; "last.join_kernel" is 14, "last.semi_tables" see
+ * rhj_get_info.  rhj_opts.probe_split: values above 2^24 act as 2^24.  Results are bit-exact from run to run. */
+int rhj_join_mult_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+                           const uint64_t *d_wS, uint64_t wS_rows, const rhj_opts *opts,
+                           uint64_t *d_out, uint64_t out_rows, uint64_t *out_total);
+/* ... on 16-byte tuples (rowR = d_R[i].key, rowS = d_S[j].key) */
+int rhj_join_mult_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                      const uint64_t *d_wS, uint64_t wS_rows, const rhj_opts *opts,
+                      uint64_t *d_out, uint64_t out_rows, uint64_t *out_total);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:
@@ -412,6 +445,12 @@ int rhj_rows_filter_equal(rhj_ctx *ctx, const uint64_t *d_colA, const uint64_t *
                           const uint64_t *d_rowsB, uint64_t n, uint64_t *d_pos_out, uint64_t *n_out);
 /* rhj_sum_gather: column_proj (Query.cpp:66-74): *sum = sum of d_col[d_rows[i]] (mod 2^64) */
 int rhj_sum_gather(rhj_ctx *ctx, const uint64_t *d_col, const uint64_t *d_rows, uint64_t n, uint64_t *sum);
+/* rhj_mul_u64: d_dst[i] = d_a[i] * d_b[i]  (mod 2^64); d_dst may be d_a (the product of a tree query's messages) */
+int rhj_mul_u64(rhj_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, uint64_t n, uint64_t *d_dst);
+/* rhj_sum_gather_weighted: *sum = sum of d_col[d_rows[i]] * d_w[i]  (mod 2^64); d_rows == NULL: the row is i;
+ *   d_col == NULL: *sum = sum of d_w[i].  sum is a HOST word; the call synchronises. */
+int rhj_sum_gather_weighted(rhj_ctx *ctx, const uint64_t *d_col, const uint64_t *d_rows, const uint64_t *d_w, uint64_t n,
+                            uint64_t *sum);
 
 /* raw HBM helpers so a plain C/C++ host (no HIP headers) can use the device-resident API.  rhj_dev_free must be
  * given the context that allocated the block; released blocks are kept by the context for re-use (its work is

@@ -11,7 +11,8 @@ From torch: ``idx_R, idx_S = Engine(0).join_columns(keys_R, keys_S)`` joins two 
 (``rhj_join_cols_dev``: the relations as columns, rowID = index); ``Engine(0).semi_join_columns(keys_R, keys_S, anti=False)``
 returns the indices of the keys of R that occur (``anti=True``: do not occur) in S (``rhj_semi_join_cols_dev``);
 ``count, sums = Engine(0).join_sum_columns(keys_R, keys_S, weights)`` is COUNT(*) and SUM(weights[k][i]) over the join's pairs
-without the pairs (``rhj_join_sum_cols_dev``).
+without the pairs (``rhj_join_sum_cols_dev``); ``mult, total = Engine(0).join_multiplicity_columns(keys_R, keys_S, weights_S=None)``
+is, per key of R, how many keys of S equal it -- or the sum of their weights (``rhj_join_mult_cols_dev``).
 """
 from .binding import (  # noqa: F401
     ANTI,

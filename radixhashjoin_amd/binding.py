@@ -80,6 +80,8 @@ SYMBOLS = {
     "rhj_semi_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_join_sum_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _P(_u64), _P(_u64)]),
     "rhj_join_sum_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _P(_u64), _P(_u64)]),
+    "rhj_join_mult_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_join_mult_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -110,6 +112,8 @@ SYMBOLS = {
     "rhj_gather_u64": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
     "rhj_rows_filter_equal": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _P(_u64)]),
     "rhj_sum_gather": (C.c_int, [_vp, _vp, _vp, _u64, _P(_u64)]),
+    "rhj_mul_u64": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
+    "rhj_sum_gather_weighted": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _P(_u64)]),
     "rhj_dev_alloc": (C.c_int, [_vp, _u64, _P(_vp)]),
     "rhj_dev_free": (C.c_int, [_vp, _vp]),
     "rhj_copy_h2d": (C.c_int, [_vp, _vp, _vp, _u64]),
@@ -450,10 +454,27 @@ class Engine:
                                             C.byref(opts) if opts is not None else None, C.byref(n), sums))
         return n.value, [int(sums[j]) for j in range(len(d_cols))]
 
+    def join_mult_cols_dev(self, d_valR, d_idR, nR, d_valS, d_idS, nS, d_out, out_rows, d_wS=None, wS_rows=0, opts=None):
+        """rhj_join_mult_cols_dev: d_out (out_rows uint64 words, zeroed by the call) receives, per rowID of R, the number of tuples
+        of S with that tuple's join value -- with d_wS (wS_rows words indexed by S's rowID) the sum of their weights -- mod 2^64;
+        returns the sum of all of them (unweighted: |R join S|) as a Python int"""
+        total = _u64()
+        self._chk(self.lib.rhj_join_mult_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), _addr(d_idS), nS,
+                                                  _addr(d_wS), wS_rows, C.byref(opts) if opts is not None else None,
+                                                  _addr(d_out), out_rows, C.byref(total)))
+        return total.value
+
+    def join_mult_dev(self, d_R, nR, d_S, nS, d_out, out_rows, d_wS=None, wS_rows=0, opts=None):
+        """rhj_join_mult_dev: join_mult_cols_dev on 16-byte tuples (rowR / rowS = .key)"""
+        total = _u64()
+        self._chk(self.lib.rhj_join_mult_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, _addr(d_wS), wS_rows,
+                                             C.byref(opts) if opts is not None else None, _addr(d_out), out_rows, C.byref(total)))
+        return total.value
+
     @contextlib.contextmanager
-    def _on_torch_stream(self, keys_R, keys_S, weights=()):
-        """What join_columns, semi_join_columns and join_sum_columns share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
-        engine's device (ValueError otherwise); weights: tensors of the same kind, each as long as keys_R.  The body runs ordered behind the work torch has queued on its current stream: on a
+    def _on_torch_stream(self, keys_R, keys_S, weights=(), weights_on_S=False):
+        """What join_columns, semi_join_columns, join_sum_columns and join_multiplicity_columns share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
+        engine's device (ValueError otherwise); weights: tensors of the same kind, each as long as keys_R (weights_on_S: as keys_S).  The body runs ordered behind the work torch has queued on its current stream: on a
         stream of its own (torch.cuda.stream(s)) the engine runs on that stream for the length of the body; torch's default stream
         has no handle to hand over (its raw value is 0, which rhj_set_stream reads as "the context's own stream"), so there the call
         waits on the host for the stream first and runs on the stream the engine has.  Either way the results are complete when
@@ -467,9 +488,10 @@ class Engine:
                 raise ValueError(f"{name}: the tensor must live on the engine's device (cuda:{self.device}), not {k.device}")
             if not k.is_contiguous():
                 raise ValueError(f"{name}: the tensor must be contiguous")
+        side, keys = ("S", keys_S) if weights_on_S else ("R", keys_R)
         for i, w in enumerate(weights):
-            if w.numel() != keys_R.numel():
-                raise ValueError(f"weights[{i}]: {w.numel()} elements for {keys_R.numel()} keys of R")
+            if w.numel() != keys.numel():
+                raise ValueError(f"weights[{i}]: {w.numel()} elements for {keys.numel()} keys of {side}")
         dev = keys_R.device
         with torch.cuda.device(dev):
             torch_stream = torch.cuda.current_stream(dev)
@@ -533,6 +555,31 @@ class Engine:
         with self._on_torch_stream(keys_R, keys_S, weights):
             nR, nS = keys_R.numel(), keys_S.numel()
             return self.join_sum_cols_dev(keys_R, None, nR, keys_S, nS, weights, nR)
+
+    def join_multiplicity_columns(self, keys_R, keys_S, weights_S=None):
+        """(mult, total): mult[i] = the number of j with keys_S[j] == keys_R[i] -- with weights_S, the sum of weights_S[j] over
+        those j, mod 2^64 -- as an int64 tensor of len(keys_R) on the keys' device that holds the bit pattern of the uint64 result
+        (the degree of every key; value_counts looked up per row); total = the sum of mult mod 2^64 as a Python int in [0, 2^64),
+        unweighted the number of pairs join_columns would return.  No pair is written: linear in the inputs however often a key
+        repeats.  weights_S: a contiguous 1-D 64-bit integer tensor of len(keys_S) on the engine's device.  Tensors, streams and
+        completion as join_columns."""
+        import torch
+        weights = () if weights_S is None else (weights_S,)
+        with self._on_torch_stream(keys_R, keys_S, weights, weights_on_S=True) as dev:
+            nR, nS = keys_R.numel(), keys_S.numel()
+            mult = torch.empty(nR, dtype=torch.int64, device=dev)
+            total = self.join_mult_cols_dev(keys_R, None, nR, keys_S, None, nS, mult if nR else None, nR, weights_S, nS)
+        return mult, total
+
+    def mul_u64(self, d_a, d_b, n, d_dst):
+        """rhj_mul_u64: d_dst[i] = d_a[i] * d_b[i] mod 2^64 (d_dst may be d_a)"""
+        self._chk(self.lib.rhj_mul_u64(self.ctx, _addr(d_a), _addr(d_b), n, _addr(d_dst)))
+
+    def sum_gather_weighted(self, d_col, d_rows, d_w, n):
+        """rhj_sum_gather_weighted: the sum of d_col[d_rows[i] or i] * d_w[i] mod 2^64 (d_col None: the sum of d_w)"""
+        s = _u64()
+        self._chk(self.lib.rhj_sum_gather_weighted(self.ctx, _addr(d_col), _addr(d_rows), _addr(d_w), n, C.byref(s)))
+        return s.value
 
     def histogram(self, d_rel, n, shift, bits, d_hist):
         self._chk(self.lib.rhj_histogram(self.ctx, _addr(d_rel), n, shift, bits, _addr(d_hist)))

@@ -238,6 +238,11 @@ struct rhj_ctx {
     u32 agg_ncols = 0;
     u64 agg_col_rows = 0;
     u64 *agg_sums_out = nullptr;       // ... and where agg_phase leaves the ncols sums (host)
+    // a multiplicity join's arguments, for the length of the call (its device words are agg_out's: [0] total, [5] u32 MULT_BAD_ROW_*)
+    const u64 *mult_w = nullptr;       // weights by S's rowID (device), or null
+    u64 mult_w_rows = 0;
+    u64 *mult_out = nullptr;           // out_rows words (device)
+    u64 mult_out_rows = 0;
     DevBuf narrow_flag;                // u32: a rowID >= 2^32 met a narrow scatter -> the join re-runs in the 16-byte format
     // ... the next join tries the narrow format again; consecutive fall-backs make the context skip the attempt for the next
     // 2, 4, ... 32 eligible joins (a caller whose rowIDs are always wide pays one extra histogram per relation now and then)
@@ -1356,8 +1361,9 @@ int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
 }
 
 // What a join reports once both sides are partitioned: the pairs (join_phase), the rowIDs of the tuples of R with (RHJ_SEMI) or
-// without (RHJ_ANTI) a partner in S (semi_phase), or the pair count and sums over the pairs (agg_phase).
-enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2 };
+// without (RHJ_ANTI) a partner in S (semi_phase), the pair count and sums over the pairs (agg_phase), or every row of R's
+// multiplicity in S (mult_phase).
+enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3 };
 
 // Semi / anti join phase on the partitions partition_phase left: k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
 // Reads the skip word behind its kernel and answers with the retry codes of join_phase_on.
@@ -1480,6 +1486,74 @@ int agg_phase(rhj_ctx *ctx, u64 *out_count)
         return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= col_rows: the weight columns have no such row");
     *out_count = agg[0];
     for (u32 j = 0; j < ctx->agg_ncols; j++) ctx->agg_sums_out[j] = agg[1 + j];
+    return RHJ_OK;
+}
+
+// Multiplicity join phase on the partitions partition_phase left: k_make_semi_tasks (anti = 0) + k_mult_bkt over the
+// weights and the output words the entry point left in the context.  EVERY attempt zeroes the output words, the total and the
+// guard flags before its kernel: a repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes as semi_phase.
+int mult_phase(rhj_ctx *ctx, u64 *out_total)
+{
+    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
+    const bool narrow = ctx->cur_narrow != 0;
+    u32 split = ctx->cur_probe_split;
+    if (split == 0) split = 32768;
+    if (split > AGG_MAX_SPLIT) split = AGG_MAX_SPLIT;
+    const u64 max_tasks64 = nparts + nR / split + 1;
+    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
+    const u32 max_tasks = (u32)max_tasks64;
+    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
+    RHJCHK(ensure(ctx, ctx->counters, 64));
+    RHJCHK(ensure(ctx, ctx->agg_out, 64));
+    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
+    {
+        Span s(ctx, RHJ_K_AUX);
+        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));   // (a paired partition pass has cleared them already)
+        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
+        if (ctx->mult_out_rows) HIPCHK(ctx, hipMemsetAsync(ctx->mult_out, 0, ctx->mult_out_rows * 8, ctx->stream));
+    }
+    ctx->counters_clean = false;
+    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
+        Span s(ctx, RHJ_K_AUX);
+        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+        launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+    }
+    ctx->last_join_kind = JK_MULT;
+    ctx->sniff_ready = false;                          // (the samples of the partition phase are not asked)
+    {
+        Span s(ctx, RHJ_K_TASKS);
+        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, ctx->cur_psS, nparts, split, 0, (JoinTask *)ctx->tasks.p,
+                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
+    }
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        launch_mult_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
+                         ctx->cur_radix_bits, ctx->mult_w, ctx->mult_w_rows, ctx->mult_out, ctx->mult_out_rows, d_agg,
+                         (u32 *)(d_agg + AGG_MAX_COLS + 1), d_count + 7,
+                         narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
+                         narrow ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
+                         narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+    }
+    RHJCHK(check_launch(ctx, "multiplicity join phase"));
+    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, oversized table side, -, most tables of a task (if > 1)
+    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // total, -, -, -, -, guard flags
+    u32 wide_rowid = 0;
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
+    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
+    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
+    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
+    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
+    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
+    ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
+    if (host[5])
+        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    const u32 bad = (u32)agg[AGG_MAX_COLS + 1];
+    if (bad & MULT_BAD_ROW_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= out_rows: d_out has no such word");
+    if (bad & MULT_BAD_ROW_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= wS_rows: the weight column has no such row");
+    *out_total = agg[0];
     return RHJ_OK;
 }
 
@@ -1610,7 +1684,7 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
 
 // partition + join.  A run in the narrow format whose histogram kernel met a rowID >= 2^32 costs two histogram launches
 // (every later kernel of the run returns at once) and is repeated in the 16-byte format; the fall-back is per join.
-// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase (which always take the
+// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase (which always take the
 // unfused path: the one-pass form has the pair join built into its launches).
 int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan, void *d_out,
                        u64 cap, u64 *out_count, std::function<int()> *before_S = nullptr, JoinOutput what = OUT_PAIRS)
@@ -1618,7 +1692,8 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
     if (what == OUT_PAIRS && fused_one_pass_ok(ctx, nR, nS, plan))
         return join_one_pass_fused(ctx, d_R, nR, d_S, nS, plan, d_out, cap, out_count, before_S);
     auto after_partition = [&]() {
-        return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : what == OUT_SUMS ? agg_phase(ctx, out_count) : semi_phase(ctx, what, d_out, cap, out_count);
+        return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : what == OUT_SUMS ? agg_phase(ctx, out_count) :
+               what == OUT_MULT ? mult_phase(ctx, out_count) : semi_phase(ctx, what, d_out, cap, out_count);
     };
     int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S);
     if (rc != RHJ_OK) { ctx->counters_clean = false; return rc; }
@@ -2101,6 +2176,62 @@ int rhj_join_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *
     ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = nullptr;      // S has no id column: rowID = index, never looked at
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
     const int rc = join_sum_common(ctx, nullptr, nR, nullptr, nS, d_cols, ncols, col_rows, opts, out_count, out_sums);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// Multiplicity join: the partition phase and the repeat ladder of rhj_join_dev / rhj_join_cols_dev, then mult_phase.
+// d_R / d_S null: the relations are ctx->cols_in.
+static int join_mult_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const uint64_t *d_wS, uint64_t wS_rows,
+                            const rhj_opts *opts, uint64_t *d_out, uint64_t out_rows, uint64_t *out_total)
+{
+    if (out_rows && !d_out) return fail(ctx, RHJ_E_INVALID, "d_out is null");
+    if (nR == 0 || nS == 0) {                          // all zero, and complete when the call returns
+        if (out_rows) {
+            HIPCHK(ctx, hipMemsetAsync(d_out, 0, out_rows * 8, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return join_nothing(ctx);
+    }
+    rhj_opts plan;
+    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+    ctx->mult_w = (const u64 *)d_wS;
+    ctx->mult_w_rows = d_wS ? wS_rows : 0;
+    ctx->mult_out = (u64 *)d_out;
+    ctx->mult_out_rows = out_rows;
+    const int rc = partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_total, nullptr, OUT_MULT);
+    ctx->mult_w = nullptr;
+    ctx->mult_out = nullptr;
+    ctx->mult_w_rows = ctx->mult_out_rows = 0;
+    return rc;
+}
+
+int rhj_join_mult_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                      const uint64_t *d_wS, uint64_t wS_rows, const rhj_opts *opts,
+                      uint64_t *d_out, uint64_t out_rows, uint64_t *out_total)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_total) return fail(ctx, RHJ_E_INVALID, "out_total is null");
+    *out_total = 0;
+    prof_reset(ctx);
+    if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return join_mult_common(ctx, d_R, nR, d_S, nS, d_wS, wS_rows, opts, d_out, out_rows, out_total);
+}
+
+int rhj_join_mult_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+                           const uint64_t *d_wS, uint64_t wS_rows, const rhj_opts *opts,
+                           uint64_t *d_out, uint64_t out_rows, uint64_t *out_total)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_total) return fail(ctx, RHJ_E_INVALID, "out_total is null");
+    *out_total = 0;
+    prof_reset(ctx);
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
+    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;   // S's rowIDs name its weights
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = join_mult_common(ctx, nullptr, nR, nullptr, nS, d_wS, wS_rows, opts, d_out, out_rows, out_total);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

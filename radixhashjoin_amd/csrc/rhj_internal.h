@@ -276,6 +276,23 @@ static_assert(agg_lds_bytes() <= 160 * 1024 && AGG_FILL + AGG_BUILD_TILE <= (1u 
 void launch_agg_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
                      int radix_bits, const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_sums, u32 *d_bad, u64 *d_max_tables,
                      const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
+// ---- the multiplicity join kernel (k_mult_bkt): k_agg_bkt's geometry, a wider slot ----------------------------------
+// k_agg_bkt's table, tiles, close rule and probe tile.  Beside every key slot: the 32-bit occurrence count (unweighted, 96 KiB as
+// k_agg_bkt) or a 64-bit sum of the weights of S's tuples with that key (weighted: 8192 x (8 + 8) B = 128 KiB); either way one
+// workgroup of 1024 threads per CU.
+constexpr int JK_MULT = JK_AGG + 1;               // "last.join_kernel" of a multiplicity join (14)
+constexpr size_t mult_lds_bytes(bool weighted) { return ((size_t)(weighted ? 16 : 12) << AGG_SLOT_BITS) + 16; }
+static_assert(mult_lds_bytes(true) <= 160 * 1024 && mult_lds_bytes(false) == agg_lds_bytes() &&
+              (size_t)(AGG_THREADS / 64) * 8 <= ((size_t)8 << AGG_SLOT_BITS), "k_mult_bkt's geometry");
+constexpr u32 MULT_BAD_ROW_R = 1, MULT_BAD_ROW_S = 2;   // bits of *d_bad
+// The task list is launch_make_semi_tasks with anti = 0.  d_w: device column of w_rows words indexed by S's rowID, or null (every
+// tuple of S weighs 1); d_out: out_rows words (zeroed by the caller), word rowR receives the tuple's multiplicity by a global atomic
+// add; d_total: one word (zeroed by the caller), the sum of all multiplicities; d_bad: OR-ed with MULT_BAD_ROW_R when a rowID of R
+// >= out_rows was met (never stored to), with MULT_BAD_ROW_S when a rowID of S >= w_rows was (never loaded from; d_w != null only);
+// the rest as launch_semi_join.
+void launch_mult_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                      int radix_bits, const u64 *d_w, u64 w_rows, u64 *d_out, u64 out_rows, u64 *d_total, u32 *d_bad,
+                      u64 *d_max_tables, const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
 // in_narrow: d_in is a payload array (u64).  key_base / d_wide (16-byte input): d_wide (may be null) is OR-ed with 1 when some
 // rowID - key_base does not fit 32 bits.  d_unit_rng (may be null): explicit pass-1 units (launch_seg_units).
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,

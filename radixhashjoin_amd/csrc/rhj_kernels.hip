@@ -2746,6 +2746,187 @@ k_agg_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ tas
 }
 
 // ------------------------------------------------------------------------------------------------
+// Multiplicity join of one task: for every tuple of R the (weighted) number of tuples of S with its join value, added
+// to out[rowR] -- what k_agg_bkt computes per tuple and folds into one accumulator, returned per row.
+//   * k_agg_bkt's table unchanged: keys of S, open-addressed, insert-if-absent by a 64-bit LDS compare-and-swap, all-ones = empty
+//     with the all-ones key kept beside the table, whole 1024-tuple build tiles, closed at AGG_FILL.  Beside every slot: the 32-bit
+//     occurrence count (!WEIGHTED), or a 64-bit sum (WEIGHTED): every tuple of S does an LDS 64-bit atomic add of w[rowS] on the
+//     slot its key occupies.  w[rowS] is loaded only where rowS < w_rows; a tuple beyond adds 0 and raises MULT_BAD_ROW_S.
+//   * a tuple of R with rowID r meets c = this table's share of its key (0: absent, or weights that sum to 0 mod 2^64) and, where
+//     c != 0, does ONE 64-bit global atomic add of c on out[r], return value unused.  An ADD, never a store: tables are additive --
+//     a partition of S beyond one table splits a key's weight among tables and every table's sweep of R adds its share -- and two
+//     tuples of R may name one row.  r >= out_rows is never stored to: the tuple adds nothing and raises MULT_BAD_ROW_R.
+//   * end of task: the shares the task added, reduced by wavefront shuffles and one LDS round into one global atomic on *total.
+// ------------------------------------------------------------------------------------------------
+template <bool WEIGHTED>
+__device__ __forceinline__ void mult_lds_add(typename std::conditional<WEIGHTED, u64, u32>::type *p, typename std::conditional<WEIGHTED, u64, u32>::type v)
+{
+    if constexpr (WEIGHTED) atomicAdd((unsigned long long *)p, (unsigned long long)v);
+    else atomicAdd(p, v);
+}
+
+template <bool NARROW, bool WEIGHTED>
+__global__ void __launch_bounds__(AGG_THREADS, 4)
+k_mult_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks,
+           int radix_bits, const u64 *__restrict__ wcol, u64 w_rows, u64 *__restrict__ out, u64 out_rows, u64 *__restrict__ total,
+           u32 *__restrict__ bad, u64 *__restrict__ max_tables, const u32 *__restrict__ skip)
+{
+    if (skip != nullptr && *skip != 0) return;
+    if (blockIdx.x >= *ntasks) return;
+    constexpr int THREADS = AGG_THREADS, NW = THREADS / 64, EPT = AGG_EPT, TILE = THREADS * EPT;
+    constexpr u32 SLOTS = 1u << AGG_SLOT_BITS;
+    static_assert(AGG_BPT == 1, "one tuple of S per thread per build tile");
+    typedef typename std::conditional<WEIGHTED, u64, u32>::type Cnt;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64 *tab = reinterpret_cast<u64 *>(smem);                                // SLOTS keys
+    Cnt *cnt = reinterpret_cast<Cnt *>(tab + SLOTS);                         // SLOTS counts / weight sums, by slot
+    Cnt *ones = cnt + SLOTS;                                                 // ... of the all-ones key (8 bytes are kept for it)
+    u32 *nkeys = reinterpret_cast<u32 *>(smem + mult_lds_bytes(WEIGHTED) - 8);   // distinct keys in the table
+
+    const JoinTask task = tasks[blockIdx.x];
+    typedef typename RelView<NARROW>::Both Both;
+    const RelView<NARROW> Sv = S.at(task.bbeg);
+    const u32 ns = task.blen, np = task.plen;
+    if (ns == 0 || np == 0) return;                                          // (a task has both sides)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const typename RelView<NARROW>::Buf PB = R.at(task.pbeg).buf(0, np);
+
+    bool wild_r = false, wild_s = false;
+    const v2u64 *tab2 = reinterpret_cast<const v2u64 *>(tab);
+    auto count_on = [&](u64 key, u32 b) -> Cnt {                             // k_agg_bkt's paired walk from pair b on (key != SEMI_EMPTY)
+        for (;; b = (b + 1) & (SLOTS / 2 - 1)) {
+            const v2u64 e = tab2[b];
+            if (e.x == key) return cnt[2 * b];
+            if (e.y == key) return cnt[2 * b + 1];
+            if (e.x == SEMI_EMPTY || e.y == SEMI_EMPTY) return (Cnt)0;
+        }
+    };
+    auto insert = [&](u64 key, Cnt wt) -> bool {                             // true: the key was not there; adds the tuple's weight either way
+        if (key == SEMI_EMPTY) { mult_lds_add<WEIGHTED>(ones, wt); return false; }
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            bool fresh = false;
+            if (cur != key) {
+                if (cur != SEMI_EMPTY) continue;
+                const u64 old = atomicCAS((unsigned long long *)&tab[s], (unsigned long long)SEMI_EMPTY, (unsigned long long)key);
+                if (old == SEMI_EMPTY) fresh = true;
+                else if (old != key) continue;
+            }
+            mult_lds_add<WEIGHTED>(&cnt[s], wt);
+            return fresh;
+        }
+    };
+    // the tile of S that starts at tuple `at` (< ns): this thread's key, and (WEIGHTED) its rowID
+    auto load_tuple = [&](Both &dst, u32 at) {
+        const typename RelView<NARROW>::Buf SB = Sv.buf(at, ns - at < AGG_BUILD_TILE ? ns - at : AGG_BUILD_TILE);
+        if constexpr (WEIGHTED) dst = SB.both(0u, (u32)tid);
+        else dst.payload = SB.payload(0u, (u32)tid);
+    };
+    auto weight_of = [&](const Both &t, bool valid) -> Cnt {                 // valid: the thread has a tuple in the tile
+        if constexpr (WEIGHTED) {
+            if (!valid) return 0;
+            if ((u64)t.key >= w_rows) { wild_s = true; return 0; }
+            return wcol[(u64)t.key];
+        } else return (Cnt)1;
+    };
+
+    Both st, st_next;
+    st.key = 0; st_next.key = 0; st_next.payload = 0;
+    load_tuple(st, 0);
+    Both p[EPT], p_next[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; k++) p[k] = PB.both((u32)k * THREADS, (u32)tid);
+    Cnt wt = weight_of(st, (u32)tid < (ns < AGG_BUILD_TILE ? ns : AGG_BUILD_TILE)), wt_next = 0;
+
+    u64 acc_total = 0;
+    u32 sdone = 0, ntab = 0;
+    bool last;
+    do {
+        // ---- build: the next whole tiles of S's partition (k_agg_bkt's close rule) ---------------------
+        for (u32 i = tid; i < SLOTS; i += THREADS) { tab[i] = SEMI_EMPTY; cnt[i] = 0; }
+        if (tid == 0) { *nkeys = 0; *ones = 0; }
+        __syncthreads();
+        u32 filled = 0;
+        while (sdone < ns && filled + AGG_BUILD_TILE <= AGG_FILL) {
+            const u32 nt = ns - sdone < AGG_BUILD_TILE ? ns - sdone : AGG_BUILD_TILE;
+            const bool more = sdone + nt < ns;
+            if (more) load_tuple(st_next, sdone + nt);
+            {
+                const bool fresh = (u32)tid < nt && insert(st.payload, wt);
+                const unsigned long long m = __ballot(fresh);
+                if (lane == 0 && m) atomicAdd(nkeys, (u32)__popcll(m));
+            }
+            if (more) {                                                      // the next tile's weights travel behind the two barriers
+                const u32 left = ns - (sdone + nt);
+                wt_next = weight_of(st_next, (u32)tid < (left < AGG_BUILD_TILE ? left : AGG_BUILD_TILE));
+            }
+            __syncthreads();
+            filled = *nkeys;
+            __syncthreads();                                                 // (everybody has read the count before the next tile adds to it)
+            sdone += nt;
+            if (more) { st = st_next; wt = wt_next; }
+        }
+        ntab++;
+        last = sdone >= ns;
+
+        // ---- probe: every tile of the task's R range adds this table's share to its rows -----------------
+        const Cnt c_ones = *ones;
+        for (u32 tb = 0; tb < np; tb += TILE) {
+            const u32 tn = tb + TILE < np ? tb + (u32)TILE : 0u;
+            const bool fetch = tn != tb && !(last && tn == 0);
+            if (fetch) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) p_next[k] = PB.both(tn + (u32)k * THREADS, (u32)tid);
+            }
+            v2u64 e0[EPT];                                                   // the first pair of every slot row, read together
+#pragma unroll
+            for (int k = 0; k < EPT; k++) e0[k] = tab2[bj_bucket<AGG_SLOT_BITS - 1>(p[k].payload, radix_bits)];
+            Cnt c[EPT];
+#pragma unroll
+            for (int k = 0; k < EPT; k++) {
+                const u32 i = tb + (u32)k * THREADS + tid;
+                c[k] = 0;
+                if (i < np) {
+                    const u64 key = p[k].payload;
+                    const u32 b = bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);
+                    const v2u64 e = e0[k];
+                    if (key == SEMI_EMPTY) c[k] = c_ones;
+                    else if (e.x == key) c[k] = cnt[2 * b];
+                    else if (e.y == key) c[k] = cnt[2 * b + 1];
+                    else if (e.x != SEMI_EMPTY && e.y != SEMI_EMPTY) c[k] = count_on(key, (b + 1) & (SLOTS / 2 - 1));
+                    if ((u64)p[k].key >= out_rows) { c[k] = 0; wild_r = true; }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < EPT; k++)
+                if (c[k] != 0) {
+                    acc_total += c[k];
+                    atomicAdd((unsigned long long *)&out[(u64)p[k].key], (unsigned long long)c[k]);
+                }
+            if (fetch) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) p[k] = p_next[k];
+            }
+        }
+        __syncthreads();                                                     // the table is cleared for the next tiles of S
+    } while (!last);
+
+    // ---- the task's total: wavefront, workgroup (the table's first bytes are free now), one global atomic ----
+    const u32 flags = (__ballot(wild_r) ? MULT_BAD_ROW_R : 0u) | (__ballot(wild_s) ? MULT_BAD_ROW_S : 0u);
+    if (flags && lane == 0) atomicOr(bad, flags);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc_total += __shfl_down(acc_total, off, 64);
+    if (lane == 0) tab[w] = acc_total;
+    __syncthreads();
+    if (tid == 0) {
+        u64 t = 0;
+        for (int i = 0; i < NW; i++) t += tab[i];
+        if (t) atomicAdd((unsigned long long *)total, (unsigned long long)t);
+        if (ntab > 1) atomicMax((unsigned long long *)max_tables, (unsigned long long)ntab);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K4 (compact-table form): bucket join for partitions whose build side does not fit a 16 B/tuple LDS table but
 // whose radix plan has removed >= 16 payload bits (BASELINE config 3: 8+8 bits at 10^9 tuples, 15.3 K-tuple
 // partitions).  Same job as k_join_bkt (JoinJob::run + Result::join_buckets, Result.cpp:43-76, + add_result /
@@ -3465,6 +3646,10 @@ static void allow_big_lds()
     SET_LDS(k_semi_bkt<false>, semi_lds_bytes());
     SET_LDS(k_agg_bkt<true>, agg_lds_bytes());
     SET_LDS(k_agg_bkt<false>, agg_lds_bytes());
+    SET_LDS((k_mult_bkt<true, false>), mult_lds_bytes(false));
+    SET_LDS((k_mult_bkt<false, false>), mult_lds_bytes(false));
+    SET_LDS((k_mult_bkt<true, true>), mult_lds_bytes(true));
+    SET_LDS((k_mult_bkt<false, true>), mult_lds_bytes(true));
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<IN_AOS>, wn_lds_bytes(WN_MAX_BITS));
@@ -4075,6 +4260,27 @@ void launch_agg_join(hipStream_t st, const void *d_R, const void *d_S, const Joi
         hipLaunchKernelGGL(k_agg_bkt<false>, dim3(grid), dim3(AGG_THREADS), agg_lds_bytes(), st, RelView<false>{(const Tup *)d_R},
                            RelView<false>{(const Tup *)d_S}, d_tasks, d_ntasks, radix_bits, cols, ncols, col_rows, d_sums, d_bad,
                            d_max_tables, d_skip);
+}
+
+void launch_mult_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                      int radix_bits, const u64 *d_w, u64 w_rows, u64 *d_out, u64 out_rows, u64 *d_total, u32 *d_bad,
+                      u64 *d_max_tables, const u32 *d_RK, const u32 *d_SK, const u32 *d_skip)
+{
+    if (grid == 0) return;
+    allow_big_lds();
+    auto go = [&](auto kernel, auto Rv, auto Sv, size_t lds) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(AGG_THREADS), lds, st, Rv, Sv, d_tasks, d_ntasks, radix_bits, d_w, w_rows, d_out,
+                           out_rows, d_total, d_bad, d_max_tables, d_skip);
+    };
+    if (d_RK != nullptr) {                                                   // narrow partitions: d_R, d_S are payload arrays
+        const RelView<true> Rv{(const u64 *)d_R, d_RK}, Sv{(const u64 *)d_S, d_SK};
+        if (d_w != nullptr) go(k_mult_bkt<true, true>, Rv, Sv, mult_lds_bytes(true));
+        else go(k_mult_bkt<true, false>, Rv, Sv, mult_lds_bytes(false));
+    } else {
+        const RelView<false> Rv{(const Tup *)d_R}, Sv{(const Tup *)d_S};
+        if (d_w != nullptr) go(k_mult_bkt<false, true>, Rv, Sv, mult_lds_bytes(true));
+        else go(k_mult_bkt<false, false>, Rv, Sv, mult_lds_bytes(false));
+    }
 }
 
 // Unpartitioned join of two small relations in ONE launch: build side = S when nR >= nS (JobScheduler.cpp:187).

@@ -101,6 +101,29 @@ k_sum_gather(const u64 *__restrict__ col, const u64 *__restrict__ rows, u64 n, u
     if (threadIdx.x == 0) atomicAdd(sum, wtot[0] + wtot[1] + wtot[2] + wtot[3]);
 }
 
+__global__ void __launch_bounds__(256)
+k_mul_u64(const u64 *a, const u64 *__restrict__ b, u64 n, u64 *dst)          // (dst may be a: no __restrict__ on the two)
+{
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) dst[i] = a[i] * b[i];
+}
+
+// col == nullptr: the plain sum of w
+__global__ void __launch_bounds__(256)
+k_sum_gather_weighted(const u64 *__restrict__ col, const u64 *__restrict__ rows, const u64 *__restrict__ w, u64 n, u64 *__restrict__ sum)
+{
+    __shared__ u64 wtot[4];
+    u64 acc = 0;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+        const u64 wi = w[i];
+        acc += col == nullptr ? wi : wi == 0 ? 0 : col[rows ? rows[i] : i] * wi;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(sum, wtot[0] + wtot[1] + wtot[2] + wtot[3]);
+}
+
 unsigned grid_for(u64 n)
 {
     u64 g = (n + 255) / 256;
@@ -176,6 +199,31 @@ int rhj_sum_gather(rhj_ctx *ctx, const uint64_t *d_col, const uint64_t *d_rows, 
     return with_counter(ctx, sum, "rhj_sum_gather", [&](u64 *acc, hipStream_t st) {
         hipLaunchKernelGGL(k_sum_gather, dim3(grid_for(n)), dim3(256), 0, st, (const u64 *)d_col, (const u64 *)d_rows, (u64)n, acc);
     });
+}
+
+int rhj_sum_gather_weighted(rhj_ctx *ctx, const uint64_t *d_col, const uint64_t *d_rows, const uint64_t *d_w, uint64_t n,
+                            uint64_t *sum)
+{
+    int rc = rhj_internal_use_device(ctx);
+    if (rc != RHJ_OK) return rc;
+    if (!sum || (n && !d_w)) return rhj_internal_fail(ctx, RHJ_E_INVALID, "bad rhj_sum_gather_weighted argument");
+    *sum = 0;
+    if (n == 0) return RHJ_OK;
+    return with_counter(ctx, sum, "rhj_sum_gather_weighted", [&](u64 *acc, hipStream_t st) {
+        hipLaunchKernelGGL(k_sum_gather_weighted, dim3(grid_for(n)), dim3(256), 0, st, (const u64 *)d_col, (const u64 *)d_rows,
+                           (const u64 *)d_w, (u64)n, acc);
+    });
+}
+
+int rhj_mul_u64(rhj_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, uint64_t n, uint64_t *d_dst)
+{
+    int rc = rhj_internal_use_device(ctx);
+    if (rc != RHJ_OK) return rc;
+    if (n && (!d_a || !d_b || !d_dst)) return rhj_internal_fail(ctx, RHJ_E_INVALID, "bad rhj_mul_u64 argument");
+    if (n == 0) return RHJ_OK;
+    hipLaunchKernelGGL(k_mul_u64, dim3(grid_for(n)), dim3(256), 0, rhj_internal_stream(ctx), (const u64 *)d_a, (const u64 *)d_b,
+                       (u64)n, (u64 *)d_dst);
+    return check(ctx, "rhj_mul_u64");
 }
 
 int rhj_gather_tuples(rhj_ctx *ctx, const uint64_t *d_col, const uint64_t *d_rows, uint64_t n, int key_is_position,

@@ -309,7 +309,7 @@ static void log_join(const relation &R, const relation &S, const Result &res)
 }
 
 // RHJ_QUERY_MODE=cols / agg (rhj_query_dev.cpp): one line "cols <nR> <nS> <count>" per rhj_join_cols_dev call, "sum <nR> <nS> <count>"
-// per rhj_join_sum_cols_dev call -- a test sees that the path ran (an unknown mode value silently runs the device path)
+// per rhj_join_sum_cols_dev call; RHJ_QUERY_MODE=tree: "mult <nR> <nS> <total>" per rhj_join_mult_cols_dev call -- a test sees that the path ran (an unknown mode value silently runs the device path)
 void log_cols_join(const char *what, uint64_t nR, uint64_t nS, uint64_t count)
 {
     const char *path = getenv("RHJ_JOIN_LOG");
@@ -420,7 +420,8 @@ void Query::execute_batch(JobScheduler &js, vector<Query> &queries, vector<relLi
 void Query::execute(JobScheduler &js, vector<relList> &relations)
 {
     // default: the whole query device-resident (rhj_query_dev.cpp; RHJ_QUERY_MODE=cols: with columnar join inputs,
-    // rhj_join_cols_dev; RHJ_QUERY_MODE=agg: ... and the SUMs over the last join by rhj_join_sum_cols_dev); RHJ_QUERY_MODE=host keeps filters and
+    // rhj_join_cols_dev; RHJ_QUERY_MODE=agg: ... and the SUMs over the last join by rhj_join_sum_cols_dev; RHJ_QUERY_MODE=tree: ... and a query whose
+    // join graph is a tree without any pairs, by rhj_join_mult_cols_dev); RHJ_QUERY_MODE=host keeps filters and
     // intermediates on the host and sends every equi-join through Result::multiRadixHashJoin with exactly the
     // join inputs the reference builds
     static const bool host_mode = getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "host";

@@ -78,7 +78,11 @@ struct Query {                                /* Query.h:34-59 */
        $RHJ_QUERY_MODE == "agg": as "cols", and when the last predicate of the join list is an equi-join between a new alias and the
        intermediate (or between two new aliases with nothing joined before) its pairs are never produced: the projections are grouped
        by the side of that join their alias arrives on and summed by rhj_join_sum_cols_dev, one call per side and per
-       RHJ_SUM_MAX_COLS projections (count 0: the query is filtered out; an alias outside the final intermediate sums to 0) */
+       RHJ_SUM_MAX_COLS projections (count 0: the query is filtered out; an alias outside the final intermediate sums to 0);
+       $RHJ_QUERY_MODE == "tree": as "agg", and a query whose equi-joins form a tree over all its aliases -- every join predicate
+       links exactly one new alias to the joined ones, every same-alias predicate comes before its alias is joined -- produces no
+       pairs at all: per projected alias, the rows' weights are the product of rhj_join_mult_cols_dev messages from its neighbours
+       and the SUMs are rhj_sum_gather_weighted, at most 2 x (aliases - 1) join calls; arithmetic mod 2^64 */
     void execute_device(JobScheduler &js, std::vector<relList> &relations);
     bool run_filters(std::vector<relList> &relations,
                      std::unordered_map<uint64_t, std::unordered_set<uint64_t> > &filtered);
@@ -98,7 +102,7 @@ private:
 };
 
 /* test hook of the "cols" and "agg" modes: appends "<what> <nR> <nS> <count>" to $RHJ_JOIN_LOG -- what = "cols": one line per
-   rhj_join_cols_dev call; "sum": one per rhj_join_sum_cols_dev call */
+   rhj_join_cols_dev call; "sum": one per rhj_join_sum_cols_dev call; "mult": one per rhj_join_mult_cols_dev call */
 void log_cols_join(const char *what, uint64_t nR, uint64_t nS, uint64_t count);
 
 /* intermediate.h:10-14.  parse_table: false when the same-alias predicate leaves no row */

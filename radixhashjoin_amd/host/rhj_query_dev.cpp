@@ -9,6 +9,9 @@
 // (no kernel at all) for an alias without a row list, one 8-byte gather otherwise -- instead of 16-byte tuples.
 // RHJ_QUERY_MODE=agg: as cols, except that a query whose LAST predicate is an equi-join through the hot path never produces that
 // join's pairs: its SUMs come from rhj_join_sum_cols_dev (sum_last_join below) instead of join + split + regather + rhj_sum_gather.
+// RHJ_QUERY_MODE=tree: as agg, except that a query whose join graph is a tree (tree_edges below) produces no pairs at all: every
+// SUM is a sum over the rows of its alias weighted by the product of per-row multiplicities, rhj_join_mult_cols_dev's messages
+// (TreeQuery below).
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -86,9 +89,15 @@ DevArr join_pairs(rhj_ctx *ctx, const DevArr &R, uint64_t nR, const DevArr &S, u
     }
 }
 
-bool agg_mode()
+bool tree_mode()
 {
-    static const bool on = getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "agg";
+    static const bool on = getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "tree";
+    return on;
+}
+
+bool agg_mode()                                        // (tree: a query that is not eligible runs as in agg)
+{
+    static const bool on = tree_mode() || (getenv("RHJ_QUERY_MODE") && std::string(getenv("RHJ_QUERY_MODE")) == "agg");
     return on;
 }
 
@@ -165,6 +174,131 @@ uint64_t join_sums(rhj_ctx *ctx, const ColSide &P, uint64_t nP, const ColSide &B
     return count;
 }
 
+// a same-alias predicate (parse_table) on an alias that is not joined yet: a filter on its row list.  false: no row is left
+bool same_alias_filter(rhj_ctx *ctx, const relList &rel, const join_info &j, Rows &r)
+{
+    const uint64_t *c1 = device_column(ctx, rel, j.column1), *c2 = device_column(ctx, rel, j.column2);
+    DevArr pos(ctx, r.n * 8);
+    uint64_t m = 0;
+    OK(ctx, rhj_rows_filter_equal(ctx, c1, r.ptr(), c2, r.ptr(), r.n, pos.p, &m));
+    if (m == 0) return false;
+    if (r.ptr() == nullptr) { pos.n = m; r.list = std::move(pos); }       // positions ARE the rowIDs
+    else {
+        DevArr next(ctx, m * 8);
+        OK(ctx, rhj_gather_u64(ctx, r.ptr(), pos.p, m, next.p));
+        next.n = m;
+        r.list = std::move(next);
+    }
+    r.n = m;
+    return true;
+}
+
+// The equi-joins of a query the "tree" mode takes, or nothing.  Walking the predicates in order with the set of joined aliases: a
+// same-alias predicate on an alias not joined yet is a filter on its row list (it stays in q.join, not here); a same-alias predicate
+// on a joined alias, a predicate between two joined aliases (also one that appears twice), one between two new aliases while others
+// are joined (the dropped-columns case of execute_device) or an alias that is never joined make the query not eligible.  What is
+// left is a tree over all aliases: na - 1 edges.
+bool tree_edges(const Query &q, std::vector<const join_info *> &edges)
+{
+    const size_t na = q.table.size();
+    std::vector<bool> joined(na, false);
+    bool any = false;
+    edges.clear();
+    for (const join_info &j : q.join) {
+        if (j.table1 == j.table2) {
+            if (joined[j.table1]) return false;
+            continue;
+        }
+        if (joined[j.table1] && joined[j.table2]) return false;
+        if (!joined[j.table1] && !joined[j.table2] && any) return false;
+        joined[j.table1] = joined[j.table2] = any = true;
+        edges.push_back(&j);
+    }
+    for (size_t a = 0; a < na; a++)
+        if (!joined[a]) return false;
+    return true;
+}
+
+// An eligible query after its filters.  Every alias is a positional vector over its row list; for a projected alias a,
+// SUM(a.c) = sum over its rows of c[row] * W_a[row], W_a the product over a's neighbours of the message "how many combinations of
+// the subtree behind this neighbour match this row".  The message u -> v over u.cu = v.cv is one rhj_join_mult_cols_dev call with
+// v's values as R, u's as S and, as S's weights, the product of the messages INTO u from its other neighbours; messages are kept per
+// directed edge, so a query costs at most 2 x (aliases - 1) calls.  A message total or a count of 0: no row, the NULL line.
+struct TreeQuery {
+    rhj_ctx *ctx;
+    Query &q;
+    std::vector<relList> &relations;
+    std::vector<Rows> &rows;
+    const std::vector<const join_info *> &edges;
+    std::map<std::pair<size_t, uint64_t>, DevArr> gathered;       // (alias, column) -> the column through the alias' row list
+    struct Message { DevArr w; uint64_t total = 0; bool done = false; };
+    std::vector<Message> msg;                                     // [2 e + d]: over edge e, d = 0: table2 -> table1, 1: table1 -> table2
+    bool none = false;                                            // a message came out all zero: the query has no row
+    TreeQuery(rhj_ctx *c, Query &query, std::vector<relList> &rels, std::vector<Rows> &r, const std::vector<const join_info *> &e)
+        : ctx(c), q(query), relations(rels), rows(r), edges(e) {}
+
+    const uint64_t *values(size_t a, uint64_t c)
+    {
+        const uint64_t *col = device_column(ctx, relations[q.table[a]], c);
+        if (rows[a].ptr() == nullptr) return col;
+        auto it = gathered.find({a, c});
+        if (it == gathered.end()) {
+            DevArr g(ctx, rows[a].n * 8);
+            OK(ctx, rhj_gather_u64(ctx, col, rows[a].ptr(), rows[a].n, g.p));
+            it = gathered.emplace(std::make_pair(a, c), std::move(g)).first;
+        }
+        return it->second.p;
+    }
+    // the product of the messages into alias a over every edge but `except` (-1: all): nullptr when there is none (all ones); `own`
+    // holds the product when it had to be formed
+    const uint64_t *weights(size_t a, int except, DevArr &own)
+    {
+        const uint64_t *w = nullptr;
+        for (size_t e = 0; e < edges.size() && !none; e++) {
+            if ((int)e == except || (edges[e]->table1 != a && edges[e]->table2 != a)) continue;
+            const Message &m = message(e, edges[e]->table1 == a ? 0 : 1);
+            if (none) break;
+            if (w == nullptr) { w = m.w.p; continue; }
+            if (own.empty()) own = DevArr(ctx, rows[a].n * 8);
+            OK(ctx, rhj_mul_u64(ctx, w, m.w.p, rows[a].n, own.p));
+            w = own.p;
+        }
+        return w;
+    }
+    const Message &message(size_t e, int d)
+    {
+        Message &m = msg[2 * e + d];
+        if (m.done) return m;
+        const join_info &j = *edges[e];
+        const size_t u = d ? j.table1 : j.table2, v = d ? j.table2 : j.table1;
+        const uint64_t cu = d ? j.column1 : j.column2, cv = d ? j.column2 : j.column1;
+        DevArr own;
+        const uint64_t *wS = weights(u, (int)e, own);
+        m.done = true;
+        if (none) return m;
+        m.w = DevArr(ctx, rows[v].n * 8);
+        OK(ctx, rhj_join_mult_cols_dev(ctx, values(v, cv), nullptr, rows[v].n, values(u, cu), nullptr, rows[u].n, wS, rows[u].n, nullptr,
+                                       m.w.p, rows[v].n, &m.total));
+        log_cols_join("mult", rows[v].n, rows[u].n, m.total);
+        if (m.total == 0) none = true;
+        return m;
+    }
+    void run()
+    {
+        msg.resize(2 * edges.size());
+        std::map<size_t, DevArr> product;                         // W_a of a projected alias with several neighbours
+        for (proj_info &p : q.proj) {
+            const size_t a = p.table;
+            DevArr &own = product[a];
+            const uint64_t *W = weights(a, -1, own);              // (memoised messages: a second projection of a costs its products only)
+            uint64_t count = 0;
+            if (!none) OK(ctx, rhj_sum_gather_weighted(ctx, nullptr, nullptr, W, rows[a].n, &count));
+            if (none || count == 0) { q.filtered_out = true; return; }
+            OK(ctx, rhj_sum_gather_weighted(ctx, device_column(ctx, relations[q.table[a]], p.column), rows[a].ptr(), W, rows[a].n, &p.sum));
+        }
+    }
+};
+
 }  // namespace
 
 // Query::execute on the device.  Returns through this->filtered_out / proj[i].sum like the host path.
@@ -189,6 +323,18 @@ void Query::execute_device(JobScheduler &js, std::vector<relList> &relations)
         r.n = m;
     }
 
+    // ---- RHJ_QUERY_MODE=tree, join graph a tree: same-alias predicates, then sums by message passing, no pairs -------------------
+    std::vector<const join_info *> edges;
+    if (tree_mode() && tree_edges(*this, edges)) {
+        for (const join_info &j : join) {
+            if (j.table1 != j.table2) continue;
+            if (!same_alias_filter(ctx, relations[table[j.table1]], j, rows[j.table1])) { filtered_out = true; return; }
+        }
+        TreeQuery t(ctx, *this, relations, rows, edges);
+        t.run();
+        return;
+    }
+
     // ---- join chain (Query.cpp:164-201) -------------------------------------------------------
     std::vector<DevArr> inter(na);                     // inter[a]: rowID of alias a per intermediate row
     uint64_t T = 0;                                    // intermediate rows
@@ -199,19 +345,7 @@ void Query::execute_device(JobScheduler &js, std::vector<relList> &relations)
         if (j.table1 == j.table2 || (in1 && in2)) {
             // a row filter: same-alias predicate (parse_table) or both aliases already joined (case 3)
             if (j.table1 == j.table2 && !in1) {
-                Rows &r = rows[j.table1];
-                DevArr pos(ctx, r.n * 8);
-                uint64_t m = 0;
-                OK(ctx, rhj_rows_filter_equal(ctx, c1, r.ptr(), c2, r.ptr(), r.n, pos.p, &m));
-                if (m == 0) { filtered_out = true; return; }
-                if (r.ptr() == nullptr) { pos.n = m; r.list = std::move(pos); }       // positions ARE the rowIDs
-                else {
-                    DevArr next(ctx, m * 8);
-                    OK(ctx, rhj_gather_u64(ctx, r.ptr(), pos.p, m, next.p));
-                    next.n = m;
-                    r.list = std::move(next);
-                }
-                r.n = m;
+                if (!same_alias_filter(ctx, rel1, j, rows[j.table1])) { filtered_out = true; return; }
                 continue;
             }
             DevArr pos(ctx, T * 8);

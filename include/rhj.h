@@ -136,9 +136,12 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * by themselves for partitions of 2-5 K tuples), 11 a smaller table with 12-bit arrival indices (plans of 12 bits); the sizes are
  * the rows of JOIN_GEOM in radixhashjoin_amd/csrc/rhj_internal.h; 12 the semi / anti join kernel: rhj_semi_join_dev /
  * rhj_semi_join_cols_dev, whatever the plan; 13 the aggregating join kernel: rhj_join_sum_dev / rhj_join_sum_cols_dev, whatever
- * the plan; 14 the multiplicity join kernel: rhj_join_mult_dev / rhj_join_mult_cols_dev, whatever the plan),
+ * the plan; 14 the multiplicity join kernel: rhj_join_mult_dev / rhj_join_mult_cols_dev, whatever the plan; 15 the group-by kernel:
+ * rhj_group_sum_dev / rhj_group_sum_cols_dev, whatever the plan),
  * "last.semi_tables" (the largest number of LDS tables any one task of the last
  * semi / anti join, aggregating join or multiplicity join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
+ * "last.group_rounds" (the largest number of LDS table builds any one task of the last group-by made: 1 when every partition fitted
+ * one table, 0 when no task ran, and 0 after every other call; "last.semi_tables" is 0 after a group-by),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -286,6 +289,50 @@ int rhj_join_mult_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
 int rhj_join_mult_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                       const uint64_t *d_wS, uint64_t wS_rows, const rhj_opts *opts,
                       uint64_t *d_out, uint64_t out_rows, uint64_t *out_total);
+
+/* ---- group-by on a key column: one output row per DISTINCT join value of R -- the value, how many tuples carry it, and up to four
+ * sums over those tuples (SELECT key, COUNT(*), SUM(x) FROM R GROUP BY key; value_counts; torch.unique + index_add_).  One relation:
+ * R goes through the partition phase of the joins, then one workgroup per partition keeps its distinct keys in an LDS table with a
+ * 64-bit word beside every key. */
+#define RHJ_GROUP_MAX_COLS 4
+/* one output row per DISTINCT join value of R: the value, how many tuples carry it, and for j < ncols the sum over those tuples of
+ * d_cols[j][rowR] (mod 2^64)
+ * R as columns exactly as rhj_join_cols_dev: rowR = d_idR[i], or i when d_idR == NULL (rowID = index).  Ids are partitioned with the
+ * values whenever they are given, also with ncols == 0.
+ * Output: group g is the triple d_out_keys[g], d_out_counts[g], d_out_sums[j][g].  d_out_keys[g] is the caller's value, not rhj_mix64
+ * of it.  The ORDER of groups is unspecified; the SET of groups is exact and the same from run to run (so is every count and sum:
+ * integer addition does not depend on the order).  d_out_sums: HOST array of ncols DEVICE columns, each out_capacity words long;
+ * d_cols: HOST array of ncols DEVICE columns, each col_rows words long, indexed by R's rowID, as in rhj_join_sum_cols_dev.
+ * out_groups: a HOST word; the call synchronises.
+ * Count only: d_out_keys == NULL with out_capacity == 0 counts the distinct values only -- no sum sweep runs and d_cols is never
+ * read.  With a non-NULL d_out_keys, d_out_counts may be NULL and is then not written.
+ * Overflow: RHJ_E_OVERFLOW with the exact *out_groups when out_capacity is too small: slots [0, capacity) of every output array then
+ * hold complete, distinct groups of the result, and nothing at or past capacity is written.
+ * Row guard: a rowR >= col_rows is never dereferenced: it raises a flag word in HBM and the call returns RHJ_E_INVALID, for every such
+ * tuple the kernel sees (ncols > 0 and not count-only: otherwise no column is read and col_rows is ignored).  The outputs are then
+ * undefined; the context stays usable.
+ * nR == 0: 0 groups, no launch.  RHJ_E_INVALID: ncols > RHJ_GROUP_MAX_COLS; a NULL d_cols, d_out_sums or column with ncols > 0 and a
+ * non-NULL d_out_keys; a NULL value column (relation) with nR > 0; NULL out_groups; NULL d_out_keys with out_capacity > 0.
+ * Plan: the one rhj_plan(nR, nR, ...) resolves for a device-resident join -- R is planned as an aggregating join with itself would
+ * be.  rhj_opts.probe_split is ignored: a partition is never cut (one task per non-empty partition, the whole partition; a partition
+ * of >= 2^32 tuples: RHJ_E_INVALID, use more radix bits).  Options, timings, "last.narrow", "last.countfree_R" and "last.cols_R" as
+ * rhj_join_cols_dev / rhj_join_dev on (nR, nR) -- same partition kernels, same repeats: a count-free overflow repeats with exact
+ * cursors, a rowID >= 2^32 in a narrow format repeats at 16 bytes, and every attempt starts from a zeroed group counter --, except
+ * that a one-pass plan always runs as separate partition and group launches; "last.countfree_S" and "last.cols_S" are 0 (there is no
+ * S: no second relation-sized buffer is allocated or touched); "last.join_kernel" is 15; "last.group_rounds" see rhj_get_info;
+ * "last.semi_tables" is 0.
+ * Costs to know: a partition is one workgroup's work, so one value repeated n times is summed by one workgroup -- linear
+ * in n, not balanced across the chip; a partition with D distinct keys beyond one table costs about 2 D / 4608 sweeps of itself.
+ * Inputs are neither modified nor retained (an unpartitioned plan reads the 16-byte array in place); outputs must not overlap them. */
+int rhj_group_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                           uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
+                           uint64_t out_capacity, uint64_t *out_groups);
+/* ... on 16-byte tuples (value = .payload, rowR = .key) */
+int rhj_group_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
+                      const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                      uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
+                      uint64_t out_capacity, uint64_t *out_groups);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:

@@ -12,7 +12,9 @@ From torch: ``idx_R, idx_S = Engine(0).join_columns(keys_R, keys_S)`` joins two 
 returns the indices of the keys of R that occur (``anti=True``: do not occur) in S (``rhj_semi_join_cols_dev``);
 ``count, sums = Engine(0).join_sum_columns(keys_R, keys_S, weights)`` is COUNT(*) and SUM(weights[k][i]) over the join's pairs
 without the pairs (``rhj_join_sum_cols_dev``); ``mult, total = Engine(0).join_multiplicity_columns(keys_R, keys_S, weights_S=None)``
-is, per key of R, how many keys of S equal it -- or the sum of their weights (``rhj_join_mult_cols_dev``).
+is, per key of R, how many keys of S equal it -- or the sum of their weights (``rhj_join_mult_cols_dev``);
+``unique_keys, counts, sums = Engine(0).group_by_columns(keys, weights)`` is GROUP BY on one key tensor: its distinct values, their
+counts and the per-group sums of the weight tensors (``rhj_group_sum_cols_dev``).
 """
 from .binding import (  # noqa: F401
     ANTI,
@@ -20,6 +22,7 @@ from .binding import (  # noqa: F401
     TUPLE,
     DeviceBuffer,
     Engine,
+    GROUP_MAX_COLS,
     Opts,
     RhjError,
     SEMI,
@@ -31,5 +34,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "SUM_MAX_COLS"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "SUM_MAX_COLS", "GROUP_MAX_COLS"]
 __version__ = "0.1.0"

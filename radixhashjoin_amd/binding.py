@@ -82,6 +82,8 @@ SYMBOLS = {
     "rhj_join_sum_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _P(_u64), _P(_u64)]),
     "rhj_join_mult_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_join_mult_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_group_sum_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64, _P(_u64)]),
+    "rhj_group_sum_dev": (C.c_int, [_vp, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64, _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -181,6 +183,7 @@ def narrow_bytes(n):
 
 
 SUM_MAX_COLS = 4                                         # include/rhj.h RHJ_SUM_MAX_COLS: weight columns of a join_sum_* call
+GROUP_MAX_COLS = 4                                       # include/rhj.h RHJ_GROUP_MAX_COLS: weight columns of a group_sum_* call
 SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
@@ -293,7 +296,7 @@ class Engine:
         self._chk(self.lib.rhj_set_option(self.ctx, name.encode(), int(value)))
 
     def info(self, name):
-        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables";
+        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.group_rounds";
         include/rhj.h)"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
@@ -471,9 +474,41 @@ class Engine:
                                              C.byref(opts) if opts is not None else None, _addr(d_out), out_rows, C.byref(total)))
         return total.value
 
+    def _group_args(self, d_cols, d_out_sums):
+        """the two host arrays of a group_sum_* call (a sum column that is missing goes in as NULL: the library answers)"""
+        k = max(len(d_cols), 1)
+        sums = list(d_out_sums)[:len(d_cols)]
+        return (_vp * k)(*[_addr(c) for c in d_cols]), (_vp * k)(*[_addr(c) for c in sums + [None] * (len(d_cols) - len(sums))])
+
+    def group_sum_cols_dev(self, d_valR, d_idR, nR, d_cols=(), col_rows=0, d_out_keys=None, d_out_counts=None, d_out_sums=(),
+                           capacity=0, opts=None, allow_overflow=False):
+        """rhj_group_sum_cols_dev: one output row per distinct join value of R (uint64 value column; uint64 rowIDs, or None: the
+        rowID of a tuple is its index) -- d_out_keys[g] the value, d_out_counts[g] (may be None) how many tuples carry it,
+        d_out_sums[j][g] the sum of d_cols[j][rowID] over them mod 2^64 (at most GROUP_MAX_COLS device columns of col_rows uint64) --
+        in no particular order; every output is uint64[capacity] in HBM.  d_out_keys None with capacity 0 counts the distinct
+        values only.  Returns the number of groups (with allow_overflow also when it exceeds capacity)"""
+        n = _u64()
+        cols, sums = self._group_args(d_cols, d_out_sums)
+        rc = self.lib.rhj_group_sum_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, cols, len(d_cols), col_rows,
+                                             C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_counts),
+                                             sums, capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_sum_dev(self, d_R, nR, d_cols=(), col_rows=0, d_out_keys=None, d_out_counts=None, d_out_sums=(), capacity=0, opts=None,
+                      allow_overflow=False):
+        """rhj_group_sum_dev: group_sum_cols_dev on 16-byte tuples (value = .payload, rowID = .key)"""
+        n = _u64()
+        cols, sums = self._group_args(d_cols, d_out_sums)
+        rc = self.lib.rhj_group_sum_dev(self.ctx, _addr(d_R), nR, cols, len(d_cols), col_rows,
+                                        C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_counts), sums,
+                                        capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
     @contextlib.contextmanager
     def _on_torch_stream(self, keys_R, keys_S, weights=(), weights_on_S=False):
-        """What join_columns, semi_join_columns, join_sum_columns and join_multiplicity_columns share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
+        """What join_columns, semi_join_columns, join_sum_columns, join_multiplicity_columns and group_by_columns (keys_S = keys_R) share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
         engine's device (ValueError otherwise); weights: tensors of the same kind, each as long as keys_R (weights_on_S: as keys_S).  The body runs ordered behind the work torch has queued on its current stream: on a
         stream of its own (torch.cuda.stream(s)) the engine runs on that stream for the length of the body; torch's default stream
         has no handle to hand over (its raw value is 0, which rhj_set_stream reads as "the context's own stream"), so there the call
@@ -570,6 +605,26 @@ class Engine:
             mult = torch.empty(nR, dtype=torch.int64, device=dev)
             total = self.join_mult_cols_dev(keys_R, None, nR, keys_S, None, nS, mult if nR else None, nR, weights_S, nS)
         return mult, total
+
+    def group_by_columns(self, keys, weights=()):
+        """(unique_keys, counts, sums): the distinct values of keys, how often each occurs, and per tensor of weights the sum of
+        weights[k][i] over the rows i that carry the value, mod 2^64 (SELECT key, COUNT(*), SUM(x) FROM R GROUP BY key; torch.unique
+        with return_counts + index_add_) -- int64 tensors of one length on the keys' device, sums a list of len(weights) of them,
+        group g of all at index g, groups in no particular order.  keys: a contiguous 1-D 64-bit integer tensor on the engine's
+        device; weights: up to GROUP_MAX_COLS tensors of the same kind and length.  Negative keys and weights are bit patterns: a
+        key comes back as it went in, an int64 sum is the two's complement sum.  The outputs are allocated at len(keys), the upper
+        bound, and returned as the views [:groups].  Streams and completion as join_columns."""
+        import torch
+        weights = tuple(weights)
+        if len(weights) > GROUP_MAX_COLS:
+            raise ValueError(f"at most {GROUP_MAX_COLS} weight tensors per call, not {len(weights)}")
+        with self._on_torch_stream(keys, keys, weights) as dev:
+            n = keys.numel()
+            out_keys = torch.empty(n, dtype=torch.int64, device=dev)
+            counts = torch.empty(n, dtype=torch.int64, device=dev)
+            sums = [torch.empty(n, dtype=torch.int64, device=dev) for _ in weights]
+            groups = self.group_sum_cols_dev(keys, None, n, weights, n, out_keys, counts, sums, n) if n else 0
+        return out_keys[:groups], counts[:groups], [s[:groups] for s in sums]
 
     def mul_u64(self, d_a, d_b, n, d_dst):
         """rhj_mul_u64: d_dst[i] = d_a[i] * d_b[i] mod 2^64 (d_dst may be d_a)"""

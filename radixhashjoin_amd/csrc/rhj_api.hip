@@ -243,6 +243,13 @@ struct rhj_ctx {
     u64 mult_w_rows = 0;
     u64 *mult_out = nullptr;           // out_rows words (device)
     u64 mult_out_rows = 0;
+    // a group-by's arguments, for the length of the call (input columns: agg_cols / agg_ncols / agg_col_rows; device words: agg_out's
+    // [0] groups, [5] u32 a rowID >= col_rows was met)
+    bool one_sided = false;            // partition_phase partitions R alone: no kernel touches a buffer of S, part_S does not grow
+    u64 *group_keys = nullptr, *group_counts = nullptr;   // capacity words each (device; counts may be null)
+    u64 *group_sums[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    u64 group_cap = 0;
+    int last_group_rounds = 0;         // "last.group_rounds": table builds of the busiest task of the last group-by (0: another call)
     DevBuf narrow_flag;                // u32: a rowID >= 2^32 met a narrow scatter -> the join re-runs in the 16-byte format
     // ... the next join tries the narrow format again; consecutive fall-backs make the context skip the attempt for the next
     // 2, 4, ... 32 eligible joins (a caller whose rowIDs are always wide pays one extra histogram per relation now and then)
@@ -456,6 +463,7 @@ void prof_reset(rhj_ctx *ctx)
     memset(&ctx->last, 0, sizeof(ctx->last));
     ctx->last_cols[0] = ctx->last_cols[1] = 0;      // "last.cols_*": every join or stage call starts here; rhj_join_cols_dev sets them as it goes
     ctx->last_semi_tables = 0;                      // "last.semi_tables": ... and semi_phase this one
+    ctx->last_group_rounds = 0;                     // "last.group_rounds": ... and group_phase this one
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -1146,9 +1154,13 @@ int cols_to_aos(rhj_ctx *ctx, u64 nR, const void *&d_R, u64 nS, const void *&d_S
 // before_S (optional, consumed by the first call that gets it): invoked once, after the kernels that partition R have been
 // enqueued and before anything reads S -- rhj_join uploads S there, so that S crosses PCIe while R is being partitioned
 // (plans that push both relations through the same launches call it first).
+// ctx->one_sided (a group-by): R alone is partitioned, under the plan, the format and the count-free choice of a join of (nR, nS = nR)
+// -- S is skipped explicitly: no kernel reads or writes a buffer of S, part_S is not grown, nothing is sampled (one side has no tie
+// to break), R takes the one-stream path and, under a one-pass plan, run_pass instead of the paired launches.  cur_S is null.
 int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan,
                     std::function<int()> *before_S = nullptr)
 {
+    const bool one = ctx->one_sided;
     ctx->sniff_ready = false;
     auto s_ready = [&]() -> int {
         if (!before_S || !*before_S) return RHJ_OK;
@@ -1173,7 +1185,10 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
         HIPCHK(ctx, hipMemsetAsync(ctx->narrow_flag.p, 0, 64, ctx->stream));
     }
     // a columnar join: the fused two-pass path in a narrow format reads the columns; every other path takes 16-byte copies
-    if (!(plan.passes == 2 && ctx->cur_narrow && narrow_fused_plan(plan))) RHJCHK(cols_to_aos(ctx, nR, d_R, nS, d_S));
+    if (!(plan.passes == 2 && ctx->cur_narrow && narrow_fused_plan(plan))) {
+        if (one) RHJCHK(cols_to_aos(ctx, 0, nR, d_R));
+        else RHJCHK(cols_to_aos(ctx, nR, d_R, nS, d_S));
+    }
     if (plan.passes == 0) {
         RHJCHK(s_ready());
         RHJCHK(ensure(ctx, ctx->ps_R, 64));
@@ -1181,10 +1196,10 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
         if (!is_direct(ctx, 1, nR, nS)) {                               // boundaries {0, n} for the task list (the direct launch needs none)
             Span s(ctx, RHJ_K_AUX);
             launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
-            launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+            if (!one) launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
         }
         ctx->cur_R = d_R;
-        ctx->cur_S = d_S;
+        ctx->cur_S = one ? nullptr : d_S;
         ctx->cur_nparts = 1;
         ctx->cur_radix_bits = 0;
     } else {
@@ -1194,20 +1209,20 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
         RHJCHK(ensure(ctx, ctx->ps_R, (np + 1) * 8));
         RHJCHK(ensure(ctx, ctx->ps_S, (np + 1) * 8));
         RHJCHK(ensure(ctx, ctx->part_R, (size_t)(nR ? nR : 1) * 16));
-        RHJCHK(ensure(ctx, ctx->part_S, (size_t)(nS ? nS : 1) * 16));
+        if (!one) RHJCHK(ensure(ctx, ctx->part_S, (size_t)(nS ? nS : 1) * 16));
         if (ctx->cur_narrow && !narrow_fused_plan(plan)) {
-            const bool sniff = sniff_on(ctx);
+            const bool sniff = sniff_on(ctx) && !one;
             if (sniff) RHJCHK(ensure(ctx, ctx->sniff_tab, (size_t)2 * SNIFF_SLOTS * 4));
             ctx->sniff_side = sniff ? 0 : -1;
             int prc = partition_relation_narrow2(ctx, d_R, nR, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p, nullptr, mix);
             if (prc == RHJ_OK) prc = s_ready();
             ctx->sniff_side = sniff ? 1 : -1;
-            if (prc == RHJ_OK)
+            if (prc == RHJ_OK && !one)
                 prc = partition_relation_narrow2(ctx, d_S, nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p, nullptr, mix);
             ctx->sniff_side = -1;
             RHJCHK(prc);
             ctx->sniff_ready = sniff;
-        } else if (two_streams_ok(ctx, nR, nS, plan, before_S)) {
+        } else if (!one && two_streams_ok(ctx, nR, nS, plan, before_S)) {
             // Mid-size joins are launch-bound (a fused two-pass partition is ~11 short dependent launches per relation): R and S
             // are independent until the join, so S is partitioned on a second stream, in a second set of scratch tables, while R
             // runs on the first -- the gaps between one relation's launches are filled by the other's kernels.
@@ -1233,7 +1248,7 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
             HIPCHK(ctx, hipEventRecord(ctx->aux_ev[1], ctx->aux_stream));
             HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));
         } else if (ctx->cur_narrow) {
-            const bool sniff = sniff_on(ctx);
+            const bool sniff = sniff_on(ctx) && !one;
             if (sniff) RHJCHK(ensure(ctx, ctx->sniff_tab, (size_t)2 * SNIFF_SLOTS * 4));
             ctx->sniff_side = sniff ? 0 : -1;
             int prc = RHJ_OK;
@@ -1242,23 +1257,23 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
                                                ctx->cur_narrow, mix, nullptr, cf_side_for(ctx, 0, nR, nS, plan, mix));
             if (prc == RHJ_OK) prc = s_ready();
             ctx->sniff_side = sniff ? 1 : -1;
-            if (prc == RHJ_OK)
+            if (prc == RHJ_OK && !one)
                 prc = partition_relation_fused(ctx, fused_input(ctx, 1, d_S), nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p,
                                                ctx->cur_narrow, mix, nullptr, cf_side_for(ctx, 1, nR, nS, plan, mix));
             ctx->sniff_side = -1;
             RHJCHK(prc);
             ctx->sniff_ready = sniff;
-        } else if (plan.passes == 1 && plan.bits1 <= PASS_PAIR_MAX_BITS) {
+        } else if (!one && plan.passes == 1 && plan.bits1 <= PASS_PAIR_MAX_BITS) {
             RHJCHK(s_ready());
             RHJCHK(run_pass_pair(ctx, d_R, nR, ctx->part_R.p, (u64 *)ctx->ps_R.p, d_S, nS, ctx->part_S.p, (u64 *)ctx->ps_S.p,
                                  plan.bits1));
         } else {
             RHJCHK(partition_relation(ctx, d_R, nR, plan.passes, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p, mix));
             RHJCHK(s_ready());
-            RHJCHK(partition_relation(ctx, d_S, nS, plan.passes, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p, mix));
+            if (!one) RHJCHK(partition_relation(ctx, d_S, nS, plan.passes, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p, mix));
         }
         ctx->cur_R = ctx->part_R.p;
-        ctx->cur_S = ctx->part_S.p;
+        ctx->cur_S = one ? nullptr : ctx->part_S.p;
         ctx->cur_nparts = np;
         ctx->cur_radix_bits = tb;
     }
@@ -1363,7 +1378,8 @@ int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
 // What a join reports once both sides are partitioned: the pairs (join_phase), the rowIDs of the tuples of R with (RHJ_SEMI) or
 // without (RHJ_ANTI) a partner in S (semi_phase), the pair count and sums over the pairs (agg_phase), or every row of R's
 // multiplicity in S (mult_phase).
-enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3 };
+// OUT_GROUP: one row per distinct join value of R alone (group_phase; partition_phase in its one-sided mode).
+enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3, OUT_GROUP = 4 };
 
 // Semi / anti join phase on the partitions partition_phase left: k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
 // Reads the skip word behind its kernel and answers with the retry codes of join_phase_on.
@@ -1557,6 +1573,71 @@ int mult_phase(rhj_ctx *ctx, u64 *out_total)
     return RHJ_OK;
 }
 
+// Group-by phase on the partitions of R that a one-sided partition_phase left: k_make_semi_tasks with anti = 1 over a
+// ZEROED boundary array of S and split = 2^32 - 1 -- one task per non-empty partition of R, the whole partition -- then k_group_bkt
+// over the columns and outputs the entry point left in the context.  EVERY attempt zeroes the group counter and the guard flag
+// before its kernel: a repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes as semi_phase.
+int group_phase(rhj_ctx *ctx, u64 *out_groups)
+{
+    const u64 nR = ctx->cur_nR, nparts = ctx->cur_nparts;
+    const bool narrow = ctx->cur_narrow != 0;
+    const u32 split = 0xffffffffu;                     // a partition is never cut: its keys would be emitted twice
+    const u64 max_tasks64 = nparts + nR / split + 1;
+    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
+    const u32 max_tasks = (u32)max_tasks64;
+    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
+    RHJCHK(ensure(ctx, ctx->counters, 64));
+    RHJCHK(ensure(ctx, ctx->agg_out, 64));
+    RHJCHK(ensure(ctx, ctx->ps_S, (size_t)(nparts + 1) * 8));
+    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
+    {
+        Span s(ctx, RHJ_K_AUX);
+        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->ps_S.p, 0, (size_t)(nparts + 1) * 8, ctx->stream));   // every partition of S: empty, at 0
+    }
+    ctx->counters_clean = false;
+    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
+        Span s(ctx, RHJ_K_AUX);
+        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+    }
+    ctx->last_join_kind = JK_GROUP;
+    ctx->sniff_ready = false;
+    {
+        Span s(ctx, RHJ_K_TASKS);
+        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, (const u64 *)ctx->ps_S.p, nparts, split, 1, (JoinTask *)ctx->tasks.p,
+                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
+    }
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        launch_group(ctx->stream, ctx->cur_R, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks, ctx->cur_radix_bits,
+                     ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, ctx->agg_cols, ctx->agg_ncols, ctx->agg_col_rows,
+                     ctx->group_keys, ctx->group_counts, ctx->group_sums, ctx->group_cap, d_agg, (u32 *)(d_agg + AGG_MAX_COLS + 1),
+                     d_count + 7, narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
+                     narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+    }
+    RHJCHK(check_launch(ctx, "group-by phase"));
+    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, -, -, -, -, most table builds of a task (if > 1)
+    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // groups, -, -, -, -, guard flag
+    u32 wide_rowid = 0;
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
+    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
+    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
+    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
+    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
+    ctx->last_max_part[1] = 0;
+    ctx->last_group_rounds = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
+    if (host[2] >> 32)                                           // (such a partition was cut in two: its groups are not the result)
+        return fail(ctx, RHJ_E_INVALID, "a partition of R has " + std::to_string(host[2]) + " tuples (>= 2^32): use more radix bits");
+    if ((u32)agg[AGG_MAX_COLS + 1])
+        return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= col_rows: the weight columns have no such row");
+    *out_groups = agg[0];
+    return RHJ_OK;
+}
+
 // bookkeeping of the narrow-format back-off (rhj.h "partition.narrow"), shared by the plain and the pipelined host path
 void narrow_note_fallback(rhj_ctx *ctx)                  // a join met a rowID >= 2^32 in the narrow format
 {
@@ -1684,7 +1765,7 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
 
 // partition + join.  A run in the narrow format whose histogram kernel met a rowID >= 2^32 costs two histogram launches
 // (every later kernel of the run returns at once) and is repeated in the 16-byte format; the fall-back is per join.
-// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase (which always take the
+// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase / group_phase (which always take the
 // unfused path: the one-pass form has the pair join built into its launches).
 int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan, void *d_out,
                        u64 cap, u64 *out_count, std::function<int()> *before_S = nullptr, JoinOutput what = OUT_PAIRS)
@@ -1693,7 +1774,8 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
         return join_one_pass_fused(ctx, d_R, nR, d_S, nS, plan, d_out, cap, out_count, before_S);
     auto after_partition = [&]() {
         return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : what == OUT_SUMS ? agg_phase(ctx, out_count) :
-               what == OUT_MULT ? mult_phase(ctx, out_count) : semi_phase(ctx, what, d_out, cap, out_count);
+               what == OUT_MULT ? mult_phase(ctx, out_count) : what == OUT_GROUP ? group_phase(ctx, out_count) :
+               semi_phase(ctx, what, d_out, cap, out_count);
     };
     int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S);
     if (rc != RHJ_OK) { ctx->counters_clean = false; return rc; }
@@ -1928,6 +2010,7 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.max_part_R") { *value = (int64_t)ctx->last_max_part[0]; return RHJ_OK; }
     if (n == "last.max_part_S") { *value = (int64_t)ctx->last_max_part[1]; return RHJ_OK; }
     if (n == "last.semi_tables") { *value = ctx->last_semi_tables; return RHJ_OK; }
+    if (n == "last.group_rounds") { *value = ctx->last_group_rounds; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }
@@ -2232,6 +2315,75 @@ int rhj_join_mult_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
     ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;   // S's rowIDs name its weights
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
     const int rc = join_mult_common(ctx, nullptr, nR, nullptr, nS, d_wS, wS_rows, opts, d_out, out_rows, out_total);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// Group-by: R alone through the partition phase and the repeat ladder of the joins (one-sided, planned as an aggregating
+// join of R with itself), then group_phase.  d_R null: the relation is ctx->cols_in[0].
+static_assert(RHJ_GROUP_MAX_COLS == AGG_MAX_COLS, "rhj.h and rhj_internal.h disagree");
+static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows,
+                        const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
+                        uint64_t out_capacity, uint64_t *out_groups)
+{
+    if (ncols > RHJ_GROUP_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncols is above RHJ_GROUP_MAX_COLS");
+    if (!d_out_keys && out_capacity) return fail(ctx, RHJ_E_INVALID, "d_out_keys is null with out_capacity > 0");
+    const u32 nsum = d_out_keys ? ncols : 0;           // count only: no sum sweep, d_cols is never read
+    if (nsum && (!d_cols || !d_out_sums)) return fail(ctx, RHJ_E_INVALID, "null weight column array or d_out_sums");
+    for (u32 j = 0; j < nsum; j++)
+        if (!d_cols[j] || !d_out_sums[j]) return fail(ctx, RHJ_E_INVALID, "null weight column or sum column");
+    if (nR == 0) return join_nothing(ctx);
+    rhj_opts plan;
+    if (resolve_plan(nR, nR, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
+        ctx->agg_cols[j] = j < nsum ? (const u64 *)d_cols[j] : nullptr;
+        ctx->group_sums[j] = j < nsum ? (u64 *)d_out_sums[j] : nullptr;
+    }
+    ctx->agg_ncols = nsum;
+    ctx->agg_col_rows = nsum ? col_rows : ~0ull;
+    ctx->group_keys = (u64 *)d_out_keys;
+    ctx->group_counts = d_out_keys ? (u64 *)d_out_counts : nullptr;
+    ctx->group_cap = d_out_keys ? out_capacity : 0;
+    ctx->one_sided = true;
+    const int rc = partition_and_join(ctx, d_R, nR, nullptr, nR, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GROUP);
+    ctx->one_sided = false;
+    ctx->agg_ncols = 0;
+    ctx->group_keys = ctx->group_counts = nullptr;
+    ctx->group_cap = 0;
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) { ctx->agg_cols[j] = nullptr; ctx->group_sums[j] = nullptr; }
+    RHJCHK(rc);
+    if (d_out_keys && *out_groups > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffers too small");
+    return RHJ_OK;
+}
+
+int rhj_group_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
+                      const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                      uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
+                      uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return group_common(ctx, d_R, nR, d_cols, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity, out_groups);
+}
+
+int rhj_group_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                           uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
+                           uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if (nR && !d_valR) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
+    ctx->cols_in[1] = ColsIn();
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = group_common(ctx, nullptr, nR, d_cols, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity,
+                                out_groups);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

@@ -293,6 +293,25 @@ constexpr u32 MULT_BAD_ROW_R = 1, MULT_BAD_ROW_S = 2;   // bits of *d_bad
 void launch_mult_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
                       int radix_bits, const u64 *d_w, u64 w_rows, u64 *d_out, u64 out_rows, u64 *d_total, u32 *d_bad,
                       u64 *d_max_tables, const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
+// ---- the group-by kernel (k_group_bkt): k_mult_bkt's weighted table over ONE relation ------------------------------
+// 8192 keys + 8192 64-bit accumulators + the tail words of mult_lds_bytes(true), then what the class walk needs: the class's first
+// group (8 B), the THREADS / 64 words of a workgroup scan and the 2 x AGG_MAX_COLS column pointers.  One workgroup of 1024 threads
+// per task, one task per partition.
+constexpr int JK_GROUP = JK_MULT + 1;             // "last.join_kernel" of a group-by (15)
+constexpr size_t GROUP_LDS_EXTRA = 8 + (size_t)(AGG_THREADS / 64) * 4 + (size_t)2 * AGG_MAX_COLS * 8;
+constexpr size_t group_lds_bytes() { return mult_lds_bytes(true) + GROUP_LDS_EXTRA; }
+static_assert(group_lds_bytes() <= 160 * 1024 && mult_lds_bytes(true) % 8 == 0 && AGG_FILL + AGG_BUILD_TILE <= (1u << AGG_SLOT_BITS) &&
+              (1u << AGG_SLOT_BITS) % AGG_THREADS == 0, "k_group_bkt's geometry");
+// The task list is launch_make_semi_tasks with anti = 1, a zeroed boundary array of S and split = 2^32 - 1: one task per non-empty
+// partition of R, the whole partition (its S range is empty and never read).  mixed: the partitions hold rhj_mix64 of the caller's
+// values (keys are unmixed on the way out).  d_cols / d_out_sums: HOST arrays of ncols (<= AGG_MAX_COLS) device columns; ncols == 0:
+// no sum sweep, neither is read.  d_out_keys / d_out_counts (may be null) / d_out_sums[j]: capacity words each; capacity == 0: count
+// only.  d_ngroups: one word (zeroed by the caller), the number of groups; d_bad: OR-ed with 1 when a rowID >= col_rows was met
+// (never dereferenced; ncols != 0 only); d_max_rounds: atomicMax of the table builds of a task, by tasks that built several; d_RK:
+// the rowID array of narrow partitions, or null; d_skip: as launch_join.
+void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits, bool mixed,
+                  const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_out_keys, u64 *d_out_counts, u64 *const *d_out_sums,
+                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip);
 // in_narrow: d_in is a payload array (u64).  key_base / d_wide (16-byte input): d_wide (may be null) is OR-ed with 1 when some
 // rowID - key_base does not fit 32 bits.  d_unit_rng (may be null): explicit pass-1 units (launch_seg_units).
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,

@@ -2927,6 +2927,210 @@ k_mult_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
 }
 
 // ------------------------------------------------------------------------------------------------
+// GROUP BY of one task: one output row per DISTINCT join value of a partition of R -- the value, how many tuples carry
+// it, and the sums of up to four columns over those tuples.  A task is a WHOLE partition: a partition cut in two would emit its keys
+// twice.
+//   * k_mult_bkt's weighted table: 8192 keys, open-addressed, insert-if-absent by a 64-bit LDS compare-and-swap, all-ones = empty
+//     with the all-ones key kept beside the table, a 64-bit accumulator beside every slot.
+//   * CLASSES.  A partition with more distinct keys than a table takes (AGG_FILL) cannot go through a second table over "the rest of
+//     the partition", as the joins do: a key met again there would be emitted twice.  It is split by HASH BITS instead: class (d, p)
+//     = the tuples whose class hash mix64(key ^ GROUP_CLASS_SALT) has the low d bits p -- a bijective mix that is not the fold
+//     bj_bucket takes its slot from, so a class spreads over the whole table.  The walk starts with class (0, 0) = everything:
+//       build-and-count sweep: the table is cleared, the partition goes through it in tiles of AGG_BUILD_TILE tuples, every tuple
+//         of the class inserts its key if absent and adds 1 on its slot; after every tile, more than AGG_FILL distinct keys: the
+//         class FAILS, nothing of it has been emitted, and its children (d + 1, p), (d + 1, p | 1 << d) take its place.  A tile adds
+//         at most AGG_BUILD_TILE keys to at most AGG_FILL, and AGG_FILL + AGG_BUILD_TILE <= slots: every probe walk meets an empty
+//         slot.  A class fails exactly when it holds more than AGG_FILL distinct keys, whatever the order of the tuples, so the set
+//         of emitted classes -- and the number of builds -- is the same from run to run.  Two distinct keys differ in some bit of a
+//         bijective hash: a class of depth 64 holds one key, the walk ends.
+//       emit: ONE global atomic add claims `base` for the class's groups; a slot's rank is its position among the occupied slots
+//         in slot order (a thread owns 8 consecutive slots; popcount + workgroup scan), the all-ones key comes last; keys (unmixed
+//         when the partition holds mix64 of the caller's values) and counts are stored where base + rank < capacity.
+//       sum sweeps (SUMS): per column the accumulators are zeroed, the class's tuples looked up again -- the table stays built --
+//         and cols[j][rowR] added on the slot, behind the rowR < col_rows guard (a row beyond is never dereferenced: *bad); emit.
+//     The next class is the prefix increment of (d, p) read with bit 0 as the most significant digit: no stack.
+//   * no global atomic per tuple; integer addition mod 2^64: every result is bit-exact from run to run.
+// ------------------------------------------------------------------------------------------------
+constexpr u64 GROUP_CLASS_SALT = 0xA0761D6478BD642Full;
+struct GroupSums { u64 *c[AGG_MAX_COLS]; };
+
+template <bool NARROW, bool SUMS>
+__global__ void __launch_bounds__(AGG_THREADS, 4)
+k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks, int radix_bits, int mixed,
+            AggCols cols, u32 ncols, u64 col_rows, u64 *__restrict__ out_keys, u64 *__restrict__ out_counts, GroupSums out_sums,
+            u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip)
+{
+    if (skip != nullptr && *skip != 0) return;
+    if (blockIdx.x >= *ntasks) return;
+    constexpr int THREADS = AGG_THREADS;
+    constexpr u32 SLOTS = 1u << AGG_SLOT_BITS, SPT = SLOTS / THREADS;         // slots a thread owns at emission
+    static_assert(AGG_BPT == 1 && SPT == 8, "one tuple per thread per build tile, eight slots per thread at emission");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64 *tab = reinterpret_cast<u64 *>(smem);                                // SLOTS keys
+    u64 *acc = tab + SLOTS;                                                  // SLOTS counts / sums, by slot
+    u64 *ones = acc + SLOTS;                                                 // ... of the all-ones key
+    u32 *nkeys = reinterpret_cast<u32 *>(ones + 1);                          // distinct keys in the table
+    u32 *has_ones = nkeys + 1;                                               // the class holds the all-ones key
+    u64 *base_s = reinterpret_cast<u64 *>(smem + mult_lds_bytes(true));      // the class's first group
+    u32 *wsum = reinterpret_cast<u32 *>(base_s + 1);                         // THREADS / 64 words of block_excl_scan
+    u64 *colp = reinterpret_cast<u64 *>(wsum + THREADS / 64);                // SUMS: the column and sum pointers, 2 x AGG_MAX_COLS words --
+                                                                             // sixteen kernel-argument SGPRs are not held across the walk
+
+    const JoinTask task = tasks[blockIdx.x];
+    const u32 np = task.plen;
+    if (np == 0) return;
+    typedef typename RelView<NARROW>::Both Both;
+    const RelView<NARROW> Rv = R.at(task.pbeg);
+    const int tid = threadIdx.x, lane = tid & 63;
+
+    if constexpr (SUMS)
+        if (tid == 0) {
+#pragma unroll
+            for (int j = 0; j < AGG_MAX_COLS; j++) { colp[j] = (u64)cols.c[j]; colp[AGG_MAX_COLS + j] = (u64)out_sums.c[j]; }
+        }                                                                    // (read behind the barriers of the first build)
+    u32 d = 0, rounds = 0;                                                   // the class (d, p); table builds so far
+    u64 p = 0;
+    bool wild = false;
+    auto in_class = [&](u64 key) -> bool {
+        if (d == 0) return true;
+        const u64 mask = d >= 64 ? ~0ull : (1ull << d) - 1;
+        return (mix64(key ^ GROUP_CLASS_SALT) & mask) == p;
+    };
+    auto insert = [&](u64 key) -> bool {                                     // true: the key was not there; counts the tuple either way
+        if (key == SEMI_EMPTY) { *has_ones = 1u; atomicAdd((unsigned long long *)ones, 1ull); return false; }
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            bool fresh = false;
+            if (cur != key) {
+                if (cur != SEMI_EMPTY) continue;
+                const u64 old = atomicCAS((unsigned long long *)&tab[s], (unsigned long long)SEMI_EMPTY, (unsigned long long)key);
+                if (old == SEMI_EMPTY) fresh = true;
+                else if (old != key) continue;
+            }
+            atomicAdd((unsigned long long *)&acc[s], 1ull);
+            return fresh;
+        }
+    };
+    auto add_on = [&](u64 key, u64 v) {                                      // the key is in the table (its class was built from these tuples)
+        if (key == SEMI_EMPTY) { atomicAdd((unsigned long long *)ones, (unsigned long long)v); return; }
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            if (cur == key) { atomicAdd((unsigned long long *)&acc[s], (unsigned long long)v); return; }
+            if (cur == SEMI_EMPTY) return;                                   // (cannot happen while the input stands still)
+        }
+    };
+    auto load_key = [&](u32 at) -> u64 {                                     // tuple at + tid of the partition; 0 beyond its end
+        return Rv.buf(at, np - at < AGG_BUILD_TILE ? np - at : AGG_BUILD_TILE).payload(0u, (u32)tid);
+    };
+
+    for (;;) {
+        // ---- build and count: the class's tuples, tile by tile ------------------------------------------------------------
+        for (u32 i = tid; i < SLOTS; i += THREADS) { tab[i] = SEMI_EMPTY; acc[i] = 0; }
+        if (tid == 0) { *ones = 0; *nkeys = 0; *has_ones = 0; }
+        __syncthreads();
+        rounds++;
+        u32 filled = 0;
+        u64 key = load_key(0), key_next = 0;
+        for (u32 done = 0; done < np;) {
+            const u32 nt = np - done < AGG_BUILD_TILE ? np - done : AGG_BUILD_TILE;
+            const bool more = done + nt < np;
+            if (more) key_next = load_key(done + nt);                        // travels behind the two barriers
+            {
+                const bool fresh = (u32)tid < nt && in_class(key) && insert(key);
+                const unsigned long long m = __ballot(fresh);
+                if (lane == 0 && m) atomicAdd(nkeys, (u32)__popcll(m));
+            }
+            __syncthreads();
+            filled = (u32)__builtin_amdgcn_readfirstlane((int)*nkeys);
+            __syncthreads();                                                 // (everybody has read the count before the next tile adds to it)
+            done += nt;
+            key = key_next;
+            if (filled > AGG_FILL) break;
+        }
+        if (filled > AGG_FILL) { d++; continue; }                            // the class fails: its first child (bit d of the hash = 0)
+
+        // ---- emit the class's keys and counts ------------------------------------------------------------------------------
+        const u32 ho = (u32)__builtin_amdgcn_readfirstlane((int)*has_ones);
+        if (tid == 0) *base_s = atomicAdd((unsigned long long *)ngroups, (unsigned long long)(filled + ho));
+        u32 occ = 0;
+#pragma unroll
+        for (u32 j = 0; j < SPT; j++) occ |= (tab[(u32)tid * SPT + j] != SEMI_EMPTY ? 1u : 0u) << j;
+        u32 tot;
+        int tq = tid;                                                        // (opaque: the scan's 16 wavefront predicates are not worth 32 SGPRs across the walk)
+        asm volatile("" : "+v"(tq));
+        const u32 ex = block_excl_scan<THREADS>((u32)__popc(occ), wsum, tot, tq);
+        const u64 g0 = *base_s + ex;                                         // this thread's first group
+        {
+            u64 g = g0;
+#pragma unroll 1
+            for (u32 j = 0; j < SPT; j++)
+                if (occ >> j & 1u) {
+                    if (g < capacity) {
+                        const u64 k = tab[(u32)tid * SPT + j];
+                        out_keys[g] = mixed ? unmix64(k) : k;
+                        if (out_counts != nullptr) out_counts[g] = acc[(u32)tid * SPT + j];
+                    }
+                    g++;
+                }
+            if (tid == 0 && ho) {
+                const u64 g1 = *base_s + filled;
+                if (g1 < capacity) {
+                    out_keys[g1] = mixed ? unmix64(SEMI_EMPTY) : SEMI_EMPTY;
+                    if (out_counts != nullptr) out_counts[g1] = *ones;
+                }
+            }
+        }
+
+        // ---- the sums, one column at a time over the table as it stands ----------------------------------------------------
+        if constexpr (SUMS) {
+            for (u32 c = 0; c < ncols; c++) {
+                const u64 *__restrict__ col = reinterpret_cast<const u64 *>(colp[c]);
+                u64 *__restrict__ dst = reinterpret_cast<u64 *>(colp[AGG_MAX_COLS + c]);
+                __syncthreads();                                             // the accumulators have been emitted
+                for (u32 i = tid; i < SLOTS; i += THREADS) acc[i] = 0;
+                if (tid == 0) *ones = 0;
+                __syncthreads();
+                Both t = Rv.buf(0u, np < (u32)THREADS ? np : (u32)THREADS).both(0u, (u32)tid), t_next = t;
+                for (u32 tb = 0; tb < np; tb += THREADS) {
+                    const u32 left = np - tb;                                // tuples from this tile on
+                    if (left > (u32)THREADS)                                 // the next tile travels behind this one's gather
+                        t_next = Rv.buf(tb + (u32)THREADS, left - THREADS < (u32)THREADS ? left - THREADS : (u32)THREADS).both(0u, (u32)tid);
+                    if ((u32)tid < left) {
+                        if ((u64)t.key >= col_rows) wild = true;
+                        else if (in_class(t.payload)) {
+                            const u64 v = col[(u64)t.key];
+                            if (v != 0) add_on(t.payload, v);
+                        }
+                    }
+                    t = t_next;
+                }
+                __syncthreads();
+                u64 g = g0;
+#pragma unroll 1
+                for (u32 j = 0; j < SPT; j++)
+                    if (occ >> j & 1u) {
+                        if (g < capacity) dst[g] = acc[(u32)tid * SPT + j];
+                        g++;
+                    }
+                if (tid == 0 && ho) {
+                    const u64 g1 = *base_s + filled;
+                    if (g1 < capacity) dst[g1] = *ones;
+                }
+            }
+        }
+
+        // ---- the next class: prefix increment, bit 0 the most significant digit ----------------------------------------------
+        while (d > 0 && (p >> (d - 1) & 1ull)) { p &= ~(1ull << (d - 1)); d--; }
+        if (d == 0) break;
+        p |= 1ull << (d - 1);
+        __syncthreads();                                                     // the table is cleared for the next class
+    }
+
+    if (__ballot(wild) && lane == 0) atomicOr(bad, 1u);
+    if (tid == 0 && rounds > 1) atomicMax((unsigned long long *)max_rounds, (unsigned long long)rounds);
+}
+
+// ------------------------------------------------------------------------------------------------
 // K4 (compact-table form): bucket join for partitions whose build side does not fit a 16 B/tuple LDS table but
 // whose radix plan has removed >= 16 payload bits (BASELINE config 3: 8+8 bits at 10^9 tuples, 15.3 K-tuple
 // partitions).  Same job as k_join_bkt (JoinJob::run + Result::join_buckets, Result.cpp:43-76, + add_result /
@@ -3650,6 +3854,10 @@ static void allow_big_lds()
     SET_LDS((k_mult_bkt<false, false>), mult_lds_bytes(false));
     SET_LDS((k_mult_bkt<true, true>), mult_lds_bytes(true));
     SET_LDS((k_mult_bkt<false, true>), mult_lds_bytes(true));
+    SET_LDS((k_group_bkt<true, false>), group_lds_bytes());
+    SET_LDS((k_group_bkt<false, false>), group_lds_bytes());
+    SET_LDS((k_group_bkt<true, true>), group_lds_bytes());
+    SET_LDS((k_group_bkt<false, true>), group_lds_bytes());
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<IN_AOS>, wn_lds_bytes(WN_MAX_BITS));
@@ -4280,6 +4488,30 @@ void launch_mult_join(hipStream_t st, const void *d_R, const void *d_S, const Jo
         const RelView<false> Rv{(const Tup *)d_R}, Sv{(const Tup *)d_S};
         if (d_w != nullptr) go(k_mult_bkt<false, true>, Rv, Sv, mult_lds_bytes(true));
         else go(k_mult_bkt<false, false>, Rv, Sv, mult_lds_bytes(false));
+    }
+}
+
+void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits, bool mixed,
+                  const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_out_keys, u64 *d_out_counts, u64 *const *d_out_sums,
+                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip)
+{
+    if (grid == 0) return;
+    allow_big_lds();
+    AggCols cols;
+    GroupSums sums;
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) { cols.c[j] = j < ncols ? d_cols[j] : nullptr; sums.c[j] = j < ncols ? d_out_sums[j] : nullptr; }
+    auto go = [&](auto kernel, auto Rv) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(AGG_THREADS), group_lds_bytes(), st, Rv, d_tasks, d_ntasks, radix_bits, mixed ? 1 : 0,
+                           cols, ncols, col_rows, d_out_keys, d_out_counts, sums, capacity, d_ngroups, d_bad, d_max_rounds, d_skip);
+    };
+    if (d_RK != nullptr) {                                                   // narrow partitions: d_R is a payload array
+        const RelView<true> Rv{(const u64 *)d_R, d_RK};
+        if (ncols != 0) go(k_group_bkt<true, true>, Rv);
+        else go(k_group_bkt<true, false>, Rv);
+    } else {
+        const RelView<false> Rv{(const Tup *)d_R};
+        if (ncols != 0) go(k_group_bkt<false, true>, Rv);
+        else go(k_group_bkt<false, false>, Rv);
     }
 }
 

@@ -137,11 +137,12 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * the rows of JOIN_GEOM in radixhashjoin_amd/csrc/rhj_internal.h; 12 the semi / anti join kernel: rhj_semi_join_dev /
  * rhj_semi_join_cols_dev, whatever the plan; 13 the aggregating join kernel: rhj_join_sum_dev / rhj_join_sum_cols_dev, whatever
  * the plan; 14 the multiplicity join kernel: rhj_join_mult_dev / rhj_join_mult_cols_dev, whatever the plan; 15 the group-by kernel:
- * rhj_group_sum_dev / rhj_group_sum_cols_dev, whatever the plan),
+ * rhj_group_sum_dev / rhj_group_sum_cols_dev, whatever the plan; 16 the group-by join kernel: rhj_group_join_dev /
+ * rhj_group_join_cols_dev, whatever the plan),
  * "last.semi_tables" (the largest number of LDS tables any one task of the last
  * semi / anti join, aggregating join or multiplicity join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
- * "last.group_rounds" (the largest number of LDS table builds any one task of the last group-by made: 1 when every partition fitted
- * one table, 0 when no task ran, and 0 after every other call; "last.semi_tables" is 0 after a group-by),
+ * "last.group_rounds" (the largest number of LDS table builds any one task of the last group-by or group-by join made: 1 when every
+ * partition of R fitted one table, 0 when no task ran, and 0 after every call that is neither; "last.semi_tables" is 0 after both),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -333,6 +334,70 @@ int rhj_group_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
                       const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
                       uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
                       uint64_t out_capacity, uint64_t *out_groups);
+
+/* ---- join with GROUP BY on the key: one output row per join value of R join S -- the value, how many tuples of each side carry it,
+ * and up to four sums per side over those tuples (SELECT key, COUNT(*), SUM(r.a), SUM(s.b) FROM R JOIN S USING (key) GROUP BY key, and
+ * the LEFT JOIN form; the per-key degree product of a join; intersect1d with counts).  No pair is formed: both relations go through
+ * the partition phase of the joins, then one workgroup per partition keeps R's distinct keys in an LDS table with a 64-bit word beside
+ * every key, and S looks its keys up. */
+#define RHJ_GJ_INNER 0      /* one row per join value that occurs in R and in S */
+#define RHJ_GJ_LEFT  1      /* one row per distinct join value of R; cntS may be 0 */
+#define RHJ_GROUP_JOIN_MAX_COLS 4      /* per side */
+/* R and S as columns exactly as rhj_join_mult_cols_dev: rowR = d_idR[i], or i when d_idR == NULL (rowID = index); rowS likewise.  Ids
+ * are partitioned with the values whenever they are given, also with no column.
+ * Raw per-side results: group g is d_out_keys[g], d_out_cntR[g], d_out_cntS[g], d_out_sumsR[j][g], d_out_sumsS[j][g].  d_out_keys[g] is
+ * the caller's value, not rhj_mix64 of it.  cntR[g] is the number of tuples of R with that value, cntS[g] the number of tuples of S;
+ * sumsR[j][g] is the sum over those tuples of R of d_colsR[j][rowR] (mod 2^64), sumsS[j][g] the sum over those tuples of S of
+ * d_colsS[j][rowS].  The SQL aggregates over the pairs of the group are products of these (mod 2^64):
+ *     COUNT(*) = cntR·cntS        SUM(r.a) = sumsR·cntS        SUM(s.b) = sumsS·cntR
+ * The raw values are returned so that a caller can also form averages or per-side counts.
+ * Modes: RHJ_GJ_INNER emits the values present on both sides; RHJ_GJ_LEFT emits every distinct value of R, with cntS and sumsS 0
+ * where S has none (a LEFT JOIN's unmatched row counts once: the caller multiplies by max(cntS, 1)).
+ * The ORDER of groups is unspecified; the SET of groups, every count and every sum are exact and bit-identical from run to run
+ * (integer addition does not depend on the order).  d_out_sumsR / d_out_sumsS: HOST arrays of ncolsR / ncolsS DEVICE columns, each
+ * out_capacity words long; d_colsR / d_colsS: HOST arrays of ncolsR / ncolsS DEVICE columns, each colR_rows / colS_rows words long,
+ * indexed by the side's rowID, as in rhj_join_sum_cols_dev.  out_groups: a HOST word; the call synchronises.
+ * Count only: d_out_keys == NULL with out_capacity == 0 counts the groups only -- no sum sweep runs and no column is read.  With a
+ * non-NULL d_out_keys, d_out_cntR and d_out_cntS may each be NULL and are then not written.
+ * Overflow: RHJ_E_OVERFLOW with the exact *out_groups when out_capacity is too small: slots [0, capacity) of every output array then
+ * hold complete, distinct groups of the result, and nothing at or past capacity is written.
+ * Row guard: a rowR >= colR_rows or a rowS >= colS_rows is never dereferenced: it raises a flag word in HBM and the call returns
+ * RHJ_E_INVALID with a message that says which side, for every such tuple a sum sweep meets (the side has columns and the call is
+ * not count-only: otherwise no column of that side is read and its *_rows is ignored; a partition no task is made for, and a class
+ * of keys that emits no group, get no sum sweep).  The outputs are then undefined; the context stays usable.
+ * Empty sides: nR == 0: 0 groups, no launch.  nS == 0: RHJ_GJ_INNER gives 0 groups, no launch; RHJ_GJ_LEFT gives the group-by of R
+ * with zero S fields (R alone is partitioned, under the plan of rhj_group_sum_cols_dev).
+ * RHJ_E_INVALID: a mode that is neither RHJ_GJ_INNER nor RHJ_GJ_LEFT; ncolsR or ncolsS > RHJ_GROUP_JOIN_MAX_COLS; with ncolsR > 0
+ * and a non-NULL d_out_keys a NULL d_colsR, d_out_sumsR or column of either, and the same for S's side; a NULL value column
+ * (relation) with a non-zero row count; NULL out_groups; NULL d_out_keys with out_capacity > 0.
+ * Plan: the one rhj_plan(nR, nS, ...) resolves for a device-resident join.  rhj_opts.probe_split is ignored: a partition is never
+ * cut (one task per partition, both whole partitions; a partition of >= 2^32 tuples on either side: RHJ_E_INVALID,
+ * use more radix bits).  Options, timings, "last.narrow", "last.countfree_*" and "last.cols_*" as rhj_join_mult_cols_dev / rhj_join_mult_dev on the
+ * same sizes -- same partition kernels, same repeats; both sides' ids are read, so a rowID >= 2^32 on either side in a narrow format
+ * repeats at 16 bytes, a count-free overflow repeats with exact cursors, and every attempt starts from a zeroed group counter and
+ * flag word; "last.join_kernel" is 16; "last.group_rounds" see rhj_get_info; "last.semi_tables" is 0.
+ * Costs to know: a partition is one workgroup's work; partitions are read 1 + ncols times per side and class; the
+ * table is always built on R, so under RHJ_GJ_INNER an R with many more distinct values than S pays class walks that the call with
+ * the sides exchanged would not.
+ * Inputs are neither modified nor retained (an unpartitioned plan reads 16-byte arrays in place); outputs must not overlap them. */
+int rhj_group_join_cols_dev(rhj_ctx *ctx,
+        const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+        const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+        const uint64_t *const *d_colsR, uint32_t ncolsR, uint64_t colR_rows,
+        const uint64_t *const *d_colsS, uint32_t ncolsS, uint64_t colS_rows,
+        int mode, const rhj_opts *opts,
+        uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+        uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS,
+        uint64_t out_capacity, uint64_t *out_groups);
+/* ... on 16-byte tuples (value = .payload, rowID = .key) */
+int rhj_group_join_dev(rhj_ctx *ctx,
+        const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+        const uint64_t *const *d_colsR, uint32_t ncolsR, uint64_t colR_rows,
+        const uint64_t *const *d_colsS, uint32_t ncolsS, uint64_t colS_rows,
+        int mode, const rhj_opts *opts,
+        uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+        uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS,
+        uint64_t out_capacity, uint64_t *out_groups);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:

@@ -84,6 +84,10 @@ SYMBOLS = {
     "rhj_join_mult_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_group_sum_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64, _P(_u64)]),
     "rhj_group_sum_dev": (C.c_int, [_vp, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64, _P(_u64)]),
+    "rhj_group_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(_vp), C.c_uint32, _u64, C.c_int,
+                                          _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64)]),
+    "rhj_group_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(_vp), C.c_uint32, _u64, C.c_int,
+                                     _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -184,6 +188,8 @@ def narrow_bytes(n):
 
 SUM_MAX_COLS = 4                                         # include/rhj.h RHJ_SUM_MAX_COLS: weight columns of a join_sum_* call
 GROUP_MAX_COLS = 4                                       # include/rhj.h RHJ_GROUP_MAX_COLS: weight columns of a group_sum_* call
+GROUP_JOIN_MAX_COLS = 4                                  # include/rhj.h RHJ_GROUP_JOIN_MAX_COLS: weight columns per side of a group_join_* call
+GJ_INNER, GJ_LEFT = 0, 1                                 # include/rhj.h RHJ_GJ_INNER / RHJ_GJ_LEFT: the mode of a group_join_* call
 SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
@@ -506,9 +512,41 @@ class Engine:
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
 
+    def group_join_cols_dev(self, d_valR, d_idR, nR, d_valS, d_idS, nS, d_colsR=(), colR_rows=0, d_colsS=(), colS_rows=0, mode=GJ_INNER,
+                            d_out_keys=None, d_out_cntR=None, d_out_cntS=None, d_out_sumsR=(), d_out_sumsS=(), capacity=0, opts=None,
+                            allow_overflow=False):
+        """rhj_group_join_cols_dev: one output row per join value of R join S (uint64 value columns; uint64 rowIDs, or None: the
+        rowID of a tuple is its index) -- d_out_keys[g] the value, d_out_cntR[g] / d_out_cntS[g] (each may be None) how many tuples
+        of R / S carry it, d_out_sumsR[j][g] / d_out_sumsS[j][g] the sums of d_colsR[j][rowR] / d_colsS[j][rowS] over them mod 2^64
+        (at most GROUP_JOIN_MAX_COLS device columns per side, of colR_rows / colS_rows uint64) -- in no particular order; every
+        output is uint64[capacity] in HBM.  mode GJ_INNER: the values both sides have; GJ_LEFT: every value of R (cntS may be 0).
+        COUNT(*) = cntR*cntS, SUM(r.a) = sumsR*cntS, SUM(s.b) = sumsS*cntR.  d_out_keys None with capacity 0 counts the groups
+        only.  Returns the number of groups (with allow_overflow also when it exceeds capacity)"""
+        n = _u64()
+        colsR, sumsR = self._group_args(d_colsR, d_out_sumsR)
+        colsS, sumsS = self._group_args(d_colsS, d_out_sumsS)
+        rc = self.lib.rhj_group_join_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), _addr(d_idS), nS,
+                                              colsR, len(d_colsR), colR_rows, colsS, len(d_colsS), colS_rows, mode,
+                                              C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_cntR),
+                                              _addr(d_out_cntS), sumsR, sumsS, capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_join_dev(self, d_R, nR, d_S, nS, d_colsR=(), colR_rows=0, d_colsS=(), colS_rows=0, mode=GJ_INNER, d_out_keys=None,
+                       d_out_cntR=None, d_out_cntS=None, d_out_sumsR=(), d_out_sumsS=(), capacity=0, opts=None, allow_overflow=False):
+        """rhj_group_join_dev: group_join_cols_dev on 16-byte tuples (value = .payload, rowID = .key)"""
+        n = _u64()
+        colsR, sumsR = self._group_args(d_colsR, d_out_sumsR)
+        colsS, sumsS = self._group_args(d_colsS, d_out_sumsS)
+        rc = self.lib.rhj_group_join_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, colsR, len(d_colsR), colR_rows, colsS, len(d_colsS),
+                                         colS_rows, mode, C.byref(opts) if opts is not None else None, _addr(d_out_keys),
+                                         _addr(d_out_cntR), _addr(d_out_cntS), sumsR, sumsS, capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
     @contextlib.contextmanager
-    def _on_torch_stream(self, keys_R, keys_S, weights=(), weights_on_S=False):
-        """What join_columns, semi_join_columns, join_sum_columns, join_multiplicity_columns and group_by_columns (keys_S = keys_R) share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
+    def _on_torch_stream(self, keys_R, keys_S, weights=(), weights_on_S=False, weights_S=()):
+        """What join_columns, semi_join_columns, join_sum_columns, join_multiplicity_columns, group_by_columns (keys_S = keys_R) and join_group_by_columns (weights_S: further tensors, each as long as keys_S) share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
         engine's device (ValueError otherwise); weights: tensors of the same kind, each as long as keys_R (weights_on_S: as keys_S).  The body runs ordered behind the work torch has queued on its current stream: on a
         stream of its own (torch.cuda.stream(s)) the engine runs on that stream for the length of the body; torch's default stream
         has no handle to hand over (its raw value is 0, which rhj_set_stream reads as "the context's own stream"), so there the call
@@ -516,7 +554,8 @@ class Engine:
         the block is left, and a stream bound earlier with set_stream is bound again.  Yields the tensors' device."""
         import torch
         ints = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)
-        for name, k in (("keys_R", keys_R), ("keys_S", keys_S)) + tuple((f"weights[{i}]", w) for i, w in enumerate(weights)):
+        for name, k in ((("keys_R", keys_R), ("keys_S", keys_S)) + tuple((f"weights[{i}]", w) for i, w in enumerate(weights)) +
+                        tuple((f"weights_S[{i}]", w) for i, w in enumerate(weights_S))):
             if not isinstance(k, torch.Tensor) or k.dtype not in ints or k.dim() != 1:
                 raise ValueError(f"{name}: a 1-D torch tensor of 64-bit integers is needed")
             if k.device.type != "cuda" or (k.device.index or 0) != self.device:
@@ -527,6 +566,9 @@ class Engine:
         for i, w in enumerate(weights):
             if w.numel() != keys.numel():
                 raise ValueError(f"weights[{i}]: {w.numel()} elements for {keys.numel()} keys of {side}")
+        for i, w in enumerate(weights_S):
+            if w.numel() != keys_S.numel():
+                raise ValueError(f"weights_S[{i}]: {w.numel()} elements for {keys_S.numel()} keys of S")
         dev = keys_R.device
         with torch.cuda.device(dev):
             torch_stream = torch.cuda.current_stream(dev)
@@ -625,6 +667,40 @@ class Engine:
             sums = [torch.empty(n, dtype=torch.int64, device=dev) for _ in weights]
             groups = self.group_sum_cols_dev(keys, None, n, weights, n, out_keys, counts, sums, n) if n else 0
         return out_keys[:groups], counts[:groups], [s[:groups] for s in sums]
+
+    def join_group_by_columns(self, keys_R, keys_S, weights_R=(), weights_S=(), how="inner"):
+        """(keys, count, sums_R, sums_S): SELECT key, COUNT(*), SUM(r.a).., SUM(s.b).. FROM R JOIN S USING (key) GROUP BY key -- per
+        join value the number of index pairs (i, j) with keys_R[i] == keys_S[j] == key, and per tensor of weights_R / weights_S the
+        sum of weights_R[k][i] / weights_S[k][j] over those pairs, mod 2^64 -- without the pairs: int64 tensors of one length on the
+        keys' device, sums_R / sums_S lists of len(weights_R) / len(weights_S) of them, group g of all at index g, groups in no
+        particular order.  how="inner": the values both tensors have.  how="left" (LEFT JOIN): every distinct value of keys_R; a
+        value keys_S lacks is one row per occurrence in keys_R with NULLs for S, so its count is its number of occurrences, its
+        sums_R their plain sums and its sums_S 0.  The products are formed from the raw per-side results of rhj_group_join_cols_dev
+        with wrapping int64 multiplies (count = cntR * cntS, sums_R = sumsR * cntS, sums_S = sumsS * cntR; under how="left"
+        max(cntS, 1) multiplies R's side).  keys_R / keys_S: contiguous 1-D 64-bit integer tensors on the engine's device; weights_R
+        / weights_S: up to GROUP_JOIN_MAX_COLS tensors each, of the same kind, as long as keys_R / keys_S.  Negative keys and weights
+        are bit patterns: a key comes back as it went in, an int64 sum is the two's complement sum.  The outputs are allocated at
+        len(keys_R), the upper bound, and returned as views [:groups] or products of them.  Streams and completion as join_columns."""
+        import torch
+        weights_R, weights_S = tuple(weights_R), tuple(weights_S)
+        if how not in ("inner", "left"):
+            raise ValueError(f"how: 'inner' or 'left', not {how!r}")
+        for name, w in (("weights_R", weights_R), ("weights_S", weights_S)):
+            if len(w) > GROUP_JOIN_MAX_COLS:
+                raise ValueError(f"at most {GROUP_JOIN_MAX_COLS} {name} tensors per call, not {len(w)}")
+        with self._on_torch_stream(keys_R, keys_S, weights_R, weights_S=weights_S) as dev:
+            nR, nS = keys_R.numel(), keys_S.numel()
+            new = lambda: torch.empty(nR, dtype=torch.int64, device=dev)
+            out_keys, cntR, cntS = new(), new(), new()
+            sumsR = [new() for _ in weights_R]
+            # (tensors without elements have no address to hand over: an empty S goes in without columns, its sums are 0)
+            sumsS = [new() if nS else torch.zeros(nR, dtype=torch.int64, device=dev) for _ in weights_S]
+            groups = self.group_join_cols_dev(keys_R, None, nR, keys_S if nS else None, None, nS, weights_R, nR,
+                                              weights_S if nS else (), nS, GJ_LEFT if how == "left" else GJ_INNER, out_keys, cntR, cntS,
+                                              sumsR, sumsS if nS else (), nR) if nR else 0
+        cntR, cntS = cntR[:groups], cntS[:groups]
+        mult_R = cntS.clamp(min=1) if how == "left" else cntS    # (counts are < 2^63: clamp on int64 is on the true values)
+        return out_keys[:groups], cntR * mult_R, [s[:groups] * mult_R for s in sumsR], [s[:groups] * cntR for s in sumsS]
 
     def mul_u64(self, d_a, d_b, n, d_dst):
         """rhj_mul_u64: d_dst[i] = d_a[i] * d_b[i] mod 2^64 (d_dst may be d_a)"""

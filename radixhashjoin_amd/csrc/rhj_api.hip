@@ -249,7 +249,15 @@ struct rhj_ctx {
     u64 *group_keys = nullptr, *group_counts = nullptr;   // capacity words each (device; counts may be null)
     u64 *group_sums[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
     u64 group_cap = 0;
-    int last_group_rounds = 0;         // "last.group_rounds": table builds of the busiest task of the last group-by (0: another call)
+    int last_group_rounds = 0;         // "last.group_rounds": table builds of the busiest task of the last group-by or group-by join (0: another call)
+    // a group-by join's arguments beyond the group-by's (R's side: agg_cols / agg_ncols / agg_col_rows, group_keys, group_counts = cntR,
+    // group_sums, group_cap; device words: agg_out's [0] groups, [5] u32 GJOIN_BAD_ROW_R / _S)
+    const u64 *gjoin_colsS[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    u32 gjoin_ncolsS = 0;
+    u64 gjoin_colS_rows = 0;
+    u64 *gjoin_cntS = nullptr;         // capacity words (device; may be null)
+    u64 *gjoin_sumsS[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    bool gjoin_left = false;           // RHJ_GJ_LEFT
     DevBuf narrow_flag;                // u32: a rowID >= 2^32 met a narrow scatter -> the join re-runs in the 16-byte format
     // ... the next join tries the narrow format again; consecutive fall-backs make the context skip the attempt for the next
     // 2, 4, ... 32 eligible joins (a caller whose rowIDs are always wide pays one extra histogram per relation now and then)
@@ -1379,7 +1387,8 @@ int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
 // without (RHJ_ANTI) a partner in S (semi_phase), the pair count and sums over the pairs (agg_phase), or every row of R's
 // multiplicity in S (mult_phase).
 // OUT_GROUP: one row per distinct join value of R alone (group_phase; partition_phase in its one-sided mode).
-enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3, OUT_GROUP = 4 };
+// OUT_GJOIN: one row per join value of R join S, with the counts and sums of both sides (gjoin_phase).
+enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3, OUT_GROUP = 4, OUT_GJOIN = 5 };
 
 // Semi / anti join phase on the partitions partition_phase left: k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
 // Reads the skip word behind its kernel and answers with the retry codes of join_phase_on.
@@ -1638,6 +1647,81 @@ int group_phase(rhj_ctx *ctx, u64 *out_groups)
     return RHJ_OK;
 }
 
+// Group-by join phase on the partitions partition_phase left: k_make_semi_tasks over the boundary arrays of R and S with
+// split = 2^32 - 1 -- a partition is never cut -- and anti = 1 under RHJ_GJ_LEFT (a task wherever R_k is non-empty), 0 under
+// RHJ_GJ_INNER (R_k and S_k non-empty), then k_gjoin_bkt over the columns and outputs the entry point left in the context.  After a
+// one-sided partition_phase (LEFT with an empty S) S's boundary array is a zeroed one, as in group_phase.  EVERY attempt zeroes the
+// group counter and the guard flags before its kernel: a repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes
+// as semi_phase.
+int gjoin_phase(rhj_ctx *ctx, u64 *out_groups)
+{
+    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
+    const bool narrow = ctx->cur_narrow != 0, one = ctx->one_sided;
+    const u32 split = 0xffffffffu;                     // a partition is never cut: its keys would be emitted twice
+    const u64 max_tasks64 = nparts + nR / split + 1;
+    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
+    const u32 max_tasks = (u32)max_tasks64;
+    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
+    RHJCHK(ensure(ctx, ctx->counters, 64));
+    RHJCHK(ensure(ctx, ctx->agg_out, 64));
+    if (one) RHJCHK(ensure(ctx, ctx->ps_S, (size_t)(nparts + 1) * 8));
+    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
+    {
+        Span s(ctx, RHJ_K_AUX);
+        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
+        if (one) HIPCHK(ctx, hipMemsetAsync(ctx->ps_S.p, 0, (size_t)(nparts + 1) * 8, ctx->stream));   // every partition of S: empty, at 0
+    }
+    ctx->counters_clean = false;
+    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
+        Span s(ctx, RHJ_K_AUX);
+        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+        if (!one) launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+    }
+    ctx->last_join_kind = JK_GJOIN;
+    ctx->sniff_ready = false;
+    const u64 *psS = one ? (const u64 *)ctx->ps_S.p : ctx->cur_psS;
+    {
+        Span s(ctx, RHJ_K_TASKS);
+        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, psS, nparts, split, ctx->gjoin_left ? 1 : 0, (JoinTask *)ctx->tasks.p,
+                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
+    }
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        launch_group_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
+                          ctx->cur_radix_bits, ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, ctx->gjoin_left, ctx->agg_cols,
+                          ctx->agg_ncols, ctx->agg_col_rows, ctx->gjoin_colsS, ctx->gjoin_ncolsS, ctx->gjoin_colS_rows, ctx->group_keys,
+                          ctx->group_counts, ctx->gjoin_cntS, ctx->group_sums, ctx->gjoin_sumsS, ctx->group_cap, d_agg,
+                          (u32 *)(d_agg + AGG_MAX_COLS + 1), d_count + 7,
+                          narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
+                          narrow && ctx->cur_S ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
+                          narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+    }
+    RHJCHK(check_launch(ctx, "group-by join phase"));
+    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, an |S_k| >= 2^32, -, most table builds of a task (if > 1)
+    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // groups, -, -, -, -, guard flags
+    u32 wide_rowid = 0;
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
+    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
+    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
+    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
+    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
+    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
+    ctx->last_group_rounds = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
+    if (host[2] >> 32)                                           // (such a partition was cut in two: its groups are not the result)
+        return fail(ctx, RHJ_E_INVALID, "a partition of R has " + std::to_string(host[2]) + " tuples (>= 2^32): use more radix bits");
+    if (host[5])
+        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    const u32 bad = (u32)agg[AGG_MAX_COLS + 1];
+    if (bad & GJOIN_BAD_ROW_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= colR_rows: the weight columns of R have no such row");
+    if (bad & GJOIN_BAD_ROW_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= colS_rows: the weight columns of S have no such row");
+    *out_groups = agg[0];
+    return RHJ_OK;
+}
+
 // bookkeeping of the narrow-format back-off (rhj.h "partition.narrow"), shared by the plain and the pipelined host path
 void narrow_note_fallback(rhj_ctx *ctx)                  // a join met a rowID >= 2^32 in the narrow format
 {
@@ -1765,7 +1849,7 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
 
 // partition + join.  A run in the narrow format whose histogram kernel met a rowID >= 2^32 costs two histogram launches
 // (every later kernel of the run returns at once) and is repeated in the 16-byte format; the fall-back is per join.
-// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase / group_phase (which always take the
+// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase / group_phase / gjoin_phase (which always take the
 // unfused path: the one-pass form has the pair join built into its launches).
 int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan, void *d_out,
                        u64 cap, u64 *out_count, std::function<int()> *before_S = nullptr, JoinOutput what = OUT_PAIRS)
@@ -1775,6 +1859,7 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
     auto after_partition = [&]() {
         return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : what == OUT_SUMS ? agg_phase(ctx, out_count) :
                what == OUT_MULT ? mult_phase(ctx, out_count) : what == OUT_GROUP ? group_phase(ctx, out_count) :
+               what == OUT_GJOIN ? gjoin_phase(ctx, out_count) :
                semi_phase(ctx, what, d_out, cap, out_count);
     };
     int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S);
@@ -2384,6 +2469,103 @@ int rhj_group_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
     const int rc = group_common(ctx, nullptr, nR, d_cols, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity,
                                 out_groups);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// Group-by join: the two-sided partition phase and the repeat ladder of rhj_join_mult_dev / rhj_join_mult_cols_dev,
+// then gjoin_phase.  d_R / d_S null: the relations are ctx->cols_in.  An empty S under RHJ_GJ_LEFT: R alone, one-sided and planned
+// as the group-by plans it, over a zeroed boundary array of S.
+static_assert(RHJ_GROUP_JOIN_MAX_COLS == AGG_MAX_COLS, "rhj.h and rhj_internal.h disagree");
+static int group_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS,
+                             const uint64_t *const *d_colsR, uint32_t ncolsR, uint64_t colR_rows,
+                             const uint64_t *const *d_colsS, uint32_t ncolsS, uint64_t colS_rows, int mode, const rhj_opts *opts,
+                             uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+                             uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS, uint64_t out_capacity, uint64_t *out_groups)
+{
+    if (mode != RHJ_GJ_INNER && mode != RHJ_GJ_LEFT) return fail(ctx, RHJ_E_INVALID, "mode is neither RHJ_GJ_INNER nor RHJ_GJ_LEFT");
+    if (ncolsR > RHJ_GROUP_JOIN_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncolsR is above RHJ_GROUP_JOIN_MAX_COLS");
+    if (ncolsS > RHJ_GROUP_JOIN_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncolsS is above RHJ_GROUP_JOIN_MAX_COLS");
+    if (!d_out_keys && out_capacity) return fail(ctx, RHJ_E_INVALID, "d_out_keys is null with out_capacity > 0");
+    const u32 nsumR = d_out_keys ? ncolsR : 0, nsumS = d_out_keys ? ncolsS : 0;   // count only: no sum sweep, no column is read
+    if (nsumR && (!d_colsR || !d_out_sumsR)) return fail(ctx, RHJ_E_INVALID, "null weight column array of R or d_out_sumsR");
+    if (nsumS && (!d_colsS || !d_out_sumsS)) return fail(ctx, RHJ_E_INVALID, "null weight column array of S or d_out_sumsS");
+    for (u32 j = 0; j < nsumR; j++)
+        if (!d_colsR[j] || !d_out_sumsR[j]) return fail(ctx, RHJ_E_INVALID, "null weight column or sum column of R");
+    for (u32 j = 0; j < nsumS; j++)
+        if (!d_colsS[j] || !d_out_sumsS[j]) return fail(ctx, RHJ_E_INVALID, "null weight column or sum column of S");
+    if (nR == 0 || (nS == 0 && mode == RHJ_GJ_INNER)) return join_nothing(ctx);
+    const bool one = nS == 0;                          // LEFT over an empty S: the group-by of R with zero S fields
+    rhj_opts plan;
+    if (resolve_plan(nR, one ? nR : nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
+        ctx->agg_cols[j] = j < nsumR ? (const u64 *)d_colsR[j] : nullptr;
+        ctx->group_sums[j] = j < nsumR ? (u64 *)d_out_sumsR[j] : nullptr;
+        ctx->gjoin_colsS[j] = j < nsumS ? (const u64 *)d_colsS[j] : nullptr;
+        ctx->gjoin_sumsS[j] = j < nsumS ? (u64 *)d_out_sumsS[j] : nullptr;
+    }
+    ctx->agg_ncols = nsumR;
+    ctx->agg_col_rows = nsumR ? colR_rows : ~0ull;
+    ctx->gjoin_ncolsS = nsumS;
+    ctx->gjoin_colS_rows = nsumS ? colS_rows : ~0ull;
+    ctx->group_keys = (u64 *)d_out_keys;
+    ctx->group_counts = d_out_keys ? (u64 *)d_out_cntR : nullptr;
+    ctx->gjoin_cntS = d_out_keys ? (u64 *)d_out_cntS : nullptr;
+    ctx->group_cap = d_out_keys ? out_capacity : 0;
+    ctx->gjoin_left = mode == RHJ_GJ_LEFT;
+    ctx->one_sided = one;
+    const int rc = partition_and_join(ctx, d_R, nR, one ? nullptr : d_S, one ? nR : nS, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GJOIN);
+    ctx->one_sided = false;
+    ctx->gjoin_left = false;
+    ctx->agg_ncols = ctx->gjoin_ncolsS = 0;
+    ctx->group_keys = ctx->group_counts = ctx->gjoin_cntS = nullptr;
+    ctx->group_cap = 0;
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
+        ctx->agg_cols[j] = ctx->gjoin_colsS[j] = nullptr;
+        ctx->group_sums[j] = ctx->gjoin_sumsS[j] = nullptr;
+    }
+    RHJCHK(rc);
+    if (d_out_keys && *out_groups > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffers too small");
+    return RHJ_OK;
+}
+
+int rhj_group_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                       const uint64_t *const *d_colsR, uint32_t ncolsR, uint64_t colR_rows,
+                       const uint64_t *const *d_colsS, uint32_t ncolsS, uint64_t colS_rows,
+                       int mode, const rhj_opts *opts,
+                       uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+                       uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS,
+                       uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return group_join_common(ctx, d_R, nR, d_S, nS, d_colsR, ncolsR, colR_rows, d_colsS, ncolsS, colS_rows, mode, opts, d_out_keys,
+                             d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
+}
+
+int rhj_group_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                            const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+                            const uint64_t *const *d_colsR, uint32_t ncolsR, uint64_t colR_rows,
+                            const uint64_t *const *d_colsS, uint32_t ncolsS, uint64_t colS_rows,
+                            int mode, const rhj_opts *opts,
+                            uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+                            uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS,
+                            uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with no column)
+    if (nS) { ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS; }
+    else ctx->cols_in[1] = ColsIn();
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, ncolsR, colR_rows, d_colsS, ncolsS, colS_rows, mode, opts,
+                                     d_out_keys, d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

@@ -312,6 +312,27 @@ static_assert(group_lds_bytes() <= 160 * 1024 && mult_lds_bytes(true) % 8 == 0 &
 void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits, bool mixed,
                   const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_out_keys, u64 *d_out_counts, u64 *const *d_out_sums,
                   u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip);
+// ---- the group-by join kernel (k_gjoin_bkt): k_group_bkt's table and class walk over R, looked up by S ---------------
+// group_lds_bytes() plus room for the pointers of S's side (4 x AGG_MAX_COLS column and output pointers in all) and for nine more
+// kernel arguments, which would otherwise spill SGPRs.  The slot word holds
+// cntR | cntS << 32 during the count sweeps (a second 32 KiB count array would end 16 bytes above 160 KiB).
+constexpr int JK_GJOIN = JK_GROUP + 1;            // "last.join_kernel" of a group-by join (16)
+constexpr u32 GJOIN_BAD_ROW_R = 1, GJOIN_BAD_ROW_S = 2;   // bits of *d_bad
+constexpr u32 GJOIN_PAR_WORDS = 9;                // further kernel arguments kept in LDS across the class walk (k_gjoin_bkt)
+constexpr size_t gjoin_lds_bytes() { return group_lds_bytes() + (size_t)(2 * AGG_MAX_COLS + GJOIN_PAR_WORDS) * 8; }
+static_assert(gjoin_lds_bytes() <= 160 * 1024 && gjoin_lds_bytes() % 8 == 0, "k_gjoin_bkt's geometry");
+// The task list is launch_make_semi_tasks over the boundary arrays of R and S with split = 2^32 - 1 and anti = left_mode: one task
+// per partition k with R_k non-empty (left_mode) or R_k and S_k non-empty (inner), both whole partitions; a task's range of S may be
+// empty and is then never read (d_S may be null when every one is).  mixed as launch_group.  d_colsR / d_out_sumsR: HOST arrays of
+// ncolsR (<= AGG_MAX_COLS) device columns, d_colsS / d_out_sumsS of ncolsS; both 0: no sum sweep.  d_out_keys / d_out_cntR (may be
+// null) / d_out_cntS (may be null) / sums: capacity words each; capacity == 0: count only.  d_ngroups: one word (zeroed by the
+// caller); d_bad: OR-ed with GJOIN_BAD_ROW_R / _S when a rowID >= colR_rows / colS_rows was met (never dereferenced); d_max_rounds as
+// launch_group; d_RK / d_SK: the rowID arrays of narrow partitions, or d_RK null: 16-byte tuples; d_skip: as launch_join.
+void launch_group_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                       int radix_bits, bool mixed, bool left_mode, const u64 *const *d_colsR, u32 ncolsR, u64 colR_rows,
+                       const u64 *const *d_colsS, u32 ncolsS, u64 colS_rows, u64 *d_out_keys, u64 *d_out_cntR, u64 *d_out_cntS,
+                       u64 *const *d_out_sumsR, u64 *const *d_out_sumsS, u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds,
+                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
 // in_narrow: d_in is a payload array (u64).  key_base / d_wide (16-byte input): d_wide (may be null) is OR-ed with 1 when some
 // rowID - key_base does not fit 32 bits.  d_unit_rng (may be null): explicit pass-1 units (launch_seg_units).
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,

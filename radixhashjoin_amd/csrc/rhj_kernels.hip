@@ -3131,6 +3131,243 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
 }
 
 // ------------------------------------------------------------------------------------------------
+// JOIN with GROUP BY on the key, one task: one output row per join value of a partition of R (left_mode) or per value
+// that the partitions of R and S share (inner) -- the value, how many tuples of R and of S carry it, and the sums of up to four
+// columns per side over those tuples.  A task is the WHOLE partition k of R and the WHOLE partition k of S.
+//   * k_group_bkt's table and class walk, unchanged: the keys are R's, a class fails when it holds more than AGG_FILL distinct keys
+//     of R.  S only looks up: a miss ends at an empty slot (a built table has at least SLOTS - AGG_FILL - AGG_BUILD_TILE of them).
+//   * PACKED COUNTS.  A second count array does not fit beside the table (131,088 + 32,768 B is 16 B above 160 KiB), so during the
+//     count sweeps the 64-bit word of a slot holds both: cntR in its low half (+1 per tuple of R), cntS in its high half (+1 << 32
+//     per tuple of S).  Both partitions have < 2^32 tuples (the task maker refuses larger ones): neither half can carry.  The
+//     word of the all-ones key is packed the same way.
+//   * per class that survives its build: count sweep over S (skipped when S's partition is empty); the EMITTING mask of a thread's
+//     8 slots -- occupied (left_mode), or occupied with a non-zero high half (inner) --, ranks by popcount + workgroup scan, the
+//     all-ones key last; ONE global atomic add claims the class's groups; keys, cntR, cntS stored where base + rank < capacity.  A
+//     class that emits nothing goes no further.  SUMS: per column of R the words are zeroed, R's class tuples looked up again and
+//     colsR[j][rowR] added behind the rowR < colR_rows guard, emitted at the saved mask and ranks; then the same over S's tuples for
+//     every column of S (a tuple of S whose key is not in the table adds nothing).
+//   * plain vector loads and stores, LDS atomics, one global atomic per class; integer addition mod 2^64: bit-exact from run to run.
+// ------------------------------------------------------------------------------------------------
+template <bool NARROW, bool SUMS>
+__global__ void __launch_bounds__(AGG_THREADS, 4)
+k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks, int radix_bits,
+            int mixed, int left_mode, AggCols colsR, u32 ncolsR, u64 colR_rows, AggCols colsS, u32 ncolsS, u64 colS_rows,
+            u64 *__restrict__ out_keys, u64 *__restrict__ out_cntR, u64 *__restrict__ out_cntS, GroupSums out_sumsR, GroupSums out_sumsS,
+            u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip)
+{
+    if (skip != nullptr && *skip != 0) return;
+    if (blockIdx.x >= *ntasks) return;
+    constexpr int THREADS = AGG_THREADS;
+    constexpr u32 SLOTS = 1u << AGG_SLOT_BITS, SPT = SLOTS / THREADS;         // slots a thread owns at emission
+    static_assert(AGG_BPT == 1 && SPT == 8, "one tuple per thread per build tile, eight slots per thread at emission");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64 *tab = reinterpret_cast<u64 *>(smem);                                // SLOTS keys (of R)
+    u64 *acc = tab + SLOTS;                                                  // SLOTS words: cntR | cntS << 32, then one sum at a time
+    u64 *ones = acc + SLOTS;                                                 // ... of the all-ones key
+    u32 *nkeys = reinterpret_cast<u32 *>(ones + 1);                          // distinct keys in the table
+    u32 *has_ones = nkeys + 1;                                               // the class of R holds the all-ones key
+    u64 *base_s = reinterpret_cast<u64 *>(smem + mult_lds_bytes(true));      // the class's first group
+    u32 *wsum = reinterpret_cast<u32 *>(base_s + 1);                         // THREADS / 64 words of block_excl_scan
+    u64 *colp = reinterpret_cast<u64 *>(wsum + THREADS / 64);                // SUMS: colsR, sumsR, colsS, sumsS -- AGG_MAX_COLS words each
+    u64 *par = colp + 4 * AGG_MAX_COLS;                                      // GJOIN_PAR_WORDS more kernel arguments that the walk does not
+                                                                             // hold in SGPRs: colR_rows, colS_rows, out_keys, out_cntR, out_cntS, capacity, ngroups, bad, max_rounds
+
+    const JoinTask task = tasks[blockIdx.x];
+    const u32 np = task.plen, ns = task.blen;
+    if (np == 0) return;
+    typedef typename RelView<NARROW>::Both Both;
+    const RelView<NARROW> Rv = R.at(task.pbeg), Sv = S.at(task.bbeg);
+    const int tid = threadIdx.x, lane = tid & 63;
+
+    if (tid == 0) {
+        par[0] = colR_rows; par[1] = colS_rows; par[2] = (u64)out_keys; par[3] = (u64)out_cntR; par[4] = (u64)out_cntS; par[5] = capacity;
+        par[6] = (u64)ngroups; par[7] = (u64)bad; par[8] = (u64)max_rounds;
+    }                                                                        // (read behind the barriers of the first build)
+    if constexpr (SUMS)
+        if (tid == 0) {
+#pragma unroll
+            for (int j = 0; j < AGG_MAX_COLS; j++) {
+                colp[j] = (u64)colsR.c[j]; colp[AGG_MAX_COLS + j] = (u64)out_sumsR.c[j];
+                colp[2 * AGG_MAX_COLS + j] = (u64)colsS.c[j]; colp[3 * AGG_MAX_COLS + j] = (u64)out_sumsS.c[j];
+            }
+        }
+    u32 d = 0, rounds = 0;                                                   // the class (d, p); table builds so far
+    u64 p = 0;
+    u32 wild = 0;                                                            // GJOIN_BAD_ROW_* this thread met
+    auto in_class = [&](u64 key) -> bool {
+        if (d == 0) return true;
+        const u64 mask = d >= 64 ? ~0ull : (1ull << d) - 1;
+        return (mix64(key ^ GROUP_CLASS_SALT) & mask) == p;
+    };
+    auto insert = [&](u64 key) -> bool {                                     // R: true: the key was not there; counts the tuple either way
+        if (key == SEMI_EMPTY) { *has_ones = 1u; atomicAdd((unsigned long long *)ones, 1ull); return false; }
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            bool fresh = false;
+            if (cur != key) {
+                if (cur != SEMI_EMPTY) continue;
+                const u64 old = atomicCAS((unsigned long long *)&tab[s], (unsigned long long)SEMI_EMPTY, (unsigned long long)key);
+                if (old == SEMI_EMPTY) fresh = true;
+                else if (old != key) continue;
+            }
+            atomicAdd((unsigned long long *)&acc[s], 1ull);
+            return fresh;
+        }
+    };
+    auto add_on = [&](u64 key, u64 v) {                                      // lookup only: a key that is not in the table adds nothing
+        if (key == SEMI_EMPTY) { atomicAdd((unsigned long long *)ones, (unsigned long long)v); return; }   // (read only where R has the key)
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            if (cur == key) { atomicAdd((unsigned long long *)&acc[s], (unsigned long long)v); return; }
+            if (cur == SEMI_EMPTY) return;
+        }
+    };
+    auto load_key = [&](const RelView<NARROW> &V, u32 n, u32 at) -> u64 {    // tuple at + tid of a partition of n; 0 beyond its end
+        return V.buf(at, n - at < AGG_BUILD_TILE ? n - at : AGG_BUILD_TILE).payload(0u, (u32)tid);
+    };
+
+    for (;;) {
+        // ---- build and count over R: the class's tuples, tile by tile (k_group_bkt's sweep) ---------------------------------
+        for (u32 i = tid; i < SLOTS; i += THREADS) { tab[i] = SEMI_EMPTY; acc[i] = 0; }
+        if (tid == 0) { *ones = 0; *nkeys = 0; *has_ones = 0; }
+        __syncthreads();
+        rounds++;
+        u32 filled = 0;
+        {
+            u64 key = load_key(Rv, np, 0), key_next = 0;
+            for (u32 done = 0; done < np;) {
+                const u32 nt = np - done < AGG_BUILD_TILE ? np - done : AGG_BUILD_TILE;
+                const bool more = done + nt < np;
+                if (more) key_next = load_key(Rv, np, done + nt);            // travels behind the two barriers
+                {
+                    const bool fresh = (u32)tid < nt && in_class(key) && insert(key);
+                    const unsigned long long m = __ballot(fresh);
+                    if (lane == 0 && m) atomicAdd(nkeys, (u32)__popcll(m));
+                }
+                __syncthreads();
+                filled = (u32)__builtin_amdgcn_readfirstlane((int)*nkeys);
+                __syncthreads();                                             // (everybody has read the count before the next tile adds to it)
+                done += nt;
+                key = key_next;
+                if (filled > AGG_FILL) break;
+            }
+        }
+        if (filled > AGG_FILL) { d++; continue; }                            // the class fails: its first child (bit d of the hash = 0)
+
+        // ---- count over S: the class's tuples look their key up and add 1 to the high half ---------------------------------
+        if (ns != 0) {
+            u64 key = load_key(Sv, ns, 0), key_next = 0;
+            for (u32 tb = 0; tb < ns; tb += AGG_BUILD_TILE) {
+                const u32 rest = ns - tb;                                    // tuples from this tile on
+                if (rest > AGG_BUILD_TILE) key_next = load_key(Sv, ns, tb + AGG_BUILD_TILE);
+                if ((u32)tid < rest && in_class(key)) add_on(key, 1ull << 32);
+                key = key_next;
+            }
+            __syncthreads();
+        }
+
+        // ---- emit the class's keys and counts ------------------------------------------------------------------------------
+        u32 em = 0;                                                          // the emitting slots among this thread's SPT
+#pragma unroll
+        for (u32 j = 0; j < SPT; j++) {
+            const u32 s = (u32)tid * SPT + j;
+            const bool on = tab[s] != SEMI_EMPTY && (left_mode || (acc[s] >> 32) != 0);
+            em |= (on ? 1u : 0u) << j;
+        }
+        const u32 hoe = (u32)__builtin_amdgcn_readfirstlane((int)(*has_ones != 0 && (left_mode || (*ones >> 32) != 0) ? 1u : 0u));
+        u32 tot;
+        int tq = tid;                                                        // (opaque, as in k_group_bkt)
+        asm volatile("" : "+v"(tq));
+        const u32 ex = block_excl_scan<THREADS>((u32)__popc(em), wsum, tot, tq);
+        tot = (u32)__builtin_amdgcn_readfirstlane((int)tot);
+        if (tot + hoe != 0) {                                                // (uniform) a class with nothing to emit goes no further
+            if (tid == 0) *base_s = atomicAdd(reinterpret_cast<unsigned long long *>(par[6]), (unsigned long long)(tot + hoe));
+            __syncthreads();
+            const u64 g0 = *base_s + ex;                                     // this thread's first group
+            {
+                const u64 capacity = par[5];
+                u64 *__restrict__ out_keys = reinterpret_cast<u64 *>(par[2]);
+                u64 *__restrict__ out_cntR = reinterpret_cast<u64 *>(par[3]), *__restrict__ out_cntS = reinterpret_cast<u64 *>(par[4]);
+                u64 g = g0;
+#pragma unroll 1
+                for (u32 j = 0; j < SPT; j++)
+                    if (em >> j & 1u) {
+                        if (g < capacity) {
+                            const u64 k = tab[(u32)tid * SPT + j], c = acc[(u32)tid * SPT + j];
+                            out_keys[g] = mixed ? unmix64(k) : k;
+                            if (out_cntR != nullptr) out_cntR[g] = c & 0xffffffffull;
+                            if (out_cntS != nullptr) out_cntS[g] = c >> 32;
+                        }
+                        g++;
+                    }
+                if (tid == 0 && hoe) {
+                    const u64 g1 = *base_s + tot, c = *ones;
+                    if (g1 < capacity) {
+                        out_keys[g1] = mixed ? unmix64(SEMI_EMPTY) : SEMI_EMPTY;
+                        if (out_cntR != nullptr) out_cntR[g1] = c & 0xffffffffull;
+                        if (out_cntS != nullptr) out_cntS[g1] = c >> 32;
+                    }
+                }
+            }
+
+            // ---- the sums, one column at a time over the table as it stands: R's columns over R's tuples, then S's over S's --
+            if constexpr (SUMS) {
+                const u32 nc = ncolsR + ncolsS;
+                for (u32 c = 0; c < nc; c++) {
+                    const bool on_s = c >= ncolsR;                           // (uniform) R's columns over R's tuples, then S's over S's
+                    const RelView<NARROW> V = on_s ? Sv : Rv;
+                    const u32 n = on_s ? ns : np, ci = on_s ? 2u * AGG_MAX_COLS + (c - ncolsR) : c;
+                    const u64 *__restrict__ col = reinterpret_cast<const u64 *>(colp[ci]);
+                    u64 *__restrict__ dst = reinterpret_cast<u64 *>(colp[ci + AGG_MAX_COLS]);
+                    const u64 rows = par[on_s ? 1 : 0], capacity = par[5];
+                    __syncthreads();                                         // the words have been emitted
+                    for (u32 i = tid; i < SLOTS; i += THREADS) acc[i] = 0;
+                    if (tid == 0) *ones = 0;
+                    __syncthreads();
+                    if (n != 0) {
+                        Both t = V.buf(0u, n < (u32)THREADS ? n : (u32)THREADS).both(0u, (u32)tid), t_next = t;
+                        for (u32 tb = 0; tb < n; tb += THREADS) {
+                            const u32 rest = n - tb;                         // tuples from this tile on
+                            if (rest > (u32)THREADS)                         // the next tile travels behind this one's gather
+                                t_next = V.buf(tb + (u32)THREADS, rest - THREADS < (u32)THREADS ? rest - THREADS : (u32)THREADS).both(0u, (u32)tid);
+                            if ((u32)tid < rest) {
+                                if ((u64)t.key >= rows) wild |= on_s ? GJOIN_BAD_ROW_S : GJOIN_BAD_ROW_R;
+                                else if (in_class(t.payload)) {
+                                    const u64 v = col[(u64)t.key];
+                                    if (v != 0) add_on(t.payload, v);
+                                }
+                            }
+                            t = t_next;
+                        }
+                    }
+                    __syncthreads();
+                    u64 g = g0;
+#pragma unroll 1
+                    for (u32 j = 0; j < SPT; j++)
+                        if (em >> j & 1u) {
+                            if (g < capacity) dst[g] = acc[(u32)tid * SPT + j];
+                            g++;
+                        }
+                    if (tid == 0 && hoe) {
+                        const u64 g1 = *base_s + tot;
+                        if (g1 < capacity) dst[g1] = *ones;
+                    }
+                }
+            }
+        }
+
+        // ---- the next class: prefix increment, bit 0 the most significant digit ----------------------------------------------
+        while (d > 0 && (p >> (d - 1) & 1ull)) { p &= ~(1ull << (d - 1)); d--; }
+        if (d == 0) break;
+        p |= 1ull << (d - 1);
+        __syncthreads();                                                     // the table is cleared for the next class
+    }
+
+    if (wild) atomicOr(reinterpret_cast<u32 *>(par[7]), wild);                // (a call that meets one is refused: never the fast path)
+    if (tid == 0 && rounds > 1) atomicMax(reinterpret_cast<unsigned long long *>(par[8]), (unsigned long long)rounds);
+}
+
+// ------------------------------------------------------------------------------------------------
 // K4 (compact-table form): bucket join for partitions whose build side does not fit a 16 B/tuple LDS table but
 // whose radix plan has removed >= 16 payload bits (BASELINE config 3: 8+8 bits at 10^9 tuples, 15.3 K-tuple
 // partitions).  Same job as k_join_bkt (JoinJob::run + Result::join_buckets, Result.cpp:43-76, + add_result /
@@ -3858,6 +4095,10 @@ static void allow_big_lds()
     SET_LDS((k_group_bkt<false, false>), group_lds_bytes());
     SET_LDS((k_group_bkt<true, true>), group_lds_bytes());
     SET_LDS((k_group_bkt<false, true>), group_lds_bytes());
+    SET_LDS((k_gjoin_bkt<true, false>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<false, false>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<true, true>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<false, true>), gjoin_lds_bytes());
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<IN_AOS>, wn_lds_bytes(WN_MAX_BITS));
@@ -4512,6 +4753,37 @@ void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, cons
         const RelView<false> Rv{(const Tup *)d_R};
         if (ncols != 0) go(k_group_bkt<false, true>, Rv);
         else go(k_group_bkt<false, false>, Rv);
+    }
+}
+
+void launch_group_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                       int radix_bits, bool mixed, bool left_mode, const u64 *const *d_colsR, u32 ncolsR, u64 colR_rows,
+                       const u64 *const *d_colsS, u32 ncolsS, u64 colS_rows, u64 *d_out_keys, u64 *d_out_cntR, u64 *d_out_cntS,
+                       u64 *const *d_out_sumsR, u64 *const *d_out_sumsS, u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds,
+                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip)
+{
+    if (grid == 0) return;
+    allow_big_lds();
+    AggCols colsR, colsS;
+    GroupSums sumsR, sumsS;
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
+        colsR.c[j] = j < ncolsR ? d_colsR[j] : nullptr; sumsR.c[j] = j < ncolsR ? d_out_sumsR[j] : nullptr;
+        colsS.c[j] = j < ncolsS ? d_colsS[j] : nullptr; sumsS.c[j] = j < ncolsS ? d_out_sumsS[j] : nullptr;
+    }
+    auto go = [&](auto kernel, auto Rv, auto Sv) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(AGG_THREADS), gjoin_lds_bytes(), st, Rv, Sv, d_tasks, d_ntasks, radix_bits,
+                           mixed ? 1 : 0, left_mode ? 1 : 0, colsR, ncolsR, colR_rows, colsS, ncolsS, colS_rows, d_out_keys, d_out_cntR,
+                           d_out_cntS, sumsR, sumsS, capacity, d_ngroups, d_bad, d_max_rounds, d_skip);
+    };
+    const bool sums = ncolsR + ncolsS != 0;
+    if (d_RK != nullptr) {                                                   // narrow partitions: d_R / d_S are payload arrays
+        const RelView<true> Rv{(const u64 *)d_R, d_RK}, Sv{(const u64 *)d_S, d_SK};
+        if (sums) go(k_gjoin_bkt<true, true>, Rv, Sv);
+        else go(k_gjoin_bkt<true, false>, Rv, Sv);
+    } else {
+        const RelView<false> Rv{(const Tup *)d_R}, Sv{(const Tup *)d_S};
+        if (sums) go(k_gjoin_bkt<false, true>, Rv, Sv);
+        else go(k_gjoin_bkt<false, false>, Rv, Sv);
     }
 }
 

@@ -214,6 +214,12 @@ void launch_group(hipStream_t st, const void *, const JoinTask *, const u32 *, u
 {
     fake_enqueue(st, [=] { *d_ngroups += FAKE_PAIRS; });
 }
+void launch_group_join(hipStream_t st, const void *, const void *, const JoinTask *, const u32 *, u32, int, bool, bool, const u64 *const *, u32,
+                       u64, const u64 *const *, u32, u64, u64 *, u64 *, u64 *, u64 *const *, u64 *const *, u64, u64 *d_ngroups, u32 *, u64 *,
+                       const u32 *, const u32 *, const u32 *)
+{
+    fake_enqueue(st, [=] { *d_ngroups += FAKE_PAIRS; });
+}
 int build_tie_shift() { return 4; }
 size_t fuse_ctl_bytes() { return 12352; }
 u32 *fuse_join_ticket(void *d_ctl) { return (u32 *)((unsigned char *)d_ctl + 12288) + 1; }

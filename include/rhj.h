@@ -138,7 +138,7 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * rhj_semi_join_cols_dev, whatever the plan; 13 the aggregating join kernel: rhj_join_sum_dev / rhj_join_sum_cols_dev, whatever
  * the plan; 14 the multiplicity join kernel: rhj_join_mult_dev / rhj_join_mult_cols_dev, whatever the plan; 15 the group-by kernel:
  * rhj_group_sum_dev / rhj_group_sum_cols_dev, whatever the plan; 16 the group-by join kernel: rhj_group_join_dev /
- * rhj_group_join_cols_dev, whatever the plan),
+ * rhj_group_join_cols_dev, whatever the plan; the rhj_group_agg_* and rhj_group_join_agg_* entries are 15 and 16 too),
  * "last.semi_tables" (the largest number of LDS tables any one task of the last
  * semi / anti join, aggregating join or multiplicity join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
  * "last.group_rounds" (the largest number of LDS table builds any one task of the last group-by or group-by join made: 1 when every
@@ -397,6 +397,73 @@ int rhj_group_join_dev(rhj_ctx *ctx,
         int mode, const rhj_opts *opts,
         uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
         uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS,
+        uint64_t out_capacity, uint64_t *out_groups);
+
+/* ---- MIN and MAX beside SUM: the two group-by entries and the two group-by join entries with an aggregate PER COLUMN (SELECT key,
+ * MIN(x), MAX(x), SUM(y) FROM R GROUP BY key; first and last timestamp per key; scatter_reduce_(amin / amax) keyed by value).  The same
+ * kernels' families, tables, class walk and host path: a minimum or maximum is the column sweep of a sum with another
+ * LDS atomic and another starting word. */
+#define RHJ_AGG_SUM     0   /* sum mod 2^64 (what rhj_group_sum_* / rhj_group_join_* compute) */
+#define RHJ_AGG_MIN_U64 1   /* minimum / maximum of the column words as unsigned 64-bit ... */
+#define RHJ_AGG_MAX_U64 2
+#define RHJ_AGG_MIN_I64 3   /* ... and as two's-complement signed 64-bit */
+#define RHJ_AGG_MAX_I64 4
+/* rhj_group_sum_cols_dev with ops: a HOST array of ncols words, column j is aggregated with ops[j] (an RHJ_AGG_*), and
+ * d_out_aggs[j][g] is that aggregate of d_cols[j][rowR] over the tuples of group g.  ops == NULL: every column is RHJ_AGG_SUM.  The
+ * same column pointer may appear twice with different ops (MIN and MAX of one column in one call).  A group has at least one tuple,
+ * so its minimum / maximum is always a column value.  A call whose ops are all RHJ_AGG_SUM returns what rhj_group_sum_cols_dev
+ * returns, bit for bit.
+ * Everything else is the contract of rhj_group_sum_cols_dev, word for word: the order of groups is unspecified, the set and every
+ * value exact and bit-identical from run to run (minimum and maximum do not depend on the order either); count only with a NULL
+ * d_out_keys and out_capacity 0 -- no sweep, no column read --; RHJ_E_OVERFLOW with the exact *out_groups, complete distinct groups
+ * in [0, capacity) and nothing at or past capacity written; the row guard (a rowR >= col_rows is never dereferenced, under any op);
+ * nR == 0; plans, repeats, probe_split ignored; "last.join_kernel" is 15, "last.group_rounds" as there.
+ * RHJ_E_INVALID beyond that contract's: an ops[j] above RHJ_AGG_MAX_I64 -- checked before any launch, also in a count-only call;
+ * rhj_last_error names the column.
+ * Costs: those of rhj_group_sum_cols_dev, whatever the ops -- one sweep of the partition per column and class, one workgroup per
+ * partition. */
+int rhj_group_agg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols, uint64_t col_rows,
+                           const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                           uint64_t *const *d_out_aggs, uint64_t out_capacity, uint64_t *out_groups);
+/* ... on 16-byte tuples (value = .payload, rowR = .key) */
+int rhj_group_agg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
+                      const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols, uint64_t col_rows,
+                      const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                      uint64_t *const *d_out_aggs, uint64_t out_capacity, uint64_t *out_groups);
+/* rhj_group_join_cols_dev with opsR / opsS: HOST arrays of ncolsR / ncolsS words (NULL: every column of that side is RHJ_AGG_SUM).
+ * The RAW per-side value is returned, as for sums: d_out_aggsR[j][g] is opsR[j] over the tuples of R with the group's value,
+ * d_out_aggsS[j][g] is opsS[j] over the tuples of S.  A minimum or maximum over the PAIRS of a group is the per-side one as it stands
+ * (MIN(r.a) over the pairs is the minimum over R's tuples: no product with the other side's count, unlike a sum).
+ * Identity rule: under RHJ_GJ_LEFT a group with cntS == 0 has no tuple of S to take a minimum or maximum of; its MIN / MAX columns of
+ * S hold the op's identity -- RHJ_AGG_MIN_U64: 0xFFFFFFFFFFFFFFFF, RHJ_AGG_MAX_U64: 0, RHJ_AGG_MIN_I64: INT64_MAX
+ * (0x7FFFFFFFFFFFFFFF), RHJ_AGG_MAX_I64: INT64_MIN (0x8000000000000000) -- and its RHJ_AGG_SUM columns of S stay 0.  cntS tells the
+ * caller which rows these are (cntS == 0: SQL's NULL).  Under RHJ_GJ_INNER both counts of every group are non-zero and every
+ * minimum / maximum is a column value.
+ * Everything else is the contract of rhj_group_join_cols_dev, word for word (modes, count only, RHJ_E_OVERFLOW, the row guard and
+ * its message that says which side, nR == 0 / nS == 0 -- RHJ_GJ_LEFT over an empty S: the group-by of R, S's columns at the identity
+ * of their op --, plans, repeats, probe_split ignored, "last.join_kernel" is 16, "last.group_rounds").  A call whose ops are all
+ * RHJ_AGG_SUM returns what rhj_group_join_cols_dev returns, bit for bit.
+ * RHJ_E_INVALID beyond that contract's: an opsR[j] or opsS[j] above RHJ_AGG_MAX_I64 -- checked before any launch, also in a
+ * count-only call; rhj_last_error names the side and the column.
+ * Costs: those of rhj_group_join_cols_dev, whatever the ops. */
+int rhj_group_join_agg_cols_dev(rhj_ctx *ctx,
+        const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+        const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+        const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+        const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows,
+        int mode, const rhj_opts *opts,
+        uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+        uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
+        uint64_t out_capacity, uint64_t *out_groups);
+/* ... on 16-byte tuples (value = .payload, rowID = .key) */
+int rhj_group_join_agg_dev(rhj_ctx *ctx,
+        const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+        const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+        const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows,
+        int mode, const rhj_opts *opts,
+        uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+        uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
         uint64_t out_capacity, uint64_t *out_groups);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------

@@ -14,12 +14,18 @@ returns the indices of the keys of R that occur (``anti=True``: do not occur) in
 without the pairs (``rhj_join_sum_cols_dev``); ``mult, total = Engine(0).join_multiplicity_columns(keys_R, keys_S, weights_S=None)``
 is, per key of R, how many keys of S equal it -- or the sum of their weights (``rhj_join_mult_cols_dev``);
 ``unique_keys, counts, sums = Engine(0).group_by_columns(keys, weights)`` is GROUP BY on one key tensor: its distinct values, their
-counts and the per-group sums of the weight tensors (``rhj_group_sum_cols_dev``);
+counts and the per-group sums of the weight tensors (``rhj_group_sum_cols_dev``) -- with ``ops=["min", "max", "sum"]`` the per-group
+minimum, maximum or sum per weight tensor (``rhj_group_agg_cols_dev``);
 ``keys, count, sums_R, sums_S = Engine(0).join_group_by_columns(keys_R, keys_S, weights_R, weights_S, how="inner")`` is the join
 with GROUP BY on the key: per join value COUNT(*) and the SUMs of both sides' weights over its pairs, without the pairs
-(``rhj_group_join_cols_dev``).
+(``rhj_group_join_cols_dev``); ``ops_R`` / ``ops_S`` make a column a minimum or maximum there too (``rhj_group_join_agg_cols_dev``).
 """
 from .binding import (  # noqa: F401
+    AGG_MAX_I64,
+    AGG_MAX_U64,
+    AGG_MIN_I64,
+    AGG_MIN_U64,
+    AGG_SUM,
     ANTI,
     PAIR,
     TUPLE,
@@ -40,5 +46,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64"]
 __version__ = "0.1.0"

@@ -88,6 +88,14 @@ SYMBOLS = {
                                           _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64)]),
     "rhj_group_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(_vp), C.c_uint32, _u64, C.c_int,
                                      _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64)]),
+    "rhj_group_agg_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64,
+                                         _P(_u64)]),
+    "rhj_group_agg_dev": (C.c_int, [_vp, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64, _P(_u64)]),
+    "rhj_group_join_agg_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(_vp),
+                                              _P(C.c_uint32), C.c_uint32, _u64, C.c_int, _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64,
+                                              _P(_u64)]),
+    "rhj_group_join_agg_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(_vp), _P(C.c_uint32),
+                                         C.c_uint32, _u64, C.c_int, _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -190,6 +198,22 @@ SUM_MAX_COLS = 4                                         # include/rhj.h RHJ_SUM
 GROUP_MAX_COLS = 4                                       # include/rhj.h RHJ_GROUP_MAX_COLS: weight columns of a group_sum_* call
 GROUP_JOIN_MAX_COLS = 4                                  # include/rhj.h RHJ_GROUP_JOIN_MAX_COLS: weight columns per side of a group_join_* call
 GJ_INNER, GJ_LEFT = 0, 1                                 # include/rhj.h RHJ_GJ_INNER / RHJ_GJ_LEFT: the mode of a group_join_* call
+# include/rhj.h RHJ_AGG_*: the aggregate of a column of a group_agg_* / group_join_agg_* call
+AGG_SUM, AGG_MIN_U64, AGG_MAX_U64, AGG_MIN_I64, AGG_MAX_I64 = 0, 1, 2, 3, 4
+# ... of an int64 tensor by name (group_by_columns / join_group_by_columns), and what a minimum / maximum over no tuple holds
+_AGG_BY_NAME = {"sum": AGG_SUM, "min": AGG_MIN_I64, "max": AGG_MAX_I64}
+_AGG_IDENTITY_I64 = {AGG_SUM: 0, AGG_MIN_I64: 2**63 - 1, AGG_MAX_I64: -2**63}
+
+
+def _agg_ops(ops, n, name):
+    """the RHJ_AGG_* of n int64 weight tensors from their names ("sum" | "min" | "max"); ValueError on a wrong length or name"""
+    ops = list(ops)
+    if len(ops) != n:
+        raise ValueError(f"{name}: {len(ops)} ops for {n} weight tensors")
+    for i, o in enumerate(ops):
+        if o not in _AGG_BY_NAME:
+            raise ValueError(f"{name}[{i}]: 'sum', 'min' or 'max', not {o!r}")
+    return [_AGG_BY_NAME[o] for o in ops]
 SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
@@ -486,6 +510,16 @@ class Engine:
         sums = list(d_out_sums)[:len(d_cols)]
         return (_vp * k)(*[_addr(c) for c in d_cols]), (_vp * k)(*[_addr(c) for c in sums + [None] * (len(d_cols) - len(sums))])
 
+    @staticmethod
+    def _ops_arg(ops, ncols):
+        """the host array of a side's ops, one per column (None: NULL, every column a sum)"""
+        if ops is None:
+            return None
+        ops = list(ops)
+        if len(ops) != ncols:
+            raise ValueError(f"{len(ops)} ops for {ncols} columns")
+        return (C.c_uint32 * max(ncols, 1))(*ops)
+
     def group_sum_cols_dev(self, d_valR, d_idR, nR, d_cols=(), col_rows=0, d_out_keys=None, d_out_counts=None, d_out_sums=(),
                            capacity=0, opts=None, allow_overflow=False):
         """rhj_group_sum_cols_dev: one output row per distinct join value of R (uint64 value column; uint64 rowIDs, or None: the
@@ -508,6 +542,30 @@ class Engine:
         cols, sums = self._group_args(d_cols, d_out_sums)
         rc = self.lib.rhj_group_sum_dev(self.ctx, _addr(d_R), nR, cols, len(d_cols), col_rows,
                                         C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_counts), sums,
+                                        capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_agg_cols_dev(self, d_valR, d_idR, nR, d_cols=(), ops=None, col_rows=0, d_out_keys=None, d_out_counts=None, d_out_aggs=(),
+                           capacity=0, opts=None, allow_overflow=False):
+        """rhj_group_agg_cols_dev: group_sum_cols_dev with an aggregate per column -- ops[j] one of AGG_SUM, AGG_MIN_U64, AGG_MAX_U64,
+        AGG_MIN_I64, AGG_MAX_I64 (None: every column a sum), d_out_aggs[j][g] that aggregate of d_cols[j][rowID] over the tuples of
+        group g.  The same column may be given twice with different ops.  Costs and everything else as group_sum_cols_dev."""
+        n = _u64()
+        cols, aggs = self._group_args(d_cols, d_out_aggs)
+        rc = self.lib.rhj_group_agg_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, cols, self._ops_arg(ops, len(d_cols)), len(d_cols),
+                                             col_rows, C.byref(opts) if opts is not None else None, _addr(d_out_keys),
+                                             _addr(d_out_counts), aggs, capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_agg_dev(self, d_R, nR, d_cols=(), ops=None, col_rows=0, d_out_keys=None, d_out_counts=None, d_out_aggs=(), capacity=0,
+                      opts=None, allow_overflow=False):
+        """rhj_group_agg_dev: group_agg_cols_dev on 16-byte tuples (value = .payload, rowID = .key)"""
+        n = _u64()
+        cols, aggs = self._group_args(d_cols, d_out_aggs)
+        rc = self.lib.rhj_group_agg_dev(self.ctx, _addr(d_R), nR, cols, self._ops_arg(ops, len(d_cols)), len(d_cols), col_rows,
+                                        C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_counts), aggs,
                                         capacity, C.byref(n))
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
@@ -541,6 +599,40 @@ class Engine:
         rc = self.lib.rhj_group_join_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, colsR, len(d_colsR), colR_rows, colsS, len(d_colsS),
                                          colS_rows, mode, C.byref(opts) if opts is not None else None, _addr(d_out_keys),
                                          _addr(d_out_cntR), _addr(d_out_cntS), sumsR, sumsS, capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_join_agg_cols_dev(self, d_valR, d_idR, nR, d_valS, d_idS, nS, d_colsR=(), opsR=None, colR_rows=0, d_colsS=(), opsS=None,
+                                colS_rows=0, mode=GJ_INNER, d_out_keys=None, d_out_cntR=None, d_out_cntS=None, d_out_aggsR=(),
+                                d_out_aggsS=(), capacity=0, opts=None, allow_overflow=False):
+        """rhj_group_join_agg_cols_dev: group_join_cols_dev with an aggregate per column and side -- opsR[j] / opsS[j] one of the AGG_*
+        (None: every column of that side a sum); d_out_aggsR[j][g] / d_out_aggsS[j][g] the RAW per-side aggregate (a minimum or
+        maximum over the pairs of a group is the per-side one as it stands: no product with the other side's count).  Under GJ_LEFT
+        a group with cntS == 0 holds the op's identity in S's MIN / MAX columns (MIN_U64: 2^64 - 1, MAX_U64: 0, MIN_I64: INT64_MAX,
+        MAX_I64: INT64_MIN) and 0 in its SUM columns: cntS tells which rows these are.  Costs and everything else as
+        group_join_cols_dev."""
+        n = _u64()
+        colsR, aggsR = self._group_args(d_colsR, d_out_aggsR)
+        colsS, aggsS = self._group_args(d_colsS, d_out_aggsS)
+        rc = self.lib.rhj_group_join_agg_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), _addr(d_idS), nS,
+                                                  colsR, self._ops_arg(opsR, len(d_colsR)), len(d_colsR), colR_rows,
+                                                  colsS, self._ops_arg(opsS, len(d_colsS)), len(d_colsS), colS_rows, mode,
+                                                  C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_cntR),
+                                                  _addr(d_out_cntS), aggsR, aggsS, capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_join_agg_dev(self, d_R, nR, d_S, nS, d_colsR=(), opsR=None, colR_rows=0, d_colsS=(), opsS=None, colS_rows=0, mode=GJ_INNER,
+                           d_out_keys=None, d_out_cntR=None, d_out_cntS=None, d_out_aggsR=(), d_out_aggsS=(), capacity=0, opts=None,
+                           allow_overflow=False):
+        """rhj_group_join_agg_dev: group_join_agg_cols_dev on 16-byte tuples (value = .payload, rowID = .key)"""
+        n = _u64()
+        colsR, aggsR = self._group_args(d_colsR, d_out_aggsR)
+        colsS, aggsS = self._group_args(d_colsS, d_out_aggsS)
+        rc = self.lib.rhj_group_join_agg_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, colsR, self._ops_arg(opsR, len(d_colsR)),
+                                             len(d_colsR), colR_rows, colsS, self._ops_arg(opsS, len(d_colsS)), len(d_colsS), colS_rows,
+                                             mode, C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_cntR),
+                                             _addr(d_out_cntS), aggsR, aggsS, capacity, C.byref(n))
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
 
@@ -648,27 +740,38 @@ class Engine:
             total = self.join_mult_cols_dev(keys_R, None, nR, keys_S, None, nS, mult if nR else None, nR, weights_S, nS)
         return mult, total
 
-    def group_by_columns(self, keys, weights=()):
+    def group_by_columns(self, keys, weights=(), ops=None):
         """(unique_keys, counts, sums): the distinct values of keys, how often each occurs, and per tensor of weights the sum of
         weights[k][i] over the rows i that carry the value, mod 2^64 (SELECT key, COUNT(*), SUM(x) FROM R GROUP BY key; torch.unique
         with return_counts + index_add_) -- int64 tensors of one length on the keys' device, sums a list of len(weights) of them,
         group g of all at index g, groups in no particular order.  keys: a contiguous 1-D 64-bit integer tensor on the engine's
         device; weights: up to GROUP_MAX_COLS tensors of the same kind and length.  Negative keys and weights are bit patterns: a
         key comes back as it went in, an int64 sum is the two's complement sum.  The outputs are allocated at len(keys), the upper
-        bound, and returned as the views [:groups].  Streams and completion as join_columns."""
+        bound, and returned as the views [:groups].  Streams and completion as join_columns.
+        ops: None -- every tensor of weights is summed (rhj_group_sum_cols_dev) --, or one of "sum" | "min" | "max" per tensor of
+        weights (SELECT key, MIN(x), MAX(x), SUM(y) ..; scatter_reduce_ with amin / amax): sums[k] is then that aggregate of weights[k]
+        over the group, minimum and maximum of the int64 values (rhj_group_agg_cols_dev; the same tensor may be given twice).  A
+        wrong length or name: ValueError before any launch.  Costs as for sums, whatever the ops."""
         import torch
         weights = tuple(weights)
         if len(weights) > GROUP_MAX_COLS:
             raise ValueError(f"at most {GROUP_MAX_COLS} weight tensors per call, not {len(weights)}")
+        if ops is not None:
+            ops = _agg_ops(ops, len(weights), "ops")
         with self._on_torch_stream(keys, keys, weights) as dev:
             n = keys.numel()
             out_keys = torch.empty(n, dtype=torch.int64, device=dev)
             counts = torch.empty(n, dtype=torch.int64, device=dev)
             sums = [torch.empty(n, dtype=torch.int64, device=dev) for _ in weights]
-            groups = self.group_sum_cols_dev(keys, None, n, weights, n, out_keys, counts, sums, n) if n else 0
+            if not n:
+                groups = 0
+            elif ops is None:
+                groups = self.group_sum_cols_dev(keys, None, n, weights, n, out_keys, counts, sums, n)
+            else:
+                groups = self.group_agg_cols_dev(keys, None, n, weights, ops, n, out_keys, counts, sums, n)
         return out_keys[:groups], counts[:groups], [s[:groups] for s in sums]
 
-    def join_group_by_columns(self, keys_R, keys_S, weights_R=(), weights_S=(), how="inner"):
+    def join_group_by_columns(self, keys_R, keys_S, weights_R=(), weights_S=(), how="inner", ops_R=None, ops_S=None):
         """(keys, count, sums_R, sums_S): SELECT key, COUNT(*), SUM(r.a).., SUM(s.b).. FROM R JOIN S USING (key) GROUP BY key -- per
         join value the number of index pairs (i, j) with keys_R[i] == keys_S[j] == key, and per tensor of weights_R / weights_S the
         sum of weights_R[k][i] / weights_S[k][j] over those pairs, mod 2^64 -- without the pairs: int64 tensors of one length on the
@@ -680,7 +783,13 @@ class Engine:
         max(cntS, 1) multiplies R's side).  keys_R / keys_S: contiguous 1-D 64-bit integer tensors on the engine's device; weights_R
         / weights_S: up to GROUP_JOIN_MAX_COLS tensors each, of the same kind, as long as keys_R / keys_S.  Negative keys and weights
         are bit patterns: a key comes back as it went in, an int64 sum is the two's complement sum.  The outputs are allocated at
-        len(keys_R), the upper bound, and returned as views [:groups] or products of them.  Streams and completion as join_columns."""
+        len(keys_R), the upper bound, and returned as views [:groups] or products of them.  Streams and completion as join_columns.
+        ops_R / ops_S: None -- every tensor of that side is summed --, or one of "sum" | "min" | "max" per tensor of weights_R /
+        weights_S (SELECT key, MIN(r.a), MAX(s.b) ..): a "min" / "max" entry of sums_R / sums_S is the minimum / maximum of the int64
+        values over the group's pairs, which is the one over that side's rows: it is returned RAW, with no multiplication by the
+        other side's count.  Under how="left" S's "min" / "max" of a value keys_S lacks is the op's identity (min: INT64_MAX, max:
+        INT64_MIN; SQL's NULL), its "sum" 0.  With both None the call is rhj_group_join_cols_dev, otherwise
+        rhj_group_join_agg_cols_dev.  A wrong length or name: ValueError before any launch.  Costs as for sums, whatever the ops."""
         import torch
         weights_R, weights_S = tuple(weights_R), tuple(weights_S)
         if how not in ("inner", "left"):
@@ -688,19 +797,31 @@ class Engine:
         for name, w in (("weights_R", weights_R), ("weights_S", weights_S)):
             if len(w) > GROUP_JOIN_MAX_COLS:
                 raise ValueError(f"at most {GROUP_JOIN_MAX_COLS} {name} tensors per call, not {len(w)}")
+        with_ops = ops_R is not None or ops_S is not None
+        ops_R = [AGG_SUM] * len(weights_R) if ops_R is None else _agg_ops(ops_R, len(weights_R), "ops_R")
+        ops_S = [AGG_SUM] * len(weights_S) if ops_S is None else _agg_ops(ops_S, len(weights_S), "ops_S")
         with self._on_torch_stream(keys_R, keys_S, weights_R, weights_S=weights_S) as dev:
             nR, nS = keys_R.numel(), keys_S.numel()
             new = lambda: torch.empty(nR, dtype=torch.int64, device=dev)
             out_keys, cntR, cntS = new(), new(), new()
             sumsR = [new() for _ in weights_R]
             # (tensors without elements have no address to hand over: an empty S goes in without columns, its sums are 0)
-            sumsS = [new() if nS else torch.zeros(nR, dtype=torch.int64, device=dev) for _ in weights_S]
-            groups = self.group_join_cols_dev(keys_R, None, nR, keys_S if nS else None, None, nS, weights_R, nR,
-                                              weights_S if nS else (), nS, GJ_LEFT if how == "left" else GJ_INNER, out_keys, cntR, cntS,
-                                              sumsR, sumsS if nS else (), nR) if nR else 0
+            # ... or, for a minimum / maximum, the op's identity)
+            sumsS = [new() if nS else torch.full((nR,), _AGG_IDENTITY_I64[o], dtype=torch.int64, device=dev) for o in ops_S]
+            mode = GJ_LEFT if how == "left" else GJ_INNER
+            if not nR:
+                groups = 0
+            elif not with_ops:
+                groups = self.group_join_cols_dev(keys_R, None, nR, keys_S if nS else None, None, nS, weights_R, nR,
+                                                  weights_S if nS else (), nS, mode, out_keys, cntR, cntS, sumsR, sumsS if nS else (), nR)
+            else:
+                groups = self.group_join_agg_cols_dev(keys_R, None, nR, keys_S if nS else None, None, nS, weights_R, ops_R, nR,
+                                                      weights_S if nS else (), ops_S if nS else None, nS, mode, out_keys, cntR, cntS,
+                                                      sumsR, sumsS if nS else (), nR)
         cntR, cntS = cntR[:groups], cntS[:groups]
         mult_R = cntS.clamp(min=1) if how == "left" else cntS    # (counts are < 2^63: clamp on int64 is on the true values)
-        return out_keys[:groups], cntR * mult_R, [s[:groups] * mult_R for s in sumsR], [s[:groups] * cntR for s in sumsS]
+        return (out_keys[:groups], cntR * mult_R, [s[:groups] * mult_R if o == AGG_SUM else s[:groups] for s, o in zip(sumsR, ops_R)],
+                [s[:groups] * cntR if o == AGG_SUM else s[:groups] for s, o in zip(sumsS, ops_S)])
 
     def mul_u64(self, d_a, d_b, n, d_dst):
         """rhj_mul_u64: d_dst[i] = d_a[i] * d_b[i] mod 2^64 (d_dst may be d_a)"""

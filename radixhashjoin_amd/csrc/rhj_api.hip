@@ -249,6 +249,7 @@ struct rhj_ctx {
     u64 *group_keys = nullptr, *group_counts = nullptr;   // capacity words each (device; counts may be null)
     u64 *group_sums[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
     u64 group_cap = 0;
+    u32 group_ops = 0;                 // the columns' packed op words (AGG_OP_*; a group-by join's: both sides'); 0: every column a sum
     int last_group_rounds = 0;         // "last.group_rounds": table builds of the busiest task of the last group-by or group-by join (0: another call)
     // a group-by join's arguments beyond the group-by's (R's side: agg_cols / agg_ncols / agg_col_rows, group_keys, group_counts = cntR,
     // group_sums, group_cap; device words: agg_out's [0] groups, [5] u32 GJOIN_BAD_ROW_R / _S)
@@ -1623,7 +1624,7 @@ int group_phase(rhj_ctx *ctx, u64 *out_groups)
                      ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, ctx->agg_cols, ctx->agg_ncols, ctx->agg_col_rows,
                      ctx->group_keys, ctx->group_counts, ctx->group_sums, ctx->group_cap, d_agg, (u32 *)(d_agg + AGG_MAX_COLS + 1),
                      d_count + 7, narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                     narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+                     narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops);
     }
     RHJCHK(check_launch(ctx, "group-by phase"));
     u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, -, -, -, -, most table builds of a task (if > 1)
@@ -1695,7 +1696,7 @@ int gjoin_phase(rhj_ctx *ctx, u64 *out_groups)
                           (u32 *)(d_agg + AGG_MAX_COLS + 1), d_count + 7,
                           narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
                           narrow && ctx->cur_S ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
-                          narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+                          narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops);
     }
     RHJCHK(check_launch(ctx, "group-by join phase"));
     u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, an |S_k| >= 2^32, -, most table builds of a task (if > 1)
@@ -2407,11 +2408,28 @@ int rhj_join_mult_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
 // Group-by: R alone through the partition phase and the repeat ladder of the joins (one-sided, planned as an aggregating
 // join of R with itself), then group_phase.  d_R null: the relation is ctx->cols_in[0].
 static_assert(RHJ_GROUP_MAX_COLS == AGG_MAX_COLS, "rhj.h and rhj_internal.h disagree");
-static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows,
-                        const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
-                        uint64_t out_capacity, uint64_t *out_groups)
+// The RHJ_AGG_* of a call's columns (null: every one RHJ_AGG_SUM) as the kernels' op words (AGG_OP_*), column j at bit AGG_OP_BITS *
+// (first + j) of *packed.  Returns the first column whose op is none of them, or ncols.
+static u32 pack_ops(const uint32_t *ops, u32 ncols, u32 first, u32 *packed)
+{
+    static const u32 word[RHJ_AGG_MAX_I64 + 1] = {AGG_OP_ADD, AGG_OP_MIN, AGG_OP_MAX, AGG_OP_MIN | AGG_OP_SIGNED, AGG_OP_MAX | AGG_OP_SIGNED};
+    static_assert(RHJ_AGG_SUM == 0 && RHJ_AGG_MIN_U64 == 1 && RHJ_AGG_MAX_U64 == 2 && RHJ_AGG_MIN_I64 == 3 && RHJ_AGG_MAX_I64 == 4, "word[]");
+    for (u32 j = 0; ops && j < ncols; j++) {
+        if (ops[j] > RHJ_AGG_MAX_I64) return j;
+        *packed |= word[ops[j]] << (AGG_OP_BITS * (first + j));
+    }
+    return ncols;
+}
+
+static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols,
+                        uint64_t col_rows, const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                        uint64_t *const *d_out_sums, uint64_t out_capacity, uint64_t *out_groups)
 {
     if (ncols > RHJ_GROUP_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncols is above RHJ_GROUP_MAX_COLS");
+    u32 packed = 0;
+    if (const u32 j = pack_ops(ops, ncols, 0, &packed); j != ncols)
+        return fail(ctx, RHJ_E_INVALID, "ops[" + std::to_string(j) + "] = " + std::to_string(ops[j]) + " of column " + std::to_string(j) +
+                                            " is above RHJ_AGG_MAX_I64");
     if (!d_out_keys && out_capacity) return fail(ctx, RHJ_E_INVALID, "d_out_keys is null with out_capacity > 0");
     const u32 nsum = d_out_keys ? ncols : 0;           // count only: no sum sweep, d_cols is never read
     if (nsum && (!d_cols || !d_out_sums)) return fail(ctx, RHJ_E_INVALID, "null weight column array or d_out_sums");
@@ -2429,10 +2447,12 @@ static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *c
     ctx->group_keys = (u64 *)d_out_keys;
     ctx->group_counts = d_out_keys ? (u64 *)d_out_counts : nullptr;
     ctx->group_cap = d_out_keys ? out_capacity : 0;
+    ctx->group_ops = packed;
     ctx->one_sided = true;
     const int rc = partition_and_join(ctx, d_R, nR, nullptr, nR, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GROUP);
     ctx->one_sided = false;
     ctx->agg_ncols = 0;
+    ctx->group_ops = 0;
     ctx->group_keys = ctx->group_counts = nullptr;
     ctx->group_cap = 0;
     for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) { ctx->agg_cols[j] = nullptr; ctx->group_sums[j] = nullptr; }
@@ -2451,7 +2471,7 @@ int rhj_group_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
     *out_groups = 0;
     prof_reset(ctx);
     if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
-    return group_common(ctx, d_R, nR, d_cols, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity, out_groups);
+    return group_common(ctx, d_R, nR, d_cols, nullptr, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity, out_groups);
 }
 
 int rhj_group_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
@@ -2467,7 +2487,40 @@ int rhj_group_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
     ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
     ctx->cols_in[1] = ColsIn();
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_common(ctx, nullptr, nR, d_cols, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity,
+    const int rc = group_common(ctx, nullptr, nR, d_cols, nullptr, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity,
+                                out_groups);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// ... with an aggregate per column: the same host path, the columns' ops beside them
+int rhj_group_agg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
+                      const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                      uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_aggs,
+                      uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return group_common(ctx, d_R, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity, out_groups);
+}
+
+int rhj_group_agg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                           uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_aggs,
+                           uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if (nR && !d_valR) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
+    ctx->cols_in[1] = ColsIn();
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = group_common(ctx, nullptr, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity,
                                 out_groups);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
@@ -2478,14 +2531,21 @@ int rhj_group_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
 // as the group-by plans it, over a zeroed boundary array of S.
 static_assert(RHJ_GROUP_JOIN_MAX_COLS == AGG_MAX_COLS, "rhj.h and rhj_internal.h disagree");
 static int group_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS,
-                             const uint64_t *const *d_colsR, uint32_t ncolsR, uint64_t colR_rows,
-                             const uint64_t *const *d_colsS, uint32_t ncolsS, uint64_t colS_rows, int mode, const rhj_opts *opts,
+                             const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+                             const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows, int mode, const rhj_opts *opts,
                              uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
                              uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS, uint64_t out_capacity, uint64_t *out_groups)
 {
     if (mode != RHJ_GJ_INNER && mode != RHJ_GJ_LEFT) return fail(ctx, RHJ_E_INVALID, "mode is neither RHJ_GJ_INNER nor RHJ_GJ_LEFT");
     if (ncolsR > RHJ_GROUP_JOIN_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncolsR is above RHJ_GROUP_JOIN_MAX_COLS");
     if (ncolsS > RHJ_GROUP_JOIN_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncolsS is above RHJ_GROUP_JOIN_MAX_COLS");
+    u32 packed = 0;
+    if (const u32 j = pack_ops(opsR, ncolsR, 0, &packed); j != ncolsR)
+        return fail(ctx, RHJ_E_INVALID, "opsR[" + std::to_string(j) + "] = " + std::to_string(opsR[j]) + " of column " + std::to_string(j) +
+                                            " of R is above RHJ_AGG_MAX_I64");
+    if (const u32 j = pack_ops(opsS, ncolsS, AGG_MAX_COLS, &packed); j != ncolsS)
+        return fail(ctx, RHJ_E_INVALID, "opsS[" + std::to_string(j) + "] = " + std::to_string(opsS[j]) + " of column " + std::to_string(j) +
+                                            " of S is above RHJ_AGG_MAX_I64");
     if (!d_out_keys && out_capacity) return fail(ctx, RHJ_E_INVALID, "d_out_keys is null with out_capacity > 0");
     const u32 nsumR = d_out_keys ? ncolsR : 0, nsumS = d_out_keys ? ncolsS : 0;   // count only: no sum sweep, no column is read
     if (nsumR && (!d_colsR || !d_out_sumsR)) return fail(ctx, RHJ_E_INVALID, "null weight column array of R or d_out_sumsR");
@@ -2513,10 +2573,12 @@ static int group_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *
     ctx->gjoin_cntS = d_out_keys ? (u64 *)d_out_cntS : nullptr;
     ctx->group_cap = d_out_keys ? out_capacity : 0;
     ctx->gjoin_left = mode == RHJ_GJ_LEFT;
+    ctx->group_ops = packed;
     ctx->one_sided = one;
     const int rc = partition_and_join(ctx, d_R, nR, one ? nullptr : d_S, one ? nR : nS, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GJOIN);
     ctx->one_sided = false;
     ctx->gjoin_left = false;
+    ctx->group_ops = 0;
     ctx->agg_ncols = ctx->gjoin_ncolsS = 0;
     ctx->group_keys = ctx->group_counts = ctx->gjoin_cntS = nullptr;
     ctx->group_cap = 0;
@@ -2542,8 +2604,8 @@ int rhj_group_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rh
     *out_groups = 0;
     prof_reset(ctx);
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
-    return group_join_common(ctx, d_R, nR, d_S, nS, d_colsR, ncolsR, colR_rows, d_colsS, ncolsS, colS_rows, mode, opts, d_out_keys,
-                             d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
+    return group_join_common(ctx, d_R, nR, d_S, nS, d_colsR, nullptr, ncolsR, colR_rows, d_colsS, nullptr, ncolsS, colS_rows, mode, opts,
+                             d_out_keys, d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
 }
 
 int rhj_group_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
@@ -2564,8 +2626,50 @@ int rhj_group_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t
     if (nS) { ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS; }
     else ctx->cols_in[1] = ColsIn();
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, ncolsR, colR_rows, d_colsS, ncolsS, colS_rows, mode, opts,
-                                     d_out_keys, d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
+    const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, nullptr, ncolsR, colR_rows, d_colsS, nullptr, ncolsS, colS_rows,
+                                     mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// ... with an aggregate per column: the same host path, each side's ops beside its columns
+int rhj_group_join_agg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                           const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+                           const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows,
+                           int mode, const rhj_opts *opts,
+                           uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+                           uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
+                           uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return group_join_common(ctx, d_R, nR, d_S, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows, mode, opts,
+                             d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups);
+}
+
+int rhj_group_join_agg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                                const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+                                const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+                                const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows,
+                                int mode, const rhj_opts *opts,
+                                uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+                                uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
+                                uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with no column)
+    if (nS) { ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS; }
+    else ctx->cols_in[1] = ColsIn();
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows,
+                                     mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

@@ -2948,18 +2948,39 @@ k_mult_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
 //         when the partition holds mix64 of the caller's values) and counts are stored where base + rank < capacity.
 //       sum sweeps (SUMS): per column the accumulators are zeroed, the class's tuples looked up again -- the table stays built --
 //         and cols[j][rowR] added on the slot, behind the rowR < col_rows guard (a row beyond is never dereferenced: *bad); emit.
+//       aggregate sweeps (GB_OPS): the sum sweep with the column's op -- the accumulators start from the op's identity,
+//         the word is biased, the LDS atomic is an add, an unsigned minimum or an unsigned maximum, the emitted word is un-biased.
 //     The next class is the prefix increment of (d, p) read with bit 0 as the most significant digit: no stack.
 //   * no global atomic per tuple; integer addition mod 2^64: every result is bit-exact from run to run.
 // ------------------------------------------------------------------------------------------------
 constexpr u64 GROUP_CLASS_SALT = 0xA0761D6478BD642Full;
 struct GroupSums { u64 *c[AGG_MAX_COLS]; };
+// What a group kernel does beyond keys and counts: nothing, a sum per column, or per column the aggregate its op word names
+// (DESIGN 4.17).  GB_OPS is GB_SUMS with three things made a per-column choice -- the word the accumulators start from, the word a
+// sweep may skip (both the op's identity: 0 for add and max, all ones for min) and the LDS atomic -- and a bias: the signed ops XOR
+// 1 << 63 into the gathered word and into the accumulator on its way out, so the table only ever takes an unsigned minimum or
+// maximum.  The op words of a call travel in one kernel argument, four bits per column (AGG_OP_*), and wait in LDS beside the column
+// pointers; a column's word is read once per sweep and selects the sweep's loop, not an atomic inside it.
+enum : int { GB_COUNT = 0, GB_SUMS = 1, GB_OPS = 2 };
+using AggAdd = std::integral_constant<u32, AGG_OP_ADD>;
+using AggMin = std::integral_constant<u32, AGG_OP_MIN>;
+using AggMax = std::integral_constant<u32, AGG_OP_MAX>;
+template <u32 KIND>
+__device__ __forceinline__ void lds_agg(u64 *w, u64 v)
+{
+    if constexpr (KIND == AGG_OP_ADD) atomicAdd((unsigned long long *)w, (unsigned long long)v);
+    else if constexpr (KIND == AGG_OP_MIN) atomicMin((unsigned long long *)w, (unsigned long long)v);
+    else atomicMax((unsigned long long *)w, (unsigned long long)v);
+}
 
-template <bool NARROW, bool SUMS>
+template <bool NARROW, int AGG>
 __global__ void __launch_bounds__(AGG_THREADS, 4)
 k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks, int radix_bits, int mixed,
             AggCols cols, u32 ncols, u64 col_rows, u64 *__restrict__ out_keys, u64 *__restrict__ out_counts, GroupSums out_sums,
-            u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip)
+            u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip,
+            u32 ops)
 {
+    constexpr bool SUMS = AGG != GB_COUNT;
     if (skip != nullptr && *skip != 0) return;
     if (blockIdx.x >= *ntasks) return;
     constexpr int THREADS = AGG_THREADS;
@@ -2987,6 +3008,7 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
         if (tid == 0) {
 #pragma unroll
             for (int j = 0; j < AGG_MAX_COLS; j++) { colp[j] = (u64)cols.c[j]; colp[AGG_MAX_COLS + j] = (u64)out_sums.c[j]; }
+            if constexpr (AGG == GB_OPS) colp[2 * AGG_MAX_COLS] = ops;       // GB_OPS: the op words behind the pointers
         }                                                                    // (read behind the barriers of the first build)
     u32 d = 0, rounds = 0;                                                   // the class (d, p); table builds so far
     u64 p = 0;
@@ -3017,6 +3039,14 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
             const u64 cur = tab[s];
             if (cur == key) { atomicAdd((unsigned long long *)&acc[s], (unsigned long long)v); return; }
             if (cur == SEMI_EMPTY) return;                                   // (cannot happen while the input stands still)
+        }
+    };
+    auto agg_on = [&](u64 key, u64 v, auto kind) {                           // GB_OPS: add_on with the LDS atomic of the column's op
+        if (key == SEMI_EMPTY) { lds_agg<decltype(kind)::value>(ones, v); return; }
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            if (cur == key) { lds_agg<decltype(kind)::value>(&acc[s], v); return; }
+            if (cur == SEMI_EMPTY) return;
         }
     };
     auto load_key = [&](u32 at) -> u64 {                                     // tuple at + tid of the partition; 0 beyond its end
@@ -3086,6 +3116,48 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
             for (u32 c = 0; c < ncols; c++) {
                 const u64 *__restrict__ col = reinterpret_cast<const u64 *>(colp[c]);
                 u64 *__restrict__ dst = reinterpret_cast<u64 *>(colp[AGG_MAX_COLS + c]);
+                if constexpr (AGG == GB_OPS) {                               // the column's op word decides start, skip, atomic and bias
+                    const u32 op = (u32)__builtin_amdgcn_readfirstlane((int)((u32)colp[2 * AGG_MAX_COLS] >> (AGG_OP_BITS * c)));
+                    u64 init = (op & AGG_OP_KIND) == AGG_OP_MIN ? ~0ull : 0ull;   // the op's identity: where a word starts, what a sweep may skip
+                    u64 bias = op & AGG_OP_SIGNED ? 1ull << 63 : 0ull;
+                    asm volatile("" : "+v"(init), "+v"(bias));                     // (opaque: uniform, but four SGPRs across the sweep are four spilled)
+                    __syncthreads();                                         // the accumulators have been emitted
+                    for (u32 i = tid; i < SLOTS; i += THREADS) acc[i] = init;
+                    if (tid == 0) *ones = init;
+                    __syncthreads();
+                    auto sweep = [&](auto kind) {                            // the sweep below, per LDS atomic: the select stays outside the tiles
+                        Both t = Rv.buf(0u, np < (u32)THREADS ? np : (u32)THREADS).both(0u, (u32)tid), t_next = t;
+                        for (u32 tb = 0; tb < np; tb += THREADS) {
+                            const u32 left = np - tb;
+                            if (left > (u32)THREADS)
+                                t_next = Rv.buf(tb + (u32)THREADS, left - THREADS < (u32)THREADS ? left - THREADS : (u32)THREADS).both(0u, (u32)tid);
+                            if ((u32)tid < left) {
+                                if ((u64)t.key >= col_rows) wild = true;
+                                else if (in_class(t.payload)) {
+                                    const u64 v = col[(u64)t.key] ^ bias;
+                                    if (v != init) agg_on(t.payload, v, kind);
+                                }
+                            }
+                            t = t_next;
+                        }
+                    };
+                    if ((op & AGG_OP_KIND) == AGG_OP_MIN) sweep(AggMin{});
+                    else if ((op & AGG_OP_KIND) == AGG_OP_MAX) sweep(AggMax{});
+                    else sweep(AggAdd{});
+                    __syncthreads();
+                    u64 g = g0;
+#pragma unroll 1
+                    for (u32 j = 0; j < SPT; j++)
+                        if (occ >> j & 1u) {
+                            if (g < capacity) dst[g] = acc[(u32)tid * SPT + j] ^ bias;
+                            g++;
+                        }
+                    if (tid == 0 && ho) {
+                        const u64 g1 = *base_s + filled;
+                        if (g1 < capacity) dst[g1] = *ones ^ bias;
+                    }
+                    continue;
+                }
                 __syncthreads();                                             // the accumulators have been emitted
                 for (u32 i = tid; i < SLOTS; i += THREADS) acc[i] = 0;
                 if (tid == 0) *ones = 0;
@@ -3145,16 +3217,19 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
 //     all-ones key last; ONE global atomic add claims the class's groups; keys, cntR, cntS stored where base + rank < capacity.  A
 //     class that emits nothing goes no further.  SUMS: per column of R the words are zeroed, R's class tuples looked up again and
 //     colsR[j][rowR] added behind the rowR < colR_rows guard, emitted at the saved mask and ranks; then the same over S's tuples for
-//     every column of S (a tuple of S whose key is not in the table adds nothing).
+//     every column of S (a tuple of S whose key is not in the table adds nothing).  GB_OPS: k_group_bkt's aggregate
+//     sweeps per column of either side; a group no tuple of S carries (left_mode) keeps the identity of the op, un-biased.
 //   * plain vector loads and stores, LDS atomics, one global atomic per class; integer addition mod 2^64: bit-exact from run to run.
 // ------------------------------------------------------------------------------------------------
-template <bool NARROW, bool SUMS>
+template <bool NARROW, int AGG>
 __global__ void __launch_bounds__(AGG_THREADS, 4)
 k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks, int radix_bits,
             int mixed, int left_mode, AggCols colsR, u32 ncolsR, u64 colR_rows, AggCols colsS, u32 ncolsS, u64 colS_rows,
             u64 *__restrict__ out_keys, u64 *__restrict__ out_cntR, u64 *__restrict__ out_cntS, GroupSums out_sumsR, GroupSums out_sumsS,
-            u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip)
+            u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip,
+            u32 ops)
 {
+    constexpr bool SUMS = AGG != GB_COUNT;
     if (skip != nullptr && *skip != 0) return;
     if (blockIdx.x >= *ntasks) return;
     constexpr int THREADS = AGG_THREADS;
@@ -3182,6 +3257,7 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
     if (tid == 0) {
         par[0] = colR_rows; par[1] = colS_rows; par[2] = (u64)out_keys; par[3] = (u64)out_cntR; par[4] = (u64)out_cntS; par[5] = capacity;
         par[6] = (u64)ngroups; par[7] = (u64)bad; par[8] = (u64)max_rounds;
+        if constexpr (AGG == GB_OPS) par[GJOIN_PAR_WORDS] = ops;             // GB_OPS: the op words, R's columns in the low half, S's above
     }                                                                        // (read behind the barriers of the first build)
     if constexpr (SUMS)
         if (tid == 0) {
@@ -3219,6 +3295,14 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
         for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
             const u64 cur = tab[s];
             if (cur == key) { atomicAdd((unsigned long long *)&acc[s], (unsigned long long)v); return; }
+            if (cur == SEMI_EMPTY) return;
+        }
+    };
+    auto agg_on = [&](u64 key, u64 v, auto kind) {                           // GB_OPS: add_on with the LDS atomic of the column's op
+        if (key == SEMI_EMPTY) { lds_agg<decltype(kind)::value>(ones, v); return; }
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            if (cur == key) { lds_agg<decltype(kind)::value>(&acc[s], v); return; }
             if (cur == SEMI_EMPTY) return;
         }
     };
@@ -3313,6 +3397,7 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
             // ---- the sums, one column at a time over the table as it stands: R's columns over R's tuples, then S's over S's --
             if constexpr (SUMS) {
                 const u32 nc = ncolsR + ncolsS;
+                if constexpr (AGG == GB_OPS) __builtin_assume(nc != 0);      // (launch_group_join: no column, no op -- a hoisted test is two SGPRs spilled)
                 for (u32 c = 0; c < nc; c++) {
                     const bool on_s = c >= ncolsR;                           // (uniform) R's columns over R's tuples, then S's over S's
                     const RelView<NARROW> V = on_s ? Sv : Rv;
@@ -3320,6 +3405,51 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
                     const u64 *__restrict__ col = reinterpret_cast<const u64 *>(colp[ci]);
                     u64 *__restrict__ dst = reinterpret_cast<u64 *>(colp[ci + AGG_MAX_COLS]);
                     const u64 rows = par[on_s ? 1 : 0], capacity = par[5];
+                    if constexpr (AGG == GB_OPS) {                           // the column's op word decides start, skip, atomic and bias
+                        const u32 op = (u32)__builtin_amdgcn_readfirstlane(
+                            (int)((u32)par[GJOIN_PAR_WORDS] >> (AGG_OP_BITS * (on_s ? (u32)AGG_MAX_COLS + (c - ncolsR) : c))));
+                        u64 init = (op & AGG_OP_KIND) == AGG_OP_MIN ? ~0ull : 0ull;   // the op's identity: where a word starts, what a sweep may skip
+                        u64 bias = op & AGG_OP_SIGNED ? 1ull << 63 : 0ull;
+                        asm volatile("" : "+v"(init), "+v"(bias));                     // (opaque: uniform, but four SGPRs across the sweep are four spilled)
+                        __syncthreads();                                     // the words have been emitted
+                        for (u32 i = tid; i < SLOTS; i += THREADS) acc[i] = init;
+                        if (tid == 0) *ones = init;
+                        __syncthreads();
+                        auto sweep = [&](auto kind) {                        // the sweep below, per LDS atomic: the select stays outside the tiles
+                            Both t = V.buf(0u, n < (u32)THREADS ? n : (u32)THREADS).both(0u, (u32)tid), t_next = t;
+                            for (u32 tb = 0; tb < n; tb += THREADS) {
+                                const u32 rest = n - tb;
+                                if (rest > (u32)THREADS)
+                                    t_next = V.buf(tb + (u32)THREADS, rest - THREADS < (u32)THREADS ? rest - THREADS : (u32)THREADS).both(0u, (u32)tid);
+                                if ((u32)tid < rest) {
+                                    if ((u64)t.key >= rows) wild |= on_s ? GJOIN_BAD_ROW_S : GJOIN_BAD_ROW_R;
+                                    else if (in_class(t.payload)) {
+                                        const u64 v = col[(u64)t.key] ^ bias;
+                                        if (v != init) agg_on(t.payload, v, kind);
+                                    }
+                                }
+                                t = t_next;
+                            }
+                        };
+                        if (n != 0) {
+                            if ((op & AGG_OP_KIND) == AGG_OP_MIN) sweep(AggMin{});
+                            else if ((op & AGG_OP_KIND) == AGG_OP_MAX) sweep(AggMax{});
+                            else sweep(AggAdd{});
+                        }
+                        __syncthreads();
+                        u64 g = g0;
+#pragma unroll 1
+                        for (u32 j = 0; j < SPT; j++)
+                            if (em >> j & 1u) {
+                                if (g < capacity) dst[g] = acc[(u32)tid * SPT + j] ^ bias;   // (no tuple of S under LEFT: the identity, unbiased)
+                                g++;
+                            }
+                        if (tid == 0 && hoe) {
+                            const u64 g1 = *base_s + tot;
+                            if (g1 < capacity) dst[g1] = *ones ^ bias;
+                        }
+                        continue;
+                    }
                     __syncthreads();                                         // the words have been emitted
                     for (u32 i = tid; i < SLOTS; i += THREADS) acc[i] = 0;
                     if (tid == 0) *ones = 0;
@@ -4091,14 +4221,18 @@ static void allow_big_lds()
     SET_LDS((k_mult_bkt<false, false>), mult_lds_bytes(false));
     SET_LDS((k_mult_bkt<true, true>), mult_lds_bytes(true));
     SET_LDS((k_mult_bkt<false, true>), mult_lds_bytes(true));
-    SET_LDS((k_group_bkt<true, false>), group_lds_bytes());
-    SET_LDS((k_group_bkt<false, false>), group_lds_bytes());
-    SET_LDS((k_group_bkt<true, true>), group_lds_bytes());
-    SET_LDS((k_group_bkt<false, true>), group_lds_bytes());
-    SET_LDS((k_gjoin_bkt<true, false>), gjoin_lds_bytes());
-    SET_LDS((k_gjoin_bkt<false, false>), gjoin_lds_bytes());
-    SET_LDS((k_gjoin_bkt<true, true>), gjoin_lds_bytes());
-    SET_LDS((k_gjoin_bkt<false, true>), gjoin_lds_bytes());
+    SET_LDS((k_group_bkt<true, GB_COUNT>), group_lds_bytes());
+    SET_LDS((k_group_bkt<false, GB_COUNT>), group_lds_bytes());
+    SET_LDS((k_group_bkt<true, GB_SUMS>), group_lds_bytes());
+    SET_LDS((k_group_bkt<false, GB_SUMS>), group_lds_bytes());
+    SET_LDS((k_gjoin_bkt<true, GB_COUNT>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<false, GB_COUNT>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<true, GB_SUMS>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<false, GB_SUMS>), gjoin_lds_bytes());
+    SET_LDS((k_group_bkt<true, GB_OPS>), group_lds_bytes());
+    SET_LDS((k_group_bkt<false, GB_OPS>), group_lds_bytes());
+    SET_LDS((k_gjoin_bkt<true, GB_OPS>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<false, GB_OPS>), gjoin_lds_bytes());
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<IN_AOS>, wn_lds_bytes(WN_MAX_BITS));
@@ -4734,7 +4868,7 @@ void launch_mult_join(hipStream_t st, const void *d_R, const void *d_S, const Jo
 
 void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits, bool mixed,
                   const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_out_keys, u64 *d_out_counts, u64 *const *d_out_sums,
-                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip)
+                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip, u32 ops)
 {
     if (grid == 0) return;
     allow_big_lds();
@@ -4743,16 +4877,19 @@ void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, cons
     for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) { cols.c[j] = j < ncols ? d_cols[j] : nullptr; sums.c[j] = j < ncols ? d_out_sums[j] : nullptr; }
     auto go = [&](auto kernel, auto Rv) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(AGG_THREADS), group_lds_bytes(), st, Rv, d_tasks, d_ntasks, radix_bits, mixed ? 1 : 0,
-                           cols, ncols, col_rows, d_out_keys, d_out_counts, sums, capacity, d_ngroups, d_bad, d_max_rounds, d_skip);
+                           cols, ncols, col_rows, d_out_keys, d_out_counts, sums, capacity, d_ngroups, d_bad, d_max_rounds, d_skip, ops);
     };
+    const bool with_ops = ncols != 0 && ops != 0;                            // (all sums: the sums instantiations)
     if (d_RK != nullptr) {                                                   // narrow partitions: d_R is a payload array
         const RelView<true> Rv{(const u64 *)d_R, d_RK};
-        if (ncols != 0) go(k_group_bkt<true, true>, Rv);
-        else go(k_group_bkt<true, false>, Rv);
+        if (with_ops) go(k_group_bkt<true, GB_OPS>, Rv);
+        else if (ncols != 0) go(k_group_bkt<true, GB_SUMS>, Rv);
+        else go(k_group_bkt<true, GB_COUNT>, Rv);
     } else {
         const RelView<false> Rv{(const Tup *)d_R};
-        if (ncols != 0) go(k_group_bkt<false, true>, Rv);
-        else go(k_group_bkt<false, false>, Rv);
+        if (with_ops) go(k_group_bkt<false, GB_OPS>, Rv);
+        else if (ncols != 0) go(k_group_bkt<false, GB_SUMS>, Rv);
+        else go(k_group_bkt<false, GB_COUNT>, Rv);
     }
 }
 
@@ -4760,7 +4897,7 @@ void launch_group_join(hipStream_t st, const void *d_R, const void *d_S, const J
                        int radix_bits, bool mixed, bool left_mode, const u64 *const *d_colsR, u32 ncolsR, u64 colR_rows,
                        const u64 *const *d_colsS, u32 ncolsS, u64 colS_rows, u64 *d_out_keys, u64 *d_out_cntR, u64 *d_out_cntS,
                        u64 *const *d_out_sumsR, u64 *const *d_out_sumsS, u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds,
-                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip)
+                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip, u32 ops)
 {
     if (grid == 0) return;
     allow_big_lds();
@@ -4773,17 +4910,19 @@ void launch_group_join(hipStream_t st, const void *d_R, const void *d_S, const J
     auto go = [&](auto kernel, auto Rv, auto Sv) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(AGG_THREADS), gjoin_lds_bytes(), st, Rv, Sv, d_tasks, d_ntasks, radix_bits,
                            mixed ? 1 : 0, left_mode ? 1 : 0, colsR, ncolsR, colR_rows, colsS, ncolsS, colS_rows, d_out_keys, d_out_cntR,
-                           d_out_cntS, sumsR, sumsS, capacity, d_ngroups, d_bad, d_max_rounds, d_skip);
+                           d_out_cntS, sumsR, sumsS, capacity, d_ngroups, d_bad, d_max_rounds, d_skip, ops);
     };
-    const bool sums = ncolsR + ncolsS != 0;
+    const bool sums = ncolsR + ncolsS != 0, with_ops = sums && ops != 0;     // (all sums: the sums instantiations)
     if (d_RK != nullptr) {                                                   // narrow partitions: d_R / d_S are payload arrays
         const RelView<true> Rv{(const u64 *)d_R, d_RK}, Sv{(const u64 *)d_S, d_SK};
-        if (sums) go(k_gjoin_bkt<true, true>, Rv, Sv);
-        else go(k_gjoin_bkt<true, false>, Rv, Sv);
+        if (with_ops) go(k_gjoin_bkt<true, GB_OPS>, Rv, Sv);
+        else if (sums) go(k_gjoin_bkt<true, GB_SUMS>, Rv, Sv);
+        else go(k_gjoin_bkt<true, GB_COUNT>, Rv, Sv);
     } else {
         const RelView<false> Rv{(const Tup *)d_R}, Sv{(const Tup *)d_S};
-        if (sums) go(k_gjoin_bkt<false, true>, Rv, Sv);
-        else go(k_gjoin_bkt<false, false>, Rv, Sv);
+        if (with_ops) go(k_gjoin_bkt<false, GB_OPS>, Rv, Sv);
+        else if (sums) go(k_gjoin_bkt<false, GB_SUMS>, Rv, Sv);
+        else go(k_gjoin_bkt<false, GB_COUNT>, Rv, Sv);
     }
 }
 

@@ -466,6 +466,75 @@ int rhj_group_join_agg_dev(rhj_ctx *ctx,
         uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
         uint64_t out_capacity, uint64_t *out_groups);
 
+/* ---- group ids per row: the INVERSE INDEX of the group-by and of the group-by join (torch.unique's return_inverse; pandas.factorize;
+ * dictionary-encoding a 64-bit key column into dense ids; a joint encoding of two key columns with "no partner" marked).  The same
+ * kernels, tables, class walk and host path: after the last column sweep of a class, every slot word takes its group's index and the
+ * class's tuples store the word of their key at their row. */
+/* rhj_group_agg_cols_dev with d_out_gid: a DEVICE array of gid_rows words indexed by R's rowID.  For every tuple of R,
+ * d_out_gid[rowR] = g, where group g is the one at d_out_keys[g] OF THIS CALL.  The order of groups is unspecified and may differ
+ * from run to run, so ids are consistent with this call's outputs only; the PARTITION of the rows into groups is exact and the same
+ * every run.  Ids are read as there: they are partitioned with the values whenever they are given.  Words of d_out_gid that no
+ * tuple's rowID names are left untouched.  Two tuples with the same rowID and different values leave one of the two ids, unspecified.
+ * d_out_gid == NULL: gid_rows is ignored and the call is rhj_group_agg_cols_dev.
+ * Overflow: an id is never compared with out_capacity.  Under RHJ_E_OVERFLOW the ids are still the exact group indices in
+ * [0, *out_groups); ids >= out_capacity name groups whose rows were not stored.  Count only (d_out_keys == NULL, out_capacity == 0)
+ * may be given an id array: a dense labelling without the dictionary; no column is read, as there.
+ * Row guard: a rowR >= gid_rows is never written: it raises the flag word and the call returns RHJ_E_INVALID -- rhj_last_error names
+ * d_out_gid --, for every such tuple the kernel sees; nothing at or past gid_rows is touched; the other words of d_out_gid and the
+ * outputs are then undefined; the context stays usable.
+ * Everything else is the contract of rhj_group_agg_cols_dev, word for word: ops (checked before any launch), count only,
+ * RHJ_E_OVERFLOW, the row guard of the columns, nR == 0 (0 groups, no launch, d_out_gid untouched), plans and repeats -- a repeat
+ * starts from nothing and writes every id again --, probe_split ignored, "last.join_kernel" is 15, "last.group_rounds".
+ * Costs beyond rhj_group_agg_cols_dev's: one more sweep of the partition per class, and one scattered 8-byte store per tuple. */
+int rhj_group_agg_ids_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                               const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols, uint64_t col_rows,
+                               const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                               uint64_t *const *d_out_aggs, uint64_t out_capacity, uint64_t *out_groups,
+                               uint64_t *d_out_gid, uint64_t gid_rows);
+/* ... on 16-byte tuples (value = .payload, rowR = .key) */
+int rhj_group_agg_ids_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
+                          const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols, uint64_t col_rows,
+                          const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                          uint64_t *const *d_out_aggs, uint64_t out_capacity, uint64_t *out_groups,
+                          uint64_t *d_out_gid, uint64_t gid_rows);
+/* rhj_group_join_agg_cols_dev with d_out_gidR / d_out_gidS: DEVICE arrays of gidR_rows / gidS_rows words indexed by the side's rowID.
+ * d_out_gidR[rowR] = g for every tuple of R whose value has a group -- every tuple under RHJ_GJ_LEFT, the tuples whose value occurs
+ * in S under RHJ_GJ_INNER; d_out_gidS[rowS] = g for every tuple of S whose value has a group -- in both modes the tuples whose value
+ * occurs in R.  Group g is the one at d_out_keys[g] of this call, as above.
+ * EVERY OTHER word of [0, gidR_rows) and [0, gidS_rows) is all ones when the call returns (SQL's NULL; -1 as int64): both arrays are
+ * filled before the kernel, on every attempt, so this holds for partitions that get no task, for classes that emit nothing, across
+ * the in-call repeats, and where no kernel runs -- nR == 0, or nS == 0 under RHJ_GJ_INNER: 0 groups, both arrays all ones; nS == 0
+ * under RHJ_GJ_LEFT: the group-by of R with ids.  Two tuples with the same rowID leave one of their words, unspecified.
+ * Either pointer may be NULL on its own (its *_rows is ignored, that side gets no sweep); both NULL: the call is
+ * rhj_group_join_agg_cols_dev.
+ * Overflow and count only as above: ids are exact group indices in [0, *out_groups) whatever out_capacity is.
+ * Row guard: a rowR >= gidR_rows or a rowS >= gidS_rows is never written: RHJ_E_INVALID, rhj_last_error names d_out_gidR or
+ * d_out_gidS, for every such tuple an id sweep meets (a partition no task is made for, and a class of keys that emits no group, get
+ * no sweep); nothing at or past *_rows is touched; the context stays usable.
+ * Everything else is the contract of rhj_group_join_agg_cols_dev, word for word; "last.join_kernel" is 16.
+ * Costs beyond it: the fill -- 8 bytes written per word of either array --, one more sweep of each side's partition per class that
+ * emits, and one scattered 8-byte store per tuple that has a group. */
+int rhj_group_join_agg_ids_cols_dev(rhj_ctx *ctx,
+        const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+        const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+        const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+        const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows,
+        int mode, const rhj_opts *opts,
+        uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+        uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
+        uint64_t out_capacity, uint64_t *out_groups,
+        uint64_t *d_out_gidR, uint64_t gidR_rows, uint64_t *d_out_gidS, uint64_t gidS_rows);
+/* ... on 16-byte tuples (value = .payload, rowID = .key) */
+int rhj_group_join_agg_ids_dev(rhj_ctx *ctx,
+        const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+        const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+        const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows,
+        int mode, const rhj_opts *opts,
+        uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+        uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
+        uint64_t out_capacity, uint64_t *out_groups,
+        uint64_t *d_out_gidR, uint64_t gidR_rows, uint64_t *d_out_gidS, uint64_t gidS_rows);
+
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:
  *   d_hist[b] = #{ i : ((payload_i >> shift) & (2^bits-1)) == b },  d_hist has 2^bits uint64. */

@@ -96,6 +96,16 @@ SYMBOLS = {
                                               _P(_u64)]),
     "rhj_group_join_agg_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(_vp), _P(C.c_uint32),
                                          C.c_uint32, _u64, C.c_int, _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64)]),
+    "rhj_group_agg_ids_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp),
+                                             _u64, _P(_u64), _vp, _u64]),
+    "rhj_group_agg_ids_dev": (C.c_int, [_vp, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64,
+                                        _P(_u64), _vp, _u64]),
+    "rhj_group_join_agg_ids_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(_vp),
+                                                  _P(C.c_uint32), C.c_uint32, _u64, C.c_int, _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp),
+                                                  _u64, _P(_u64), _vp, _u64, _vp, _u64]),
+    "rhj_group_join_agg_ids_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(_vp), _P(C.c_uint32),
+                                             C.c_uint32, _u64, C.c_int, _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64),
+                                             _vp, _u64, _vp, _u64]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -636,6 +646,66 @@ class Engine:
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
 
+    def group_agg_ids_cols_dev(self, d_valR, d_idR, nR, d_cols=(), ops=None, col_rows=0, d_out_keys=None, d_out_counts=None,
+                               d_out_aggs=(), capacity=0, d_out_gid=None, gid_rows=0, opts=None, allow_overflow=False):
+        """rhj_group_agg_ids_cols_dev: group_agg_cols_dev with the group of every row -- d_out_gid[rowID] = g, the index of the
+        tuple's group in this call's d_out_keys (uint64[gid_rows] in HBM; words no rowID names are left as they are; a rowID >=
+        gid_rows is never written: RhjError).  Ids are exact group indices also beyond capacity (allow_overflow) and in a count-only
+        call.  d_out_gid None: group_agg_cols_dev."""
+        n = _u64()
+        cols, aggs = self._group_args(d_cols, d_out_aggs)
+        rc = self.lib.rhj_group_agg_ids_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, cols, self._ops_arg(ops, len(d_cols)),
+                                                 len(d_cols), col_rows, C.byref(opts) if opts is not None else None, _addr(d_out_keys),
+                                                 _addr(d_out_counts), aggs, capacity, C.byref(n), _addr(d_out_gid), gid_rows)
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_agg_ids_dev(self, d_R, nR, d_cols=(), ops=None, col_rows=0, d_out_keys=None, d_out_counts=None, d_out_aggs=(), capacity=0,
+                          d_out_gid=None, gid_rows=0, opts=None, allow_overflow=False):
+        """rhj_group_agg_ids_dev: group_agg_ids_cols_dev on 16-byte tuples (value = .payload, rowID = .key)"""
+        n = _u64()
+        cols, aggs = self._group_args(d_cols, d_out_aggs)
+        rc = self.lib.rhj_group_agg_ids_dev(self.ctx, _addr(d_R), nR, cols, self._ops_arg(ops, len(d_cols)), len(d_cols), col_rows,
+                                            C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_counts), aggs,
+                                            capacity, C.byref(n), _addr(d_out_gid), gid_rows)
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_join_agg_ids_cols_dev(self, d_valR, d_idR, nR, d_valS, d_idS, nS, d_colsR=(), opsR=None, colR_rows=0, d_colsS=(), opsS=None,
+                                    colS_rows=0, mode=GJ_INNER, d_out_keys=None, d_out_cntR=None, d_out_cntS=None, d_out_aggsR=(),
+                                    d_out_aggsS=(), capacity=0, d_out_gidR=None, gidR_rows=0, d_out_gidS=None, gidS_rows=0, opts=None,
+                                    allow_overflow=False):
+        """rhj_group_join_agg_ids_cols_dev: group_join_agg_cols_dev with the group of every row of either side -- d_out_gidR[rowR] /
+        d_out_gidS[rowS] = g, the index of the tuple's group in this call's d_out_keys, for the tuples whose value has a group;
+        every other word of the two arrays (uint64[gidR_rows] / uint64[gidS_rows] in HBM) is all ones when the call returns.  Either
+        may be None; a rowID >= its array's length is never written: RhjError that names the array."""
+        n = _u64()
+        colsR, aggsR = self._group_args(d_colsR, d_out_aggsR)
+        colsS, aggsS = self._group_args(d_colsS, d_out_aggsS)
+        rc = self.lib.rhj_group_join_agg_ids_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), _addr(d_idS), nS,
+                                                      colsR, self._ops_arg(opsR, len(d_colsR)), len(d_colsR), colR_rows,
+                                                      colsS, self._ops_arg(opsS, len(d_colsS)), len(d_colsS), colS_rows, mode,
+                                                      C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_cntR),
+                                                      _addr(d_out_cntS), aggsR, aggsS, capacity, C.byref(n), _addr(d_out_gidR), gidR_rows,
+                                                      _addr(d_out_gidS), gidS_rows)
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_join_agg_ids_dev(self, d_R, nR, d_S, nS, d_colsR=(), opsR=None, colR_rows=0, d_colsS=(), opsS=None, colS_rows=0,
+                               mode=GJ_INNER, d_out_keys=None, d_out_cntR=None, d_out_cntS=None, d_out_aggsR=(), d_out_aggsS=(),
+                               capacity=0, d_out_gidR=None, gidR_rows=0, d_out_gidS=None, gidS_rows=0, opts=None, allow_overflow=False):
+        """rhj_group_join_agg_ids_dev: group_join_agg_ids_cols_dev on 16-byte tuples (value = .payload, rowID = .key)"""
+        n = _u64()
+        colsR, aggsR = self._group_args(d_colsR, d_out_aggsR)
+        colsS, aggsS = self._group_args(d_colsS, d_out_aggsS)
+        rc = self.lib.rhj_group_join_agg_ids_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, colsR, self._ops_arg(opsR, len(d_colsR)),
+                                                 len(d_colsR), colR_rows, colsS, self._ops_arg(opsS, len(d_colsS)), len(d_colsS),
+                                                 colS_rows, mode, C.byref(opts) if opts is not None else None, _addr(d_out_keys),
+                                                 _addr(d_out_cntR), _addr(d_out_cntS), aggsR, aggsS, capacity, C.byref(n),
+                                                 _addr(d_out_gidR), gidR_rows, _addr(d_out_gidS), gidS_rows)
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
     @contextlib.contextmanager
     def _on_torch_stream(self, keys_R, keys_S, weights=(), weights_on_S=False, weights_S=()):
         """What join_columns, semi_join_columns, join_sum_columns, join_multiplicity_columns, group_by_columns (keys_S = keys_R) and join_group_by_columns (weights_S: further tensors, each as long as keys_S) share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
@@ -751,7 +821,19 @@ class Engine:
         ops: None -- every tensor of weights is summed (rhj_group_sum_cols_dev) --, or one of "sum" | "min" | "max" per tensor of
         weights (SELECT key, MIN(x), MAX(x), SUM(y) ..; scatter_reduce_ with amin / amax): sums[k] is then that aggregate of weights[k]
         over the group, minimum and maximum of the int64 values (rhj_group_agg_cols_dev; the same tensor may be given twice).  A
-        wrong length or name: ValueError before any launch.  Costs as for sums, whatever the ops."""
+        wrong length or name: ValueError before any launch.  Costs as for sums, whatever the ops.
+        The group of every row beside them: group_by_columns_with_inverse."""
+        return self._group_by_columns(keys, weights, ops, False)
+
+    def group_by_columns_with_inverse(self, keys, weights=(), ops=None):
+        """(unique_keys, counts, sums, inverse): group_by_columns with torch.unique's return_inverse -- inverse an int64 tensor of
+        len(keys) with unique_keys[inverse] == keys, the group every row belongs to, so that whatever the ops do not cover (a mean,
+        a float sum, an argmin, the group's total broadcast back to its rows) is a direct-indexed torch op behind one call.  The
+        order of groups is unspecified and may differ from run to run: inverse goes with this call's unique_keys.  Everything else
+        as group_by_columns (rhj_group_agg_ids_cols_dev: one more sweep per class and one scattered 8-byte store per row)."""
+        return self._group_by_columns(keys, weights, ops, True)
+
+    def _group_by_columns(self, keys, weights, ops, return_inverse):
         import torch
         weights = tuple(weights)
         if len(weights) > GROUP_MAX_COLS:
@@ -763,13 +845,25 @@ class Engine:
             out_keys = torch.empty(n, dtype=torch.int64, device=dev)
             counts = torch.empty(n, dtype=torch.int64, device=dev)
             sums = [torch.empty(n, dtype=torch.int64, device=dev) for _ in weights]
+            inverse = torch.empty(n, dtype=torch.int64, device=dev) if return_inverse else None
             if not n:
                 groups = 0
+            elif return_inverse:
+                groups = self.group_agg_ids_cols_dev(keys, None, n, weights, ops, n, out_keys, counts, sums, n, inverse, n)
             elif ops is None:
                 groups = self.group_sum_cols_dev(keys, None, n, weights, n, out_keys, counts, sums, n)
             else:
                 groups = self.group_agg_cols_dev(keys, None, n, weights, ops, n, out_keys, counts, sums, n)
+        if return_inverse:
+            return out_keys[:groups], counts[:groups], [s[:groups] for s in sums], inverse
         return out_keys[:groups], counts[:groups], [s[:groups] for s in sums]
+
+    def factorize_columns(self, keys):
+        """(codes, uniques): pandas.factorize without the ordering promise -- uniques the distinct values of keys in no particular
+        order, codes an int64 tensor of len(keys) with uniques[codes] == keys (dictionary encoding of a 64-bit key column into dense
+        ids).  Tensors, streams and completion as group_by_columns_with_inverse, which this is without the counts."""
+        uniques, _, _, codes = self._group_by_columns(keys, (), None, True)
+        return codes, uniques
 
     def join_group_by_columns(self, keys_R, keys_S, weights_R=(), weights_S=(), how="inner", ops_R=None, ops_S=None):
         """(keys, count, sums_R, sums_S): SELECT key, COUNT(*), SUM(r.a).., SUM(s.b).. FROM R JOIN S USING (key) GROUP BY key -- per
@@ -789,7 +883,20 @@ class Engine:
         values over the group's pairs, which is the one over that side's rows: it is returned RAW, with no multiplication by the
         other side's count.  Under how="left" S's "min" / "max" of a value keys_S lacks is the op's identity (min: INT64_MAX, max:
         INT64_MIN; SQL's NULL), its "sum" 0.  With both None the call is rhj_group_join_cols_dev, otherwise
-        rhj_group_join_agg_cols_dev.  A wrong length or name: ValueError before any launch.  Costs as for sums, whatever the ops."""
+        rhj_group_join_agg_cols_dev.  A wrong length or name: ValueError before any launch.  Costs as for sums, whatever the ops.
+        The group of every row of either side beside them: join_group_by_columns_with_inverse."""
+        return self._join_group_by_columns(keys_R, keys_S, weights_R, weights_S, how, ops_R, ops_S, False)
+
+    def join_group_by_columns_with_inverse(self, keys_R, keys_S, weights_R=(), weights_S=(), how="inner", ops_R=None, ops_S=None):
+        """(keys, count, sums_R, sums_S, (inverse_R, inverse_S)): join_group_by_columns with the group of every row -- int64 tensors
+        of len(keys_R) / len(keys_S) with keys[inverse_R[i]] == keys_R[i] and keys[inverse_S[j]] == keys_S[j] where the row's value
+        has a group, and -1 (SQL's NULL) where it has none: under how="inner" the rows whose value the other tensor lacks, under
+        how="left" only such rows of keys_S.  A joint dictionary encoding of two key tensors: shared dense ids, "no partner" marked.
+        Ids go with this call's keys.  Everything else as join_group_by_columns (rhj_group_join_agg_ids_cols_dev: both id tensors are
+        filled, then one more sweep per side and class and one scattered 8-byte store per row that has a group)."""
+        return self._join_group_by_columns(keys_R, keys_S, weights_R, weights_S, how, ops_R, ops_S, True)
+
+    def _join_group_by_columns(self, keys_R, keys_S, weights_R, weights_S, how, ops_R, ops_S, return_inverse):
         import torch
         weights_R, weights_S = tuple(weights_R), tuple(weights_S)
         if how not in ("inner", "left"):
@@ -809,8 +916,15 @@ class Engine:
             # ... or, for a minimum / maximum, the op's identity)
             sumsS = [new() if nS else torch.full((nR,), _AGG_IDENTITY_I64[o], dtype=torch.int64, device=dev) for o in ops_S]
             mode = GJ_LEFT if how == "left" else GJ_INNER
+            if return_inverse:
+                inv_R = new()
+                inv_S = torch.full((nS,), -1, dtype=torch.int64, device=dev)     # (an empty tensor has no address: it stays out of the call)
             if not nR:
                 groups = 0
+            elif return_inverse:
+                groups = self.group_join_agg_ids_cols_dev(keys_R, None, nR, keys_S if nS else None, None, nS, weights_R, ops_R, nR,
+                                                          weights_S if nS else (), ops_S if nS else None, nS, mode, out_keys, cntR, cntS,
+                                                          sumsR, sumsS if nS else (), nR, inv_R, nR, inv_S if nS else None, nS)
             elif not with_ops:
                 groups = self.group_join_cols_dev(keys_R, None, nR, keys_S if nS else None, None, nS, weights_R, nR,
                                                   weights_S if nS else (), nS, mode, out_keys, cntR, cntS, sumsR, sumsS if nS else (), nR)
@@ -820,8 +934,9 @@ class Engine:
                                                       sumsR, sumsS if nS else (), nR)
         cntR, cntS = cntR[:groups], cntS[:groups]
         mult_R = cntS.clamp(min=1) if how == "left" else cntS    # (counts are < 2^63: clamp on int64 is on the true values)
-        return (out_keys[:groups], cntR * mult_R, [s[:groups] * mult_R if o == AGG_SUM else s[:groups] for s, o in zip(sumsR, ops_R)],
-                [s[:groups] * cntR if o == AGG_SUM else s[:groups] for s, o in zip(sumsS, ops_S)])
+        out = (out_keys[:groups], cntR * mult_R, [s[:groups] * mult_R if o == AGG_SUM else s[:groups] for s, o in zip(sumsR, ops_R)],
+               [s[:groups] * cntR if o == AGG_SUM else s[:groups] for s, o in zip(sumsS, ops_S)])
+        return out + ((inv_R, inv_S),) if return_inverse else out
 
     def mul_u64(self, d_a, d_b, n, d_dst):
         """rhj_mul_u64: d_dst[i] = d_a[i] * d_b[i] mod 2^64 (d_dst may be d_a)"""

@@ -259,6 +259,11 @@ struct rhj_ctx {
     u64 *gjoin_cntS = nullptr;         // capacity words (device; may be null)
     u64 *gjoin_sumsS[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
     bool gjoin_left = false;           // RHJ_GJ_LEFT
+    // the id arrays of a group-by ([0]) or group-by join ([0] R's, [1] S's) with ids, for the length of the call: device
+    // arrays of gid_rows[.] words indexed by the side's rowID, null: none; device words: agg_out's [1 .. 4], flag bits GROUP_BAD_GID /
+    // GJOIN_BAD_GID_*
+    u64 *gid[2] = {nullptr, nullptr};
+    u64 gid_rows[2] = {0, 0};
     DevBuf narrow_flag;                // u32: a rowID >= 2^32 met a narrow scatter -> the join re-runs in the 16-byte format
     // ... the next join tries the narrow format again; consecutive fall-backs make the context skip the attempt for the next
     // 2, 4, ... 32 eligible joins (a caller whose rowIDs are always wide pays one extra histogram per relation now and then)
@@ -1605,6 +1610,7 @@ int group_phase(rhj_ctx *ctx, u64 *out_groups)
         if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(ctx->ps_S.p, 0, (size_t)(nparts + 1) * 8, ctx->stream));   // every partition of S: empty, at 0
+        if (ctx->gid[0]) launch_group_id_words(ctx->stream, d_agg, ctx->gid[0], ctx->gid_rows[0], nullptr, 0);
     }
     ctx->counters_clean = false;
     if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
@@ -1624,7 +1630,7 @@ int group_phase(rhj_ctx *ctx, u64 *out_groups)
                      ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, ctx->agg_cols, ctx->agg_ncols, ctx->agg_col_rows,
                      ctx->group_keys, ctx->group_counts, ctx->group_sums, ctx->group_cap, d_agg, (u32 *)(d_agg + AGG_MAX_COLS + 1),
                      d_count + 7, narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                     narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops);
+                     narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops, ctx->gid[0] != nullptr);
     }
     RHJCHK(check_launch(ctx, "group-by phase"));
     u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, -, -, -, -, most table builds of a task (if > 1)
@@ -1642,9 +1648,20 @@ int group_phase(rhj_ctx *ctx, u64 *out_groups)
     ctx->last_group_rounds = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
     if (host[2] >> 32)                                           // (such a partition was cut in two: its groups are not the result)
         return fail(ctx, RHJ_E_INVALID, "a partition of R has " + std::to_string(host[2]) + " tuples (>= 2^32): use more radix bits");
-    if ((u32)agg[AGG_MAX_COLS + 1])
+    if ((u32)agg[AGG_MAX_COLS + 1] & GROUP_BAD_ROW)
         return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= col_rows: the weight columns have no such row");
+    if ((u32)agg[AGG_MAX_COLS + 1] & GROUP_BAD_GID)
+        return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= gid_rows: d_out_gid has no such word");
     *out_groups = agg[0];
+    return RHJ_OK;
+}
+
+// The id arrays of a group-by join, all ones -- "no group" -- in every word, on the context's stream.
+static int fill_no_group(rhj_ctx *ctx)
+{
+    for (int side = 0; side < 2; side++)
+        if (ctx->gid[side] && ctx->gid_rows[side])
+            HIPCHK(ctx, hipMemsetAsync(ctx->gid[side], 0xff, (size_t)ctx->gid_rows[side] * 8, ctx->stream));
     return RHJ_OK;
 }
 
@@ -1657,7 +1674,7 @@ int group_phase(rhj_ctx *ctx, u64 *out_groups)
 int gjoin_phase(rhj_ctx *ctx, u64 *out_groups)
 {
     const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
-    const bool narrow = ctx->cur_narrow != 0, one = ctx->one_sided;
+    const bool narrow = ctx->cur_narrow != 0, one = ctx->one_sided, ids = ctx->gid[0] != nullptr || ctx->gid[1] != nullptr;
     const u32 split = 0xffffffffu;                     // a partition is never cut: its keys would be emitted twice
     const u64 max_tasks64 = nparts + nR / split + 1;
     if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
@@ -1672,6 +1689,10 @@ int gjoin_phase(rhj_ctx *ctx, u64 *out_groups)
         if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
         if (one) HIPCHK(ctx, hipMemsetAsync(ctx->ps_S.p, 0, (size_t)(nparts + 1) * 8, ctx->stream));   // every partition of S: empty, at 0
+        if (ids) {                                     // "no group" everywhere, on every attempt: the kernel stores group indices only
+            RHJCHK(fill_no_group(ctx));
+            launch_group_id_words(ctx->stream, d_agg, ctx->gid[0], ctx->gid_rows[0], ctx->gid[1], ctx->gid_rows[1]);
+        }
     }
     ctx->counters_clean = false;
     if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
@@ -1696,7 +1717,7 @@ int gjoin_phase(rhj_ctx *ctx, u64 *out_groups)
                           (u32 *)(d_agg + AGG_MAX_COLS + 1), d_count + 7,
                           narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
                           narrow && ctx->cur_S ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
-                          narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops);
+                          narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops, ids);
     }
     RHJCHK(check_launch(ctx, "group-by join phase"));
     u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, an |S_k| >= 2^32, -, most table builds of a task (if > 1)
@@ -1719,6 +1740,8 @@ int gjoin_phase(rhj_ctx *ctx, u64 *out_groups)
     const u32 bad = (u32)agg[AGG_MAX_COLS + 1];
     if (bad & GJOIN_BAD_ROW_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= colR_rows: the weight columns of R have no such row");
     if (bad & GJOIN_BAD_ROW_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= colS_rows: the weight columns of S have no such row");
+    if (bad & GJOIN_BAD_GID_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= gidR_rows: d_out_gidR has no such word");
+    if (bad & GJOIN_BAD_GID_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= gidS_rows: d_out_gidS has no such word");
     *out_groups = agg[0];
     return RHJ_OK;
 }
@@ -2423,7 +2446,8 @@ static u32 pack_ops(const uint32_t *ops, u32 ncols, u32 first, u32 *packed)
 
 static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols,
                         uint64_t col_rows, const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
-                        uint64_t *const *d_out_sums, uint64_t out_capacity, uint64_t *out_groups)
+                        uint64_t *const *d_out_sums, uint64_t out_capacity, uint64_t *out_groups, uint64_t *d_out_gid = nullptr,
+                        uint64_t gid_rows = 0)
 {
     if (ncols > RHJ_GROUP_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncols is above RHJ_GROUP_MAX_COLS");
     u32 packed = 0;
@@ -2448,9 +2472,13 @@ static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *c
     ctx->group_counts = d_out_keys ? (u64 *)d_out_counts : nullptr;
     ctx->group_cap = d_out_keys ? out_capacity : 0;
     ctx->group_ops = packed;
+    ctx->gid[0] = (u64 *)d_out_gid;
+    ctx->gid_rows[0] = d_out_gid ? gid_rows : 0;
     ctx->one_sided = true;
     const int rc = partition_and_join(ctx, d_R, nR, nullptr, nR, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GROUP);
     ctx->one_sided = false;
+    ctx->gid[0] = nullptr;
+    ctx->gid_rows[0] = 0;
     ctx->agg_ncols = 0;
     ctx->group_ops = 0;
     ctx->group_keys = ctx->group_counts = nullptr;
@@ -2526,6 +2554,40 @@ int rhj_group_agg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
     return rc;
 }
 
+// ... with the group of every row: the same host path, the id array beside the outputs; a null array: the entry above
+int rhj_group_agg_ids_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
+                          const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                          uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_aggs,
+                          uint64_t out_capacity, uint64_t *out_groups, uint64_t *d_out_gid, uint64_t gid_rows)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return group_common(ctx, d_R, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity, out_groups,
+                        d_out_gid, gid_rows);
+}
+
+int rhj_group_agg_ids_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                               const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
+                               uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_aggs,
+                               uint64_t out_capacity, uint64_t *out_groups, uint64_t *d_out_gid, uint64_t gid_rows)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if (nR && !d_valR) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
+    ctx->cols_in[1] = ColsIn();
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = group_common(ctx, nullptr, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity,
+                                out_groups, d_out_gid, gid_rows);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
 // Group-by join: the two-sided partition phase and the repeat ladder of rhj_join_mult_dev / rhj_join_mult_cols_dev,
 // then gjoin_phase.  d_R / d_S null: the relations are ctx->cols_in.  An empty S under RHJ_GJ_LEFT: R alone, one-sided and planned
 // as the group-by plans it, over a zeroed boundary array of S.
@@ -2534,7 +2596,8 @@ static int group_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *
                              const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
                              const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows, int mode, const rhj_opts *opts,
                              uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
-                             uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS, uint64_t out_capacity, uint64_t *out_groups)
+                             uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS, uint64_t out_capacity, uint64_t *out_groups,
+                             uint64_t *d_out_gidR = nullptr, uint64_t gidR_rows = 0, uint64_t *d_out_gidS = nullptr, uint64_t gidS_rows = 0)
 {
     if (mode != RHJ_GJ_INNER && mode != RHJ_GJ_LEFT) return fail(ctx, RHJ_E_INVALID, "mode is neither RHJ_GJ_INNER nor RHJ_GJ_LEFT");
     if (ncolsR > RHJ_GROUP_JOIN_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncolsR is above RHJ_GROUP_JOIN_MAX_COLS");
@@ -2554,7 +2617,14 @@ static int group_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *
         if (!d_colsR[j] || !d_out_sumsR[j]) return fail(ctx, RHJ_E_INVALID, "null weight column or sum column of R");
     for (u32 j = 0; j < nsumS; j++)
         if (!d_colsS[j] || !d_out_sumsS[j]) return fail(ctx, RHJ_E_INVALID, "null weight column or sum column of S");
-    if (nR == 0 || (nS == 0 && mode == RHJ_GJ_INNER)) return join_nothing(ctx);
+    ctx->gid[0] = (u64 *)d_out_gidR; ctx->gid_rows[0] = d_out_gidR ? gidR_rows : 0;
+    ctx->gid[1] = (u64 *)d_out_gidS; ctx->gid_rows[1] = d_out_gidS ? gidS_rows : 0;
+    struct GidReset { rhj_ctx *c; ~GidReset() { c->gid[0] = c->gid[1] = nullptr; c->gid_rows[0] = c->gid_rows[1] = 0; } } gid_reset{ctx};
+    if (nR == 0 || (nS == 0 && mode == RHJ_GJ_INNER)) {    // no group, no kernel: every id word says so when the call returns
+        RHJCHK(fill_no_group(ctx));
+        if (ctx->gid[0] || ctx->gid[1]) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return join_nothing(ctx);
+    }
     const bool one = nS == 0;                          // LEFT over an empty S: the group-by of R with zero S fields
     rhj_opts plan;
     if (resolve_plan(nR, one ? nR : nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
@@ -2670,6 +2740,52 @@ int rhj_group_join_agg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
     const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows,
                                      mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// ... with the group of every row of either side: the same host path, the id arrays beside the outputs
+int rhj_group_join_agg_ids_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                               const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+                               const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows,
+                               int mode, const rhj_opts *opts,
+                               uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+                               uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
+                               uint64_t out_capacity, uint64_t *out_groups,
+                               uint64_t *d_out_gidR, uint64_t gidR_rows, uint64_t *d_out_gidS, uint64_t gidS_rows)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return group_join_common(ctx, d_R, nR, d_S, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows, mode, opts,
+                             d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups,
+                             d_out_gidR, gidR_rows, d_out_gidS, gidS_rows);
+}
+
+int rhj_group_join_agg_ids_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                                    const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
+                                    const uint64_t *const *d_colsR, const uint32_t *opsR, uint32_t ncolsR, uint64_t colR_rows,
+                                    const uint64_t *const *d_colsS, const uint32_t *opsS, uint32_t ncolsS, uint64_t colS_rows,
+                                    int mode, const rhj_opts *opts,
+                                    uint64_t *d_out_keys, uint64_t *d_out_cntR, uint64_t *d_out_cntS,
+                                    uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
+                                    uint64_t out_capacity, uint64_t *out_groups,
+                                    uint64_t *d_out_gidR, uint64_t gidR_rows, uint64_t *d_out_gidS, uint64_t gidS_rows)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with no column)
+    if (nS) { ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS; }
+    else ctx->cols_in[1] = ColsIn();
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows,
+                                     mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups,
+                                     d_out_gidR, gidR_rows, d_out_gidS, gidS_rows);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

@@ -298,6 +298,7 @@ void launch_mult_join(hipStream_t st, const void *d_R, const void *d_S, const Jo
 // group (8 B), the THREADS / 64 words of a workgroup scan, the 2 x AGG_MAX_COLS column pointers and one word for the columns' op
 // words (k_group_bkt<., GB_OPS>).  One workgroup of 1024 threads per task, one task per partition.
 constexpr int JK_GROUP = JK_MULT + 1;             // "last.join_kernel" of a group-by (15)
+constexpr u32 GROUP_BAD_ROW = 1, GROUP_BAD_GID = 2;      // bits of *d_bad: a rowID >= col_rows; (a launch with ids) a rowID >= gid_rows
 constexpr size_t GROUP_LDS_EXTRA = 8 + (size_t)(AGG_THREADS / 64) * 4 + (size_t)(2 * AGG_MAX_COLS + 1) * 8;
 // The aggregate of a column, as the group kernels take it: AGG_OP_BITS bits per column -- the LDS atomic, and whether
 // the word is biased by 1 << 63 on its way in and out (a signed minimum or maximum as an unsigned one).  A call's op words are
@@ -316,15 +317,22 @@ static_assert(group_lds_bytes() <= 160 * 1024 && mult_lds_bytes(true) % 8 == 0 &
 // (never dereferenced; ncols != 0 only); d_max_rounds: atomicMax of the table builds of a task, by tasks that built several; d_RK:
 // the rowID array of narrow partitions, or null; d_skip: as launch_join.  ops: the columns' packed op words (AGG_OP_*); 0 -- every
 // column a sum -- launches k_group_bkt<., GB_COUNT | GB_SUMS> as before, anything else with ncols != 0 k_group_bkt<., GB_OPS>.
+// ids: the same kernel with an id sweep behind the last column sweep of every class (k_group_bkt<., . | GB_IDS>);
+// d_ngroups is then FIVE words, the four behind the counter written by launch_group_id_words before this launch (the second pair
+// unused); d_bad is OR-ed with 2 when a rowID >= gid_rows was met (never stored to).  false: the launch is the one it was.
 void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits, bool mixed,
                   const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_out_keys, u64 *d_out_counts, u64 *const *d_out_sums,
-                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip, u32 ops);
+                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip, u32 ops,
+                  bool ids = false);
+// The id arrays of a launch with ids (either may be null: no sweep of that side) and their lengths in words, into d_ngroups[1 .. 4].
+void launch_group_id_words(hipStream_t st, u64 *d_ngroups, u64 *d_gidR, u64 gidR_rows, u64 *d_gidS, u64 gidS_rows);
 // ---- the group-by join kernel (k_gjoin_bkt): k_group_bkt's table and class walk over R, looked up by S ---------------
 // group_lds_bytes() plus room for the pointers of S's side (4 x AGG_MAX_COLS column and output pointers in all) and for nine more
 // kernel arguments, which would otherwise spill SGPRs; group_lds_bytes()'s word of op words comes last (k_gjoin_bkt<., GB_OPS>).  The slot word holds
 // cntR | cntS << 32 during the count sweeps (a second 32 KiB count array would end 16 bytes above 160 KiB).
 constexpr int JK_GJOIN = JK_GROUP + 1;            // "last.join_kernel" of a group-by join (16)
 constexpr u32 GJOIN_BAD_ROW_R = 1, GJOIN_BAD_ROW_S = 2;   // bits of *d_bad
+constexpr u32 GJOIN_BAD_GID_R = 4, GJOIN_BAD_GID_S = 8;   // ... of a launch with ids: a rowID >= gidR_rows / gidS_rows was met
 constexpr u32 GJOIN_PAR_WORDS = 9;                // further kernel arguments kept in LDS across the class walk (k_gjoin_bkt)
 constexpr size_t gjoin_lds_bytes() { return group_lds_bytes() + (size_t)(2 * AGG_MAX_COLS + GJOIN_PAR_WORDS) * 8; }
 static_assert(gjoin_lds_bytes() <= 160 * 1024 && gjoin_lds_bytes() % 8 == 0, "k_gjoin_bkt's geometry");
@@ -336,11 +344,13 @@ static_assert(gjoin_lds_bytes() <= 160 * 1024 && gjoin_lds_bytes() % 8 == 0, "k_
 // caller); d_bad: OR-ed with GJOIN_BAD_ROW_R / _S when a rowID >= colR_rows / colS_rows was met (never dereferenced); d_max_rounds as
 // launch_group; d_RK / d_SK: the rowID arrays of narrow partitions, or d_RK null: 16-byte tuples; d_skip: as launch_join.  ops: both
 // sides' packed op words (AGG_OP_*); 0 launches k_gjoin_bkt<., GB_COUNT | GB_SUMS> as before, anything else with a column k_gjoin_bkt<., GB_OPS>.
+// ids as launch_group: d_ngroups[1 .. 4] = gidR, gidR_rows, gidS, gidS_rows; the kernel stores a group index for the tuples that
+// have one and nothing else -- the caller fills both arrays with all ones first; d_bad is OR-ed with GJOIN_BAD_GID_R / _S.
 void launch_group_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
                        int radix_bits, bool mixed, bool left_mode, const u64 *const *d_colsR, u32 ncolsR, u64 colR_rows,
                        const u64 *const *d_colsS, u32 ncolsS, u64 colS_rows, u64 *d_out_keys, u64 *d_out_cntR, u64 *d_out_cntS,
                        u64 *const *d_out_sumsR, u64 *const *d_out_sumsS, u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds,
-                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip, u32 ops);
+                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip, u32 ops, bool ids = false);
 // in_narrow: d_in is a payload array (u64).  key_base / d_wide (16-byte input): d_wide (may be null) is OR-ed with 1 when some
 // rowID - key_base does not fit 32 bits.  d_unit_rng (may be null): explicit pass-1 units (launch_seg_units).
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,

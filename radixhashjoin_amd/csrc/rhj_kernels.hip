@@ -2961,7 +2961,14 @@ struct GroupSums { u64 *c[AGG_MAX_COLS]; };
 // 1 << 63 into the gathered word and into the accumulator on its way out, so the table only ever takes an unsigned minimum or
 // maximum.  The op words of a call travel in one kernel argument, four bits per column (AGG_OP_*), and wait in LDS beside the column
 // pointers; a column's word is read once per sweep and selects the sweep's loop, not an atomic inside it.
-enum : int { GB_COUNT = 0, GB_SUMS = 1, GB_OPS = 2 };
+enum : int { GB_COUNT = 0, GB_SUMS = 1, GB_OPS = 2, GB_KIND = 3, GB_IDS = 4 };
+// GB_IDS, OR-ed to any of the three: after the last column sweep of a class that emitted, one more sweep stores every
+// tuple's group index at gid[rowID].  The slot words are free by then: each takes its slot's group index (base + rank, from the saved
+// mask; all ones where the slot emits nothing), the word of the all-ones key takes that key's, and the class's tuples look their key
+// up as a column sweep does -- but read the word where a column sweep adds to it, and store it behind the rowID < gid_rows guard (a
+// row beyond is never written: *bad).  No atomic; an id is never compared with the capacity.  The id arrays and their lengths are not
+// kernel arguments (the walk has no SGPR to hold them in and LDS no word): they wait in the words behind the group counter,
+// ngroups[1 .. 4] = gidR, gidR_rows, gidS, gidS_rows (launch_group_id_words; a null array gets no sweep; k_group_bkt reads the first two).
 using AggAdd = std::integral_constant<u32, AGG_OP_ADD>;
 using AggMin = std::integral_constant<u32, AGG_OP_MIN>;
 using AggMax = std::integral_constant<u32, AGG_OP_MAX>;
@@ -2980,7 +2987,8 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
             u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip,
             u32 ops)
 {
-    constexpr bool SUMS = AGG != GB_COUNT;
+    constexpr int KIND = AGG & GB_KIND;
+    constexpr bool SUMS = KIND != GB_COUNT, IDS = (AGG & GB_IDS) != 0;
     if (skip != nullptr && *skip != 0) return;
     if (blockIdx.x >= *ntasks) return;
     constexpr int THREADS = AGG_THREADS;
@@ -3008,11 +3016,11 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
         if (tid == 0) {
 #pragma unroll
             for (int j = 0; j < AGG_MAX_COLS; j++) { colp[j] = (u64)cols.c[j]; colp[AGG_MAX_COLS + j] = (u64)out_sums.c[j]; }
-            if constexpr (AGG == GB_OPS) colp[2 * AGG_MAX_COLS] = ops;       // GB_OPS: the op words behind the pointers
+            if constexpr (KIND == GB_OPS) colp[2 * AGG_MAX_COLS] = ops;       // GB_OPS: the op words behind the pointers
         }                                                                    // (read behind the barriers of the first build)
     u32 d = 0, rounds = 0;                                                   // the class (d, p); table builds so far
     u64 p = 0;
-    bool wild = false;
+    bool wild = false, wild_id = false;
     auto in_class = [&](u64 key) -> bool {
         if (d == 0) return true;
         const u64 mask = d >= 64 ? ~0ull : (1ull << d) - 1;
@@ -3048,6 +3056,13 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
             if (cur == key) { lds_agg<decltype(kind)::value>(&acc[s], v); return; }
             if (cur == SEMI_EMPTY) return;
         }
+    };
+    auto word_of = [&](u64 key) -> u64 {                                     // GB_IDS: add_on's walk, reading the slot word; all ones: the key is not there
+        u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);          // (one exit and selects behind it: every nested branch of a
+        u64 cur = tab[s];                                                    // walk that returns from three places is an exec mask in SGPRs)
+        while (cur != key && cur != SEMI_EMPTY) { s = (s + 1) & (SLOTS - 1); cur = tab[s]; }
+        const u64 w = acc[s], o = *ones;                                     // (the all-ones key ends at the first empty slot, and takes `ones`)
+        return key == SEMI_EMPTY ? o : cur == key ? w : ~0ull;
     };
     auto load_key = [&](u32 at) -> u64 {                                     // tuple at + tid of the partition; 0 beyond its end
         return Rv.buf(at, np - at < AGG_BUILD_TILE ? np - at : AGG_BUILD_TILE).payload(0u, (u32)tid);
@@ -3116,7 +3131,7 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
             for (u32 c = 0; c < ncols; c++) {
                 const u64 *__restrict__ col = reinterpret_cast<const u64 *>(colp[c]);
                 u64 *__restrict__ dst = reinterpret_cast<u64 *>(colp[AGG_MAX_COLS + c]);
-                if constexpr (AGG == GB_OPS) {                               // the column's op word decides start, skip, atomic and bias
+                if constexpr (KIND == GB_OPS) {                               // the column's op word decides start, skip, atomic and bias
                     const u32 op = (u32)__builtin_amdgcn_readfirstlane((int)((u32)colp[2 * AGG_MAX_COLS] >> (AGG_OP_BITS * c)));
                     u64 init = (op & AGG_OP_KIND) == AGG_OP_MIN ? ~0ull : 0ull;   // the op's identity: where a word starts, what a sweep may skip
                     u64 bias = op & AGG_OP_SIGNED ? 1ull << 63 : 0ull;
@@ -3191,6 +3206,37 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
             }
         }
 
+        // ---- the ids: every slot word takes its group, the class's tuples read it and store it at their row ------------------
+        if constexpr (IDS) {
+            u64 *__restrict__ gid = reinterpret_cast<u64 *>(ngroups[1]);
+            const u64 gid_rows = ngroups[2];
+            if (gid != nullptr) {
+                __syncthreads();                                             // the accumulators have been emitted
+                {
+                    u64 g = g0;
+#pragma unroll 1
+                    for (u32 j = 0; j < SPT; j++)
+                        if (occ >> j & 1u) acc[(u32)tid * SPT + j] = g++;
+                    if (tid == 0 && ho) *ones = *base_s + filled;
+                }
+                __syncthreads();
+                Both t = Rv.buf(0u, np < (u32)THREADS ? np : (u32)THREADS).both(0u, (u32)tid), t_next = t;
+                for (u32 tb = 0; tb < np; tb += THREADS) {
+                    const u32 left = np - tb;                                // tuples from this tile on
+                    if (left > (u32)THREADS)                                 // the next tile travels behind this one's stores
+                        t_next = Rv.buf(tb + (u32)THREADS, left - THREADS < (u32)THREADS ? left - THREADS : (u32)THREADS).both(0u, (u32)tid);
+                    if ((u32)tid < left) {
+                        if ((u64)t.key >= gid_rows) wild_id = true;
+                        else if (in_class(t.payload)) {
+                            const u64 g = word_of(t.payload);
+                            if (g != ~0ull) gid[(u64)t.key] = g;
+                        }
+                    }
+                    t = t_next;
+                }
+            }
+        }
+
         // ---- the next class: prefix increment, bit 0 the most significant digit ----------------------------------------------
         while (d > 0 && (p >> (d - 1) & 1ull)) { p &= ~(1ull << (d - 1)); d--; }
         if (d == 0) break;
@@ -3199,6 +3245,8 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
     }
 
     if (__ballot(wild) && lane == 0) atomicOr(bad, 1u);
+    if constexpr (IDS)
+        if (__ballot(wild_id) && lane == 0) atomicOr(bad, GROUP_BAD_GID);
     if (tid == 0 && rounds > 1) atomicMax((unsigned long long *)max_rounds, (unsigned long long)rounds);
 }
 
@@ -3229,7 +3277,8 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
             u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip,
             u32 ops)
 {
-    constexpr bool SUMS = AGG != GB_COUNT;
+    constexpr int KIND = AGG & GB_KIND;
+    constexpr bool SUMS = KIND != GB_COUNT, IDS = (AGG & GB_IDS) != 0;
     if (skip != nullptr && *skip != 0) return;
     if (blockIdx.x >= *ntasks) return;
     constexpr int THREADS = AGG_THREADS;
@@ -3244,7 +3293,9 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
     u64 *base_s = reinterpret_cast<u64 *>(smem + mult_lds_bytes(true));      // the class's first group
     u32 *wsum = reinterpret_cast<u32 *>(base_s + 1);                         // THREADS / 64 words of block_excl_scan
     u64 *colp = reinterpret_cast<u64 *>(wsum + THREADS / 64);                // SUMS: colsR, sumsR, colsS, sumsS -- AGG_MAX_COLS words each
-    u64 *par = colp + 4 * AGG_MAX_COLS;                                      // GJOIN_PAR_WORDS more kernel arguments that the walk does not
+    u32 zv = 0;
+    if constexpr (IDS) asm volatile("" : "+v"(zv));                          // (an opaque zero: the id kernels address par[] from one VGPR, not from an SGPR per word)
+    u64 *par = colp + 4 * AGG_MAX_COLS + zv;                                 // GJOIN_PAR_WORDS more kernel arguments that the walk does not
                                                                              // hold in SGPRs: colR_rows, colS_rows, out_keys, out_cntR, out_cntS, capacity, ngroups, bad, max_rounds
 
     const JoinTask task = tasks[blockIdx.x];
@@ -3257,7 +3308,7 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
     if (tid == 0) {
         par[0] = colR_rows; par[1] = colS_rows; par[2] = (u64)out_keys; par[3] = (u64)out_cntR; par[4] = (u64)out_cntS; par[5] = capacity;
         par[6] = (u64)ngroups; par[7] = (u64)bad; par[8] = (u64)max_rounds;
-        if constexpr (AGG == GB_OPS) par[GJOIN_PAR_WORDS] = ops;             // GB_OPS: the op words, R's columns in the low half, S's above
+        if constexpr (KIND == GB_OPS) par[GJOIN_PAR_WORDS] = ops;             // GB_OPS: the op words, R's columns in the low half, S's above
     }                                                                        // (read behind the barriers of the first build)
     if constexpr (SUMS)
         if (tid == 0) {
@@ -3270,6 +3321,8 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
     u32 d = 0, rounds = 0;                                                   // the class (d, p); table builds so far
     u64 p = 0;
     u32 wild = 0;                                                            // GJOIN_BAD_ROW_* this thread met
+    int lm = left_mode;
+    if constexpr (IDS) asm volatile("" : "+v"(lm));                          // (opaque: uniform, but the id kernels have no SGPR for it across the walk)
     auto in_class = [&](u64 key) -> bool {
         if (d == 0) return true;
         const u64 mask = d >= 64 ? ~0ull : (1ull << d) - 1;
@@ -3306,6 +3359,13 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
             if (cur == SEMI_EMPTY) return;
         }
     };
+    auto word_of = [&](u64 key) -> u64 {                                     // GB_IDS: add_on's walk, reading the slot word; all ones: the key is not there
+        u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);          // (one exit and selects behind it: every nested branch of a
+        u64 cur = tab[s];                                                    // walk that returns from three places is an exec mask in SGPRs)
+        while (cur != key && cur != SEMI_EMPTY) { s = (s + 1) & (SLOTS - 1); cur = tab[s]; }
+        const u64 w = acc[s], o = *ones;                                     // (the all-ones key ends at the first empty slot, and takes `ones`)
+        return key == SEMI_EMPTY ? o : cur == key ? w : ~0ull;
+    };
     auto load_key = [&](const RelView<NARROW> &V, u32 n, u32 at) -> u64 {    // tuple at + tid of a partition of n; 0 beyond its end
         return V.buf(at, n - at < AGG_BUILD_TILE ? n - at : AGG_BUILD_TILE).payload(0u, (u32)tid);
     };
@@ -3316,6 +3376,7 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
         if (tid == 0) { *ones = 0; *nkeys = 0; *has_ones = 0; }
         __syncthreads();
         rounds++;
+        if constexpr (IDS) asm volatile("" : "+v"(p), "+v"(rounds));         // (opaque: uniform, but the id kernels have no three SGPRs for them across the walk)
         u32 filled = 0;
         {
             u64 key = load_key(Rv, np, 0), key_next = 0;
@@ -3355,10 +3416,10 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
 #pragma unroll
         for (u32 j = 0; j < SPT; j++) {
             const u32 s = (u32)tid * SPT + j;
-            const bool on = tab[s] != SEMI_EMPTY && (left_mode || (acc[s] >> 32) != 0);
+            const bool on = tab[s] != SEMI_EMPTY && (lm || (acc[s] >> 32) != 0);
             em |= (on ? 1u : 0u) << j;
         }
-        const u32 hoe = (u32)__builtin_amdgcn_readfirstlane((int)(*has_ones != 0 && (left_mode || (*ones >> 32) != 0) ? 1u : 0u));
+        const u32 hoe = (u32)__builtin_amdgcn_readfirstlane((int)(*has_ones != 0 && (lm || (*ones >> 32) != 0) ? 1u : 0u));
         u32 tot;
         int tq = tid;                                                        // (opaque, as in k_group_bkt)
         asm volatile("" : "+v"(tq));
@@ -3397,7 +3458,7 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
             // ---- the sums, one column at a time over the table as it stands: R's columns over R's tuples, then S's over S's --
             if constexpr (SUMS) {
                 const u32 nc = ncolsR + ncolsS;
-                if constexpr (AGG == GB_OPS) __builtin_assume(nc != 0);      // (launch_group_join: no column, no op -- a hoisted test is two SGPRs spilled)
+                if constexpr (KIND == GB_OPS || IDS) __builtin_assume(nc != 0);   // (launch_group_join: no column, no op, no SUMS -- a hoisted test is two SGPRs spilled)
                 for (u32 c = 0; c < nc; c++) {
                     const bool on_s = c >= ncolsR;                           // (uniform) R's columns over R's tuples, then S's over S's
                     const RelView<NARROW> V = on_s ? Sv : Rv;
@@ -3405,7 +3466,7 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
                     const u64 *__restrict__ col = reinterpret_cast<const u64 *>(colp[ci]);
                     u64 *__restrict__ dst = reinterpret_cast<u64 *>(colp[ci + AGG_MAX_COLS]);
                     const u64 rows = par[on_s ? 1 : 0], capacity = par[5];
-                    if constexpr (AGG == GB_OPS) {                           // the column's op word decides start, skip, atomic and bias
+                    if constexpr (KIND == GB_OPS) {                           // the column's op word decides start, skip, atomic and bias
                         const u32 op = (u32)__builtin_amdgcn_readfirstlane(
                             (int)((u32)par[GJOIN_PAR_WORDS] >> (AGG_OP_BITS * (on_s ? (u32)AGG_MAX_COLS + (c - ncolsR) : c))));
                         u64 init = (op & AGG_OP_KIND) == AGG_OP_MIN ? ~0ull : 0ull;   // the op's identity: where a word starts, what a sweep may skip
@@ -3483,6 +3544,46 @@ k_gjoin_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ t
                         if (g1 < capacity) dst[g1] = *ones;
                     }
                 }
+            }
+
+            // ---- the ids: every slot word takes its group (all ones where it emits none); R's class tuples store theirs at
+            // gidR[rowR], then S's at gidS[rowS] -- a tuple whose key has no group stores nothing (the host filled both arrays) ----
+            if constexpr (IDS) {
+                __syncthreads();                                             // the words have been emitted
+                {
+                    u64 g = g0;
+#pragma unroll 1
+                    for (u32 j = 0; j < SPT; j++) acc[(u32)tid * SPT + j] = em >> j & 1u ? g++ : ~0ull;
+                    if (tid == 0) *ones = hoe ? *base_s + tot : ~0ull;
+                }
+                __syncthreads();
+                auto sweep = [&](const RelView<NARROW> &V, u32 n, u32 at, u32 flag) {   // one side: its tuples, its array, its guard bit
+                    const u64 *idp = reinterpret_cast<const u64 *>(par[6]) + 1 + at;  // the array and its length, behind the group counter
+                    if (n == 0 || !__builtin_amdgcn_readfirstlane((int)(idp[0] != 0))) return;   // (uniform) S's partition is empty; or not asked for
+                    u64 gidw = idp[0], rows = idp[1];
+                    asm volatile("" : "+v"(gidw), "+v"(rows));               // (opaque: uniform, but four SGPRs across the sweep are four spilled)
+                    u64 *__restrict__ gid = reinterpret_cast<u64 *>(gidw);
+                    // (one load site, inside the loop: a first tile read ahead of it has its two descriptors hoisted out of the whole
+                    // walk, eight SGPRs that the narrow instantiations spill)
+                    Both t = Both(), t_next = t;
+                    for (u32 tb = 0;; tb += THREADS) {                       // round tb / THREADS loads tile tb and handles the one before
+                        if (tb < n)                                          // the next tile travels behind this one's stores
+                            t_next = V.buf(tb, n - tb < (u32)THREADS ? n - tb : (u32)THREADS).both(0u, (u32)tid);
+                        if (tb != 0) {
+                            const u32 rest = n - (tb - (u32)THREADS);        // tuples from the handled tile on
+                            const bool beyond = (u32)tid < rest && (u64)t.key >= rows;   // (flat predicates: every nested branch is two SGPRs)
+                            wild |= beyond ? flag : 0u;
+                            if ((u32)tid < rest && !beyond && in_class(t.payload)) {
+                                const u64 g = word_of(t.payload);
+                                if (g != ~0ull) gid[(u64)t.key] = g;
+                            }
+                        }
+                        if (tb >= n) break;
+                        t = t_next;
+                    }
+                };
+                sweep(Rv, np, 0u, GJOIN_BAD_GID_R);
+                sweep(Sv, ns, 2u, GJOIN_BAD_GID_S);
             }
         }
 
@@ -4233,6 +4334,18 @@ static void allow_big_lds()
     SET_LDS((k_group_bkt<false, GB_OPS>), group_lds_bytes());
     SET_LDS((k_gjoin_bkt<true, GB_OPS>), gjoin_lds_bytes());
     SET_LDS((k_gjoin_bkt<false, GB_OPS>), gjoin_lds_bytes());
+    SET_LDS((k_group_bkt<true, GB_COUNT | GB_IDS>), group_lds_bytes());
+    SET_LDS((k_group_bkt<false, GB_COUNT | GB_IDS>), group_lds_bytes());
+    SET_LDS((k_group_bkt<true, GB_SUMS | GB_IDS>), group_lds_bytes());
+    SET_LDS((k_group_bkt<false, GB_SUMS | GB_IDS>), group_lds_bytes());
+    SET_LDS((k_group_bkt<true, GB_OPS | GB_IDS>), group_lds_bytes());
+    SET_LDS((k_group_bkt<false, GB_OPS | GB_IDS>), group_lds_bytes());
+    SET_LDS((k_gjoin_bkt<true, GB_COUNT | GB_IDS>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<false, GB_COUNT | GB_IDS>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<true, GB_SUMS | GB_IDS>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<false, GB_SUMS | GB_IDS>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<true, GB_OPS | GB_IDS>), gjoin_lds_bytes());
+    SET_LDS((k_gjoin_bkt<false, GB_OPS | GB_IDS>), gjoin_lds_bytes());
     SET_LDS(k_scatter_wc_n<WC_THREADS>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS));
     SET_LDS(k_scatter_wc_n<WC_THREADS_SMALL>, wc_lds_bytes(WC_MAX_BITS, WC_THREADS_SMALL));
     SET_LDS(k_scatter_wcn<IN_AOS>, wn_lds_bytes(WN_MAX_BITS));
@@ -4868,7 +4981,7 @@ void launch_mult_join(hipStream_t st, const void *d_R, const void *d_S, const Jo
 
 void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits, bool mixed,
                   const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_out_keys, u64 *d_out_counts, u64 *const *d_out_sums,
-                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip, u32 ops)
+                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip, u32 ops, bool ids)
 {
     if (grid == 0) return;
     allow_big_lds();
@@ -4882,22 +4995,42 @@ void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, cons
     const bool with_ops = ncols != 0 && ops != 0;                            // (all sums: the sums instantiations)
     if (d_RK != nullptr) {                                                   // narrow partitions: d_R is a payload array
         const RelView<true> Rv{(const u64 *)d_R, d_RK};
-        if (with_ops) go(k_group_bkt<true, GB_OPS>, Rv);
+        if (ids) {
+            if (with_ops) go(k_group_bkt<true, GB_OPS | GB_IDS>, Rv);
+            else if (ncols != 0) go(k_group_bkt<true, GB_SUMS | GB_IDS>, Rv);
+            else go(k_group_bkt<true, GB_COUNT | GB_IDS>, Rv);
+        } else if (with_ops) go(k_group_bkt<true, GB_OPS>, Rv);
         else if (ncols != 0) go(k_group_bkt<true, GB_SUMS>, Rv);
         else go(k_group_bkt<true, GB_COUNT>, Rv);
     } else {
         const RelView<false> Rv{(const Tup *)d_R};
-        if (with_ops) go(k_group_bkt<false, GB_OPS>, Rv);
+        if (ids) {
+            if (with_ops) go(k_group_bkt<false, GB_OPS | GB_IDS>, Rv);
+            else if (ncols != 0) go(k_group_bkt<false, GB_SUMS | GB_IDS>, Rv);
+            else go(k_group_bkt<false, GB_COUNT | GB_IDS>, Rv);
+        } else if (with_ops) go(k_group_bkt<false, GB_OPS>, Rv);
         else if (ncols != 0) go(k_group_bkt<false, GB_SUMS>, Rv);
         else go(k_group_bkt<false, GB_COUNT>, Rv);
     }
+}
+
+// the id arrays of a GB_IDS launch, into the four words behind the group counter (one workgroup, plain vector stores)
+__global__ void k_group_id_words(u64 *__restrict__ ngroups, u64 gidR, u64 gidR_rows, u64 gidS, u64 gidS_rows)
+{
+    const u64 w = threadIdx.x == 0 ? gidR : threadIdx.x == 1 ? gidR_rows : threadIdx.x == 2 ? gidS : gidS_rows;
+    if (threadIdx.x < 4) ngroups[1 + threadIdx.x] = w;
+}
+
+void launch_group_id_words(hipStream_t st, u64 *d_ngroups, u64 *d_gidR, u64 gidR_rows, u64 *d_gidS, u64 gidS_rows)
+{
+    hipLaunchKernelGGL(k_group_id_words, dim3(1), dim3(64), 0, st, d_ngroups, (u64)d_gidR, gidR_rows, (u64)d_gidS, gidS_rows);
 }
 
 void launch_group_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
                        int radix_bits, bool mixed, bool left_mode, const u64 *const *d_colsR, u32 ncolsR, u64 colR_rows,
                        const u64 *const *d_colsS, u32 ncolsS, u64 colS_rows, u64 *d_out_keys, u64 *d_out_cntR, u64 *d_out_cntS,
                        u64 *const *d_out_sumsR, u64 *const *d_out_sumsS, u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds,
-                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip, u32 ops)
+                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip, u32 ops, bool ids)
 {
     if (grid == 0) return;
     allow_big_lds();
@@ -4915,12 +5048,20 @@ void launch_group_join(hipStream_t st, const void *d_R, const void *d_S, const J
     const bool sums = ncolsR + ncolsS != 0, with_ops = sums && ops != 0;     // (all sums: the sums instantiations)
     if (d_RK != nullptr) {                                                   // narrow partitions: d_R / d_S are payload arrays
         const RelView<true> Rv{(const u64 *)d_R, d_RK}, Sv{(const u64 *)d_S, d_SK};
-        if (with_ops) go(k_gjoin_bkt<true, GB_OPS>, Rv, Sv);
+        if (ids) {
+            if (with_ops) go(k_gjoin_bkt<true, GB_OPS | GB_IDS>, Rv, Sv);
+            else if (sums) go(k_gjoin_bkt<true, GB_SUMS | GB_IDS>, Rv, Sv);
+            else go(k_gjoin_bkt<true, GB_COUNT | GB_IDS>, Rv, Sv);
+        } else if (with_ops) go(k_gjoin_bkt<true, GB_OPS>, Rv, Sv);
         else if (sums) go(k_gjoin_bkt<true, GB_SUMS>, Rv, Sv);
         else go(k_gjoin_bkt<true, GB_COUNT>, Rv, Sv);
     } else {
         const RelView<false> Rv{(const Tup *)d_R}, Sv{(const Tup *)d_S};
-        if (with_ops) go(k_gjoin_bkt<false, GB_OPS>, Rv, Sv);
+        if (ids) {
+            if (with_ops) go(k_gjoin_bkt<false, GB_OPS | GB_IDS>, Rv, Sv);
+            else if (sums) go(k_gjoin_bkt<false, GB_SUMS | GB_IDS>, Rv, Sv);
+            else go(k_gjoin_bkt<false, GB_COUNT | GB_IDS>, Rv, Sv);
+        } else if (with_ops) go(k_gjoin_bkt<false, GB_OPS>, Rv, Sv);
         else if (sums) go(k_gjoin_bkt<false, GB_SUMS>, Rv, Sv);
         else go(k_gjoin_bkt<false, GB_COUNT>, Rv, Sv);
     }

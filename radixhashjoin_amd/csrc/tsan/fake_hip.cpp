@@ -210,15 +210,19 @@ void launch_mult_join(hipStream_t st, const void *, const void *, const JoinTask
     fake_enqueue(st, [=] { if (out_rows) d_out[0] += FAKE_PAIRS; *d_total += FAKE_PAIRS; });
 }
 void launch_group(hipStream_t st, const void *, const JoinTask *, const u32 *, u32, int, bool, const u64 *const *, u32, u64, u64 *, u64 *,
-                  u64 *const *, u64, u64 *d_ngroups, u32 *, u64 *, const u32 *, const u32 *, u32)
+                  u64 *const *, u64, u64 *d_ngroups, u32 *, u64 *, const u32 *, const u32 *, u32, bool)
 {
     fake_enqueue(st, [=] { *d_ngroups += FAKE_PAIRS; });
 }
 void launch_group_join(hipStream_t st, const void *, const void *, const JoinTask *, const u32 *, u32, int, bool, bool, const u64 *const *, u32,
                        u64, const u64 *const *, u32, u64, u64 *, u64 *, u64 *, u64 *const *, u64 *const *, u64, u64 *d_ngroups, u32 *, u64 *,
-                       const u32 *, const u32 *, const u32 *, u32)
+                       const u32 *, const u32 *, const u32 *, u32, bool)
 {
     fake_enqueue(st, [=] { *d_ngroups += FAKE_PAIRS; });
+}
+void launch_group_id_words(hipStream_t st, u64 *d_ngroups, u64 *d_gidR, u64 gidR_rows, u64 *d_gidS, u64 gidS_rows)
+{
+    fake_enqueue(st, [=] { d_ngroups[1] = (u64)d_gidR; d_ngroups[2] = gidR_rows; d_ngroups[3] = (u64)d_gidS; d_ngroups[4] = gidS_rows; });
 }
 int build_tie_shift() { return 4; }
 size_t fuse_ctl_bytes() { return 12352; }

@@ -143,6 +143,10 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * semi / anti join, aggregating join or multiplicity join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
  * "last.group_rounds" (the largest number of LDS table builds any one task of the last group-by or group-by join made: 1 when every
  * partition of R fitted one table, 0 when no task ran, and 0 after every call that is neither; "last.semi_tables" is 0 after both),
+ * "last.outer_sweeps" (the anti sweeps the last rhj_outer_join_dev / rhj_outer_join_cols_dev ran: 0, 1 or 2, one per preserved side
+ * that had tuples to report on; 0 after every other call.  After an outer join "last.semi_tables" is the largest number of tables any
+ * task of those sweeps built -- 0 when no sweep ran a task --, and "last.join_kernel" the pair kernel as rhj_join_cols_dev reports it,
+ * 12 when an empty side left only a sweep to run, -1 when nothing ran),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -211,7 +215,7 @@ int rhj_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_id
                       const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count);
 
 /* ---- semi-join and anti-join: WHICH tuples of R have a partner in S at all (RHJ_SEMI: EXISTS, isin on key columns, semi-join
- * reduction) or have none (RHJ_ANTI: NOT EXISTS; a left outer join is the inner join plus the anti-join's rows).  R as columns
+ * reduction) or have none (RHJ_ANTI: NOT EXISTS; for a left, right or full outer join see rhj_outer_join_cols_dev).  R as columns
  * exactly as in rhj_join_cols_dev (d_idR == NULL: rowID = i); S is its value column alone: S has no id column, its rowIDs never
  * reach the result.
  * Output: d_out_ids receives the rowID (id[i], or i for a NULL id column; .key for tuples) of every tuple of R that qualifies, each
@@ -234,6 +238,41 @@ int rhj_semi_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
 int rhj_semi_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                       int kind, const rhj_opts *opts,
                       uint64_t *d_out_ids, uint64_t out_capacity, uint64_t *out_count);
+
+/* ---- outer joins: the pairs of rhj_join_cols_dev and, behind them, one row per tuple of a PRESERVED side whose join value does not
+ * occur on the other side, the missing rowID being RHJ_NO_ROW (LEFT / RIGHT / FULL OUTER JOIN; merge(how="left" / "right" / "outer")).
+ * Both sides are partitioned ONCE; the pair join runs, then one anti sweep (the kernel of rhj_semi_join_cols_dev, writing 16-byte
+ * rows) per preserved side over the same partitions, on the same stream and the same result counter.
+ * how: RHJ_OUTER_LEFT (bit 0) keeps the tuples of R without a partner in S as {rowR, RHJ_NO_ROW}; RHJ_OUTER_RIGHT (bit 1) those of S
+ * without a partner in R as {RHJ_NO_ROW, rowS}; RHJ_OUTER_FULL both.  Each such tuple is reported ONCE: two tuples of R with the same
+ * unmatched value are two rows.  The matched rows are the pair multiset of rhj_join_cols_dev on the same inputs.  Relations as
+ * columns exactly as in rhj_join_cols_dev (a NULL id column: rowID = index; the two sides are independent); a caller's rowID that is
+ * itself all ones cannot be told from RHJ_NO_ROW.
+ * Sections: *out_count is the total; out_sections, a HOST array of three words that may be NULL, receives {matched, R-only, S-only},
+ * a section the mode does not ask for being 0.  In d_out the matched pairs occupy [0, matched), the R-only rows
+ * [matched, matched + R-only), the S-only rows come behind them: a caller slices instead of scanning for RHJ_NO_ROW.  Order inside a
+ * section is unspecified.
+ * d_out == NULL with out_capacity 0 counts only.  Returns RHJ_E_OVERFLOW when out_capacity is too small: *out_count and out_sections
+ * are exact, slots [0, capacity) hold distinct rows of the result in the section layout above, nothing at or past capacity is written.
+ * nR == 0: under bit 1 every tuple of S as {RHJ_NO_ROW, rowS}, otherwise 0 rows; nS == 0: symmetric; both 0: 0 rows, no launch.
+ * how outside 1..3, a NULL out_count, a NULL value column (relation) with n > 0: RHJ_E_INVALID.  Inputs are neither modified nor
+ * retained.
+ * Plan, options, timings, "last.narrow", "last.countfree_*", "last.cols_*" and "last.max_part_*" as rhj_join_cols_dev / rhj_join_dev on
+ * the same sizes (same partition kernels, same repeats after a count-free overflow or a rowID >= 2^32 in a narrow format: a repeat
+ * starts from a zeroed counter and produces every section again), except that a one-pass plan always runs as separate partition and
+ * join launches; rhj_timings.ntasks counts the tasks of the pair join and of the sweeps together, RHJ_K_TASKS / RHJ_K_JOIN include the
+ * sweeps; "last.join_kernel", "last.outer_sweeps" and "last.semi_tables" see rhj_get_info.  In a sweep rhj_opts.probe_split above
+ * 32768 acts as 32768.  An empty side: the other side is swept unpartitioned, without a partition phase. */
+#define RHJ_NO_ROW      0xFFFFFFFFFFFFFFFFull   /* the missing side of an unmatched row: all ones, -1 as int64 (as the group ids' "no group") */
+#define RHJ_OUTER_LEFT  1   /* bit 0: keep the tuples of R without a partner in S */
+#define RHJ_OUTER_RIGHT 2   /* bit 1: keep the tuples of S without a partner in R */
+#define RHJ_OUTER_FULL  3
+int rhj_outer_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                            const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS, int how, const rhj_opts *opts,
+                            rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count, uint64_t *out_sections);
+/* ... on 16-byte tuples (value = .payload, rowID = .key) */
+int rhj_outer_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, int how,
+                       const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count, uint64_t *out_sections);
 
 /* ---- aggregating join: COUNT(*) and SUM(column of R) over R join S without producing the pairs (SELECT COUNT(*), SUM(r.x) FROM R JOIN
  * S USING (key)).  For a join value repeated n times on both sides the pair set holds n^2 pairs; this call reads both relations once

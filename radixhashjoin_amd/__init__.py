@@ -10,6 +10,8 @@ CPU fallback: if the HIP library is missing or no GPU is present, construction o
 From torch: ``idx_R, idx_S = Engine(0).join_columns(keys_R, keys_S)`` joins two int64 key tensors on the engine's device
 (``rhj_join_cols_dev``: the relations as columns, rowID = index); ``Engine(0).semi_join_columns(keys_R, keys_S, anti=False)``
 returns the indices of the keys of R that occur (``anti=True``: do not occur) in S (``rhj_semi_join_cols_dev``);
+``idx_R, idx_S = Engine(0).outer_join_columns(keys_R, keys_S, how="left")`` is the left, right or full outer join: the matched index
+pairs first, then the unmatched rows of the preserved side(s) with -1 on the missing side (``rhj_outer_join_cols_dev``);
 ``count, sums = Engine(0).join_sum_columns(keys_R, keys_S, weights)`` is COUNT(*) and SUM(weights[k][i]) over the join's pairs
 without the pairs (``rhj_join_sum_cols_dev``); ``mult, total = Engine(0).join_multiplicity_columns(keys_R, keys_S, weights_S=None)``
 is, per key of R, how many keys of S equal it -- or the sum of their weights (``rhj_join_mult_cols_dev``);
@@ -35,6 +37,10 @@ from .binding import (  # noqa: F401
     GJ_LEFT,
     GROUP_JOIN_MAX_COLS,
     GROUP_MAX_COLS,
+    NO_ROW,
+    OUTER_FULL,
+    OUTER_LEFT,
+    OUTER_RIGHT,
     Opts,
     RhjError,
     SEMI,
@@ -46,5 +52,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64"]
 __version__ = "0.1.0"

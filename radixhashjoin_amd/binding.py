@@ -78,6 +78,8 @@ SYMBOLS = {
     "rhj_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_semi_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_semi_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_outer_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64), _P(_u64)]),
+    "rhj_outer_join_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64), _P(_u64)]),
     "rhj_join_sum_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _P(_u64), _P(_u64)]),
     "rhj_join_sum_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _P(_u64), _P(_u64)]),
     "rhj_join_mult_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
@@ -225,6 +227,8 @@ def _agg_ops(ops, n, name):
             raise ValueError(f"{name}[{i}]: 'sum', 'min' or 'max', not {o!r}")
     return [_AGG_BY_NAME[o] for o in ops]
 SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
+OUTER_LEFT, OUTER_RIGHT, OUTER_FULL = 1, 2, 3           # include/rhj.h RHJ_OUTER_*: the preserved side(s) of an outer_join_* call
+NO_ROW = 0xFFFFFFFFFFFFFFFF                              # include/rhj.h RHJ_NO_ROW: the missing side of an unmatched row (-1 as int64)
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
 
@@ -336,7 +340,7 @@ class Engine:
         self._chk(self.lib.rhj_set_option(self.ctx, name.encode(), int(value)))
 
     def info(self, name):
-        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.group_rounds";
+        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.outer_sweeps", "last.group_rounds";
         include/rhj.h)"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
@@ -474,6 +478,24 @@ class Engine:
                                         C.byref(opts) if opts is not None else None, _addr(d_out), capacity, C.byref(n))
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
+
+    def outer_join_cols_dev(self, d_valR, d_idR, nR, d_valS, d_idS, nS, how, d_out=None, capacity=0, opts=None, allow_overflow=False):
+        """rhj_outer_join_cols_dev: (count, (matched, R-only, S-only)) -- the pairs of join_cols_dev, then {rowR, NO_ROW} per tuple of R
+        without a partner (how & OUTER_LEFT), then {NO_ROW, rowS} per tuple of S without one (how & OUTER_RIGHT), in that order in
+        d_out: PAIR[capacity] in HBM, or None to count"""
+        n, sec = _u64(), (_u64 * 3)()
+        rc = self.lib.rhj_outer_join_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), _addr(d_idS), nS, how,
+                                              C.byref(opts) if opts is not None else None, _addr(d_out), capacity, C.byref(n), sec)
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value, tuple(int(x) for x in sec)
+
+    def outer_join_dev(self, d_R, nR, d_S, nS, how, d_out=None, capacity=0, opts=None, allow_overflow=False):
+        """rhj_outer_join_dev: outer_join_cols_dev on 16-byte tuples (value = .payload, rowID = .key)"""
+        n, sec = _u64(), (_u64 * 3)()
+        rc = self.lib.rhj_outer_join_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, how,
+                                         C.byref(opts) if opts is not None else None, _addr(d_out), capacity, C.byref(n), sec)
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value, tuple(int(x) for x in sec)
 
     @staticmethod
     def _sum_args(d_cols):
@@ -708,7 +730,7 @@ class Engine:
 
     @contextlib.contextmanager
     def _on_torch_stream(self, keys_R, keys_S, weights=(), weights_on_S=False, weights_S=()):
-        """What join_columns, semi_join_columns, join_sum_columns, join_multiplicity_columns, group_by_columns (keys_S = keys_R) and join_group_by_columns (weights_S: further tensors, each as long as keys_S) share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
+        """What join_columns, outer_join_columns, semi_join_columns, join_sum_columns, join_multiplicity_columns, group_by_columns (keys_S = keys_R) and join_group_by_columns (weights_S: further tensors, each as long as keys_S) share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
         engine's device (ValueError otherwise); weights: tensors of the same kind, each as long as keys_R (weights_on_S: as keys_S).  The body runs ordered behind the work torch has queued on its current stream: on a
         stream of its own (torch.cuda.stream(s)) the engine runs on that stream for the length of the body; torch's default stream
         has no handle to hand over (its raw value is 0, which rhj_set_stream reads as "the context's own stream"), so there the call
@@ -769,8 +791,8 @@ class Engine:
     def semi_join_columns(self, keys_R, keys_S, anti=False):
         """idx_R, an int64 tensor: every i for which keys_R[i] occurs in keys_S -- with anti=True, does NOT occur -- exactly once,
         in no particular order, however often the key is repeated in keys_S (torch.isin as indices; EXISTS / NOT EXISTS).  Tensors,
-        streams and completion as join_columns.  Count, allocate, fill.  (A left outer join is join_columns plus the rows of
-        semi_join_columns(.., anti=True).)"""
+        streams and completion as join_columns.  Count, allocate, fill.  (For a left, right or full outer join see
+        outer_join_columns: one call, both sides partitioned once.)"""
         import torch
         kind = ANTI if anti else SEMI
         with self._on_torch_stream(keys_R, keys_S) as dev:
@@ -781,6 +803,28 @@ class Engine:
                 got = self.semi_join_cols_dev(keys_R, None, nR, keys_S, nS, kind, idx_R, count)
                 assert got == count, (got, count)
         return idx_R
+
+    def outer_join_columns(self, keys_R, keys_S, how="left"):
+        """Outer equi-join of two key tensors: (idx_R, idx_S), int64 tensors of one length.  First the rows of join_columns; then,
+        for how "left" or "full", one row (i, -1) per i whose keys_R[i] does not occur in keys_S; then, for how "right" or "full", one
+        row (-1, j) per j whose keys_S[j] does not occur in keys_R (merge(how=..), how="full" being pandas' "outer"; LEFT / RIGHT /
+        FULL OUTER JOIN).  Order inside each of the three sections is unspecified.  Tensors, streams and completion as join_columns.
+        Count, allocate, fill."""
+        import torch
+        modes = {"left": OUTER_LEFT, "right": OUTER_RIGHT, "full": OUTER_FULL}
+        if not isinstance(how, str) or how not in modes:
+            raise ValueError(f"how: one of 'left', 'right', 'full' is needed, not {how!r}")
+        with self._on_torch_stream(keys_R, keys_S) as dev:
+            nR, nS = keys_R.numel(), keys_S.numel()
+            count, _ = self.outer_join_cols_dev(keys_R, None, nR, keys_S, None, nS, modes[how])
+            idx_R = torch.empty(count, dtype=torch.int64, device=dev)
+            idx_S = torch.empty(count, dtype=torch.int64, device=dev)
+            if count:
+                pairs = torch.empty((count, 2), dtype=torch.int64, device=dev)
+                got, _ = self.outer_join_cols_dev(keys_R, None, nR, keys_S, None, nS, modes[how], pairs, count)
+                assert got == count, (got, count)
+                self.pairs_split(pairs, count, idx_R, idx_S)
+        return idx_R, idx_S
 
     def join_sum_columns(self, keys_R, keys_S, weights=()):
         """(count, sums): count = the number of index pairs (i, j) with keys_R[i] == keys_S[j], sums[k] = the sum of weights[k][i]

@@ -231,6 +231,9 @@ struct rhj_ctx {
     int last_pipelined = 0;            // S chunks of the last rhj_join (0: not pipelined)
     u64 last_max_part[2] = {0, 0};     // largest partition of R / S the last task list saw (0: direct join)
     int last_semi_tables = 0;          // "last.semi_tables": LDS tables the busiest task of the last semi / anti join built (0: another call)
+    int last_outer_sweeps = 0;         // "last.outer_sweeps": anti sweeps the last outer join ran behind its pair join (0: another call)
+    int outer_how = 0;                 // an outer join's RHJ_OUTER_* bits, for the length of the call
+    u64 outer_sections[3] = {0, 0, 0}; // ... and its {matched, R-only, S-only} rows, as outer_phase leaves them
     bool counters_clean = false;       // the 64-byte join counters are zero (cleared by the partition phase's first launch)
     int cur_narrow = 0;                // partitions are in the narrow {payload, rowID} format (k_scatter_wcn); 2: so was the intermediate
     DevBuf agg_out;                    // an aggregating join's words: [0] count, [1 .. 4] sums, [5] u32 a rowID >= col_rows was met
@@ -478,6 +481,7 @@ void prof_reset(rhj_ctx *ctx)
     ctx->last_cols[0] = ctx->last_cols[1] = 0;      // "last.cols_*": every join or stage call starts here; rhj_join_cols_dev sets them as it goes
     ctx->last_semi_tables = 0;                      // "last.semi_tables": ... and semi_phase this one
     ctx->last_group_rounds = 0;                     // "last.group_rounds": ... and group_phase this one
+    ctx->last_outer_sweeps = 0;                     // "last.outer_sweeps": ... and outer_phase this one
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -1394,7 +1398,8 @@ int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
 // multiplicity in S (mult_phase).
 // OUT_GROUP: one row per distinct join value of R alone (group_phase; partition_phase in its one-sided mode).
 // OUT_GJOIN: one row per join value of R join S, with the counts and sums of both sides (gjoin_phase).
-enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3, OUT_GROUP = 4, OUT_GJOIN = 5 };
+// OUT_OUTER: the pairs, then {row, RHJ_NO_ROW} for the tuples of the preserved side(s) without a partner (outer_phase).
+enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3, OUT_GROUP = 4, OUT_GJOIN = 5, OUT_OUTER = 6 };
 
 // Semi / anti join phase on the partitions partition_phase left: k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
 // Reads the skip word behind its kernel and answers with the retry codes of join_phase_on.
@@ -1450,6 +1455,87 @@ int semi_phase(rhj_ctx *ctx, JoinOutput what, void *d_out, u64 cap, u64 *out_cou
     ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
     if (host[5])
         return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    return RHJ_OK;
+}
+
+// One anti sweep of an outer join over the partitions ctx->cur_* describe: the tuples of the preserved side -- R
+// (side 0: the tables on S's partitions) or S (side 1: the roles exchanged, the tables on R's partitions) -- without a partner, as
+// {rowID, NO_ROW} / {NO_ROW, rowID} behind whatever the result counter already counts.  Counter words 1..7 start from zero, word 0
+// goes on (cf. join_phase_on's keep_count).  *out_total: the counter after the sweep.
+int outer_sweep(rhj_ctx *ctx, int side, void *d_out, u64 cap, u64 *out_total)
+{
+    const u64 nP = side ? ctx->cur_nS : ctx->cur_nR, nT = side ? ctx->cur_nR : ctx->cur_nS, nparts = ctx->cur_nparts;
+    const void *d_P = side ? ctx->cur_S : ctx->cur_R, *d_T = side ? ctx->cur_R : ctx->cur_S;
+    const u64 *d_psP = side ? ctx->cur_psS : ctx->cur_psR, *d_psT = side ? ctx->cur_psR : ctx->cur_psS;
+    const bool narrow = ctx->cur_narrow != 0;
+    u32 split = ctx->cur_probe_split;
+    if (split == 0 || split > SEMI_MAX_SPLIT) split = SEMI_MAX_SPLIT;        // a task's match bits: 4 KiB of LDS
+    const u64 max_tasks64 = nparts + nP / split + 1;
+    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
+    const u32 max_tasks = (u32)max_tasks64;
+    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
+    u64 *d_count = (u64 *)ctx->counters.p;
+    {
+        Span s(ctx, RHJ_K_AUX);
+        HIPCHK(ctx, hipMemsetAsync((unsigned char *)ctx->counters.p + 8, 0, 56, ctx->stream));
+    }
+    {
+        Span s(ctx, RHJ_K_TASKS);
+        launch_make_semi_tasks(ctx->stream, d_psP, d_psT, nparts, split, 1, (JoinTask *)ctx->tasks.p, (u32 *)(d_count + 1), max_tasks,
+                               d_count + 2);
+    }
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        launch_outer_sweep(ctx->stream, d_P, d_T, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
+                           ctx->cur_radix_bits, side, d_out, d_out ? cap : 0, d_count, d_count + 7,
+                           narrow ? (const u32 *)((const unsigned char *)d_P + narrow_k_offset(nP)) : nullptr,
+                           narrow ? (const u32 *)((const unsigned char *)d_T + narrow_k_offset(nT)) : nullptr,
+                           narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+    }
+    RHJCHK(check_launch(ctx, "outer join sweep"));
+    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // count, ntasks, max |P_k|, max |T_k|, -, oversized table side, -, most tables of a task (if > 1)
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *out_total = host[0];
+    const u32 ntasks = (u32)(host[1] & 0xffffffffu);
+    ctx->last.ntasks += ntasks;
+    const int tables = host[7] ? (int)host[7] : (ntasks ? 1 : 0);
+    if (tables > ctx->last_semi_tables) ctx->last_semi_tables = tables;
+    ctx->last_outer_sweeps++;
+    if (host[5])
+        return fail(ctx, RHJ_E_INVALID, std::string("a partition of ") + (side ? "R" : "S") + " has " + std::to_string(host[5]) +
+                                        " tuples (>= 2^32): use more radix bits");
+    return RHJ_OK;
+}
+
+// Outer join phase on the partitions partition_phase left: join_phase -- whose retry codes come back before any sweep
+// runs: the narrow flag is final once the partition kernels have ended --, then one outer_sweep per preserved side on the same stream
+// and the same result counter.  The sections are the differences of the counter between the phases; a repeat starts from a zeroed
+// counter (join_phase_on clears it) and produces every section again.
+int outer_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
+{
+    ctx->last_outer_sweeps = 0;
+    ctx->last_semi_tables = 0;
+    ctx->outer_sections[0] = ctx->outer_sections[1] = ctx->outer_sections[2] = 0;
+    const int rc = join_phase(ctx, d_out, cap, out_count);
+    if (rc != RHJ_OK) return rc;
+    const int pair_kind = ctx->last_join_kind;                           // "last.join_kernel": the pair kernel
+    ctx->outer_sections[0] = *out_count;
+    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
+        Span s(ctx, RHJ_K_AUX);
+        launch_init_single_segment(ctx->stream, ctx->cur_nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+        launch_init_single_segment(ctx->stream, ctx->cur_nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+    }
+    u64 before = *out_count;
+    for (int side = 0; side < 2; side++) {
+        if (!(ctx->outer_how & (1 << side))) continue;
+        u64 total = before;
+        RHJCHK(outer_sweep(ctx, side, d_out, cap, &total));
+        ctx->outer_sections[1 + side] = total - before;
+        before = total;
+    }
+    *out_count = before;
+    ctx->last_join_kind = pair_kind;
     return RHJ_OK;
 }
 
@@ -1873,7 +1959,7 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
 
 // partition + join.  A run in the narrow format whose histogram kernel met a rowID >= 2^32 costs two histogram launches
 // (every later kernel of the run returns at once) and is repeated in the 16-byte format; the fall-back is per join.
-// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase / group_phase / gjoin_phase (which always take the
+// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase / group_phase / gjoin_phase / outer_phase (which always take the
 // unfused path: the one-pass form has the pair join built into its launches).
 int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan, void *d_out,
                        u64 cap, u64 *out_count, std::function<int()> *before_S = nullptr, JoinOutput what = OUT_PAIRS)
@@ -1884,6 +1970,7 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
         return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : what == OUT_SUMS ? agg_phase(ctx, out_count) :
                what == OUT_MULT ? mult_phase(ctx, out_count) : what == OUT_GROUP ? group_phase(ctx, out_count) :
                what == OUT_GJOIN ? gjoin_phase(ctx, out_count) :
+               what == OUT_OUTER ? outer_phase(ctx, d_out, cap, out_count) :
                semi_phase(ctx, what, d_out, cap, out_count);
     };
     int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S);
@@ -2120,6 +2207,7 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.max_part_S") { *value = (int64_t)ctx->last_max_part[1]; return RHJ_OK; }
     if (n == "last.semi_tables") { *value = ctx->last_semi_tables; return RHJ_OK; }
     if (n == "last.group_rounds") { *value = ctx->last_group_rounds; return RHJ_OK; }
+    if (n == "last.outer_sweeps") { *value = ctx->last_outer_sweeps; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }
@@ -2315,6 +2403,87 @@ int rhj_semi_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
     ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = nullptr;      // S has no id column: rowID = index, never reported
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
     const int rc = semi_join_common(ctx, nullptr, nR, nullptr, nS, kind, opts, d_out_ids, out_capacity, out_count);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// Outer join: the partition phase and the repeat ladder of rhj_join_dev / rhj_join_cols_dev, then outer_phase.
+// d_R / d_S null: the relations are ctx->cols_in.  One side empty: no pair, and every tuple of the other side if its bit is set -- by
+// one sweep over empty tables, that side unpartitioned and its one partition cut into tasks (semi_join_common's path for an empty S).
+static int outer_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, int how, const rhj_opts *opts,
+                             rhj_pair *d_out, u64 out_capacity, uint64_t *out_count, uint64_t *out_sections)
+{
+    const u64 cap = d_out ? out_capacity : 0;
+    ctx->outer_how = how;
+    ctx->outer_sections[0] = ctx->outer_sections[1] = ctx->outer_sections[2] = 0;
+    if (nR == 0 || nS == 0) {
+        const int side = nR == 0 ? 1 : 0;              // the side that may have tuples
+        if ((nR == 0 && nS == 0) || !(how & (1 << side))) return join_nothing(ctx);
+        ctx->cur_nR = nR;
+        ctx->cur_nS = nS;
+        ctx->cur_probe_split = 0;
+        ctx->cur_narrow = 0;
+        ctx->last_cf[0] = ctx->last_cf[1] = 0;
+        const void *d_P = side ? d_S : d_R;
+        RHJCHK(cols_to_aos(ctx, side, side ? nS : nR, d_P));
+        RHJCHK(ensure(ctx, ctx->ps_R, 64));
+        RHJCHK(ensure(ctx, ctx->ps_S, 64));
+        RHJCHK(ensure(ctx, ctx->counters, 64));
+        ctx->cur_R = ctx->cur_S = d_P;                 // (no tuple of the empty side is read)
+        ctx->cur_psR = (const u64 *)ctx->ps_R.p;
+        ctx->cur_psS = (const u64 *)ctx->ps_S.p;
+        ctx->cur_nparts = 1;
+        ctx->cur_radix_bits = 0;
+        {
+            Span s(ctx, RHJ_K_AUX);
+            HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+            launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+            launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+        }
+        ctx->counters_clean = false;
+        ctx->sniff_ready = false;
+        ctx->last_join_kind = JK_SEMI;
+        ctx->last_max_part[0] = ctx->last_max_part[1] = 0;
+        RHJCHK(outer_sweep(ctx, side, d_out, cap, (u64 *)out_count));
+        ctx->outer_sections[1 + side] = *out_count;
+    } else {
+        rhj_opts plan;
+        if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+        RHJCHK(partition_and_join(ctx, d_R, nR, d_S, nS, plan, d_out, cap, (u64 *)out_count, nullptr, OUT_OUTER));
+    }
+    if (out_sections) for (int i = 0; i < 3; i++) out_sections[i] = ctx->outer_sections[i];
+    if (d_out && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
+    return RHJ_OK;
+}
+
+int rhj_outer_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, int how,
+                       const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count, uint64_t *out_sections)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
+    *out_count = 0;
+    if (out_sections) out_sections[0] = out_sections[1] = out_sections[2] = 0;
+    prof_reset(ctx);
+    if (how < RHJ_OUTER_LEFT || how > RHJ_OUTER_FULL) return fail(ctx, RHJ_E_INVALID, "how is none of RHJ_OUTER_LEFT, RHJ_OUTER_RIGHT, RHJ_OUTER_FULL");
+    if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return outer_join_common(ctx, d_R, nR, d_S, nS, how, opts, d_out, out_capacity, out_count, out_sections);
+}
+
+int rhj_outer_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR, const uint64_t *d_valS,
+                            const uint64_t *d_idS, uint64_t nS, int how, const rhj_opts *opts, rhj_pair *d_out,
+                            uint64_t out_capacity, uint64_t *out_count, uint64_t *out_sections)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
+    *out_count = 0;
+    if (out_sections) out_sections[0] = out_sections[1] = out_sections[2] = 0;
+    prof_reset(ctx);
+    if (how < RHJ_OUTER_LEFT || how > RHJ_OUTER_FULL) return fail(ctx, RHJ_E_INVALID, "how is none of RHJ_OUTER_LEFT, RHJ_OUTER_RIGHT, RHJ_OUTER_FULL");
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
+    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = outer_join_common(ctx, nullptr, nR, nullptr, nS, how, opts, d_out, out_capacity, out_count, out_sections);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

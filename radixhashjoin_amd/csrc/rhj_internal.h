@@ -253,6 +253,14 @@ void launch_make_semi_tasks(hipStream_t st, const u64 *d_startR, const u64 *d_st
 void launch_semi_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
                       int radix_bits, int anti, u64 *d_out, u64 out_capacity, u64 *d_out_count, u64 *d_max_tables,
                       const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
+// One anti sweep of an outer join: k_semi_bkt in a 16-byte pair form, anti = 1, over the task list of
+// launch_make_semi_tasks(probe side's boundaries, table side's boundaries, .., anti = 1).  d_P / d_T: the partitions of the preserved
+// side (probed, reported) and of the side the tables are built on; preserved_is_S 0: R against S, rows {rowID, all ones};
+// 1: S against R, rows {all ones, rowID}.  d_out: rhj_pair (may be null: count only), written from the value d_out_count[0]
+// already holds on and never at or past out_capacity; d_PK / d_TK: the rowID arrays of narrow partitions, probed side first.
+void launch_outer_sweep(hipStream_t st, const void *d_P, const void *d_T, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                        int radix_bits, int preserved_is_S, void *d_out, u64 out_capacity, u64 *d_out_count, u64 *d_max_tables,
+                        const u32 *d_PK, const u32 *d_TK, const u32 *d_skip);
 // ---- the aggregating join kernel (k_agg_bkt): one geometry --------------------------------------------------------
 // k_semi_bkt's table of 8-byte keys of S with a 32-bit occurrence count beside every slot, in a parallel array: 8192 + 8192 = 96 KiB,
 // one workgroup of 1024 threads per CU -- four wavefronts per SIMD, and a 15 K-tuple partition of S in four tables where the

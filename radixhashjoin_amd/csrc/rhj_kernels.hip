@@ -2410,13 +2410,17 @@ k_join_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
 //     64 tuples of a slot row: plain stores); the last sweep probes only the tuples whose bit is still clear.
 //   * emit: per slot row a wavefront ballot + mbcnt prefix, one 64-lane scan over the (slot, wavefront) totals, one global
 //     atomicAdd per tile; 8-byte rowIDs dense in lane order, nothing at or past out_capacity, nothing at all when counting.
+//   * FORM (outer joins): 0 the 8-byte rowIDs above; 1 / 2 a 16-byte pair per row, {rowID, all ones} / {all ones, rowID},
+//     one 16-byte store each, `out` being an array of pairs.  The result counter goes on from whatever it holds, so a sweep launched
+//     behind a pair join on the same counter appends its rows to the pairs.  Build, tiles, match bits and the emit scan are shared;
+//     the pair forms on 16-byte tuples group their first table reads by two slot rows, not four (PROBE_GROUP below).
 // ------------------------------------------------------------------------------------------------
 constexpr u64 SEMI_EMPTY = ~0ull;
 constexpr int SEMI_PROBE_GROUP = 4;               // slot rows of a probe tile whose first table reads are issued together
 static_assert(SEMI_EPT % SEMI_PROBE_GROUP == 0, "whole groups");
 typedef u64 v2u64 __attribute__((ext_vector_type(2)));
 
-template <bool NARROW>
+template <bool NARROW, int FORM = 0>
 __global__ void __launch_bounds__(SEMI_THREADS, 4)
 k_semi_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks,
            int radix_bits, int anti, u64 *__restrict__ out, u64 out_capacity, u64 *__restrict__ out_count,
@@ -2426,6 +2430,9 @@ k_semi_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
     if (blockIdx.x >= *ntasks) return;
     constexpr int THREADS = SEMI_THREADS, NW = THREADS / 64, EPT = SEMI_EPT, TILE = THREADS * EPT;
     constexpr u32 SLOTS = 1u << SEMI_SLOT_BITS;
+    // slot rows whose first table reads are issued together: the pair forms on 16-byte tuples take two, not four -- a row's data
+    // must sit in four consecutive registers, and with four reads (16 registers) in flight the kernel does not fit 128 VGPRs
+    constexpr int PROBE_GROUP = FORM != 0 && !NARROW ? 2 : SEMI_PROBE_GROUP;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64 *tab = reinterpret_cast<u64 *>(smem);                                // SLOTS keys
     u32 *bm = reinterpret_cast<u32 *>(tab + SLOTS);                          // SEMI_MAX_SPLIT match bits
@@ -2482,7 +2489,11 @@ k_semi_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
     do {
         // ---- build: the next whole tiles of S's partition -----------------------------------------
         if (ns != 0) for (u32 i = tid; i < SLOTS; i += THREADS) tab[i] = SEMI_EMPTY;
-        if (tid == 0) { ctl[0] = 0; ctl[1] = 0; }
+        if constexpr (FORM == 0) {
+            if (tid == 0) { ctl[0] = 0; ctl[1] = 0; }
+        } else {
+            if (tid < 2) ctl[tid] = 0;                                       // (one word per lane: no 64-bit zero kept in registers)
+        }
         __syncthreads();
         u32 filled = 0;
         while (sdone < ns && filled + SEMI_BUILD_TILE <= SEMI_FILL) {
@@ -2519,18 +2530,18 @@ k_semi_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
             u32 emit = 0;                                                    // bit k: this lane reports its tuple of slot row k
             // The first pair of SEMI_PROBE_GROUP slot rows is read unconditionally and together (any pair index is inside the table):
             // under SEMI_FILL most probes end there, and the LDS round trips of a group overlap; only the rest walk on alone.
-            v2u64 e0[SEMI_PROBE_GROUP];
+            v2u64 e0[PROBE_GROUP];
 #pragma unroll
             for (int k = 0; k < EPT; k++) {
-                if (k % SEMI_PROBE_GROUP == 0) {
+                if (k % PROBE_GROUP == 0) {
 #pragma unroll
-                    for (int j = 0; j < SEMI_PROBE_GROUP; j++) e0[j] = tab2[bj_bucket<SEMI_SLOT_BITS - 1>(p[k + j].payload, radix_bits)];
+                    for (int j = 0; j < PROBE_GROUP; j++) e0[j] = tab2[bj_bucket<SEMI_SLOT_BITS - 1>(p[k + j].payload, radix_bits)];
                 }
                 const u32 i = tb + (u32)k * THREADS + tid;                   // < SEMI_MAX_SPLIT
                 bool hit = ntab > 1 && ((bm[i >> 5] >> (i & 31)) & 1u) != 0;
                 if (i < np && !hit && ns != 0) {                             // (ns == 0: the table was never cleared)
                     const u64 key = p[k].payload;
-                    const v2u64 e = e0[k % SEMI_PROBE_GROUP];
+                    const v2u64 e = e0[k % PROBE_GROUP];
                     if (key == SEMI_EMPTY) hit = ctl[1] != 0;
                     else if (e.x == key || e.y == key) hit = true;
                     else if (e.x != SEMI_EMPTY && e.y != SEMI_EMPTY)
@@ -2561,8 +2572,24 @@ k_semi_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
 #pragma unroll
                     for (int k = 0; k < EPT; k++) {
                         const unsigned long long m = __ballot((emit >> k) & 1u);
-                        const u64 o = g + (u32)__builtin_amdgcn_readlane((int)(inc64 - mine), k * NW + wu) + rank_in(m);
-                        if (((emit >> k) & 1u) && o < out_capacity) out[o] = (u64)p[k].key;
+                        if constexpr (FORM == 0) {
+                            const u64 o = g + (u32)__builtin_amdgcn_readlane((int)(inc64 - mine), k * NW + wu) + rank_in(m);
+                            if (((emit >> k) & 1u) && o < out_capacity) out[o] = (u64)p[k].key;
+                        } else {
+                            // the tile's base is the same in every lane: a scalar row pointer and a 32-bit row index per lane,
+                            // the bound as the tile's room behind its base (a tile reports at most TILE rows)
+                            // (32-bit compares throughout: the scalar unit orders no 64-bit words)
+                            const u32 ghi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(g >> 32)), glo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)g);
+                            const u32 chi = (u32)(out_capacity >> 32), clo = (u32)out_capacity;
+                            const u64 gu = ((u64)ghi << 32) | glo, left = out_capacity - gu;
+                            const bool full = chi < ghi || (chi == ghi && clo <= glo);
+                            const u32 room = full ? 0u : ((u32)(left >> 32) != 0 || (u32)left > (u32)TILE) ? (u32)TILE : (u32)left;
+                            v2u64 *rows = reinterpret_cast<v2u64 *>(out) + gu;
+                            const u32 r = (u32)__builtin_amdgcn_readlane((int)(inc64 - mine), k * NW + wu) + rank_in(m);
+                            if (((emit >> k) & 1u) && r < room)
+                                rows[r] = FORM == 1 ? v2u64{(u64)p[k].key, ~0ull} : v2u64{~0ull, (u64)p[k].key};
+                            __builtin_amdgcn_sched_barrier(0);               // one row's four data registers at a time, not all eight rows'
+                        }
                     }
                 }
                 // wtot / gres are rewritten only after the next tile's first barrier: safe without another one
@@ -4316,6 +4343,10 @@ static void allow_big_lds()
     allow_ct_lds<JK_CT, false, true>();                                      // the stamps aid
     SET_LDS(k_semi_bkt<true>, semi_lds_bytes());
     SET_LDS(k_semi_bkt<false>, semi_lds_bytes());
+    SET_LDS((k_semi_bkt<true, 1>), semi_lds_bytes());
+    SET_LDS((k_semi_bkt<false, 1>), semi_lds_bytes());
+    SET_LDS((k_semi_bkt<true, 2>), semi_lds_bytes());
+    SET_LDS((k_semi_bkt<false, 2>), semi_lds_bytes());
     SET_LDS(k_agg_bkt<true>, agg_lds_bytes());
     SET_LDS(k_agg_bkt<false>, agg_lds_bytes());
     SET_LDS((k_mult_bkt<true, false>), mult_lds_bytes(false));
@@ -4938,6 +4969,37 @@ void launch_semi_join(hipStream_t st, const void *d_R, const void *d_S, const Jo
         hipLaunchKernelGGL(k_semi_bkt<false>, dim3(grid), dim3(SEMI_THREADS), semi_lds_bytes(), st, RelView<false>{(const Tup *)d_R},
                            RelView<false>{(const Tup *)d_S}, d_tasks, d_ntasks, radix_bits, anti, d_out, out_capacity, d_out_count,
                            d_max_tables, d_skip);
+}
+
+template <int FORM>
+static void launch_outer_form(hipStream_t st, const void *d_P, const void *d_T, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                              int radix_bits, void *d_out, u64 out_capacity, u64 *d_out_count, u64 *d_max_tables, const u32 *d_PK,
+                              const u32 *d_TK, const u32 *d_skip)
+{
+    if (d_PK != nullptr)                                                     // narrow partitions: d_P, d_T are payload arrays
+        hipLaunchKernelGGL((k_semi_bkt<true, FORM>), dim3(grid), dim3(SEMI_THREADS), semi_lds_bytes(), st,
+                           RelView<true>{(const u64 *)d_P, d_PK}, RelView<true>{(const u64 *)d_T, d_TK}, d_tasks, d_ntasks, radix_bits, 1,
+                           (u64 *)d_out, out_capacity, d_out_count, d_max_tables, d_skip);
+    else
+        hipLaunchKernelGGL((k_semi_bkt<false, FORM>), dim3(grid), dim3(SEMI_THREADS), semi_lds_bytes(), st,
+                           RelView<false>{(const Tup *)d_P}, RelView<false>{(const Tup *)d_T}, d_tasks, d_ntasks, radix_bits, 1,
+                           (u64 *)d_out, out_capacity, d_out_count, d_max_tables, d_skip);
+}
+
+// One anti sweep of an outer join: k_semi_bkt in a pair form over the tasks of launch_make_semi_tasks(probe side's
+// boundaries, table side's boundaries, anti = 1).  d_P / d_T: the partitions of the preserved (probed) side and of the side the
+// tables are built on -- R and S for the R-only rows (preserved_is_S = 0: rows {rowID, NO_ROW}), S and R for the S-only rows
+// (preserved_is_S = 1: rows {NO_ROW, rowID}); d_PK / d_TK: their narrow rowID arrays, as launch_semi_join's.  d_out: pairs, or null.
+void launch_outer_sweep(hipStream_t st, const void *d_P, const void *d_T, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                        int radix_bits, int preserved_is_S, void *d_out, u64 out_capacity, u64 *d_out_count, u64 *d_max_tables,
+                        const u32 *d_PK, const u32 *d_TK, const u32 *d_skip)
+{
+    if (grid == 0) return;
+    allow_big_lds();
+    if (preserved_is_S)
+        launch_outer_form<2>(st, d_P, d_T, d_tasks, d_ntasks, grid, radix_bits, d_out, out_capacity, d_out_count, d_max_tables, d_PK, d_TK, d_skip);
+    else
+        launch_outer_form<1>(st, d_P, d_T, d_tasks, d_ntasks, grid, radix_bits, d_out, out_capacity, d_out_count, d_max_tables, d_PK, d_TK, d_skip);
 }
 
 void launch_agg_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,

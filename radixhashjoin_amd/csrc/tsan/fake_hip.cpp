@@ -199,6 +199,17 @@ void launch_semi_join(hipStream_t st, const void *, const void *, const JoinTask
         *d_out_count = at + FAKE_PAIRS;
     });
 }
+void launch_outer_sweep(hipStream_t st, const void *, const void *, const JoinTask *, const u32 *, u32, int, int preserved_is_S, void *d_out,
+                        u64 out_capacity, u64 *d_out_count, u64 *, const u32 *, const u32 *, const u32 *)
+{
+    fake_enqueue(st, [=] {                                          // (rows {i, all ones} / {all ones, i} behind what the counter holds)
+        const u64 at = *d_out_count;
+        u64 *pairs = (u64 *)d_out;
+        for (u64 i = at; i < at + FAKE_PAIRS; i++)
+            if (pairs && i < out_capacity) { pairs[2 * i + (preserved_is_S ? 1 : 0)] = i; pairs[2 * i + (preserved_is_S ? 0 : 1)] = ~0ull; }
+        *d_out_count = at + FAKE_PAIRS;
+    });
+}
 void launch_agg_join(hipStream_t st, const void *, const void *, const JoinTask *, const u32 *, u32, int, const u64 *const *, u32 ncols, u64,
                      u64 *d_sums, u32 *, u64 *, const u32 *, const u32 *, const u32 *)
 {

@@ -1874,6 +1874,7 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
     ctx->last.bits1 = bits;
     ctx->last.bits2 = 0;
     ctx->cur_narrow = 0;
+    ctx->last_cf[0] = ctx->last_cf[1] = 0;                   // (no partition_phase here: "last.countfree_*" must not keep the last join's)
     ctx->counters_clean = false;
     int kind = choose_join_kind(ctx, nR, nS, nbins, bits, false);
     u32 probe_split = plan.probe_split ? (u32)plan.probe_split : 32768u;

@@ -11,7 +11,8 @@ Cases:
     against join_cols_dev and semi_join_cols_dev(ANTI) in both directions;
   * one value on 1,000 rows of each side (10^6 pairs) beside values repeated 1,000 times on one side only;
   * partitions of the table side far beyond one LDS table, in both sweep directions: "last.semi_tables" >= 2, then 1, then 0;
-  * the all-ones join value (the table's empty marker) on both sides, on R only, on S only; keys 0 and 1 << 63;
+  * the all-ones join value (the table's empty marker) and unmix64 of it (the marker of a partitioned plan) on both sides, on R only, on
+    S only; keys 0 and 1 << 63;
   * partitions without a tuple of the other side; disjoint sides; n = 0 and n = 1; invalid arguments;
   * the repeats inside a call: a count-free region that overflows, one rowID of 2^32 on either side in a narrow format;
   * count-only mode and buffers that end inside each section; the AoS entry;
@@ -22,7 +23,7 @@ import torch
 
 from oracle.pyoracle import TUPLE
 from radixhashjoin_amd import ANTI, NO_ROW, OUTER_FULL, OUTER_LEFT, OUTER_RIGHT, PAIR, Engine, Opts, RhjError
-from radixhashjoin_amd.binding import RHJ_E_INVALID, RHJ_E_OVERFLOW, plan as resolve_plan
+from radixhashjoin_amd.binding import RHJ_E_INVALID, RHJ_E_OVERFLOW, mix64, plan as resolve_plan, unmix64
 
 pytestmark = pytest.mark.gpu
 PLAN = Opts(2, 8, 8)
@@ -258,11 +259,19 @@ def test_partitions_beyond_one_table(eng, opts, nT, table_side):
 
 # ---- the all-ones join value, 0 and 1 << 63 ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [3_000, 70_000])
-@pytest.mark.parametrize("ones_on", ["both", "R", "S"])
+@pytest.mark.parametrize("ones_on", ["both", "R", "S", "both-unmixed", "R-unmixed", "S-unmixed"])
 def test_all_ones_value(eng, inputs, n, ones_on):
+    """the raw all-ones value is the tables' empty marker at 3,000 rows only (unpartitioned: the kernels see the payloads); under the
+    one-pass plan of 70,000 rows they see rhj_mix64(payload), the marker there is unmix64(all ones) -- the "-unmixed" cases -- and
+    each value is an ordinary key on the other path"""
+    assert resolve_plan(n, n).passes == (0 if n == 3_000 else 1)
+    ones_on, _, unmixed = ones_on.partition("-")
     R0, S0, _ = inputs("uniform", n)
     R, S = R0.copy(), S0.copy()
     ones, top = np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64(1 << 63)
+    if unmixed:
+        ones = unmix64(ones)
+        assert int(mix64(ones)) == 0xFFFFFFFFFFFFFFFF
     if ones_on in ("both", "R"):
         R["payload"][[3, 1_500]] = ones
     if ones_on in ("both", "S"):

@@ -7,6 +7,7 @@ ids must be equal, every case runs both kinds, and the two counts sum to nR.
     narrow format (columns read directly); uniform, duplicate-heavy and Zipf 0.9 inputs; NULL and explicit ids;
   * one value on 1,000 rows of R and 10^6 rows of S: 10^9 pairs for the inner join, 1,000 ids here;
   * partitions of S far beyond one LDS table, R cut into several tasks: "last.semi_tables" >= 2, then 1, then 0 after an inner join;
+  * the all-ones join value and unmix64 of it (the empty marker of the tables under a partitioned plan) on S only, R only, both;
   * partitions without a tuple of S under an anti join; a disjoint S; n = 0 and n = 1; invalid arguments;
   * the repeats inside a call: a count-free region that overflows, one rowID of 2^32 in a narrow format;
   * count-only mode, an undersized buffer; the AoS entry; the inner join's distinct idx_R;
@@ -17,7 +18,7 @@ import torch
 
 from oracle.pyoracle import TUPLE
 from radixhashjoin_amd import ANTI, SEMI, Engine, Opts, RhjError
-from radixhashjoin_amd.binding import RHJ_E_INVALID, RHJ_E_OVERFLOW, plan as resolve_plan
+from radixhashjoin_amd.binding import RHJ_E_INVALID, RHJ_E_OVERFLOW, mix64, plan as resolve_plan, unmix64
 
 pytestmark = pytest.mark.gpu
 PLAN = Opts(2, 8, 8)
@@ -187,6 +188,35 @@ def test_partitions_beyond_one_table(eng, opts, nS):
     assert eng.info("last.semi_tables") == 0 and eng.info("last.join_kernel") != JK_SEMI
     dv.free()
     ds.free()
+
+
+# ---- the tables' empty marker as a join value ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("value", ["raw", "unmixed"])
+@pytest.mark.parametrize("ones_on", ["both", "R", "S"])
+def test_all_ones_value(eng, inputs, ones_on, value):
+    """70,000 rows, a one-pass plan: the kernel sees rhj_mix64(payload), so unmix64(all ones) is the key it keeps beside the table
+    (and the raw all-ones payload an ordinary key); on S only, on R only and on both"""
+    n = 70_000
+    assert resolve_plan(n, n).passes == 1
+    R0, S0, _ = inputs("uniform", n)
+    R, S = R0.copy(), S0.copy()
+    ones = np.uint64(0xFFFFFFFFFFFFFFFF)
+    if value == "unmixed":
+        ones = unmix64(ones)
+        assert int(mix64(ones)) == 0xFFFFFFFFFFFFFFFF
+    if ones_on in ("both", "R"):
+        R["payload"][[3, 1_500]] = ones
+    if ones_on in ("both", "S"):
+        S["payload"][[7, 8, 2_000]] = ones
+    mask = np.isin(R["payload"], S["payload"])
+    is_ones = R["payload"] == ones
+    assert int(is_ones.sum()) == (0 if ones_on == "S" else 2) and mask[is_ones].all() == (ones_on == "both" or ones_on == "S")
+    eng.set_option("partition.narrow", -1)
+
+    def after(kind):
+        assert eng.info("last.join_kernel") == JK_SEMI and eng.info("last.semi_tables") == 1 and eng.timings()["passes"] == 1
+    for ids in (True, False):
+        run_cols(eng, R, S, mask, ids, after=after)
 
 
 # ---- partitions without S, a disjoint S, degenerate sizes, invalid arguments -------------------------------------------------

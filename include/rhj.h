@@ -120,6 +120,12 @@ int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
  * that does not fit its region (heavy skew) is partitioned again with exact cursors inside the same call, and that side of the
  * context's joins then stays on the exact path for the next 2, 4, ... 32 eligible joins (setting the option re-arms);
  * automatic: relations of more than 2^28 tuples (RHJ_COUNTFREE=0 / 1 in the environment: A/B aid);
+ * "partition.countfree2": -1 automatic, 0 never, 1 whenever it applies: in a PAIR join (rhj_join_dev / rhj_join_cols_dev) a side
+ * whose pass 1 runs count-free, under a plan whose pass 1 has at least as many buckets as the device has compute units, is
+ * written by pass 2 with one workgroup per pass-1 bucket into a fixed region per final partition, so pass 2's histogram and scan
+ * are not needed; a side with a final partition that does not fit its region is partitioned again with the pass-2 histogram inside
+ * the same call and backs off like "partition.countfree", with a state of its own (setting the option re-arms); same pairs either
+ * way; automatic: wherever the automatic count-free pass 1 is on (RHJ_COUNTFREE2=0 / 1 in the environment: A/B aid); every other entry keeps exact boundaries;
  * "partition.mix": -1 automatic (= 1 unless RHJ_MIX=0 is in the environment), 1: joins take their radix digits from
  * rhj_mix64(payload), 0: from the raw payload (see rhj_opts);
  * "join.sniff": -1 automatic (= 1 unless RHJ_SNIFF=0), 1: a partitioned join samples the join values of both relations for
@@ -128,7 +134,9 @@ int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
  * without duplicates answers every probe tuple with one match); 0: the first relation wins such a tie.  Same pairs either way. */
 int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
 /* what the last join did: "last.narrow" (0 / 1 / 2, see above), "last.countfree_R" / "last.countfree_S" (pass 1 of that side:
- * 0 exact cursors, 1 count-free, 2 count-free tried and repeated with exact cursors), "last.join_kernel" (-1 none: direct small join or empty
+ * 0 exact cursors, 1 count-free, 2 count-free tried and repeated with exact cursors), "last.countfree2_R" / "last.countfree2_S" (pass 2 of
+ * that side: 0 histogram and exact cursors, 1 one writer per final partition, 2 tried and repeated with the histogram; 0 after every
+ * entry but the pair join), "last.join_kernel" (-1 none: direct small join or empty
  * input; 0 the one-table kernel; 1 the chunked 16-byte-entry kernel; 2 ... 11 the compact-table kernel, one number per geometry:
  * 2 / 3 full / half size, 4 / 5 the same with 20 instead of 16 probe slots per thread (narrow partitions only), 6 / 7 the middle
  * geometry and its half-size form, 8 the full-size table with half the buckets, 9 the half-size middle geometry skipping the slot

@@ -29,7 +29,9 @@ def short(name):
     k = m.group(1)
     t = re.search(re.escape(k) + r"<([^>]*)>", name)
     if k in ("k_scatter_wcn", "k_scatter_wcn_cf") and t:  # input format: 16-byte tuples or narrow arrays (_cf: count-free pass 1 / its pass 2)
-        k += "<in_narrow=%s>" % t.group(1).strip()
+        a = t.group(1).split(",")[0].strip()
+        e = re.search(r"InForm\)(\d)$", a)                # the InForm enumerator as rocprofv3 prints it: (...::InForm)N
+        k += "<in_narrow=%s>" % (("false", "true", "false", "false")[int(e.group(1))] if e else a)
     if k == "k_join_ct" and t:
         a = [x.strip() for x in t.group(1).split(",")]
         k += "<%s threads%s>" % (a[0], ", narrow" if a[-1] == "true" else "")
@@ -88,8 +90,10 @@ if sc:
     sys.path.insert(0, ROOT)
     from bench import source_blobs                      # the kernel sources these counters were measured on
     def one(flag):
-        v = [x for k, x in pmc.items() if k.startswith(("k_scatter_wcn<in_narrow=%s" % flag, "k_scatter_wcn_cf<in_narrow=%s" % flag))
-             and "hbm_bytes_per_launch" in x]
+        names = ("k_scatter_wcn<in_narrow=%s" % flag, "k_scatter_wcn_cf<in_narrow=%s" % flag)
+        if flag == "true" and "k_scatter_wcn_cf2" in pmc:  # pass 2 with one writer per final partition stands in for the others
+            names = ("k_scatter_wcn_cf2",)
+        v = [x for k, x in pmc.items() if k.startswith(names) and "hbm_bytes_per_launch" in x]
         return v[0]["hbm_bytes_per_launch"] if len(v) == 1 else None
     json.dump({"tuples": int(m.group(1)) if m else None, "bits": [int(b.group(1)), int(b.group(2))] if b else None,
                "scatter_hbm_bytes_per_launch": per_launch,

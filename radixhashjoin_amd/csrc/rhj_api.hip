@@ -282,6 +282,18 @@ struct rhj_ctx {
     u32 cf_over = 0;                   // the skip word as join_phase read it (bits 1, 2)
     int last_cf[2] = {0, 0};           // "last.countfree_R/_S": 0 exact, 1 count-free, 2 tried and fell back
     DevBuf cf_cnt1, cf_pre, cf_tot;
+    // count-free pass 2 with one writer per final partition (rhj.h "partition.countfree2"), per side of a PAIR join: the
+    // partitions lie in regions of cap2 slots with gaps between them, start[k] = k * cap2 in ps_R / ps_S and end[k] in cf2_end; a
+    // side one of whose partitions did not fit (the skip word's bit 8 << side) is repeated with the pass-2 histogram inside the
+    // same call, and backs off like the count-free pass 1, with a state of its own
+    int opt_countfree2 = -1;           // -1: automatic (RHJ_COUNTFREE2 env; see CF2_AUTO), 0: never, 1: whenever the case applies
+    u32 cf2_fail_streak[2] = {0, 0}, cf2_skip[2] = {0, 0};
+    bool cf2_off_once[2] = {false, false};  // the repeat of a side that fell back
+    int last_cf2[2] = {0, 0};          // "last.countfree2_R/_S": 0 histogram path, 1 count-free, 2 tried and fell back
+    DevBuf cf2_end[2];
+    const u64 *cur_end[2] = {nullptr, nullptr};   // state of the last partition phase: the side's end array, or null: contiguous partitions
+    u64 cur_slots[2] = {0, 0};         // ... and the slots of its final arrays (the rowID array starts at 8 * slots), or 0
+    int num_cus = 0;                   // compute units of the device
     // rhj_join_cols_dev: the relations of the join in progress as columns (val == nullptr: a 16-byte call); the 16-byte copy of
     // a side that a plan without a columnar first kernel asks for (converted on first use, once per call); "last.cols_R/_S"
     ColsIn cols_in[2];
@@ -762,6 +774,18 @@ CfGeom cf_geometry(u64 n, int b1)
     return c;
 }
 size_t cf_tmp_bytes(const CfGeom &c) { return (size_t)c.slots * 12; }
+// Count-free pass 2, one writer per final partition: the regions.  cap2 = the mean final partition, m2 = n / 2^(b1 + b2), plus ten
+// standard deviations of a hashed digit's count, rounded up to whole 32-tuple lines (headline: 16,512 for a mean of 15,259, +8 %:
+// 12.98 GB per relation); every region starts on a 128-byte line of both final arrays and no line has two writers.
+Cf2Geom cf2_geometry(u64 n, int b1, int b2)
+{
+    Cf2Geom c;
+    const u64 np = (u64)1 << (b1 + b2);
+    const double m = (double)n / (double)np;
+    c.cap2 = (u32)(((u64)(m + 10.0 * std::sqrt(m)) + 1 + 31) / 32 * 32);
+    c.slots = np * c.cap2;
+    return c;
+}
 // the case it applies to: 16-byte input, narrow level 2, digits of mix64(payload), both passes of at most 8 bits
 bool cf_applies(u64 n, int b1, int b2, int narrow, int mix, bool segs)
 {
@@ -773,8 +797,10 @@ bool cf_applies(u64 n, int b1, int b2, int narrow, int mix, bool segs)
 // mix (16-byte input only): MIX_STORE inside a join -- the histogram and pass 1 take their digits from mix64(payload) and pass 1
 // writes the mixed value, so that pass 2 and the bucket join work on it unchanged
 // cf_side >= 0: pass 1 runs without counts where cf_applies() (that side's bit of the skip word reports a run that did not fit)
+// d_end2 (with a count-free pass 1 only; cf2_end_for): pass 2 has one writer per final partition -- d_out is sized for the regions
+// of cf2_geometry(), d_ps receives the region starts and d_end2 the partitions' ends
 int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int b2, void *d_out, u64 *d_ps, int narrow = 0,
-                             int mix = MIX_NONE, const PartScratch *scratch = nullptr, int cf_side = -1)
+                             int mix = MIX_NONE, const PartScratch *scratch = nullptr, int cf_side = -1, u64 *d_end2 = nullptr)
 {
     // the scratch tables and the stream of this relation: the context's first set on its stream, or -- R and S of a mid-size
     // join partitioned side by side -- the second set on the auxiliary stream (partition_phase)
@@ -858,6 +884,12 @@ int partition_relation_fused(rhj_ctx *ctx, const FusedIn &in, u64 n, int b1, int
             Span s(ctx, RHJ_K_SCATTER);
             if (cols) launch_cf_pass1_cols(st, in.cols, x_part_tmp.p, cg, g1, seg0, unit_start1, (u32 *)ctx->cf_cnt1.p, wide, 2u << cf_side, sn);
             else launch_cf_pass1(st, in.aos, x_part_tmp.p, cg, g1, seg0, unit_start1, (u32 *)ctx->cf_cnt1.p, wide, 2u << cf_side, sn);
+        }
+        if (d_end2) {                                   // no piece tables, no histogram, no scan: pass 2 builds its prefix itself
+            Span s(ctx, RHJ_K_SCATTER);
+            launch_cf2_pass2(st, x_part_tmp.p, d_out, cg, cf2_geometry(n, b1, b2), (u32)nb1, b1, b2, (const u32 *)ctx->cf_cnt1.p, d_ps,
+                             d_end2, wide, 8u << cf_side);
+            return check_launch(ctx, "count-free two-pass partition");
         }
         {
             Span s(ctx, RHJ_K_AUX);
@@ -1105,6 +1137,11 @@ bool is_direct(const rhj_ctx *ctx, u64 nparts, u64 nR, u64 nS)
 }
 
 // "partition.countfree" as it stands: the option, else RHJ_COUNTFREE=0 / 1 in the environment (A/B aid), else -1 (automatic)
+// no side of the current partitions lies in regions with gaps, and none took the one-writer pass 2
+void clear_gaps(rhj_ctx *ctx)
+{
+    for (int side = 0; side < 2; side++) { ctx->last_cf2[side] = 0; ctx->cur_end[side] = nullptr; ctx->cur_slots[side] = 0; }
+}
 int cf_want(const rhj_ctx *ctx)
 {
     static const int env = getenv("RHJ_COUNTFREE") ? (int)env_u64("RHJ_COUNTFREE", 0, 0, 1) : -1;
@@ -1119,7 +1156,8 @@ bool two_streams_ok(const rhj_ctx *ctx, u64 nR, u64 nS, const rhj_opts &plan, st
     static const bool on = env_u64("RHJ_TWO_STREAMS", 1, 0, 1) != 0;
     if (!on || ctx->prof.on || (before_S && *before_S)) return false;
     // forced count-free pass 1, or the repeat of a side that overflowed: the one-stream path carries both
-    if (cf_want(ctx) == 1 || ctx->cf_keep_R || ctx->cf_off_once[0] || ctx->cf_off_once[1]) return false;
+    if (cf_want(ctx) == 1 || ctx->cf_keep_R || ctx->cf_off_once[0] || ctx->cf_off_once[1] || ctx->cf2_off_once[0] || ctx->cf2_off_once[1])
+        return false;
     if (plan.passes != 2 || !fused_two_pass_ok(plan.bits1, plan.bits2)) return false;
     if (ctx->cur_narrow && !narrow_fused_plan(plan)) return false;
     const u64 hi = nR > nS ? nR : nS, lo = nR > nS ? nS : nR;
@@ -1137,6 +1175,42 @@ int cf_side_for(rhj_ctx *ctx, int side, u64 nR, u64 nS, const rhj_opts &plan, in
     if (want < 0 && (nR > nS ? nR : nS) <= CF_AUTO_MIN_TUPLES) return -1;
     if (ctx->cf_skip[side] > 0) { ctx->cf_skip[side]--; return -1; }          // backing off after a fall-back of this side
     return side;
+}
+
+// "partition.countfree2" as it stands: the option, else RHJ_COUNTFREE2=0 / 1 in the environment (A/B aid), else -1 (automatic)
+int cf2_want(const rhj_ctx *ctx)
+{
+    static const int env = getenv("RHJ_COUNTFREE2") ? (int)env_u64("RHJ_COUNTFREE2", 0, 0, 1) : -1;
+    return ctx->opt_countfree2 >= 0 ? ctx->opt_countfree2 : env;
+}
+// Automatic mode of the one-writer pass 2: where the automatic count-free pass 1 is on (DESIGN 4.20 says what was measured).
+constexpr bool CF2_AUTO = true;
+// the case a one-writer pass 2 applies to, given that the count-free pass 1 applies: one workgroup per pass-1 bucket fills the
+// device (fewer leave compute units idle), and the bucket's U piece lengths fit the kernel's prefix table
+bool cf2_applies(const rhj_ctx *ctx, u64 n, int b1, int b2)
+{
+    if (ctx->num_cus <= 0 || ((u64)1 << b1) < (u64)ctx->num_cus) return false;
+    const CfGeom c = cf_geometry(n, b1);                  // (the kernel addresses a slot inside its bucket with 32 bits)
+    return c.U <= CF2_PRE - 1 && (u64)c.U * c.cap < ((u64)1 << 31) && (double)cf2_geometry(n, b1, b2).slots * 12.0 < 1.0e12;
+}
+// Count-free pass 2 for this side of this pair join?  cf_side: what cf_side_for() answered for it.  d_end: the side's end array
+// (buffers grown, ctx->cur_end / cur_slots / last_cf2 set), or null: exact boundaries.
+int cf2_end_for(rhj_ctx *ctx, int side, int cf_side, u64 nR, u64 nS, const rhj_opts &plan, u64 *&d_end)
+{
+    d_end = nullptr;
+    const int want = cf2_want(ctx);
+    const u64 n = side ? nS : nR;
+    if (cf_side < 0 || want == 0 || ctx->cf2_off_once[side] || !cf2_applies(ctx, n, plan.bits1, plan.bits2)) return RHJ_OK;
+    if (want < 0 && (!CF2_AUTO || (nR > nS ? nR : nS) <= CF_AUTO_MIN_TUPLES)) return RHJ_OK;
+    if (ctx->cf2_skip[side] > 0) { ctx->cf2_skip[side]--; return RHJ_OK; }    // backing off after a fall-back of this side
+    const Cf2Geom c2 = cf2_geometry(n, plan.bits1, plan.bits2);
+    RHJCHK(ensure(ctx, side ? ctx->part_S : ctx->part_R, cf2_part_bytes(c2)));
+    RHJCHK(ensure(ctx, ctx->cf2_end[side], (size_t)8 << (plan.bits1 + plan.bits2)));
+    d_end = (u64 *)ctx->cf2_end[side].p;
+    ctx->cur_end[side] = d_end;
+    ctx->cur_slots[side] = c2.slots;
+    ctx->last_cf2[side] = 1;
+    return RHJ_OK;
 }
 
 // A relation of a columnar join (rhj_join_cols_dev; a 16-byte call passes through both unchanged).  fused_input: for
@@ -1175,8 +1249,10 @@ int cols_to_aos(rhj_ctx *ctx, u64 nR, const void *&d_R, u64 nS, const void *&d_S
 // ctx->one_sided (a group-by): R alone is partitioned, under the plan, the format and the count-free choice of a join of (nR, nS = nR)
 // -- S is skipped explicitly: no kernel reads or writes a buffer of S, part_S is not grown, nothing is sampled (one side has no tie
 // to break), R takes the one-stream path and, under a one-pass plan, run_pass instead of the paired launches.  cur_S is null.
+// gaps_ok: the consumer is the pair join's join_phase, which takes partitions in regions with gaps (cf2_end_for); every other
+// consumer reads contiguous partitions under exact boundaries.
 int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan,
-                    std::function<int()> *before_S = nullptr)
+                    std::function<int()> *before_S = nullptr, bool gaps_ok = false)
 {
     const bool one = ctx->one_sided;
     ctx->sniff_ready = false;
@@ -1197,6 +1273,11 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
     const bool keep_R = ctx->cf_keep_R;
     if (!keep_R && !ctx->cf_off_once[0]) ctx->last_cf[0] = 0;
     if (!ctx->cf_off_once[1]) ctx->last_cf[1] = 0;
+    for (int side = keep_R ? 1 : 0; side < 2; side++) {
+        if (!ctx->cf2_off_once[side]) ctx->last_cf2[side] = 0;
+        ctx->cur_end[side] = nullptr;
+        ctx->cur_slots[side] = 0;
+    }
     if (ctx->cur_narrow) {
         RHJCHK(ensure(ctx, ctx->narrow_flag, 64));
         Span s(ctx, RHJ_K_AUX);
@@ -1270,14 +1351,24 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
             if (sniff) RHJCHK(ensure(ctx, ctx->sniff_tab, (size_t)2 * SNIFF_SLOTS * 4));
             ctx->sniff_side = sniff ? 0 : -1;
             int prc = RHJ_OK;
-            if (!keep_R)                                        // (the repeat after an overflow of S alone: R stands, samples included)
-                prc = partition_relation_fused(ctx, fused_input(ctx, 0, d_R), nR, plan.bits1, plan.bits2, ctx->part_R.p, (u64 *)ctx->ps_R.p,
-                                               ctx->cur_narrow, mix, nullptr, cf_side_for(ctx, 0, nR, nS, plan, mix));
+            u64 *end2 = nullptr;
+            if (!keep_R) {                                      // (the repeat after an overflow of S alone: R stands, samples included)
+                const int cfs = cf_side_for(ctx, 0, nR, nS, plan, mix);
+                if (gaps_ok && !one) prc = cf2_end_for(ctx, 0, cfs, nR, nS, plan, end2);
+                if (prc == RHJ_OK)
+                    prc = partition_relation_fused(ctx, fused_input(ctx, 0, d_R), nR, plan.bits1, plan.bits2, ctx->part_R.p,
+                                                   (u64 *)ctx->ps_R.p, ctx->cur_narrow, mix, nullptr, cfs, end2);
+            }
             if (prc == RHJ_OK) prc = s_ready();
             ctx->sniff_side = sniff ? 1 : -1;
-            if (prc == RHJ_OK && !one)
-                prc = partition_relation_fused(ctx, fused_input(ctx, 1, d_S), nS, plan.bits1, plan.bits2, ctx->part_S.p, (u64 *)ctx->ps_S.p,
-                                               ctx->cur_narrow, mix, nullptr, cf_side_for(ctx, 1, nR, nS, plan, mix));
+            if (prc == RHJ_OK && !one) {
+                const int cfs = cf_side_for(ctx, 1, nR, nS, plan, mix);
+                end2 = nullptr;
+                if (gaps_ok) prc = cf2_end_for(ctx, 1, cfs, nR, nS, plan, end2);
+                if (prc == RHJ_OK)
+                    prc = partition_relation_fused(ctx, fused_input(ctx, 1, d_S), nS, plan.bits1, plan.bits2, ctx->part_S.p,
+                                                   (u64 *)ctx->ps_S.p, ctx->cur_narrow, mix, nullptr, cfs, end2);
+            }
             ctx->sniff_side = -1;
             RHJCHK(prc);
             ctx->sniff_ready = sniff;
@@ -1306,8 +1397,10 @@ int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 
 int join_phase_on(rhj_ctx *ctx, const void *d_Rp, const u64 *d_psR, u64 nR, const void *d_Sp, const u64 *d_psS,
                   u64 nS, u64 nparts, int radix_bits, u32 probe_split, void *d_out, u64 cap, u64 *out_count, bool narrow = false,
                   const u64 *d_tag_base = nullptr, bool allow_direct = true, bool check_radix = false, bool keep_count = false,
-                  bool enqueue_only = false, bool allow13 = true)
+                  bool enqueue_only = false, bool allow13 = true, const PartEnds &pe = PartEnds(), u64 slotsR = 0, u64 slotsS = 0)
 {
+    // pe / slotsR / slotsS (narrow only): a side's partitions lie in regions with gaps -- its end array, and the slots
+    // of its final arrays, which place the rowID array (0: the side's tuple count, as always)
     // keep_count: the result counter goes on from where the previous join on this context left it (the pairs of several joins
     // land behind one another in d_out); enqueue_only: no read-back, the caller collects the counters itself
     if (probe_split == 0) probe_split = 32768;
@@ -1338,7 +1431,7 @@ int join_phase_on(rhj_ctx *ctx, const void *d_Rp, const u64 *d_psR, u64 nR, cons
     ctx->last_join_kind = direct ? -1 : kind;
     if (check_radix && !direct && jk_is_ct(kind)) {       // counters[6]: the partitions break the radix_bits contract
         Span s(ctx, RHJ_K_AUX);
-        launch_check_radix(ctx->stream, d_Rp, d_psR, d_Sp, d_psS, nparts, radix_bits, d_count + 6);
+        launch_check_radix(ctx->stream, d_Rp, d_psR, d_Sp, d_psS, nparts, radix_bits, d_count + 6, pe);
     }
     if (direct) {
         Span s(ctx, RHJ_K_JOIN);                                     // small unpartitioned join: one launch, no task list
@@ -1354,14 +1447,14 @@ int join_phase_on(rhj_ctx *ctx, const void *d_Rp, const u64 *d_psR, u64 nR, cons
             }
             ctx->sniff_ready = false;
             launch_make_tasks(ctx->stream, d_psR, d_psS, nparts, probe_split, (JoinTask *)ctx->tasks.p, d_ntasks, max_tasks,
-                              d_count + 2, kind, sv);               // counters[2..3]: largest partition of R, S
+                              d_count + 2, kind, sv, pe);           // counters[2..3]: largest partition of R, S
         }
         {
             Span s(ctx, RHJ_K_JOIN);
             launch_join(ctx->stream, d_Rp, d_psR, d_Sp, d_psS, (const JoinTask *)ctx->tasks.p, d_ntasks, max_tasks,
                         radix_bits, d_out, d_out ? cap : 0, d_count, kind,
-                        narrow ? (const u32 *)((const unsigned char *)d_Rp + narrow_k_offset(nR)) : nullptr,
-                        narrow ? (const u32 *)((const unsigned char *)d_Sp + narrow_k_offset(nS)) : nullptr,
+                        narrow ? (const u32 *)((const unsigned char *)d_Rp + narrow_k_offset(slotsR ? slotsR : nR)) : nullptr,
+                        narrow ? (const u32 *)((const unsigned char *)d_Sp + narrow_k_offset(slotsS ? slotsS : nS)) : nullptr,
                         d_tag_base, narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
         }
     }
@@ -1389,8 +1482,11 @@ int join_phase_on(rhj_ctx *ctx, const void *d_Rp, const u64 *d_psR, u64 nR, cons
 
 int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
 {
+    PartEnds pe;
+    pe.endR = ctx->cur_end[0]; pe.endS = ctx->cur_end[1]; pe.nR = ctx->cur_nR; pe.nS = ctx->cur_nS;
     return join_phase_on(ctx, ctx->cur_R, ctx->cur_psR, ctx->cur_nR, ctx->cur_S, ctx->cur_psS, ctx->cur_nS,
-                         ctx->cur_nparts, ctx->cur_radix_bits, ctx->cur_probe_split, d_out, cap, out_count, ctx->cur_narrow != 0);
+                         ctx->cur_nparts, ctx->cur_radix_bits, ctx->cur_probe_split, d_out, cap, out_count, ctx->cur_narrow != 0,
+                         nullptr, true, false, false, false, true, pe, ctx->cur_slots[0], ctx->cur_slots[1]);
 }
 
 // What a join reports once both sides are partitioned: the pairs (join_phase), the rowIDs of the tuples of R with (RHJ_SEMI) or
@@ -1875,6 +1971,7 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
     ctx->last.bits2 = 0;
     ctx->cur_narrow = 0;
     ctx->last_cf[0] = ctx->last_cf[1] = 0;                   // (no partition_phase here: "last.countfree_*" must not keep the last join's)
+    clear_gaps(ctx);
     ctx->counters_clean = false;
     int kind = choose_join_kind(ctx, nR, nS, nbins, bits, false);
     u32 probe_split = plan.probe_split ? (u32)plan.probe_split : 32768u;
@@ -1974,7 +2071,8 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
                what == OUT_OUTER ? outer_phase(ctx, d_out, cap, out_count) :
                semi_phase(ctx, what, d_out, cap, out_count);
     };
-    int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S);
+    const bool gaps_ok = what == OUT_PAIRS;                  // the pair join's task builder reads boundaries with gaps
+    int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S, gaps_ok);
     if (rc != RHJ_OK) { ctx->counters_clean = false; return rc; }
     const bool tried_narrow = ctx->cur_narrow != 0;
     rc = after_partition();
@@ -1983,22 +2081,34 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
     // as before: at most two repeats).
     for (int attempt = 0; rc == RHJ_RETRY_CF && attempt < 2; attempt++) {
         const u32 over = ctx->cf_over;
-        for (int side = 0; side < 2; side++)
+        for (int side = 0; side < 2; side++) {
             if (over & (2u << side)) {
                 ctx->cf_off_once[side] = true;
                 ctx->last_cf[side] = 2;
                 ctx->cf_fail_streak[side]++;
                 ctx->cf_skip[side] = ctx->cf_fail_streak[side] > 4 ? 32u : 1u << ctx->cf_fail_streak[side];
             }
-        ctx->cf_keep_R = !(over & 2u);
-        rc = partition_phase(ctx, d_R, nR, d_S, nS, plan);
+            // a final partition did not fit its region: that side again with the pass-2 histogram (its count-free pass 1 may stay)
+            if (over & (8u << side)) {
+                ctx->cf2_off_once[side] = true;
+                ctx->last_cf2[side] = 2;
+                ctx->cf2_fail_streak[side]++;
+                ctx->cf2_skip[side] = ctx->cf2_fail_streak[side] > 4 ? 32u : 1u << ctx->cf2_fail_streak[side];
+            }
+        }
+        ctx->cf_keep_R = !(over & (2u | 8u));
+        rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, nullptr, gaps_ok);
         ctx->cf_keep_R = false;
         if (rc == RHJ_OK) rc = after_partition();
     }
     ctx->cf_off_once[0] = ctx->cf_off_once[1] = false;
+    ctx->cf2_off_once[0] = ctx->cf2_off_once[1] = false;
     if (rc == RHJ_RETRY_CF) return fail(ctx, RHJ_E_HIP, "count-free partition: overflow flag after the exact repeat");
     if (rc == RHJ_OK)
-        for (int side = 0; side < 2; side++) if (ctx->last_cf[side] == 1) ctx->cf_fail_streak[side] = 0;
+        for (int side = 0; side < 2; side++) {
+            if (ctx->last_cf[side] == 1) ctx->cf_fail_streak[side] = 0;
+            if (ctx->last_cf2[side] == 1) ctx->cf2_fail_streak[side] = 0;
+        }
     if (rc != RHJ_OK && rc != RHJ_RETRY_WIDE) { ctx->counters_clean = false; return rc; }
     if (rc != RHJ_RETRY_WIDE) {
         if (rc == RHJ_OK && !ctx->narrow_off_once) narrow_note_done(ctx, plan, tried_narrow);   // (off_once: the repeat of a join that fell back)
@@ -2105,6 +2215,10 @@ int rhj_init(int device, rhj_ctx **out_ctx)
         return fail(nullptr, RHJ_E_HIP, "cannot create a stream on the device");
     }
     ctx->stream = ctx->own_stream;
+    if (hipDeviceGetAttribute(&ctx->num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->num_cus = 0;                                   // (unknown: the one-writer pass 2 never applies)
+    }
     *out_ctx = ctx;
     return RHJ_OK;
 }
@@ -2119,7 +2233,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->counters, &ctx->out_pairs, &ctx->small_out, &ctx->hist_tmp, &ctx->scan_tmp, &ctx->hist2,
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->agg_out, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
-                     &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
+                     &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cf2_end[0], &ctx->cf2_end[1], &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
                      &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1]};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
@@ -2188,6 +2302,11 @@ int rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value)
         for (int side = 0; side < 2; side++) ctx->cf_fail_streak[side] = ctx->cf_skip[side] = 0;
         return RHJ_OK;
     }
+    if (n == "partition.countfree2" && value >= -1 && value <= 1) {
+        ctx->opt_countfree2 = (int)value;
+        for (int side = 0; side < 2; side++) ctx->cf2_fail_streak[side] = ctx->cf2_skip[side] = 0;
+        return RHJ_OK;
+    }
     if (n == "join.fused" && value >= -1 && value <= 1) { ctx->opt_fused = (int)value; return RHJ_OK; }
     if (n == "join.sniff" && value >= -1 && value <= 1) { ctx->opt_sniff = (int)value; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_set_option: unknown option or value: " + n);
@@ -2200,6 +2319,8 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.narrow") { *value = ctx->cur_narrow; return RHJ_OK; }
     if (n == "last.countfree_R") { *value = ctx->last_cf[0]; return RHJ_OK; }
     if (n == "last.countfree_S") { *value = ctx->last_cf[1]; return RHJ_OK; }
+    if (n == "last.countfree2_R") { *value = ctx->last_cf2[0]; return RHJ_OK; }
+    if (n == "last.countfree2_S") { *value = ctx->last_cf2[1]; return RHJ_OK; }
     if (n == "last.cols_R") { *value = ctx->last_cols[0]; return RHJ_OK; }
     if (n == "last.cols_S") { *value = ctx->last_cols[1]; return RHJ_OK; }
     if (n == "last.join_kernel") { *value = ctx->last_join_kind; return RHJ_OK; }
@@ -2289,6 +2410,11 @@ int rhj_reserve(rhj_ctx *ctx, uint64_t nR, uint64_t nS, const rhj_opts *opts)
             RHJCHK(ensure(ctx, ctx->cf_cnt1, (size_t)c.U * nb1 * 4));
             RHJCHK(ensure(ctx, ctx->cf_pre, cf_pre_words((u32)units2) * 4));
             RHJCHK(ensure(ctx, ctx->cf_tot, units2 * 4));
+            // ... and a one-writer pass 2: final arrays with the regions' slack, the end array
+            if (cf2_want(ctx) == 0 || !cf2_applies(ctx, n, plan.bits1, plan.bits2)) continue;
+            if (cf2_want(ctx) < 0 && (!CF2_AUTO || (nR > nS ? nR : nS) <= CF_AUTO_MIN_TUPLES)) continue;
+            RHJCHK(ensure(ctx, side ? ctx->part_S : ctx->part_R, cf2_part_bytes(cf2_geometry(n, plan.bits1, plan.bits2))));
+            RHJCHK(ensure(ctx, ctx->cf2_end[side], (size_t)8 << (plan.bits1 + plan.bits2)));
         }
     }
     return RHJ_OK;
@@ -2358,6 +2484,7 @@ static int semi_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d
         ctx->cur_narrow = 0;
         ctx->counters_clean = false;
         ctx->last_cf[0] = ctx->last_cf[1] = 0;
+        clear_gaps(ctx);
         RHJCHK(cols_to_aos(ctx, 0, nR, d_R));
         RHJCHK(ensure(ctx, ctx->ps_R, 64));
         RHJCHK(ensure(ctx, ctx->ps_S, 64));
@@ -2425,6 +2552,7 @@ static int outer_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *
         ctx->cur_probe_split = 0;
         ctx->cur_narrow = 0;
         ctx->last_cf[0] = ctx->last_cf[1] = 0;
+        clear_gaps(ctx);
         const void *d_P = side ? d_S : d_R;
         RHJCHK(cols_to_aos(ctx, side, side ? nS : nR, d_P));
         RHJCHK(ensure(ctx, ctx->ps_R, 64));
@@ -3735,6 +3863,24 @@ extern "C" int rhj_debug_read_partitions(rhj_ctx *ctx, int side, uint64_t *paylo
     const u64 n = side ? ctx->cur_nS : ctx->cur_nR;
     const unsigned char *part = (const unsigned char *)(side ? ctx->cur_S : ctx->cur_R);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->cur_end[side] != nullptr) {                // regions with gaps: compacted here, exact prefix boundaries
+        const u64 np = ctx->cur_nparts, slots = ctx->cur_slots[side], cap2 = slots / np;
+        std::vector<u64> hp((size_t)slots), he((size_t)np);
+        std::vector<u32> hk((size_t)slots);
+        HIPCHK(ctx, hipMemcpy(hp.data(), part, (size_t)slots * 8, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(hk.data(), part + narrow_k_offset(slots), (size_t)slots * 4, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(he.data(), ctx->cur_end[side], (size_t)np * 8, hipMemcpyDeviceToHost));
+        u64 at = 0;
+        for (u64 k = 0; k < np; k++) {
+            const u64 s = k * cap2, len = he[k] > s ? he[k] - s : 0;
+            if (len > cap2 || at + len > n) return fail(ctx, RHJ_E_HIP, "rhj_debug_read_partitions: a partition's end lies outside its region");
+            bounds[k] = at;
+            for (u64 i = 0; i < len; i++) { payloads[at + i] = hp[s + i]; rowids[at + i] = hk[s + i]; }
+            at += len;
+        }
+        bounds[np] = at;
+        return RHJ_OK;
+    }
     HIPCHK(ctx, hipMemcpy(payloads, part, (size_t)n * 8, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(rowids, part + narrow_k_offset(n), (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(bounds, side ? ctx->cur_psS : ctx->cur_psR, (size_t)(ctx->cur_nparts + 1) * 8, hipMemcpyDeviceToHost));

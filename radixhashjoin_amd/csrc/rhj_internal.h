@@ -96,11 +96,15 @@ void launch_scan_units(hipStream_t st, const PassGeom &g, const u64 *d_seg_start
 void launch_scatter_units(hipStream_t st, const void *d_in, void *d_out, const PassGeom &g,
                           const u64 *d_seg_start, const u32 *d_unit_start, const u64 *d_unit_base);
 void launch_diff_hist(hipStream_t st, const u64 *d_start, u64 nbins, u64 *d_hist);
+// Boundaries with gaps: endR / endS null: partition k of that side is [start[k], start[k + 1]); else [start[k], end[k])
+// (an end below its start: empty) and nR / nS is the side's tuple count, which start[nparts] no longer is.
+struct PartEnds { const u64 *endR = nullptr, *endS = nullptr; u64 nR = 0, nS = 0; };
 void launch_check_radix(hipStream_t st, const void *d_R, const u64 *d_startR, const void *d_S, const u64 *d_startS, u64 nparts,
-                        int radix_bits, u64 *d_bad);
+                        int radix_bits, u64 *d_bad, const PartEnds &pe = PartEnds());
 void launch_prefix(hipStream_t st, const u64 *d_hist, u64 nbins, u64 *d_start);
 void launch_make_tasks(hipStream_t st, const u64 *d_startR, const u64 *d_startS, u64 nparts, u32 probe_split,
-                       JoinTask *d_tasks, u32 *d_ntasks, u32 max_tasks, u64 *d_stats, int kind, const SniffVerdict &sniff = SniffVerdict());
+                       JoinTask *d_tasks, u32 *d_ntasks, u32 max_tasks, u64 *d_stats, int kind, const SniffVerdict &sniff = SniffVerdict(),
+                       const PartEnds &pe = PartEnds());
 void launch_join(hipStream_t st, const void *d_R, const u64 *d_startR, const void *d_S, const u64 *d_startS,
                  const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits,
                  void *d_out, u64 out_capacity, u64 *d_out_count, int kind, const u32 *d_RK = nullptr, const u32 *d_SK = nullptr,
@@ -412,6 +416,14 @@ struct CfGeom { u32 U = 0, per = 0, ngroups = 0, cap = 0; u64 slots = 0; };
 constexpr u32 CF_PER_MAX = 64, CF_PRE = CF_PER_MAX + 1;  // pieces per pass-2 unit the kernels handle; words of a unit's prefix table
 constexpr u32 cf_per_max() { return CF_PER_MAX; }
 constexpr size_t cf_pre_words(u32 units2) { return (size_t)units2 * CF_PRE; }
+// Count-free pass 2 with one writer per final partition (k_scatter_wcn_cf2): final partition p of np = nb1 << b2 owns
+// slots [p * cap2, + cap2) of the final arrays; payloads (u64) at offset 0 of the partition buffer, rowIDs (u32) at
+// narrow_k_offset(slots) = 8 * slots.  The prefix of a bucket's U piece lengths lives in the kernel's LDS: U <= CF2_PRE - 1.
+struct Cf2Geom { u32 cap2 = 0; u64 slots = 0; };
+constexpr u32 CF2_PRE = 1025;
+constexpr size_t cf2_part_bytes(const Cf2Geom &c) { return (size_t)c.slots * 12 + 256; }
+void launch_cf2_pass2(hipStream_t st, const void *d_tmp, void *d_out, const CfGeom &c, const Cf2Geom &c2, u32 nb1, int b1, int b2,
+                      const u32 *d_cnt1, u64 *d_start, u64 *d_end, u32 *d_flag, u32 bit);
 void launch_cf_pass1(hipStream_t st, const void *d_in, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,
                      const u32 *d_unit_start, u32 *d_cnt1, u32 *d_flag, u32 bit, const DupSniff &sniff);
 void launch_cf_pass1_cols(hipStream_t st, const ColsIn &cols, void *d_tmp, const CfGeom &c, const PassGeom &g, const u64 *d_seg_start,

@@ -1375,11 +1375,18 @@ struct WnPeer {
 // The payload array between the two count-free passes is private to them and k_hist_pieces_n, and laid out in WORD PLANES: inside
 // every 256-byte block of 32 slots the 32 low words of h come first, then the 32 high words (slot a: word cf_w(a) and CF_HI words
 // further).  Pass 2's digit lies in the low word (bits1 + bits2 <= 16), so its histogram reads every other 128-byte line.
+// CF == 3, pass 2 with ONE WRITER per final partition: workgroup d1 reads all U pieces of pass-1 bucket d1 as one
+// dense sequence (the exclusive prefix of cnt1[.][d1] is built here, in LDS; a thread finds its slot's piece by walking on from
+// the piece of its previous slot) and writes final partition p = d1 * nbins + d2 from slot p * cap2 of the final arrays, in the
+// public narrow format -- no start cursors, hence no pass-2 histogram and no scan.  A run that would pass cap2 ends the unit before
+// anything of that tile is stored and raises `bit`; at unit end the workgroup leaves end[p] = the slot after partition p's last tuple.
 constexpr u32 CF_HI = 32;
 static_assert(WN_GR == 32, "a carry line of the count-free pass 1 is one block of word planes");
 __device__ __forceinline__ u64 cf_w(u64 a) { return ((a >> 5) << 6) | (a & 31); }
 struct WnFree {
     u32 U = 0, cap = 0, per = 0, ngroups = 0, bit = 0;
+    u32 cap2 = 0;                    // CF == 3: slots of a final partition's region
+    u64 *end = nullptr;              // CF == 3: [nb1 * nbins] end of every final partition (written)
     u32 *cnt1 = nullptr;             // CF == 1: [U][nbins] run lengths (written)
     const u32 *pre = nullptr;        // CF == 2: [units2][CF_PRE] exclusive prefix of the piece lengths, padded with the total
     DupSniff sn;                     // CF == 1
@@ -1397,7 +1404,8 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
     // IN_COLS keeps the rowID -- the index, below 2^32 -- in 32 bits from the start and has nothing to report as wide.
     constexpr bool IN_NARROW = IN == IN_NRW;
     static_assert(!PEER || IN == IN_AOS, "the peer split reads the rank's own 16-byte shard");
-    static_assert(CF == 0 || (!PEER && CF == (IN_NARROW ? 2 : 1)), "count-free: pass 1 reads the caller's tuples, pass 2 narrow pieces");
+    static_assert(CF == 0 || (!PEER && (CF == (IN_NARROW ? 2 : 1) || (CF == 3 && IN_NARROW))), "count-free: pass 1 reads the caller's tuples, pass 2 narrow pieces");
+    constexpr bool CF_REGIONS = CF == 1 || CF == 3;                          // writes into regions of its own: no start cursors
     // a rowID that does not fit 32 bits has been seen (by the histogram kernel or by an earlier workgroup of this pass):
     // the join is going to repeat itself in the 16-byte format, nothing written from here on will be read
     if (overflow != nullptr && __builtin_nontemporal_load(overflow) != 0) return;
@@ -1421,12 +1429,28 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
     u32 *own = wsc + THREADS / 64;                                           // PEER: owner rank of every digit
     u64 **pP = reinterpret_cast<u64 **>((reinterpret_cast<uintptr_t>(own + (PEER ? nbins : 0)) + 7) & ~(uintptr_t)7);   // PEER: the ranks' arrays
     u32 **pK = reinterpret_cast<u32 **>(pP + (PEER ? SEG_MAX : 0));
-    u32 *pre = own;                                                          // CF == 2: CF_PRE words
+    u32 *pre = own;                                                          // CF == 2: CF_PRE words; CF == 3: CF2_PRE words
 
     const u32 u = blockIdx.x;
     u64 beg, end;
     u64 ubase = 0;                                                           // CF == 2: first slot of the unit's first region
-    if constexpr (CF == 2) {
+    if constexpr (CF == 3) {
+        static_assert(CF != 3 || THREADS_ + 1 == CF2_PRE, "one thread per piece of the bucket");
+        if (u >= n_rng_units) return;
+        // exclusive prefix of the bucket's U <= THREADS piece lengths; entries from U on hold the total (they end every walk)
+        const u32 t_ = threadIdx.x, len = t_ < fr.U ? fr.cnt1[(u64)t_ * n_rng_units + u] : 0u;
+        const u32 inc = wave_incl_scan(len, (int)(t_ & 63));
+        if ((t_ & 63) == 63) wsc[t_ >> 6] = inc;
+        __syncthreads();
+        u32 sx = inc - len, tot = 0;
+        for (u32 i = 0; i < THREADS_ / 64; i++) { const u32 w = wsc[i]; if (i < (t_ >> 6)) sx += w; tot += w; }
+        pre[t_] = sx;
+        if (t_ == 0) pre[THREADS_] = tot;
+        __syncthreads();                                                     // (also: wsc is free again)
+        beg = 0;
+        end = tot;
+        ubase = (u64)u * fr.U * fr.cap;
+    } else if constexpr (CF == 2) {
         if (u >= n_rng_units) return;
         if (threadIdx.x < CF_PRE) pre[threadIdx.x] = fr.pre[(u64)u * CF_PRE + threadIdx.x];
         __syncthreads();
@@ -1462,24 +1486,37 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
         } else __builtin_nontemporal_store(v, &dstP(d)[o]);
     };
 
+    // CF_REGIONS: the region of digit b is [rbase(b), rbase(b) + rcap)
+    const u32 rcap = CF == 3 ? fr.cap2 : fr.cap;
+    auto rbase = [&](u32 b) -> u64 { return CF == 3 ? ((u64)u * nbins + b) * rcap : ((u64)b * fr.U + u) * rcap; };
     for (u32 b = tid; b < nbins; b += THREADS) {
         u64 g;
-        if constexpr (CF == 1) g = ((u64)b * fr.U + u) * fr.cap;
+        if constexpr (CF_REGIONS) g = rbase(b);
         else g = unit_base[(u64)u * nbins + b] + (PEER ? peer.delta[b] : 0ull);
         gnext[b] = g;
         LO[b] = (u32)(g & GM);
         cnt[b] = 0;
     }
-    if (CF == 1 && tid == 0) mtot[1] = 0;                                    // a run of this unit would pass its region
+    if (CF_REGIONS && tid == 0) mtot[1] = 0;                                    // a run of this unit would pass its region
     __syncthreads();
 
     u32 ovf = 0;                                                             // any rowID >= 2^32 seen (16-byte input only)
+    u32 pw = 0;                                                              // CF == 3: the piece of the thread's first slot of the previous tile
+    const u32 *W3 = reinterpret_cast<const u32 *>(inP) + (CF == 3 ? cf_w(ubase) : 0), *K3 = inK + (CF == 3 ? ubase : 0);   // ... the bucket's first slot
     auto load_tile = [&](u64 (&pay)[TPT], KeyT (&key)[TPT], u64 tb) {
         const u32 last = ((end - tb < (u64)TILE) ? (u32)(end - tb) : (u32)TILE) - 1u;      // tb < end
+        u32 lo3 = pw;
 #pragma unroll
         for (int k = 0; k < TPT; k++) {                                      // unconditional loads (see dev_scatter_wc)
             const u32 i0 = k * THREADS + tid, i = i0 < last ? i0 : last;
-            if constexpr (CF == 2) {                                         // slot -> (piece, offset): pre[lo] <= t < pre[lo + 1]
+            if constexpr (CF == 3) {                                         // slot -> (piece, offset): pre[lo] <= t < pre[lo + 1];
+                const u32 t = (u32)tb + i;                                   // a forward walk: t never decreases from k to k + 1 nor,
+                while (pre[lo3 + 1] <= t) lo3++;                             // at k == 0, from call to call; t < pre[U] ends it
+                if (k == 0) pw = lo3;
+                const u32 x = lo3 * fr.cap + (t - pre[lo3]);                 // slot inside the bucket: < U * cap < 2^31 (cf2_applies)
+                const u32 *W = W3 + (((x >> 5) << 6) | (x & 31));            // (cf_w; ubase is a multiple of 32)
+                pay[k] = W[0] | (u64)W[CF_HI] << 32; key[k] = K3[x];
+            } else if constexpr (CF == 2) {                                  // slot -> (piece, offset): pre[lo] <= t < pre[lo + 1]
                 const u32 t = (u32)tb + i;
                 u32 lo = 0;
 #pragma unroll
@@ -1493,7 +1530,7 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
             else { const Tup v = in[tb + i]; pay[k] = v.payload; key[k] = v.key - key_base; }
         }
     };
-    auto process = [&](u64 (&pay)[TPT], KeyT (&key)[TPT], u64 tb, auto full_tag) -> bool {     // true (CF == 1 only): the unit gives up
+    auto process = [&](u64 (&pay)[TPT], KeyT (&key)[TPT], u64 tb, auto full_tag) -> bool {     // true (CF_REGIONS only): the unit gives up
         constexpr bool FULL = decltype(full_tag)::value;
         const u32 ntile = FULL ? (u32)TILE : (u32)(end - tb);
         u32 rk[TPT], dg[TPT];
@@ -1522,7 +1559,7 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
                 c = cnt[b];
                 g0 = gnext[b]; e = g0 + c; a = (g0 + GM) & ~GM;
                 m = (e >= a) ? (u32)(e - a) : 0u;
-                if constexpr (CF == 1) { if (e > ((u64)b * fr.U + u + 1) * fr.cap) mtot[1] = 1; }
+                if constexpr (CF_REGIONS) { if (e > rbase(b) + rcap) mtot[1] = 1; }
             }
             const u32 inc = wave_incl_scan(m, lane);
             if (lane == 63) wsc[wave] = inc;
@@ -1543,7 +1580,7 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
             }
         }
         __syncthreads();                                                     // S2: plan visible
-        if constexpr (CF == 1) { if (mtot[1]) return true; }                 // (nothing of this tile has been stored)
+        if constexpr (CF_REGIONS) { if (mtot[1]) return true; }                 // (nothing of this tile has been stored)
 #pragma unroll
         for (int k = 0; k < TPT; k++) {
             const u32 i = k * THREADS + tid;
@@ -1604,16 +1641,16 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
         u64 nxt = cur + TILE;                                                // (prefetch on every path: see dev_scatter_wc)
         load_tile(pb, kb, nxt < end ? nxt : cur);
         gave_up = (nxt <= end) ? process(pa, ka, cur, std::true_type{}) : process(pa, ka, cur, std::false_type{});
-        if (CF == 1 && gave_up) break;
+        if (CF_REGIONS && gave_up) break;
         cur = nxt;
         if (cur >= end) break;
         nxt = cur + TILE;
         load_tile(pa, ka, nxt < end ? nxt : cur);
         gave_up = (nxt <= end) ? process(pb, kb, cur, std::true_type{}) : process(pb, kb, cur, std::false_type{});
-        if (CF == 1 && gave_up) break;
+        if (CF_REGIONS && gave_up) break;
         cur = nxt;
     }
-    if constexpr (CF == 1) {
+    if constexpr (CF_REGIONS) {
         if (gave_up) {                                                       // (uniform: every thread read the same LDS word)
             if (tid == 0) atomicOr(overflow, fr.bit);
             return;
@@ -1622,6 +1659,9 @@ dev_scatter_wcn(const Tup *__restrict__ in, const u64 *__restrict__ inP, const u
     __syncthreads();
     if constexpr (CF == 1) {
         for (u32 b = tid; b < nbins; b += THREADS) fr.cnt1[(u64)u * nbins + b] = (u32)(gnext[b] - ((u64)b * fr.U + u) * fr.cap);
+    }
+    if constexpr (CF == 3) {
+        for (u32 b = tid; b < nbins; b += THREADS) fr.end[(u64)u * nbins + b] = gnext[b];
     }
     // unit end: the still incomplete line of every digit (shared with the next unit's first line)
     for (u32 q = tid; q < nbins * GR; q += THREADS) {
@@ -1660,6 +1700,23 @@ k_scatter_wcn_cf(const Tup *__restrict__ in, const u64 *__restrict__ inP, const 
     dev_scatter_wcn<IN, WN_GR, WN_TPT, WN_THREADS, false, IN == IN_NRW ? 2 : 1>(in, inP, inK, outP, outK, seg_start, unit_start, 1u, L,
                                                                                     shift, bits, unit_base, nullptr, nunits, overflow, (u64)0,
                                                                                     WnTag{1u, 1u, 0u}, mix, WnPeer{}, fr);
+}
+
+// pass 2 with one writer per final partition (CF == 3): one workgroup per pass-1 bucket, nb1 of them; cnt1 is pass 1's [U][nb1]
+__global__ void __launch_bounds__(WN_THREADS)
+k_scatter_wcn_cf2(const u64 *__restrict__ inP, const u32 *__restrict__ inK, u64 *__restrict__ outP, u32 *__restrict__ outK, int shift,
+                  int bits, u32 nb1, u32 *__restrict__ overflow, WnFree fr)
+{
+    dev_scatter_wcn<IN_NRW, WN_GR, WN_TPT, WN_THREADS, false, 3>((const Tup *)nullptr, inP, inK, outP, outK, (const u64 *)nullptr,
+                                                                   (const u32 *)nullptr, 1u, (u64)0, shift, bits, (const u64 *)nullptr,
+                                                                   nullptr, nb1, overflow, (u64)0, WnTag{1u, 1u, 0u}, 0, WnPeer{}, fr);
+}
+
+// start[k] = k * cap2 for k <= nparts: the region starts of a one-writer pass 2, which a task list reads beside end[]
+__global__ void k_cf2_starts(u64 *__restrict__ start, u64 nparts, u32 cap2)
+{
+    const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k <= nparts) start[k] = k * cap2;
 }
 
 // Between the passes of a count-free partition.  k_cf_pieces: one wavefront per pass-2 unit (d, g) turns the lengths of its
@@ -1740,17 +1797,27 @@ k_hist_pieces_n(const u32 *__restrict__ W, const u32 *__restrict__ pre_all, WnFr
     for (u32 b = threadIdx.x; b < nbins; b += PART_THREADS) out[b] = cnt[b];
 }
 
+// |partition k| under boundaries start[0 .. nparts] and an optional end array: end == nullptr: start[k + 1] - start[k] (contiguous
+// partitions); else end[k] - start[k] (partitions in regions with gaps).  An end that was never written (zero: the
+// pass that writes it returned at the skip word) reads as an empty partition.
+__device__ __forceinline__ u64 part_len(const u64 *__restrict__ start, const u64 *__restrict__ end, u64 k)
+{
+    if (end == nullptr) return start[k + 1] - start[k];
+    const u64 s = start[k], e = end[k];
+    return e > s ? e - s : 0;
+}
+
 // Contract check of the public stage call rhj_bucket_join before it routes to the compact-table kernel, which compares
 // only (payload >> radix_bits): inside every partition the low radix_bits payload bits of both sides must be one value.
 // One workgroup per partition (grid-stride); *bad is OR-ed with 1 otherwise.
 __global__ void __launch_bounds__(256)
 k_check_radix(const Tup *__restrict__ R, const u64 *__restrict__ startR, const Tup *__restrict__ S, const u64 *__restrict__ startS,
-              u64 nparts, int radix_bits, u64 *__restrict__ bad)
+              u64 nparts, int radix_bits, u64 *__restrict__ bad, PartEnds pe)
 {
     const u64 mask = ((u64)1 << radix_bits) - 1;
     u64 diff = 0;
     for (u64 k = blockIdx.x; k < nparts; k += gridDim.x) {
-        const u64 r0 = startR[k], r1 = startR[k + 1], s0 = startS[k], s1 = startS[k + 1];
+        const u64 r0 = startR[k], r1 = r0 + part_len(startR, pe.endR, k), s0 = startS[k], s1 = s0 + part_len(startS, pe.endS, k);
         if (r0 == r1 && s0 == s1) continue;
         const u64 ref = r0 < r1 ? R[r0].payload : S[s0].payload;
         for (u64 i = r0 + threadIdx.x; i < r1; i += 256) diff |= (R[i].payload ^ ref) & mask;
@@ -1804,11 +1871,11 @@ __global__ void __launch_bounds__(1024) k_prefix(const u64 *__restrict__ hist, u
 // ------------------------------------------------------------------------------------------------
 // largest partition of each side (skew indicator for k_make_tasks): stats[0] = max |R_k|, stats[1] = max |S_k|
 __global__ void __launch_bounds__(256)
-k_part_max(const u64 *__restrict__ startR, const u64 *__restrict__ startS, u64 nparts, u64 *__restrict__ stats)
+k_part_max(const u64 *__restrict__ startR, const u64 *__restrict__ startS, u64 nparts, u64 *__restrict__ stats, PartEnds pe)
 {
     u64 mr = 0, ms = 0;
     for (u64 k = (u64)blockIdx.x * 256 + threadIdx.x; k < nparts; k += (u64)gridDim.x * 256) {
-        const u64 a = startR[k + 1] - startR[k], b = startS[k + 1] - startS[k];
+        const u64 a = part_len(startR, pe.endR, k), b = part_len(startS, pe.endS, k);
         mr = a > mr ? a : mr;
         ms = b > ms ? b : ms;
     }
@@ -1824,7 +1891,7 @@ k_part_max(const u64 *__restrict__ startR, const u64 *__restrict__ startS, u64 n
 __global__ void __launch_bounds__(1024)
 k_make_tasks(const u64 *__restrict__ startR, const u64 *__restrict__ startS, u64 nparts, u32 probe_split,
              JoinTask *__restrict__ tasks, u32 *__restrict__ ntasks, u32 max_tasks, u64 *__restrict__ stats,
-             u32 table_tuples, int own_max, int tie_shift, SniffVerdict sniff)
+             u32 table_tuples, int own_max, int tie_shift, SniffVerdict sniff, PartEnds pe)
 {
     __shared__ u32 wsum[16];
     __shared__ u32 gbase;
@@ -1834,7 +1901,7 @@ k_make_tasks(const u64 *__restrict__ startR, const u64 *__restrict__ startS, u64
     __syncthreads();
     u64 maxR = 0, maxS = 0;
     if (own_max) {                                     // one workgroup covers every partition: k_part_max's job done here
-        u64 mr = k < nparts ? startR[k + 1] - startR[k] : 0, ms = k < nparts ? startS[k + 1] - startS[k] : 0;
+        u64 mr = k < nparts ? part_len(startR, pe.endR, k) : 0, ms = k < nparts ? part_len(startS, pe.endS, k) : 0;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const u64 a = __shfl_down(mr, off, 64), b = __shfl_down(ms, off, 64);
@@ -1849,14 +1916,15 @@ k_make_tasks(const u64 *__restrict__ startR, const u64 *__restrict__ startS, u64
     u32 nt = 0, bis = 0;
     u64 pbeg = 0, plen = 0, bbeg = 0, blen = 0;
     if (k < nparts) {
-        const u64 r0 = startR[k], nr = startR[k + 1] - r0, s0 = startS[k], ns = startS[k + 1] - s0;
+        const u64 r0 = startR[k], nr = part_len(startR, pe.endR, k), s0 = startS[k], ns = part_len(startS, pe.endS, k);
         if (nr != 0 && ns != 0) {
             // Reference rule: build on the smaller bucket (S when |R_k| >= |S_k|, JobScheduler.cpp:187).  Exception:
             // when ONE relation's partition sizes are heavily skewed (its largest partition > 16x the mean: repeated
             // join values, e.g. a Zipf foreign key) and the other's are balanced, its small partitions are small
             // tables full of duplicates: long buckets that serialise the few probe lanes hitting them.  If the
             // balanced side fits one or two LDS tables, build on it instead: one-compare probes, same pairs.
-            const u64 meanR = startR[nparts] / nparts + 1, meanS = startS[nparts] / nparts + 1;
+            // (boundaries with gaps: the last start is the end of the regions, so the side's tuple count comes from the host)
+            const u64 meanR = (pe.endR ? pe.nR : startR[nparts]) / nparts + 1, meanS = (pe.endS ? pe.nS : startS[nparts]) / nparts + 1;
             const bool skewR = maxR > 16 * meanR, skewS = maxS > 16 * meanS;
             bool build_S = build_on_S(nr, ns, rule.shift, rule.prefer_R);
             if (skewS && !skewR && nr <= 2 * (u64)table_tuples) build_S = false;     // at most two build chunks
@@ -4387,6 +4455,7 @@ static void allow_big_lds()
     SET_LDS(k_scatter_wcn_cf<IN_COLS>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
     SET_LDS(k_scatter_wcn_cf<IN_COLS_ID>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
     SET_LDS(k_scatter_wcn_cf<IN_NRW>, wn_lds_bytes(WN_MAX_BITS) + CF_PRE * 4);
+    SET_LDS(k_scatter_wcn_cf2, wn_lds_bytes(WN_MAX_BITS) + CF2_PRE * 4);
     SET_LDS((k_scatter_wcn<IN_AOS, WN_GR, WN_TPT, WN_THREADS, true>), wn_lds_bytes(WN_MAX_BITS, WN_GR, WN_TPT, WN_THREADS, true));
     SET_LDS((k_scatter_wcn<IN_AOS, WN9_GR, WN9_TPT, WN9_THREADS>), wn_lds_bytes(WN9_MAX_BITS, WN9_GR, WN9_TPT, WN9_THREADS));
     SET_LDS((k_scatter_wcn<IN_NRW, WN9_GR, WN9_TPT, WN9_THREADS>), wn_lds_bytes(WN9_MAX_BITS, WN9_GR, WN9_TPT, WN9_THREADS));
@@ -4842,12 +4911,29 @@ void launch_cf_pass2(hipStream_t st, const void *d_tmp, void *d_out, u64 n, cons
                        d_unit_base, nb1 * c.ngroups, d_flag, 0, cf_make(c, 0, nullptr, d_pre, DupSniff()));
 }
 
+// Pass 2 with one writer per final partition: d_start[0 .. nb1 << b2] = k * cap2, d_end cleared (a unit that returns
+// at the skip word leaves its partitions empty for the kernels that read end[] without a skip test), then nb1 workgroups.
+void launch_cf2_pass2(hipStream_t st, const void *d_tmp, void *d_out, const CfGeom &c, const Cf2Geom &c2, u32 nb1, int b1, int b2,
+                      const u32 *d_cnt1, u64 *d_start, u64 *d_end, u32 *d_flag, u32 bit)
+{
+    allow_big_lds();
+    const u64 np = (u64)nb1 << b2;
+    hipLaunchKernelGGL(k_cf2_starts, dim3((unsigned)((np + 256) / 256)), dim3(256), 0, st, d_start, np, c2.cap2);
+    (void)hipMemsetAsync(d_end, 0, np * 8, st);
+    WnFree fr = cf_make(c, bit, const_cast<u32 *>(d_cnt1), nullptr, DupSniff());
+    fr.cap2 = c2.cap2;
+    fr.end = d_end;
+    hipLaunchKernelGGL(k_scatter_wcn_cf2, dim3(nb1), dim3(WN_THREADS), wn_lds_bytes(b2) + CF2_PRE * 4, st, (const u64 *)d_tmp,
+                       (const u32 *)((const unsigned char *)d_tmp + c.slots * 8), (u64 *)d_out,
+                       (u32 *)((unsigned char *)d_out + narrow_k_offset(c2.slots)), b1, b2, nb1, d_flag, fr);
+}
+
 void launch_check_radix(hipStream_t st, const void *d_R, const u64 *d_startR, const void *d_S, const u64 *d_startS, u64 nparts,
-                        int radix_bits, u64 *d_bad)
+                        int radix_bits, u64 *d_bad, const PartEnds &pe)
 {
     const unsigned grid = (unsigned)(nparts < 4096 ? nparts : 4096);
     hipLaunchKernelGGL(k_check_radix, dim3(grid ? grid : 1), dim3(256), 0, st, (const Tup *)d_R, d_startR, (const Tup *)d_S, d_startS,
-                       nparts, radix_bits, d_bad);
+                       nparts, radix_bits, d_bad, pe);
 }
 
 void launch_diff_hist(hipStream_t st, const u64 *d_start, u64 nbins, u64 *d_hist)
@@ -4861,17 +4947,18 @@ void launch_prefix(hipStream_t st, const u64 *d_hist, u64 nbins, u64 *d_start)
 }
 
 void launch_make_tasks(hipStream_t st, const u64 *d_startR, const u64 *d_startS, u64 nparts, u32 probe_split,
-                       JoinTask *d_tasks, u32 *d_ntasks, u32 max_tasks, u64 *d_stats, int kind, const SniffVerdict &sniff)
+                       JoinTask *d_tasks, u32 *d_ntasks, u32 max_tasks, u64 *d_stats, int kind, const SniffVerdict &sniff,
+                       const PartEnds &pe)
 {
     const int own_max = nparts <= 1024 ? 1 : 0;        // a single workgroup of k_make_tasks sees every partition
     if (!own_max) {
         u64 g = (nparts + 255) / 256;
         if (g > 1024) g = 1024;
-        hipLaunchKernelGGL(k_part_max, dim3((unsigned)g), dim3(256), 0, st, d_startR, d_startS, nparts, d_stats);   // d_stats zeroed by the caller
+        hipLaunchKernelGGL(k_part_max, dim3((unsigned)g), dim3(256), 0, st, d_startR, d_startS, nparts, d_stats, pe);   // d_stats zeroed by the caller
     }
     hipLaunchKernelGGL(k_make_tasks, dim3((unsigned)((nparts + 1023) / 1024)), dim3(1024), 0, st, d_startR, d_startS,
                        nparts, probe_split, d_tasks, d_ntasks, max_tasks, d_stats,
-                       join_table_tuples(kind), own_max, build_tie_shift(), sniff);
+                       join_table_tuples(kind), own_max, build_tie_shift(), sniff, pe);
 }
 
 void launch_join(hipStream_t st, const void *d_R, const u64 *d_startR, const void *d_S, const u64 *d_startS,

@@ -79,6 +79,7 @@ hipError_t hipGetLastError() { return hipSuccess; }
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "success" : "fake hip error"; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
+hipError_t hipDeviceGetAttribute(int *value, hipDeviceAttribute_t, int) { *value = 256; return hipSuccess; }
 hipError_t hipMalloc(void **p, size_t bytes) { *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void *p) { free(p); return hipSuccess; }
 hipError_t hipHostMalloc(void **p, size_t bytes, unsigned) { *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
@@ -159,9 +160,9 @@ void launch_hist_units(hipStream_t, const void *, const PassGeom &, const u64 *,
 void launch_scan_units(hipStream_t, const PassGeom &, const u64 *, const u32 *, const u32 *, u64 *, u64 *, u64 *) {}
 void launch_scatter_units(hipStream_t, const void *, void *, const PassGeom &, const u64 *, const u32 *, const u64 *) {}
 void launch_diff_hist(hipStream_t, const u64 *, u64, u64 *) {}
-void launch_check_radix(hipStream_t, const void *, const u64 *, const void *, const u64 *, u64, int, u64 *) {}
+void launch_check_radix(hipStream_t, const void *, const u64 *, const void *, const u64 *, u64, int, u64 *, const PartEnds &) {}
 void launch_prefix(hipStream_t, const u64 *, u64, u64 *) {}
-void launch_make_tasks(hipStream_t st, const u64 *, const u64 *, u64, u32, JoinTask *, u32 *d_ntasks, u32, u64 *, int, const SniffVerdict &)
+void launch_make_tasks(hipStream_t st, const u64 *, const u64 *, u64, u32, JoinTask *, u32 *d_ntasks, u32, u64 *, int, const SniffVerdict &, const PartEnds &)
 {
     fake_enqueue(st, [=] { *d_ntasks = 1; });
 }
@@ -269,6 +270,7 @@ void launch_cf_pass1(hipStream_t, const void *, void *, const CfGeom &, const Pa
 void launch_cf_tables(hipStream_t, const CfGeom &, u32, const u32 *, u32 *, u32 *, u64 *, u32 *, const u32 *) {}
 void launch_cf_hist2(hipStream_t, const void *, const CfGeom &, u32, int, int, const u32 *, u32 *, const u32 *) {}
 void launch_cf_pass2(hipStream_t, const void *, void *, u64, const CfGeom &, u32, int, int, const u64 *, const u32 *, u32 *) {}
+void launch_cf2_pass2(hipStream_t, const void *, void *, const CfGeom &, const Cf2Geom &, u32, int, int, const u32 *, u64 *, u64 *, u32 *, u32) {}
 void launch_hist2d_units(hipStream_t, const void *, bool, u64, u64, u32, int, int, u32, u32, u32 *, u32 *, u64, u32 *, const u64 *, int, const DupSniff &) {}
 void launch_hist2d_units_cols(hipStream_t, const ColsIn &, u64, u64, u32, int, int, u32, u32, u32 *, u32 *, u32 *, int, const DupSniff &) {}
 void launch_scatter_units_cols(hipStream_t, const ColsIn &, void *, const PassGeom &, const u64 *, const u32 *, const u64 *) {}

@@ -32,6 +32,8 @@ hipError_t hipGetLastError();
 const char *hipGetErrorString(hipError_t e);
 hipError_t hipSetDevice(int dev);
 hipError_t hipGetDeviceCount(int *n);
+enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount = 63 };
+hipError_t hipDeviceGetAttribute(int *value, hipDeviceAttribute_t attr, int dev);
 hipError_t hipMalloc(void **p, size_t bytes);
 hipError_t hipFree(void *p);
 hipError_t hipHostMalloc(void **p, size_t bytes, unsigned flags);

@@ -582,6 +582,91 @@ int rhj_group_join_agg_ids_dev(rhj_ctx *ctx,
         uint64_t out_capacity, uint64_t *out_groups,
         uint64_t *d_out_gidR, uint64_t gidR_rows, uint64_t *d_out_gidS, uint64_t gidS_rows);
 
+/* ---- composite keys: up to four key columns per relation packed into ONE 64-bit key column (JOIN .. ON r.a = s.a AND r.b = s.b; GROUP
+ * BY a, b; torch.unique(dim=0); merge(on=[..])).  Every operator above compares 64-bit values by bit pattern, so what it needs is an
+ * EXACT surrogate: a 64-bit word per row such that two rows of R u S get the same word if and only if all their key columns agree.
+ * rhj_keys_pack_dev makes it, the caller hands the packed columns to any *_cols_dev entry, and rhj_keys_unpack_dev turns packed words
+ * (a group-by's d_out_keys) back into the columns.  No operator changes; single-column callers are not touched. */
+#define RHJ_KEYS_MAX_COLS 4
+#define RHJ_KEYS_NO_UNPACK 1u            /* flags bit 0: keep no dictionaries; rhj_keys_unpack_dev then returns RHJ_E_INVALID */
+#define RHJ_KEYS_RANGE 0                 /* a column stored as value - base */
+#define RHJ_KEYS_DICT  1                 /* a column stored as its dense id in a dictionary the plan owns */
+#define RHJ_KEYS_MAX_FOLDS 2
+#define RHJ_KEYS_FOLD0 4                 /* field ids: 0 .. 3 the key columns, RHJ_KEYS_FOLD0 + f the output of fold step f */
+typedef struct rhj_keyplan rhj_keyplan;  /* opaque; owns its dictionaries */
+/* The layout of a packed word.  A FIELD is a key column (id j) or the output of a fold step (id RHJ_KEYS_FOLD0 + f).  Fold step f
+ * packs the fields fold_a[f] (low bits) and fold_b[f] (from bit fold_shift[f], the width of fold_a[f]) into one word and replaces the
+ * pair by that word's dense id.  The final word holds nfields fields, field i = field_id[i] in bits [field_shift[i], field_shift[i] +
+ * field_width[i]), lowest first, without gaps (a field of width 0 occupies nothing; its shift is the running sum all the same);
+ * bits at and above total_bits are 0.  The rule fixes the shape: fold 0 takes columns 0 and 1, fold 1 takes fold 0's output and
+ * column 2.  wd: the width of every dense id, bits(n_total - 1); 0 in a RANGE-only layout.  range_bits[j]: what the probe found for
+ * column j (a DICT column's field is wd wide instead).  base[j] (RANGE columns), dict_size[j] (DICT columns: the number of distinct
+ * values) and fold_size[f] are filled by rhj_keys_plan_info; rhj_keys_layout leaves them 0. */
+typedef struct {
+    uint32_t nkeys;
+    uint32_t kind[RHJ_KEYS_MAX_COLS];          /* RHJ_KEYS_RANGE or RHJ_KEYS_DICT, per key column */
+    uint32_t range_bits[RHJ_KEYS_MAX_COLS];
+    uint32_t wd;
+    uint32_t nfolds;
+    uint32_t fold_a[RHJ_KEYS_MAX_FOLDS], fold_b[RHJ_KEYS_MAX_FOLDS], fold_shift[RHJ_KEYS_MAX_FOLDS];
+    uint32_t nfields;
+    uint32_t field_id[RHJ_KEYS_MAX_COLS], field_width[RHJ_KEYS_MAX_COLS], field_shift[RHJ_KEYS_MAX_COLS];
+    uint32_t total_bits;
+    uint64_t base[RHJ_KEYS_MAX_COLS];
+    uint64_t dict_size[RHJ_KEYS_MAX_COLS];
+    uint64_t fold_size[RHJ_KEYS_MAX_FOLDS];
+} rhj_keys_layout_t;
+/* host only, no GPU: the layout the pack call will use, a pure function of its arguments.  range_bits: HOST array of nkeys widths
+ * (0 .. 64), n_total = nR + nS.  The rule (rhj_keys_pack_dev follows the same code):
+ *  1. the widths sum to <= 64: every column is RANGE, fields in column order.
+ *  2. otherwise wd = bits(n_total - 1).  While the sum is above 64, the RANGE column of greatest width above wd -- lowest index on a
+ *     tie -- becomes DICT, its field wd wide.
+ *  3. no such column left and the sum still above 64 (every field is then <= wd <= 32 bits): fold -- the first two fields of the
+ *     list become one field of width wd at the first one's place -- and check again; at most RHJ_KEYS_MAX_FOLDS folds for four columns.
+ * RHJ_E_INVALID: nkeys 0 or above RHJ_KEYS_MAX_COLS; NULL range_bits or out; a width above 64; a layout that needs a dictionary with
+ * n_total >= 2^32 (a RANGE-only layout has no such limit). */
+int rhj_keys_layout(uint32_t nkeys, const uint8_t *range_bits, uint64_t n_total, rhj_keys_layout_t *out);
+/* Packs the nkeys key columns of R (nR rows) and of S (nS rows) into d_outR (nR words) and d_outS (nS words): for every two rows x, y
+ * of R u S, packed[x] == packed[y] if and only if key_j[x] == key_j[y] for every j < nkeys.  Column j of R is compared with column j
+ * of S, by bit pattern.  d_keysR / d_keysS: HOST arrays of nkeys DEVICE columns (as d_cols elsewhere).  d_keysS NULL with nS 0: one
+ * relation (a group-by).  Packing is per position: row i of d_outR belongs to row i of the key columns, so the caller passes the
+ * same id column (or none) to the operator it calls next.  nkeys == 1 is legal: RANGE, up to 64 bits.
+ * How: one probe launch finds, per column over both sides, the unsigned minimum and maximum of v and of v ^ (1 << 63) -- the second
+ * view puts signed order into unsigned order, so an int64 column with small negative values is narrow --; per view the width is 0
+ * when max == min, else 64 - clz(max - min); the narrower view is taken (the plain one on a tie) and base is the ORIGINAL value at its
+ * minimum, so v - base (mod 2^64) < 2^width.  Then rhj_keys_layout's rule on those widths with n_total = nR + nS.  A DICT column's ids
+ * and every fold's ids come from rhj_group_agg_ids_cols_dev over the concatenation of R's and S's column (two device-to-device
+ * copies), under the automatic plan; the first dict_size words of its key output are the dictionary.  One pack launch per side.
+ * *out_plan: the plan, to be released with rhj_keys_plan_free; it owns the dictionaries unless flags has RHJ_KEYS_NO_UNPACK (the
+ * joins need none).  Dictionaries and temporaries are allocations of their own (blocks as rhj_dev_alloc hands them out), not the
+ * context's workspace (which the group-by inside and the operator that runs next reuse); temporaries are released as rhj_dev_free
+ * releases a block before the call returns, on every path.  The call
+ * synchronises.  Inputs are neither modified nor retained; outputs must not overlap them.  Pointers need 8-byte alignment only (16
+ * bytes everywhere lets every launch use 16-byte accesses).
+ * nR + nS == 0: a plan (every column RANGE, 0 bits) and no launch.
+ * RHJ_E_INVALID: nkeys 0 or above RHJ_KEYS_MAX_COLS; a NULL column array, column or output with a non-zero row count; NULL out_plan;
+ * unknown flags; a layout that needs a dictionary with nR + nS >= 2^32 -- rhj_last_error says that the RANGE-only layout has no such
+ * limit.  On failure *out_plan is NULL and the outputs are undefined.
+ * Costs: a RANGE-only layout reads every column twice (probe, pack) and writes one word per row; every DICT column and
+ * every fold is one group-by with ids over nR + nS rows, with that entry's weaknesses (all-distinct columns near 10^7 rows; a heavy
+ * value is one workgroup's work). */
+int rhj_keys_pack_dev(rhj_ctx *ctx, uint32_t nkeys,
+                      const uint64_t *const *d_keysR, uint64_t nR,
+                      const uint64_t *const *d_keysS, uint64_t nS,
+                      uint32_t flags, uint64_t *d_outR, uint64_t *d_outS, rhj_keyplan **out_plan);
+/* The inverse, for any array of n packed words the plan produced (a pack output, or the d_out_keys of a group-by over one):
+ * d_out_cols: HOST array of the plan's nkeys DEVICE columns of n words; d_out_cols[j][i] is key column j of the rows packed[i]
+ * stands for, bit for bit.  One launch: RANGE fields by shift, mask and + base, DICT fields looked up, fold fields looked up and
+ * split again.  Index guard: a word that decodes to an id >= its dictionary's size is never used as an index: it raises a flag word
+ * in HBM and the call returns RHJ_E_INVALID (the outputs are then undefined; the context stays usable).  The call synchronises.
+ * RHJ_E_INVALID also: a NULL plan; a plan packed with RHJ_KEYS_NO_UNPACK; NULL d_packed, d_out_cols or column with n > 0. */
+int rhj_keys_unpack_dev(rhj_ctx *ctx, const rhj_keyplan *plan, const uint64_t *d_packed, uint64_t n,
+                        uint64_t *const *d_out_cols);
+/* the plan's layout with base, dict_size and fold_size filled (host only) */
+int rhj_keys_plan_info(const rhj_keyplan *plan, rhj_keys_layout_t *out);
+/* frees the plan and its dictionaries; a NULL plan is fine */
+int rhj_keys_plan_free(rhj_ctx *ctx, rhj_keyplan *plan);
+
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:
  *   d_hist[b] = #{ i : ((payload_i >> shift) & (2^bits-1)) == b },  d_hist has 2^bits uint64. */

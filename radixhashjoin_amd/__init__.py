@@ -21,6 +21,9 @@ minimum, maximum or sum per weight tensor (``rhj_group_agg_cols_dev``);
 ``keys, count, sums_R, sums_S = Engine(0).join_group_by_columns(keys_R, keys_S, weights_R, weights_S, how="inner")`` is the join
 with GROUP BY on the key: per join value COUNT(*) and the SUMs of both sides' weights over its pairs, without the pairs
 (``rhj_group_join_cols_dev``); ``ops_R`` / ``ops_S`` make a column a minimum or maximum there too (``rhj_group_join_agg_cols_dev``).
+Composite keys: every one of these takes a list of up to four key tensors per side wherever it takes a key tensor (``ON r.a = s.a
+AND r.b = s.b``, ``GROUP BY a, b``); ``packed_R, packed_S, plan = Engine(0).pack_keys([a, b], [c, d])`` is the step they share -- one
+exact 64-bit key per row (``rhj_keys_pack_dev``), and ``plan.unpack(packed)`` gives the columns back (``rhj_keys_unpack_dev``).
 """
 from .binding import (  # noqa: F401
     AGG_MAX_I64,
@@ -37,6 +40,12 @@ from .binding import (  # noqa: F401
     GJ_LEFT,
     GROUP_JOIN_MAX_COLS,
     GROUP_MAX_COLS,
+    KEYS_DICT,
+    KEYS_MAX_COLS,
+    KEYS_NO_UNPACK,
+    KEYS_RANGE,
+    KeyPlan,
+    KeysLayout,
     NO_ROW,
     OUTER_FULL,
     OUTER_LEFT,
@@ -49,8 +58,9 @@ from .binding import (  # noqa: F401
     lib_path,
     load_library,
     mix64,
+    keys_layout,
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT"]
 __version__ = "0.1.0"

@@ -40,6 +40,25 @@ class Timings(C.Structure):
         return d
 
 
+class KeysLayout(C.Structure):
+    """rhj_keys_layout_t (include/rhj.h): how up to four key columns share one 64-bit word.  kind[j]: KEYS_RANGE / KEYS_DICT of key
+    column j; fold f packs the fields fold_a[f] and fold_b[f] (ids 0 .. 3: the columns, KEYS_FOLD0 + f: a fold's output) and
+    replaces them by the word's dense id; field i of the final word is field_id[i] at field_shift[i], field_width[i] bits wide."""
+    _fields_ = [("nkeys", C.c_uint32), ("kind", C.c_uint32 * 4), ("range_bits", C.c_uint32 * 4), ("wd", C.c_uint32),
+                ("nfolds", C.c_uint32), ("fold_a", C.c_uint32 * 2), ("fold_b", C.c_uint32 * 2), ("fold_shift", C.c_uint32 * 2),
+                ("nfields", C.c_uint32), ("field_id", C.c_uint32 * 4), ("field_width", C.c_uint32 * 4),
+                ("field_shift", C.c_uint32 * 4), ("total_bits", C.c_uint32), ("base", C.c_uint64 * 4),
+                ("dict_size", C.c_uint64 * 4), ("fold_size", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        k, f, m = self.nkeys, self.nfolds, self.nfields
+        return {"nkeys": k, "kind": list(self.kind[:k]), "range_bits": list(self.range_bits[:k]), "wd": self.wd,
+                "folds": [(self.fold_a[i], self.fold_b[i]) for i in range(f)], "fold_shift": list(self.fold_shift[:f]),
+                "fields": list(self.field_id[:m]), "widths": list(self.field_width[:m]), "shifts": list(self.field_shift[:m]),
+                "total_bits": self.total_bits, "base": list(self.base[:k]), "dict_size": list(self.dict_size[:k]),
+                "fold_size": list(self.fold_size[:f])}
+
+
 class RhjError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"rhj error {code}: {msg}")
@@ -108,6 +127,11 @@ SYMBOLS = {
     "rhj_group_join_agg_ids_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(_vp), _P(C.c_uint32),
                                              C.c_uint32, _u64, C.c_int, _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64),
                                              _vp, _u64, _vp, _u64]),
+    "rhj_keys_layout": (C.c_int, [C.c_uint32, _P(C.c_uint8), _u64, _P(KeysLayout)]),
+    "rhj_keys_pack_dev": (C.c_int, [_vp, C.c_uint32, _P(_vp), _u64, _P(_vp), _u64, C.c_uint32, _vp, _vp, _P(_vp)]),
+    "rhj_keys_unpack_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp)]),
+    "rhj_keys_plan_info": (C.c_int, [_vp, _P(KeysLayout)]),
+    "rhj_keys_plan_free": (C.c_int, [_vp, _vp]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -226,6 +250,8 @@ def _agg_ops(ops, n, name):
         if o not in _AGG_BY_NAME:
             raise ValueError(f"{name}[{i}]: 'sum', 'min' or 'max', not {o!r}")
     return [_AGG_BY_NAME[o] for o in ops]
+# include/rhj.h RHJ_KEYS_*: key columns per pack call; the flag of a pack that keeps no dictionaries; the kind of a column; fold ids
+KEYS_MAX_COLS, KEYS_NO_UNPACK, KEYS_RANGE, KEYS_DICT, KEYS_MAX_FOLDS, KEYS_FOLD0 = 4, 1, 0, 1, 2, 4
 SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
 OUTER_LEFT, OUTER_RIGHT, OUTER_FULL = 1, 2, 3           # include/rhj.h RHJ_OUTER_*: the preserved side(s) of an outer_join_* call
 NO_ROW = 0xFFFFFFFFFFFFFFFF                              # include/rhj.h RHJ_NO_ROW: the missing side of an unmatched row (-1 as int64)
@@ -243,6 +269,18 @@ def shard_plan(nR, nS, opts=None):
     if rc < 0:
         raise RhjError(rc, "bad options")
     return rc, out
+
+
+def keys_layout(range_bits, n_total):
+    """rhj_keys_layout: the KeysLayout a pack of key columns of these widths (bits, 0 .. 64) over n_total rows will use (host logic
+    only, works without a GPU); RhjError where there is none"""
+    lib = load_library()
+    widths = list(range_bits)
+    out = KeysLayout()
+    rc = lib.rhj_keys_layout(len(widths), (C.c_uint8 * max(len(widths), 1))(*widths), n_total, C.byref(out))
+    if rc != RHJ_OK:
+        raise RhjError(rc, f"no layout for widths {widths} over {n_total} rows")
+    return out
 
 
 def _addr(x):
@@ -290,6 +328,43 @@ class DeviceBuffer:
     def __del__(self):
         try:
             self.free()
+        except Exception:
+            pass
+
+
+class KeyPlan:
+    """An rhj_keyplan: what Engine.keys_pack_dev / pack_keys made of a set of key columns -- the layout of the packed word and, unless
+    packed with KEYS_NO_UNPACK, the dictionaries that turn packed words back into the columns.  Owns device memory: close() it (or
+    let it go out of scope, as a DeviceBuffer)."""
+
+    def __init__(self, engine, handle):
+        self.engine = engine
+        self.handle = handle
+        self.layout = KeysLayout()
+        engine._chk(engine.lib.rhj_keys_plan_info(handle, C.byref(self.layout)))
+        self.nkeys = self.layout.nkeys
+
+    def unpack(self, packed):
+        """the nkeys key columns of a 1-D tensor of packed words this plan produced (a pack output, the unique_keys of a group-by
+        over one): a list of tensors of packed's dtype and length, bit for bit the values that were packed"""
+        import torch
+        eng = self.engine
+        with eng._on_torch_stream(packed, packed) as dev:
+            n = packed.numel()
+            cols = [torch.empty(n, dtype=packed.dtype, device=dev) for _ in range(self.nkeys)]
+            if n:
+                eng.keys_unpack_dev(self, packed, n, cols)
+        return cols
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, None
+            if self.engine.ctx:
+                self.engine.lib.rhj_keys_plan_free(self.engine.ctx, h)
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
@@ -728,6 +803,71 @@ class Engine:
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
 
+    def keys_pack_dev(self, d_keysR, nR, d_keysS=(), nS=0, d_outR=None, d_outS=None, flags=0):
+        """rhj_keys_pack_dev: packs the key columns d_keysR (1 .. KEYS_MAX_COLS device columns of nR uint64) and d_keysS (as many
+        columns of nS; none with nS 0: one relation) into d_outR / d_outS (uint64[nR] / uint64[nS] in HBM) such that two rows of
+        either side get the same word exactly when all their key columns agree.  Returns the KeyPlan; flags KEYS_NO_UNPACK: one
+        without dictionaries (a join needs none)."""
+        if nS and len(d_keysS) != len(d_keysR):
+            raise ValueError(f"{len(d_keysR)} key columns of R, {len(d_keysS)} of S")
+        k = len(d_keysR)
+        colsR = (_vp * max(k, 1))(*[_addr(c) for c in d_keysR])
+        colsS = (_vp * max(k, 1))(*[_addr(c) for c in d_keysS]) if nS else None
+        h = _vp()
+        self._chk(self.lib.rhj_keys_pack_dev(self.ctx, k, colsR, nR, colsS, nS, flags, _addr(d_outR), _addr(d_outS), C.byref(h)))
+        return KeyPlan(self, h)
+
+    def keys_unpack_dev(self, plan, d_packed, n, d_out_cols):
+        """rhj_keys_unpack_dev: d_out_cols[j][i] (the plan's nkeys device columns of n uint64) = key column j of the packed word
+        d_packed[i]; a word the plan did not produce is never used as an index: RhjError"""
+        if len(d_out_cols) != plan.nkeys:
+            raise ValueError(f"{len(d_out_cols)} output columns for a plan of {plan.nkeys} key columns")
+        cols = (_vp * max(plan.nkeys, 1))(*[_addr(c) for c in d_out_cols])
+        self._chk(self.lib.rhj_keys_unpack_dev(self.ctx, plan.handle, _addr(d_packed), n, cols))
+
+    @staticmethod
+    def _key_list(keys, name):
+        """a key argument as a list of tensors: a tensor is one column; ValueError for an empty or too long sequence or unequal lengths"""
+        cols = list(keys) if isinstance(keys, (list, tuple)) else [keys]
+        if not cols:
+            raise ValueError(f"{name}: an empty sequence of key tensors")
+        if len(cols) > KEYS_MAX_COLS:
+            raise ValueError(f"{name}: at most {KEYS_MAX_COLS} key tensors, not {len(cols)}")
+        for i, c in enumerate(cols):
+            if not hasattr(c, "numel"):
+                raise ValueError(f"{name}[{i}]: a 1-D torch tensor of 64-bit integers is needed")
+            if c.numel() != cols[0].numel():
+                raise ValueError(f"{name}[{i}]: {c.numel()} elements, {name}[0] has {cols[0].numel()}")
+        return cols
+
+    def pack_keys(self, keys_R, keys_S=None, keep_dictionaries=True):
+        """(packed_R, packed_S or None, plan): composite keys as one key tensor per side.  keys_R / keys_S: sequences of 1 to
+        KEYS_MAX_COLS contiguous 1-D 64-bit integer tensors on the engine's device, one length per side, as many on either side
+        (keys_S None: one relation); column j of keys_R is compared with column j of keys_S, by bit pattern.  packed_R[i] ==
+        packed_S[k] exactly when keys_R[j][i] == keys_S[j][k] for every j (and likewise within a side), so every entry that takes a
+        key tensor takes these.  plan: the KeyPlan; plan.unpack(t) gives the columns back for a tensor of packed words
+        (keep_dictionaries=False: a plan that cannot -- enough for a join, and no dictionary is kept in HBM).  A different number of
+        columns per side, more than KEYS_MAX_COLS, none, or unequal lengths within a side: ValueError before any launch.  Streams
+        and completion as join_columns."""
+        import torch
+        cols_R = self._key_list(keys_R, "keys_R")
+        cols_S = self._key_list(keys_S, "keys_S") if keys_S is not None else []
+        if keys_S is not None and len(cols_S) != len(cols_R):
+            raise ValueError(f"keys_R has {len(cols_R)} key tensors, keys_S has {len(cols_S)}")
+        with self._on_torch_stream(cols_R[0], cols_S[0] if cols_S else cols_R[0], cols_R[1:], weights_S=cols_S[1:]) as dev:
+            nR, nS = cols_R[0].numel(), cols_S[0].numel() if cols_S else 0
+            packed_R = torch.empty(nR, dtype=cols_R[0].dtype, device=dev)
+            packed_S = torch.empty(nS, dtype=cols_S[0].dtype, device=dev) if cols_S else None
+            plan = self.keys_pack_dev(cols_R, nR, cols_S if nS else (), nS, packed_R if nR else None, packed_S if nS else None,
+                                      0 if keep_dictionaries else KEYS_NO_UNPACK)
+        return packed_R, packed_S, plan
+
+    def _packed_pair(self, keys_R, keys_S, keep_dictionaries=False):
+        """(packed_R, packed_S, plan) when either key argument is a sequence of tensors, None when both are single tensors"""
+        if not isinstance(keys_R, (list, tuple)) and not isinstance(keys_S, (list, tuple)):
+            return None
+        return self.pack_keys(keys_R, keys_S, keep_dictionaries)
+
     @contextlib.contextmanager
     def _on_torch_stream(self, keys_R, keys_S, weights=(), weights_on_S=False, weights_S=()):
         """What join_columns, outer_join_columns, semi_join_columns, join_sum_columns, join_multiplicity_columns, group_by_columns (keys_S = keys_R) and join_group_by_columns (weights_S: further tensors, each as long as keys_S) share.  keys_R / keys_S: contiguous 1-D 64-bit integer torch tensors on this
@@ -774,7 +914,13 @@ class Engine:
         every matching index pair exactly once, in no particular order.  keys_R / keys_S: contiguous 1-D 64-bit integer torch
         tensors on this engine's device, compared by bit pattern.  Count, allocate, join -- ordered behind the work torch has queued
         on its current stream (see _on_torch_stream); the results are complete when it returns, and a stream bound earlier with
-        set_stream is bound again."""
+        set_stream is bound again.
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors per side is packed first (pack_keys); rows match when every column agrees."""
+        packed = self._packed_pair(keys_R, keys_S)
+        if packed is not None:
+            packed[2].close()                      # (a join needs no dictionary: the plan holds nothing)
+            return self.join_columns(packed[0], packed[1])
+
         import torch
         with self._on_torch_stream(keys_R, keys_S) as dev:
             nR, nS = keys_R.numel(), keys_S.numel()
@@ -792,7 +938,13 @@ class Engine:
         """idx_R, an int64 tensor: every i for which keys_R[i] occurs in keys_S -- with anti=True, does NOT occur -- exactly once,
         in no particular order, however often the key is repeated in keys_S (torch.isin as indices; EXISTS / NOT EXISTS).  Tensors,
         streams and completion as join_columns.  Count, allocate, fill.  (For a left, right or full outer join see
-        outer_join_columns: one call, both sides partitioned once.)"""
+        outer_join_columns: one call, both sides partitioned once.)
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors per side is packed first (pack_keys); rows match when every column agrees."""
+        packed = self._packed_pair(keys_R, keys_S)
+        if packed is not None:
+            packed[2].close()                      # (a join needs no dictionary: the plan holds nothing)
+            return self.semi_join_columns(packed[0], packed[1], anti)
+
         import torch
         kind = ANTI if anti else SEMI
         with self._on_torch_stream(keys_R, keys_S) as dev:
@@ -809,7 +961,13 @@ class Engine:
         for how "left" or "full", one row (i, -1) per i whose keys_R[i] does not occur in keys_S; then, for how "right" or "full", one
         row (-1, j) per j whose keys_S[j] does not occur in keys_R (merge(how=..), how="full" being pandas' "outer"; LEFT / RIGHT /
         FULL OUTER JOIN).  Order inside each of the three sections is unspecified.  Tensors, streams and completion as join_columns.
-        Count, allocate, fill."""
+        Count, allocate, fill.
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors per side is packed first (pack_keys); rows match when every column agrees."""
+        packed = self._packed_pair(keys_R, keys_S)
+        if packed is not None:
+            packed[2].close()                      # (a join needs no dictionary: the plan holds nothing)
+            return self.outer_join_columns(packed[0], packed[1], how)
+
         import torch
         modes = {"left": OUTER_LEFT, "right": OUTER_RIGHT, "full": OUTER_FULL}
         if not isinstance(how, str) or how not in modes:
@@ -831,7 +989,13 @@ class Engine:
         over those pairs mod 2^64 (SELECT COUNT(*), SUM(r.x) FROM R JOIN S USING (key)), as Python ints in [0, 2^64) -- without the
         pairs, in time linear in the inputs however often a key repeats.  weights: up to SUM_MAX_COLS contiguous 1-D 64-bit integer
         tensors of len(keys_R) on the engine's device (int64 weights: read the sums as two's complement).  Tensors, streams and
-        completion as join_columns."""
+        completion as join_columns.
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors per side is packed first (pack_keys); rows match when every column agrees."""
+        packed = self._packed_pair(keys_R, keys_S)
+        if packed is not None:
+            packed[2].close()                      # (a join needs no dictionary: the plan holds nothing)
+            return self.join_sum_columns(packed[0], packed[1], weights)
+
         weights = tuple(weights)
         if len(weights) > SUM_MAX_COLS:
             raise ValueError(f"at most {SUM_MAX_COLS} weight tensors per call, not {len(weights)}")
@@ -845,7 +1009,13 @@ class Engine:
         (the degree of every key; value_counts looked up per row); total = the sum of mult mod 2^64 as a Python int in [0, 2^64),
         unweighted the number of pairs join_columns would return.  No pair is written: linear in the inputs however often a key
         repeats.  weights_S: a contiguous 1-D 64-bit integer tensor of len(keys_S) on the engine's device.  Tensors, streams and
-        completion as join_columns."""
+        completion as join_columns.
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors per side is packed first (pack_keys); rows match when every column agrees."""
+        packed = self._packed_pair(keys_R, keys_S)
+        if packed is not None:
+            packed[2].close()                      # (a join needs no dictionary: the plan holds nothing)
+            return self.join_multiplicity_columns(packed[0], packed[1], weights_S)
+
         import torch
         weights = () if weights_S is None else (weights_S,)
         with self._on_torch_stream(keys_R, keys_S, weights, weights_on_S=True) as dev:
@@ -866,7 +1036,8 @@ class Engine:
         weights (SELECT key, MIN(x), MAX(x), SUM(y) ..; scatter_reduce_ with amin / amax): sums[k] is then that aggregate of weights[k]
         over the group, minimum and maximum of the int64 values (rhj_group_agg_cols_dev; the same tensor may be given twice).  A
         wrong length or name: ValueError before any launch.  Costs as for sums, whatever the ops.
-        The group of every row beside them: group_by_columns_with_inverse."""
+        The group of every row beside them: group_by_columns_with_inverse.
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors is packed first (pack_keys); unique_keys is then a list of as many tensors."""
         return self._group_by_columns(keys, weights, ops, False)
 
     def group_by_columns_with_inverse(self, keys, weights=(), ops=None):
@@ -874,11 +1045,18 @@ class Engine:
         len(keys) with unique_keys[inverse] == keys, the group every row belongs to, so that whatever the ops do not cover (a mean,
         a float sum, an argmin, the group's total broadcast back to its rows) is a direct-indexed torch op behind one call.  The
         order of groups is unspecified and may differ from run to run: inverse goes with this call's unique_keys.  Everything else
-        as group_by_columns (rhj_group_agg_ids_cols_dev: one more sweep per class and one scattered 8-byte store per row)."""
+        as group_by_columns (rhj_group_agg_ids_cols_dev: one more sweep per class and one scattered 8-byte store per row).
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors is packed first (pack_keys); unique_keys is then a list of as many tensors."""
         return self._group_by_columns(keys, weights, ops, True)
 
     def _group_by_columns(self, keys, weights, ops, return_inverse):
         import torch
+        if isinstance(keys, (list, tuple)):
+            packed, _, plan = self.pack_keys(keys)
+            out = self._group_by_columns(packed, weights, ops, return_inverse)
+            uniques = plan.unpack(out[0])
+            plan.close()
+            return (uniques,) + out[1:]
         weights = tuple(weights)
         if len(weights) > GROUP_MAX_COLS:
             raise ValueError(f"at most {GROUP_MAX_COLS} weight tensors per call, not {len(weights)}")
@@ -905,7 +1083,8 @@ class Engine:
     def factorize_columns(self, keys):
         """(codes, uniques): pandas.factorize without the ordering promise -- uniques the distinct values of keys in no particular
         order, codes an int64 tensor of len(keys) with uniques[codes] == keys (dictionary encoding of a 64-bit key column into dense
-        ids).  Tensors, streams and completion as group_by_columns_with_inverse, which this is without the counts."""
+        ids).  Tensors, streams and completion as group_by_columns_with_inverse, which this is without the counts.
+        Composite keys: a list or tuple of key tensors gives uniques as a list of tensors, uniques[j][codes] == keys[j] for every j."""
         uniques, _, _, codes = self._group_by_columns(keys, (), None, True)
         return codes, uniques
 
@@ -928,7 +1107,8 @@ class Engine:
         other side's count.  Under how="left" S's "min" / "max" of a value keys_S lacks is the op's identity (min: INT64_MAX, max:
         INT64_MIN; SQL's NULL), its "sum" 0.  With both None the call is rhj_group_join_cols_dev, otherwise
         rhj_group_join_agg_cols_dev.  A wrong length or name: ValueError before any launch.  Costs as for sums, whatever the ops.
-        The group of every row of either side beside them: join_group_by_columns_with_inverse."""
+        The group of every row of either side beside them: join_group_by_columns_with_inverse.
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors per side is packed first (pack_keys); keys is then a list of as many tensors."""
         return self._join_group_by_columns(keys_R, keys_S, weights_R, weights_S, how, ops_R, ops_S, False)
 
     def join_group_by_columns_with_inverse(self, keys_R, keys_S, weights_R=(), weights_S=(), how="inner", ops_R=None, ops_S=None):
@@ -937,11 +1117,18 @@ class Engine:
         has a group, and -1 (SQL's NULL) where it has none: under how="inner" the rows whose value the other tensor lacks, under
         how="left" only such rows of keys_S.  A joint dictionary encoding of two key tensors: shared dense ids, "no partner" marked.
         Ids go with this call's keys.  Everything else as join_group_by_columns (rhj_group_join_agg_ids_cols_dev: both id tensors are
-        filled, then one more sweep per side and class and one scattered 8-byte store per row that has a group)."""
+        filled, then one more sweep per side and class and one scattered 8-byte store per row that has a group).
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors per side is packed first (pack_keys); keys is then a list of as many tensors."""
         return self._join_group_by_columns(keys_R, keys_S, weights_R, weights_S, how, ops_R, ops_S, True)
 
     def _join_group_by_columns(self, keys_R, keys_S, weights_R, weights_S, how, ops_R, ops_S, return_inverse):
         import torch
+        packed = self._packed_pair(keys_R, keys_S, keep_dictionaries=True)
+        if packed is not None:
+            out = self._join_group_by_columns(packed[0], packed[1], weights_R, weights_S, how, ops_R, ops_S, return_inverse)
+            keys = packed[2].unpack(out[0])
+            packed[2].close()
+            return (keys,) + out[1:]
         weights_R, weights_S = tuple(weights_R), tuple(weights_S)
         if how not in ("inner", "left"):
             raise ValueError(f"how: 'inner' or 'left', not {how!r}")

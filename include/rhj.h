@@ -146,9 +146,10 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * rhj_semi_join_cols_dev, whatever the plan; 13 the aggregating join kernel: rhj_join_sum_dev / rhj_join_sum_cols_dev, whatever
  * the plan; 14 the multiplicity join kernel: rhj_join_mult_dev / rhj_join_mult_cols_dev, whatever the plan; 15 the group-by kernel:
  * rhj_group_sum_dev / rhj_group_sum_cols_dev, whatever the plan; 16 the group-by join kernel: rhj_group_join_dev /
- * rhj_group_join_cols_dev, whatever the plan; the rhj_group_agg_* and rhj_group_join_agg_* entries are 15 and 16 too),
+ * rhj_group_join_cols_dev, whatever the plan; the rhj_group_agg_* and rhj_group_join_agg_* entries are 15 and 16 too;
+ * 17 the lookup join kernel: rhj_lookup_dev / rhj_lookup_cols_dev, whatever the plan),
  * "last.semi_tables" (the largest number of LDS tables any one task of the last
- * semi / anti join, aggregating join or multiplicity join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
+ * semi / anti join, aggregating join, multiplicity join or lookup join built: 1 when every partition of S fitted one table, 0 when no task ran, and 0 after every other call),
  * "last.group_rounds" (the largest number of LDS table builds any one task of the last group-by or group-by join made: 1 when every
  * partition of R fitted one table, 0 when no task ran, and 0 after every call that is neither; "last.semi_tables" is 0 after both),
  * "last.outer_sweeps" (the anti sweeps the last rhj_outer_join_dev / rhj_outer_join_cols_dev ran: 0, 1 or 2, one per preserved side
@@ -337,6 +338,43 @@ int rhj_join_mult_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
 int rhj_join_mult_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                       const uint64_t *d_wS, uint64_t wS_rows, const rhj_opts *opts,
                       uint64_t *d_out, uint64_t out_rows, uint64_t *out_total);
+
+/* ---- lookup join: for every row of R ONE partner row of S, aligned with R, and no pair set -- the foreign key of R looked up in a
+ * unique or nearly unique key of S (pandas.Index.get_indexer, Series.map, merge(how="left") against a dimension table, a dictionary
+ * lookup).  The multiplicity join's kernel shape with a rowID instead of a weight sum in the word beside every key.
+ *
+ * for every tuple i of R with at least one partner in S:
+ *     d_out[rowR_i] = min (RHJ_LOOKUP_FIRST) / max (RHJ_LOOKUP_LAST) of its old value and the rowS_j of the tuples j of S with
+ *     valS[j] == valR[i]
+ * rowR_i = d_idR[i] or i; rowS_j = d_idS[j] or j (id column NULL).
+ * Initialisation: the call sets all out_rows words of d_out to RHJ_NO_ROW itself, and does so again on every attempt.
+ * Update: monotone, never a plain store: two tuples of R with the same rowID leave the min / max over both tuples' partners; a word
+ * that no matched tuple of R names stays RHJ_NO_ROW (all ones, -1 as int64).
+ * out_matched: a HOST word that receives the number of words of d_out that ended different from RHJ_NO_ROW -- exact, also with
+ * repeated rowIDs of R and with a key of S spread over several LDS tables.  The call synchronises: d_out and *out_matched are
+ * complete when it returns.  With unique rowIDs of R, *out_matched == the total of rhj_join_mult_cols_dev on the same inputs says
+ * that no row of R has two partners (validate="m:1").
+ * Guards: a rowR >= out_rows is never stored to; under RHJ_LOOKUP_LAST a rowS >= 2^63 -- which a signed maximum cannot order -- is
+ * never inserted: either raises a flag word in HBM and the call returns RHJ_E_INVALID, each with its own message (d_out is then
+ * undefined, the context stays usable).  The flag is raised for every such tuple whose partition holds tuples of the other side --
+ * always when it has a partner there.  Under RHJ_LOOKUP_FIRST every rowS is ordered, but a rowS that is itself all ones cannot be
+ * told from RHJ_NO_ROW (as in the outer join): such a partner counts as none.
+ * nR == 0 or nS == 0: d_out all ones, matched 0, no join launch.  RHJ_E_INVALID: which outside 0..1, NULL d_out with out_rows > 0,
+ * NULL out_matched, a NULL value column (relation) with n > 0.  Inputs are neither modified nor retained; d_out must not overlap them.
+ * Plan, options, timings, "last.narrow", "last.countfree_*", "last.cols_*" and the repeats as rhj_join_mult_cols_dev on the same
+ * sizes (S's id column goes through the partition phase: its rowIDs are read; a rowID >= 2^32 of EITHER side in a narrow format
+ * repeats at 16 bytes, a count-free overflow with exact cursors, and a repeat starts from a d_out of all ones); a one-pass plan always
+ * runs as separate partition and join launches; "last.join_kernel" is 17, "last.semi_tables" see rhj_get_info.  Results are
+ * bit-exact from run to run. */
+#define RHJ_LOOKUP_FIRST 0      /* the smallest rowS among the partners */
+#define RHJ_LOOKUP_LAST  1      /* the largest */
+#define RHJ_LOOKUP_MAX_COLS 4   /* columns per rhj_gather_cols_fill call */
+int rhj_lookup_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                        const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS, int which, const rhj_opts *opts,
+                        uint64_t *d_out, uint64_t out_rows, uint64_t *out_matched);
+/* ... on 16-byte tuples (rowID = .key, value = .payload) */
+int rhj_lookup_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, int which,
+                   const rhj_opts *opts, uint64_t *d_out, uint64_t out_rows, uint64_t *out_matched);
 
 /* ---- group-by on a key column: one output row per DISTINCT join value of R -- the value, how many tuples carry it, and up to four
  * sums over those tuples (SELECT key, COUNT(*), SUM(x) FROM R GROUP BY key; value_counts; torch.unique + index_add_).  One relation:
@@ -818,6 +856,14 @@ int rhj_gather_tuples(rhj_ctx *ctx, const uint64_t *d_col, const uint64_t *d_row
 int rhj_pairs_split(rhj_ctx *ctx, const rhj_pair *d_pairs, uint64_t n, uint64_t *d_r, uint64_t *d_s);
 /* rhj_gather_u64: d_dst[i] = d_src[d_idx[i]]  (re-materialises one intermediate column after a join) */
 int rhj_gather_u64(rhj_ctx *ctx, const uint64_t *d_src, const uint64_t *d_idx, uint64_t n, uint64_t *d_dst);
+/* rhj_gather_cols_fill: for i < n and j < ncols: d_dsts[j][i] = d_idx[i] == RHJ_NO_ROW ? fills[j] : d_srcs[j][d_idx[i]]
+ *   -- the index column of rhj_lookup_cols_dev, or one side of an outer join's pairs, turned into up to RHJ_LOOKUP_MAX_COLS payload
+ *   columns; d_idx is read once for all columns.  d_srcs / fills / d_dsts: HOST arrays of ncols (1 .. RHJ_LOOKUP_MAX_COLS) device
+ *   columns of src_rows words / fill values / device columns of n words.  Any other index >= src_rows is never dereferenced: it
+ *   raises a flag word in HBM and the call returns RHJ_E_INVALID (the destinations are then undefined, the context stays usable),
+ *   so the call synchronises, unlike rhj_gather_u64.  n == 0: no launch.  A destination may not overlap d_idx or a source. */
+int rhj_gather_cols_fill(rhj_ctx *ctx, const uint64_t *const *d_srcs, uint32_t ncols, uint64_t src_rows,
+                         const uint64_t *d_idx, uint64_t n, const uint64_t *fills, uint64_t *const *d_dsts);
 /* rhj_rows_filter_equal: a predicate between two aliases that are BOTH in the intermediate already
  *   (intermediate.cpp:72-87,169-180) or a same-alias predicate (parse_table, intermediate.cpp:11-44):
  *   keeps the positions e with d_colA[d_rowsA[e]] == d_colB[d_rowsB[e]] in d_pos_out (capacity n). */

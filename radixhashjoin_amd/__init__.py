@@ -15,6 +15,9 @@ pairs first, then the unmatched rows of the preserved side(s) with -1 on the mis
 ``count, sums = Engine(0).join_sum_columns(keys_R, keys_S, weights)`` is COUNT(*) and SUM(weights[k][i]) over the join's pairs
 without the pairs (``rhj_join_sum_cols_dev``); ``mult, total = Engine(0).join_multiplicity_columns(keys_R, keys_S, weights_S=None)``
 is, per key of R, how many keys of S equal it -- or the sum of their weights (``rhj_join_mult_cols_dev``);
+``idx_S, matched, values = Engine(0).lookup_columns(keys_R, keys_S, values_S, fill=0, which="first")`` is the lookup of every key of
+R in S, aligned with R: the first (or last) index in S, -1 where there is none, and S's value tensors gathered by it
+(``rhj_lookup_cols_dev``, ``rhj_gather_cols_fill``);
 ``unique_keys, counts, sums = Engine(0).group_by_columns(keys, weights)`` is GROUP BY on one key tensor: its distinct values, their
 counts and the per-group sums of the weight tensors (``rhj_group_sum_cols_dev``) -- with ``ops=["min", "max", "sum"]`` the per-group
 minimum, maximum or sum per weight tensor (``rhj_group_agg_cols_dev``);
@@ -46,6 +49,9 @@ from .binding import (  # noqa: F401
     KEYS_RANGE,
     KeyPlan,
     KeysLayout,
+    LOOKUP_FIRST,
+    LOOKUP_LAST,
+    LOOKUP_MAX_COLS,
     NO_ROW,
     OUTER_FULL,
     OUTER_LEFT,
@@ -62,5 +68,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS"]
 __version__ = "0.1.0"

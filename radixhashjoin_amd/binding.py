@@ -103,6 +103,8 @@ SYMBOLS = {
     "rhj_join_sum_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _P(_u64), _P(_u64)]),
     "rhj_join_mult_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_join_mult_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_lookup_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
+    "rhj_lookup_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, C.c_int, _P(Opts), _vp, _u64, _P(_u64)]),
     "rhj_group_sum_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64, _P(_u64)]),
     "rhj_group_sum_dev": (C.c_int, [_vp, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp), _u64, _P(_u64)]),
     "rhj_group_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(_vp), C.c_uint32, _u64, _P(_vp), C.c_uint32, _u64, C.c_int,
@@ -160,6 +162,7 @@ SYMBOLS = {
     "rhj_gather_tuples": (C.c_int, [_vp, _vp, _vp, _u64, C.c_int, _vp]),
     "rhj_pairs_split": (C.c_int, [_vp, _vp, _u64, _vp, _vp]),
     "rhj_gather_u64": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
+    "rhj_gather_cols_fill": (C.c_int, [_vp, _P(_vp), C.c_uint32, _u64, _vp, _u64, _P(_u64), _P(_vp)]),
     "rhj_rows_filter_equal": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _P(_u64)]),
     "rhj_sum_gather": (C.c_int, [_vp, _vp, _vp, _u64, _P(_u64)]),
     "rhj_mul_u64": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
@@ -255,6 +258,8 @@ KEYS_MAX_COLS, KEYS_NO_UNPACK, KEYS_RANGE, KEYS_DICT, KEYS_MAX_FOLDS, KEYS_FOLD0
 SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
 OUTER_LEFT, OUTER_RIGHT, OUTER_FULL = 1, 2, 3           # include/rhj.h RHJ_OUTER_*: the preserved side(s) of an outer_join_* call
 NO_ROW = 0xFFFFFFFFFFFFFFFF                              # include/rhj.h RHJ_NO_ROW: the missing side of an unmatched row (-1 as int64)
+LOOKUP_FIRST, LOOKUP_LAST = 0, 1                         # include/rhj.h RHJ_LOOKUP_*: the smallest / largest rowID of S among the partners
+LOOKUP_MAX_COLS = 4                                      # include/rhj.h RHJ_LOOKUP_MAX_COLS: columns of a gather_cols_fill call
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
 
@@ -610,6 +615,22 @@ class Engine:
         self._chk(self.lib.rhj_join_mult_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, _addr(d_wS), wS_rows,
                                              C.byref(opts) if opts is not None else None, _addr(d_out), out_rows, C.byref(total)))
         return total.value
+
+    def lookup_cols_dev(self, d_valR, d_idR, nR, d_valS, d_idS, nS, d_out, out_rows, which=LOOKUP_FIRST, opts=None):
+        """rhj_lookup_cols_dev: d_out (out_rows uint64 words, set to NO_ROW by the call) receives, per rowID of R, the smallest
+        (LOOKUP_FIRST) or largest (LOOKUP_LAST) rowID of S among the tuples of S with that tuple's join value; returns the number
+        of words that found a partner"""
+        matched = _u64()
+        self._chk(self.lib.rhj_lookup_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, _addr(d_valS), _addr(d_idS), nS, which,
+                                               C.byref(opts) if opts is not None else None, _addr(d_out), out_rows, C.byref(matched)))
+        return matched.value
+
+    def lookup_dev(self, d_R, nR, d_S, nS, d_out, out_rows, which=LOOKUP_FIRST, opts=None):
+        """rhj_lookup_dev: lookup_cols_dev on 16-byte tuples (rowR / rowS = .key)"""
+        matched = _u64()
+        self._chk(self.lib.rhj_lookup_dev(self.ctx, _addr(d_R), nR, _addr(d_S), nS, which,
+                                          C.byref(opts) if opts is not None else None, _addr(d_out), out_rows, C.byref(matched)))
+        return matched.value
 
     def _group_args(self, d_cols, d_out_sums):
         """the two host arrays of a group_sum_* call (a sum column that is missing goes in as NULL: the library answers)"""
@@ -1024,6 +1045,41 @@ class Engine:
             total = self.join_mult_cols_dev(keys_R, None, nR, keys_S, None, nS, mult if nR else None, nR, weights_S, nS)
         return mult, total
 
+    def lookup_columns(self, keys_R, keys_S, values_S=(), fill=0, which="first"):
+        """(idx_S, matched, values): idx_S[i] = the smallest (which="first") or largest (which="last") j with keys_S[j] ==
+        keys_R[i], -1 where there is none -- an int64 tensor of len(keys_R) on the keys' device, aligned with keys_R
+        (Index.get_indexer, Series.map, merge(how="left") against a dimension table); matched = how many rows found a partner, a
+        Python int; values = one int64 tensor of len(keys_R) per tensor of values_S: values[k][i] = values_S[k][idx_S[i]], or fill
+        where idx_S[i] == -1.  No pair is written: linear in the inputs, 8 bytes out per row of R, bit-exact from run to run also
+        where S carries a key twice.  values_S: up to LOOKUP_MAX_COLS contiguous 1-D 64-bit integer tensors of len(keys_S) on the
+        engine's device; fill: an int, or one int per tensor of values_S.  matched == the total of join_multiplicity_columns on the
+        same keys says that no key of R occurs twice in S (validate="m:1").  A wrong which, tensor, length or number of value
+        tensors: ValueError before any launch.  Tensors, streams and completion as join_columns.
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors per side is packed first (pack_keys); rows match when every column agrees."""
+        modes = {"first": LOOKUP_FIRST, "last": LOOKUP_LAST}
+        if not isinstance(which, str) or which not in modes:
+            raise ValueError(f"which: one of 'first', 'last' is needed, not {which!r}")
+        values_S = tuple(values_S)
+        if len(values_S) > LOOKUP_MAX_COLS:
+            raise ValueError(f"at most {LOOKUP_MAX_COLS} value tensors per call, not {len(values_S)}")
+        fills = [fill] * len(values_S) if isinstance(fill, int) else list(fill) if isinstance(fill, (list, tuple)) else [None]
+        if len(fills) != len(values_S) or not all(isinstance(f, int) for f in fills):
+            raise ValueError(f"fill: an int, or one int per tensor of values_S ({len(values_S)}), is needed")
+        packed = self._packed_pair(keys_R, keys_S)
+        if packed is not None:
+            packed[2].close()                      # (a join needs no dictionary: the plan holds nothing)
+            return self.lookup_columns(packed[0], packed[1], values_S, fills, which)
+
+        import torch
+        with self._on_torch_stream(keys_R, keys_S, weights_S=values_S) as dev:
+            nR, nS = keys_R.numel(), keys_S.numel()
+            idx_S = torch.empty(nR, dtype=torch.int64, device=dev)
+            matched = self.lookup_cols_dev(keys_R, None, nR, keys_S, None, nS, idx_S if nR else None, nR, modes[which])
+            values = [torch.empty(nR, dtype=torch.int64, device=dev) for _ in values_S]
+            if values and nR:
+                self.gather_cols_fill(values_S, nS, idx_S, nR, fills, values)
+        return idx_S, matched, values
+
     def group_by_columns(self, keys, weights=(), ops=None):
         """(unique_keys, counts, sums): the distinct values of keys, how often each occurs, and per tensor of weights the sum of
         weights[k][i] over the rows i that carry the value, mod 2^64 (SELECT key, COUNT(*), SUM(x) FROM R GROUP BY key; torch.unique
@@ -1257,6 +1313,17 @@ class Engine:
 
     def gather_u64(self, d_src, d_idx, n, d_dst):
         self._chk(self.lib.rhj_gather_u64(self.ctx, _addr(d_src), _addr(d_idx), n, _addr(d_dst)))
+
+    def gather_cols_fill(self, d_srcs, src_rows, d_idx, n, fills, d_dsts):
+        """rhj_gather_cols_fill: d_dsts[j][i] = fills[j] where d_idx[i] == NO_ROW, d_srcs[j][d_idx[i]] otherwise -- 1 to
+        LOOKUP_MAX_COLS device columns of src_rows uint64 gathered by one index column of n uint64 into as many device columns of n
+        uint64; fills: one int per column, taken mod 2^64.  Any other index >= src_rows: RhjError, nothing is read there.  (A
+        sequence that is None goes in as NULL: the library answers.)"""
+        k = len(d_srcs) if d_srcs is not None else len(d_dsts) if d_dsts is not None else len(fills or ())
+        srcs = (_vp * max(k, 1))(*[_addr(c) for c in d_srcs]) if d_srcs is not None else None
+        dsts = (_vp * max(k, 1))(*[_addr(c) for c in d_dsts]) if d_dsts is not None else None
+        vals = (_u64 * max(k, 1))(*[int(f) & NO_ROW for f in fills]) if fills is not None else None
+        self._chk(self.lib.rhj_gather_cols_fill(self.ctx, srcs, k, src_rows, _addr(d_idx), n, vals, dsts))
 
     def rows_filter_equal(self, d_colA, d_rowsA, d_colB, d_rowsB, n, d_pos_out):
         m = _u64()

@@ -246,6 +246,7 @@ struct rhj_ctx {
     u64 mult_w_rows = 0;
     u64 *mult_out = nullptr;           // out_rows words (device)
     u64 mult_out_rows = 0;
+    int lookup_which = 0;              // a lookup join's RHJ_LOOKUP_* (its output words are mult_out / mult_out_rows, its device words agg_out's: [0] matched, [5] u32 LOOKUP_BAD_ROW_*)
     // a group-by's arguments, for the length of the call (input columns: agg_cols / agg_ncols / agg_col_rows; device words: agg_out's
     // [0] groups, [5] u32 a rowID >= col_rows was met)
     bool one_sided = false;            // partition_phase partitions R alone: no kernel touches a buffer of S, part_S does not grow
@@ -1495,7 +1496,8 @@ int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
 // OUT_GROUP: one row per distinct join value of R alone (group_phase; partition_phase in its one-sided mode).
 // OUT_GJOIN: one row per join value of R join S, with the counts and sums of both sides (gjoin_phase).
 // OUT_OUTER: the pairs, then {row, RHJ_NO_ROW} for the tuples of the preserved side(s) without a partner (outer_phase).
-enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3, OUT_GROUP = 4, OUT_GJOIN = 5, OUT_OUTER = 6 };
+// OUT_LOOKUP: one partner rowID of S per row of R, the smallest or the largest (lookup_phase).
+enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3, OUT_GROUP = 4, OUT_GJOIN = 5, OUT_OUTER = 6, OUT_LOOKUP = 7 };
 
 // Semi / anti join phase on the partitions partition_phase left: k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
 // Reads the skip word behind its kernel and answers with the retry codes of join_phase_on.
@@ -1767,6 +1769,75 @@ int mult_phase(rhj_ctx *ctx, u64 *out_total)
     if (bad & MULT_BAD_ROW_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= out_rows: d_out has no such word");
     if (bad & MULT_BAD_ROW_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= wS_rows: the weight column has no such row");
     *out_total = agg[0];
+    return RHJ_OK;
+}
+
+// Lookup join phase on the partitions partition_phase left: k_make_semi_tasks (anti = 0) + k_lookup_bkt over the output
+// words the entry point left in the context.  EVERY attempt fills the output words with all ones (RHJ_NO_ROW) and zeroes the matched
+// word and the guard flags before its kernel: a repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes as
+// semi_phase.
+int lookup_phase(rhj_ctx *ctx, u64 *out_matched)
+{
+    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
+    const bool narrow = ctx->cur_narrow != 0;
+    u32 split = ctx->cur_probe_split;
+    if (split == 0) split = 32768;
+    if (split > AGG_MAX_SPLIT) split = AGG_MAX_SPLIT;
+    const u64 max_tasks64 = nparts + nR / split + 1;
+    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
+    const u32 max_tasks = (u32)max_tasks64;
+    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
+    RHJCHK(ensure(ctx, ctx->counters, 64));
+    RHJCHK(ensure(ctx, ctx->agg_out, 64));
+    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
+    {
+        Span s(ctx, RHJ_K_AUX);
+        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));   // (a paired partition pass has cleared them already)
+        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
+        if (ctx->mult_out_rows) HIPCHK(ctx, hipMemsetAsync(ctx->mult_out, 0xFF, ctx->mult_out_rows * 8, ctx->stream));
+    }
+    ctx->counters_clean = false;
+    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
+        Span s(ctx, RHJ_K_AUX);
+        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+        launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+    }
+    ctx->last_join_kind = JK_LOOKUP;
+    ctx->sniff_ready = false;                          // (the samples of the partition phase are not asked)
+    {
+        Span s(ctx, RHJ_K_TASKS);
+        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, ctx->cur_psS, nparts, split, 0, (JoinTask *)ctx->tasks.p,
+                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
+    }
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        launch_lookup_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
+                           ctx->cur_radix_bits, ctx->lookup_which, ctx->mult_out, ctx->mult_out_rows, d_agg,
+                           (u32 *)(d_agg + AGG_MAX_COLS + 1), d_count + 7,
+                           narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
+                           narrow ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
+                           narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+    }
+    RHJCHK(check_launch(ctx, "lookup join phase"));
+    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, oversized table side, -, most tables of a task (if > 1)
+    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // matched, -, -, -, -, guard flags
+    u32 wide_rowid = 0;
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
+    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
+    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
+    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
+    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
+    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
+    ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
+    if (host[5])
+        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    const u32 bad = (u32)agg[AGG_MAX_COLS + 1];
+    if (bad & LOOKUP_BAD_ROW_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= out_rows: d_out has no such word");
+    if (bad & LOOKUP_BAD_ROW_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= 2^63: RHJ_LOOKUP_LAST orders rowIDs as signed words");
+    *out_matched = agg[0];
     return RHJ_OK;
 }
 
@@ -2057,7 +2128,7 @@ int join_one_pass_fused(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, 
 
 // partition + join.  A run in the narrow format whose histogram kernel met a rowID >= 2^32 costs two histogram launches
 // (every later kernel of the run returns at once) and is repeated in the 16-byte format; the fall-back is per join.
-// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase / group_phase / gjoin_phase / outer_phase (which always take the
+// what: the phase that follows every partition phase of the ladder -- the pair join, or semi_phase / agg_phase / mult_phase / group_phase / gjoin_phase / lookup_phase / outer_phase (which always take the
 // unfused path: the one-pass form has the pair join built into its launches).
 int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan, void *d_out,
                        u64 cap, u64 *out_count, std::function<int()> *before_S = nullptr, JoinOutput what = OUT_PAIRS)
@@ -2067,7 +2138,7 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
     auto after_partition = [&]() {
         return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : what == OUT_SUMS ? agg_phase(ctx, out_count) :
                what == OUT_MULT ? mult_phase(ctx, out_count) : what == OUT_GROUP ? group_phase(ctx, out_count) :
-               what == OUT_GJOIN ? gjoin_phase(ctx, out_count) :
+               what == OUT_GJOIN ? gjoin_phase(ctx, out_count) : what == OUT_LOOKUP ? lookup_phase(ctx, out_count) :
                what == OUT_OUTER ? outer_phase(ctx, d_out, cap, out_count) :
                semi_phase(ctx, what, d_out, cap, out_count);
     };
@@ -2722,6 +2793,60 @@ int rhj_join_mult_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
     ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;   // S's rowIDs name its weights
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
     const int rc = join_mult_common(ctx, nullptr, nR, nullptr, nS, d_wS, wS_rows, opts, d_out, out_rows, out_total);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// Lookup join: the partition phase and the repeat ladder of rhj_join_mult_dev / rhj_join_mult_cols_dev, then
+// lookup_phase.  d_R / d_S null: the relations are ctx->cols_in.
+static_assert(RHJ_LOOKUP_FIRST == 0 && RHJ_LOOKUP_LAST == 1, "launch_lookup_join's which");
+static int lookup_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, int which, const rhj_opts *opts,
+                         uint64_t *d_out, uint64_t out_rows, uint64_t *out_matched)
+{
+    if (which != RHJ_LOOKUP_FIRST && which != RHJ_LOOKUP_LAST) return fail(ctx, RHJ_E_INVALID, "which is neither RHJ_LOOKUP_FIRST nor RHJ_LOOKUP_LAST");
+    if (out_rows && !d_out) return fail(ctx, RHJ_E_INVALID, "d_out is null");
+    if (nR == 0 || nS == 0) {                          // all ones, and complete when the call returns
+        if (out_rows) {
+            HIPCHK(ctx, hipMemsetAsync(d_out, 0xFF, out_rows * 8, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return join_nothing(ctx);
+    }
+    rhj_opts plan;
+    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+    ctx->mult_out = (u64 *)d_out;
+    ctx->mult_out_rows = out_rows;
+    ctx->lookup_which = which;
+    const int rc = partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_matched, nullptr, OUT_LOOKUP);
+    ctx->mult_out = nullptr;
+    ctx->mult_out_rows = 0;
+    return rc;
+}
+
+int rhj_lookup_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, int which,
+                   const rhj_opts *opts, uint64_t *d_out, uint64_t out_rows, uint64_t *out_matched)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_matched) return fail(ctx, RHJ_E_INVALID, "out_matched is null");
+    *out_matched = 0;
+    prof_reset(ctx);
+    if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return lookup_common(ctx, d_R, nR, d_S, nS, which, opts, d_out, out_rows, out_matched);
+}
+
+int rhj_lookup_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                        const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS, int which, const rhj_opts *opts,
+                        uint64_t *d_out, uint64_t out_rows, uint64_t *out_matched)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_matched) return fail(ctx, RHJ_E_INVALID, "out_matched is null");
+    *out_matched = 0;
+    prof_reset(ctx);
+    if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
+    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;   // S's rowIDs are the answer
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = lookup_common(ctx, nullptr, nR, nullptr, nS, which, opts, d_out, out_rows, out_matched);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

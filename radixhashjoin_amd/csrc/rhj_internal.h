@@ -363,6 +363,23 @@ void launch_group_join(hipStream_t st, const void *d_R, const void *d_S, const J
                        const u64 *const *d_colsS, u32 ncolsS, u64 colS_rows, u64 *d_out_keys, u64 *d_out_cntR, u64 *d_out_cntS,
                        u64 *const *d_out_sumsR, u64 *const *d_out_sumsS, u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds,
                        const u32 *d_RK, const u32 *d_SK, const u32 *d_skip, u32 ops, bool ids = false);
+// ---- the lookup join kernel (k_lookup_bkt): k_mult_bkt's weighted table, a partner rowID in the slot word ------------
+// 8192 keys + 8192 64-bit words that start from all ones and take the minimum (first) or maximum (last) rowID of S's tuples with the
+// key, the all-ones key's word beside them: mult_lds_bytes(true), one workgroup of 1024 threads per CU.
+constexpr int JK_LOOKUP = JK_GJOIN + 1;           // "last.join_kernel" of a lookup join (17)
+constexpr size_t lookup_lds_bytes() { return mult_lds_bytes(true); }
+static_assert(lookup_lds_bytes() <= 160 * 1024 && lookup_lds_bytes() == ((size_t)16 << AGG_SLOT_BITS) + 16 &&
+              AGG_FILL + AGG_BUILD_TILE <= (1u << AGG_SLOT_BITS) && (size_t)(AGG_THREADS / 64) * 8 <= ((size_t)8 << AGG_SLOT_BITS),
+              "k_lookup_bkt's geometry");
+constexpr u32 LOOKUP_BAD_ROW_R = 1, LOOKUP_BAD_ROW_S = 2;   // bits of *d_bad
+// The task list is launch_make_semi_tasks with anti = 0.  which: 0 the smallest rowID of S among a tuple's partners, 1 the largest.
+// d_out: out_rows words (filled with all ones by the caller), word rowR receives the partner by a global atomic minimum (unsigned) /
+// maximum (signed); d_matched: one word (zeroed by the caller), the number of words that left all ones; d_bad: OR-ed with
+// LOOKUP_BAD_ROW_R when a rowID of R >= out_rows was met (never stored to), with LOOKUP_BAD_ROW_S when a rowID of S >= 2^63 was
+// (which == 1 only; never inserted); the rest as launch_semi_join.
+void launch_lookup_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                        int radix_bits, int which, u64 *d_out, u64 out_rows, u64 *d_matched, u32 *d_bad, u64 *d_max_tables,
+                        const u32 *d_RK, const u32 *d_SK, const u32 *d_skip);
 // in_narrow: d_in is a payload array (u64).  key_base / d_wide (16-byte input): d_wide (may be null) is OR-ed with 1 when some
 // rowID - key_base does not fit 32 bits.  d_unit_rng (may be null): explicit pass-1 units (launch_seg_units).
 void launch_hist2d_units(hipStream_t st, const void *d_in, bool in_narrow, u64 n, u64 L, u32 units, int b1, int b2,

@@ -3022,6 +3022,191 @@ k_mult_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ ta
 }
 
 // ------------------------------------------------------------------------------------------------
+// Lookup join of one task: for every tuple of R ONE partner rowID of S -- the smallest (WHICH == 0) or the largest
+// (WHICH == 1) among the tuples of S with its join value -- delivered to out[rowR]; out starts all ones (the caller fills it).
+//   * k_mult_bkt<., true>'s table unchanged: 8192 keys, insert-if-absent by a 64-bit LDS compare-and-swap, all-ones = empty with the
+//     all-ones key kept beside the table, whole 1024-tuple build tiles, closed at AGG_FILL.  The 64-bit word beside every slot starts
+//     from all ones -- the identity of an unsigned minimum and, read as -1, of a signed maximum -- and every tuple of S does ONE LDS
+//     64-bit atomic with its own rowID on the slot its key occupies: unsigned minimum (first), signed maximum (last).  No weight
+//     column: nothing is loaded by rowS.  Under `last` a rowS >= 2^63 has no place in a signed order: the tuple is never inserted
+//     and raises LOOKUP_BAD_ROW_S.
+//   * a tuple of R with rowID r whose key's word w is not all ones does ONE returning 64-bit global atomic -- the same minimum or
+//     maximum -- of w on out[r].  An ATOMIC, never a store: a partition of S beyond one table has a key's tuples in several tables,
+//     every table sweeps the task's whole R range, and the smallest rowS may sit in any of them; and two tuples of R may name one
+//     row.  r >= out_rows is never stored to: the tuple delivers nothing and raises LOOKUP_BAD_ROW_R.
+//   * the atomic's return value counts the matched words: a word leaves all ones exactly once.  The returns of a probe tile are
+//     consumed behind its last atomic, so the AGG_EPT of them are in flight together.
+//   * end of task: the words the task matched, reduced by wavefront shuffles and one LDS round into one global atomic on *matched.
+// ------------------------------------------------------------------------------------------------
+template <int WHICH>
+__device__ __forceinline__ void lookup_lds_update(u64 *p, u64 v)
+{
+    if constexpr (WHICH == 0) atomicMin((unsigned long long *)p, (unsigned long long)v);
+    else atomicMax((long long *)p, (long long)v);
+}
+
+template <int WHICH>
+__device__ __forceinline__ u64 lookup_global_update(u64 *p, u64 v)
+{
+    if constexpr (WHICH == 0) return (u64)atomicMin((unsigned long long *)p, (unsigned long long)v);
+    else return (u64)atomicMax((long long *)p, (long long)v);
+}
+
+template <bool NARROW, int WHICH>
+__global__ void __launch_bounds__(AGG_THREADS, 4)
+k_lookup_bkt(RelView<NARROW> R, RelView<NARROW> S, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks,
+             int radix_bits, u64 *__restrict__ out, u64 out_rows, u64 *__restrict__ matched, u32 *__restrict__ bad,
+             u64 *__restrict__ max_tables, const u32 *__restrict__ skip)
+{
+    if (skip != nullptr && *skip != 0) return;
+    if (blockIdx.x >= *ntasks) return;
+    constexpr int THREADS = AGG_THREADS, NW = THREADS / 64, EPT = AGG_EPT, TILE = THREADS * EPT;
+    constexpr u32 SLOTS = 1u << AGG_SLOT_BITS;
+    constexpr u64 NONE = ~0ull;                                              // RHJ_NO_ROW: no partner
+    static_assert(AGG_BPT == 1, "one tuple of S per thread per build tile");
+    static_assert(WHICH == 0 || WHICH == 1, "first or last");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64 *tab = reinterpret_cast<u64 *>(smem);                                // SLOTS keys
+    u64 *row = tab + SLOTS;                                                  // SLOTS partner rowIDs, by slot
+    u64 *ones = row + SLOTS;                                                 // ... of the all-ones key
+    u32 *nkeys = reinterpret_cast<u32 *>(smem + lookup_lds_bytes() - 8);     // distinct keys in the table
+
+    const JoinTask task = tasks[blockIdx.x];
+    typedef typename RelView<NARROW>::Both Both;
+    const RelView<NARROW> Sv = S.at(task.bbeg);
+    const u32 ns = task.blen, np = task.plen;
+    if (ns == 0 || np == 0) return;                                          // (a task has both sides)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const typename RelView<NARROW>::Buf PB = R.at(task.pbeg).buf(0, np);
+
+    bool wild_r = false, wild_s = false;
+    const v2u64 *tab2 = reinterpret_cast<const v2u64 *>(tab);
+    auto row_on = [&](u64 key, u32 b) -> u64 {                               // k_mult_bkt's paired walk from pair b on (key != SEMI_EMPTY)
+        for (;; b = (b + 1) & (SLOTS / 2 - 1)) {
+            const v2u64 e = tab2[b];
+            if (e.x == key) return row[2 * b];
+            if (e.y == key) return row[2 * b + 1];
+            if (e.x == SEMI_EMPTY || e.y == SEMI_EMPTY) return NONE;
+        }
+    };
+    auto insert = [&](u64 key, u64 rowS) -> bool {                           // true: the key was not there; the rowID meets the word either way
+        if constexpr (WHICH == 1) {
+            if (rowS >> 63) { wild_s = true; return false; }
+        }
+        if (key == SEMI_EMPTY) { lookup_lds_update<WHICH>(ones, rowS); return false; }
+        for (u32 s = 2u * bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);; s = (s + 1) & (SLOTS - 1)) {
+            const u64 cur = tab[s];
+            bool fresh = false;
+            if (cur != key) {
+                if (cur != SEMI_EMPTY) continue;
+                const u64 old = atomicCAS((unsigned long long *)&tab[s], (unsigned long long)SEMI_EMPTY, (unsigned long long)key);
+                if (old == SEMI_EMPTY) fresh = true;
+                else if (old != key) continue;
+            }
+            lookup_lds_update<WHICH>(&row[s], rowS);
+            return fresh;
+        }
+    };
+    auto load_tuple = [&](Both &dst, u32 at) {                               // the tile of S that starts at tuple `at` (< ns): key and rowID
+        const typename RelView<NARROW>::Buf SB = Sv.buf(at, ns - at < AGG_BUILD_TILE ? ns - at : AGG_BUILD_TILE);
+        dst = SB.both(0u, (u32)tid);
+    };
+
+    Both st, st_next;
+    load_tuple(st, 0);
+    st_next = st;
+    Both p[EPT], p_next[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; k++) p[k] = PB.both((u32)k * THREADS, (u32)tid);
+
+    u32 acc_matched = 0;
+    u32 sdone = 0, ntab = 0;
+    bool last;
+    do {
+        // ---- build: the next whole tiles of S's partition (k_mult_bkt's close rule) --------------------
+        for (u32 i = tid; i < SLOTS; i += THREADS) { tab[i] = SEMI_EMPTY; row[i] = NONE; }
+        if (tid == 0) { *nkeys = 0; *ones = NONE; }
+        __syncthreads();
+        u32 filled = 0;
+        while (sdone < ns && filled + AGG_BUILD_TILE <= AGG_FILL) {
+            const u32 nt = ns - sdone < AGG_BUILD_TILE ? ns - sdone : AGG_BUILD_TILE;
+            const bool more = sdone + nt < ns;
+            if (more) load_tuple(st_next, sdone + nt);
+            {
+                const bool fresh = (u32)tid < nt && insert(st.payload, (u64)st.key);
+                const unsigned long long m = __ballot(fresh);
+                if (lane == 0 && m) atomicAdd(nkeys, (u32)__popcll(m));
+            }
+            __syncthreads();
+            filled = *nkeys;
+            __syncthreads();                                                 // (everybody has read the count before the next tile adds to it)
+            sdone += nt;
+            if (more) st = st_next;
+        }
+        ntab++;
+        last = sdone >= ns;
+
+        // ---- probe: every tile of the task's R range delivers this table's partner to its rows -------------
+        const u64 r_ones = *ones;
+        for (u32 tb = 0; tb < np; tb += TILE) {
+            const u32 tn = tb + TILE < np ? tb + (u32)TILE : 0u;
+            const bool fetch = tn != tb && !(last && tn == 0);
+            if (fetch) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) p_next[k] = PB.both(tn + (u32)k * THREADS, (u32)tid);
+            }
+            v2u64 e0[EPT];                                                   // the first pair of every slot row, read together
+#pragma unroll
+            for (int k = 0; k < EPT; k++) e0[k] = tab2[bj_bucket<AGG_SLOT_BITS - 1>(p[k].payload, radix_bits)];
+            u64 c[EPT];
+#pragma unroll
+            for (int k = 0; k < EPT; k++) {
+                const u32 i = tb + (u32)k * THREADS + tid;
+                c[k] = NONE;
+                if (i < np) {
+                    const u64 key = p[k].payload;
+                    const u32 b = bj_bucket<AGG_SLOT_BITS - 1>(key, radix_bits);
+                    const v2u64 e = e0[k];
+                    if (key == SEMI_EMPTY) c[k] = r_ones;
+                    else if (e.x == key) c[k] = row[2 * b];
+                    else if (e.y == key) c[k] = row[2 * b + 1];
+                    else if (e.x != SEMI_EMPTY && e.y != SEMI_EMPTY) c[k] = row_on(key, (b + 1) & (SLOTS / 2 - 1));
+                    if ((u64)p[k].key >= out_rows) { c[k] = NONE; wild_r = true; }
+                }
+            }
+            u64 old[EPT];                                                    // all of a tile's atomics are issued before a return is looked at
+#pragma unroll
+            for (int k = 0; k < EPT; k++) {
+                old[k] = 0;
+                if (c[k] != NONE) old[k] = lookup_global_update<WHICH>(&out[(u64)p[k].key], c[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < EPT; k++) acc_matched += old[k] == NONE ? 1u : 0u;
+            if (fetch) {
+#pragma unroll
+                for (int k = 0; k < EPT; k++) p[k] = p_next[k];
+            }
+        }
+        __syncthreads();                                                     // the table is cleared for the next tiles of S
+    } while (!last);
+
+    // ---- the task's matched words: wavefront, workgroup (the table's first bytes are free now), one global atomic ----
+    const u32 flags = (__ballot(wild_r) ? LOOKUP_BAD_ROW_R : 0u) | (__ballot(wild_s) ? LOOKUP_BAD_ROW_S : 0u);
+    if (flags && lane == 0) atomicOr(bad, flags);
+    u64 acc = acc_matched;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if (lane == 0) tab[w] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        u64 t = 0;
+        for (int i = 0; i < NW; i++) t += tab[i];
+        if (t) atomicAdd((unsigned long long *)matched, (unsigned long long)t);
+        if (ntab > 1) atomicMax((unsigned long long *)max_tables, (unsigned long long)ntab);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // GROUP BY of one task: one output row per DISTINCT join value of a partition of R -- the value, how many tuples carry
 // it, and the sums of up to four columns over those tuples.  A task is a WHOLE partition: a partition cut in two would emit its keys
 // twice.
@@ -4421,6 +4606,10 @@ static void allow_big_lds()
     SET_LDS((k_mult_bkt<false, false>), mult_lds_bytes(false));
     SET_LDS((k_mult_bkt<true, true>), mult_lds_bytes(true));
     SET_LDS((k_mult_bkt<false, true>), mult_lds_bytes(true));
+    SET_LDS((k_lookup_bkt<true, 0>), lookup_lds_bytes());
+    SET_LDS((k_lookup_bkt<false, 0>), lookup_lds_bytes());
+    SET_LDS((k_lookup_bkt<true, 1>), lookup_lds_bytes());
+    SET_LDS((k_lookup_bkt<false, 1>), lookup_lds_bytes());
     SET_LDS((k_group_bkt<true, GB_COUNT>), group_lds_bytes());
     SET_LDS((k_group_bkt<false, GB_COUNT>), group_lds_bytes());
     SET_LDS((k_group_bkt<true, GB_SUMS>), group_lds_bytes());
@@ -5125,6 +5314,27 @@ void launch_mult_join(hipStream_t st, const void *d_R, const void *d_S, const Jo
         const RelView<false> Rv{(const Tup *)d_R}, Sv{(const Tup *)d_S};
         if (d_w != nullptr) go(k_mult_bkt<false, true>, Rv, Sv, mult_lds_bytes(true));
         else go(k_mult_bkt<false, false>, Rv, Sv, mult_lds_bytes(false));
+    }
+}
+
+void launch_lookup_join(hipStream_t st, const void *d_R, const void *d_S, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid,
+                        int radix_bits, int which, u64 *d_out, u64 out_rows, u64 *d_matched, u32 *d_bad, u64 *d_max_tables,
+                        const u32 *d_RK, const u32 *d_SK, const u32 *d_skip)
+{
+    if (grid == 0) return;
+    allow_big_lds();
+    auto go = [&](auto kernel, auto Rv, auto Sv) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(AGG_THREADS), lookup_lds_bytes(), st, Rv, Sv, d_tasks, d_ntasks, radix_bits, d_out,
+                           out_rows, d_matched, d_bad, d_max_tables, d_skip);
+    };
+    if (d_RK != nullptr) {                                                   // narrow partitions: d_R, d_S are payload arrays
+        const RelView<true> Rv{(const u64 *)d_R, d_RK}, Sv{(const u64 *)d_S, d_SK};
+        if (which == 0) go(k_lookup_bkt<true, 0>, Rv, Sv);
+        else go(k_lookup_bkt<true, 1>, Rv, Sv);
+    } else {
+        const RelView<false> Rv{(const Tup *)d_R}, Sv{(const Tup *)d_S};
+        if (which == 0) go(k_lookup_bkt<false, 0>, Rv, Sv);
+        else go(k_lookup_bkt<false, 1>, Rv, Sv);
     }
 }
 

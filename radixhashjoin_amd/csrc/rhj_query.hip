@@ -88,6 +88,43 @@ k_gather_u64(const u64 *__restrict__ src, const u64 *__restrict__ idx, u64 n, u6
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) dst[i] = src[idx[i]];
 }
 
+// k_gather_u64 over NCOLS columns with one index load per element and a fill value for the index RHJ_NO_ROW (a lookup join's "no
+// partner", an outer join's missing side).  Any other index >= src_rows is never dereferenced: the element takes the fill value and
+// raises *bad.  GATHER_EPT elements per thread and trip, a block's elements 256 apart: the index loads and the stores stay
+// coalesced, and the up to GATHER_EPT x NCOLS dependent loads -- 8 bytes from a line each, served by L2 or HBM -- are in flight together.
+constexpr int GATHER_EPT = 4;
+struct GatherCols { const u64 *src[RHJ_LOOKUP_MAX_COLS]; u64 *dst[RHJ_LOOKUP_MAX_COLS]; u64 fill[RHJ_LOOKUP_MAX_COLS]; };
+
+template <int NCOLS>
+__global__ void __launch_bounds__(256)
+k_gather_cols_fill(GatherCols c, u64 src_rows, const u64 *__restrict__ idx, u64 n, u64 *__restrict__ bad)
+{
+    bool wild = false;
+    for (u64 base = (u64)blockIdx.x * (256 * GATHER_EPT) + threadIdx.x; base < n; base += (u64)gridDim.x * (256 * GATHER_EPT)) {
+        u64 r[GATHER_EPT], v[GATHER_EPT][NCOLS];
+#pragma unroll
+        for (int k = 0; k < GATHER_EPT; k++) {
+            const u64 i = base + (u64)k * 256;
+            r[k] = i < n ? idx[i] : RHJ_NO_ROW;
+        }
+#pragma unroll
+        for (int k = 0; k < GATHER_EPT; k++) {
+            const bool there = r[k] < src_rows;
+            if (!there && r[k] != RHJ_NO_ROW) wild = true;
+#pragma unroll
+            for (int j = 0; j < NCOLS; j++) v[k][j] = there ? c.src[j][r[k]] : c.fill[j];
+        }
+#pragma unroll
+        for (int k = 0; k < GATHER_EPT; k++) {
+            const u64 i = base + (u64)k * 256;
+#pragma unroll
+            for (int j = 0; j < NCOLS; j++)
+                if (i < n) c.dst[j][i] = v[k][j];
+        }
+    }
+    if (__ballot(wild) && (threadIdx.x & 63) == 0) atomicOr((unsigned long long *)bad, 1ull);
+}
+
 __global__ void __launch_bounds__(256)
 k_sum_gather(const u64 *__restrict__ col, const u64 *__restrict__ rows, u64 n, u64 *__restrict__ sum)
 {
@@ -258,6 +295,34 @@ int rhj_gather_u64(rhj_ctx *ctx, const uint64_t *d_src, const uint64_t *d_idx, u
     hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(n)), dim3(256), 0, rhj_internal_stream(ctx), (const u64 *)d_src,
                        (const u64 *)d_idx, (u64)n, (u64 *)d_dst);
     return check(ctx, "rhj_gather_u64");
+}
+
+int rhj_gather_cols_fill(rhj_ctx *ctx, const uint64_t *const *d_srcs, uint32_t ncols, uint64_t src_rows, const uint64_t *d_idx,
+                         uint64_t n, const uint64_t *fills, uint64_t *const *d_dsts)
+{
+    int rc = rhj_internal_use_device(ctx);
+    if (rc != RHJ_OK) return rc;
+    if (ncols < 1 || ncols > RHJ_LOOKUP_MAX_COLS) return rhj_internal_fail(ctx, RHJ_E_INVALID, "ncols is not in 1 .. RHJ_LOOKUP_MAX_COLS");
+    if (n == 0) return RHJ_OK;
+    if (!d_srcs || !fills || !d_dsts || !d_idx) return rhj_internal_fail(ctx, RHJ_E_INVALID, "bad rhj_gather_cols_fill argument");
+    GatherCols c = {};
+    for (uint32_t j = 0; j < ncols; j++) {
+        if (!d_dsts[j] || (src_rows && !d_srcs[j])) return rhj_internal_fail(ctx, RHJ_E_INVALID, "null rhj_gather_cols_fill column");
+        c.src[j] = (const u64 *)d_srcs[j]; c.dst[j] = (u64 *)d_dsts[j]; c.fill[j] = fills[j];
+    }
+    uint64_t bad = 0;
+    rc = with_counter(ctx, &bad, "rhj_gather_cols_fill", [&](u64 *flag, hipStream_t st) {
+        const dim3 grid(grid_for((n + GATHER_EPT - 1) / GATHER_EPT)), block(256);
+        switch (ncols) {
+        case 1: hipLaunchKernelGGL(k_gather_cols_fill<1>, grid, block, 0, st, c, (u64)src_rows, (const u64 *)d_idx, (u64)n, flag); break;
+        case 2: hipLaunchKernelGGL(k_gather_cols_fill<2>, grid, block, 0, st, c, (u64)src_rows, (const u64 *)d_idx, (u64)n, flag); break;
+        case 3: hipLaunchKernelGGL(k_gather_cols_fill<3>, grid, block, 0, st, c, (u64)src_rows, (const u64 *)d_idx, (u64)n, flag); break;
+        default: hipLaunchKernelGGL(k_gather_cols_fill<4>, grid, block, 0, st, c, (u64)src_rows, (const u64 *)d_idx, (u64)n, flag); break;
+        }
+    });
+    if (rc != RHJ_OK) return rc;
+    if (bad) return rhj_internal_fail(ctx, RHJ_E_INVALID, "an index is neither RHJ_NO_ROW nor < src_rows: the sources have no such row");
+    return RHJ_OK;
 }
 
 }  // extern "C"

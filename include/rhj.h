@@ -620,6 +620,53 @@ int rhj_group_join_agg_ids_dev(rhj_ctx *ctx,
         uint64_t out_capacity, uint64_t *out_groups,
         uint64_t *d_out_gidR, uint64_t gidR_rows, uint64_t *d_out_gidS, uint64_t gidS_rows);
 
+/* ---- group-by argmin / argmax: WHICH ROW holds each group's minimum or maximum (the latest record per key: SELECT DISTINCT ON (key)
+ * .. ORDER BY key, t DESC; ROW_NUMBER() OVER (PARTITION BY key ORDER BY t) = 1; pandas groupby.idxmin / idxmax; drop_duplicates(keep =
+ * "first" | "last")).  The group-by's kernel family, table, class walk and host path: per value column the minimum / maximum sweep of
+ * rhj_group_agg_cols_dev and one more sweep that finds the row. */
+#define RHJ_ARG_MIN_U64 0   /* the row holding the minimum / maximum of the column words as unsigned 64-bit ... */
+#define RHJ_ARG_MAX_U64 1
+#define RHJ_ARG_MIN_I64 2   /* ... as two's-complement signed 64-bit */
+#define RHJ_ARG_MAX_I64 3
+#define RHJ_ARG_ROW     4   /* no column: the rowIDs themselves are ordered -- the first / last row of the group (d_cols[j], d_out_vals[j] ignored, may be NULL) */
+#define RHJ_ARG_TIE_FIRST 0 /* among the tuples holding the extreme: the smallest rowID (unsigned) */
+#define RHJ_ARG_TIE_LAST  1 /* the largest */
+#define RHJ_GROUP_ARG_MAX_COLS 4
+/* rhj_group_agg_cols_dev's shape with a row beside every value.  ops / ties: HOST arrays of ncols words (an RHJ_ARG_* / an
+ * RHJ_ARG_TIE_*); ties == NULL: every column is RHJ_ARG_TIE_FIRST.  d_out_vals / d_out_rows: HOST arrays of ncols DEVICE columns of
+ * out_capacity words.
+ * Values: for group g and column j, d_out_vals[j][g] is the extreme of d_cols[j][rowR] over the group's tuples -- bit for bit what
+ * rhj_group_agg_cols_dev returns under the matching RHJ_AGG_* op.
+ * Rows, the tie rule: d_out_rows[j][g] is the rowID of a tuple of the group whose column word equals that extreme -- among those tuples
+ * the smallest rowID under RHJ_ARG_TIE_FIRST, the largest under RHJ_ARG_TIE_LAST, rowIDs compared as unsigned 64-bit.
+ * RHJ_ARG_ROW: d_out_rows[j][g] is the smallest (FIRST) or largest (LAST) rowID of the group; no column is read, so there is no row
+ * guard for that column, and d_cols[j] / d_out_vals[j] are never touched.
+ * The same column pointer may appear several times: MIN and MAX of one timestamp, plus ROW / FIRST and ROW / LAST, fit in one call.
+ * Every group has a row: a group has at least one tuple, so every d_out_rows[j][g] with g < out_capacity names a real row of the
+ * group, also when the extreme is the identity of its op -- a group whose every value is all ones under RHJ_ARG_MIN_U64, 0 under
+ * RHJ_ARG_MAX_U64, INT64_MAX under RHJ_ARG_MIN_I64, INT64_MIN under RHJ_ARG_MAX_I64.
+ * Everything else is the contract of rhj_group_agg_cols_dev, word for word: the order of groups is unspecified, the set and every
+ * word exact and bit-identical from run to run; count only with a NULL d_out_keys and out_capacity 0 -- no sweep, no column read --;
+ * RHJ_E_OVERFLOW with the exact *out_groups, complete distinct groups in [0, capacity) and nothing at or past capacity written in
+ * any of the up to ten arrays, the rows arrays included; the row guard of the value ops (a rowR >= col_rows is never dereferenced: a
+ * flag word, RHJ_E_INVALID, rhj_last_error names col_rows, the context stays usable); nR == 0; plans, repeats, probe_split ignored;
+ * "last.join_kernel" is 15, "last.group_rounds" as there; ncols == 0 returns keys and counts only.
+ * RHJ_E_INVALID beyond that contract's, each checked before any launch, also in a count-only call, rhj_last_error names the column:
+ * an ops[j] above RHJ_ARG_ROW; a ties[j] above RHJ_ARG_TIE_LAST; ncols above RHJ_GROUP_ARG_MAX_COLS; with out_capacity > 0 a NULL
+ * d_out_rows[j], or a NULL d_cols[j] or d_out_vals[j] under a value op.
+ * Costs: per value column and class TWO sweeps of the partition and two gathers of the column word, and one global atomic per tuple
+ * that holds its group's extreme -- typically one per group; a heavy group whose column is constant issues one per tuple on one
+ * word.  An RHJ_ARG_ROW column costs one sweep, no gather and no global atomic. */
+int rhj_group_arg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *const *d_cols, const uint32_t *ops, const uint32_t *ties, uint32_t ncols, uint64_t col_rows,
+                           const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                           uint64_t *const *d_out_vals, uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups);
+/* ... on 16-byte tuples (value = .payload, rowR = .key) */
+int rhj_group_arg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
+                      const uint64_t *const *d_cols, const uint32_t *ops, const uint32_t *ties, uint32_t ncols, uint64_t col_rows,
+                      const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                      uint64_t *const *d_out_vals, uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups);
+
 /* ---- composite keys: up to four key columns per relation packed into ONE 64-bit key column (JOIN .. ON r.a = s.a AND r.b = s.b; GROUP
  * BY a, b; torch.unique(dim=0); merge(on=[..])).  Every operator above compares 64-bit values by bit pattern, so what it needs is an
  * EXACT surrogate: a 64-bit word per row such that two rows of R u S get the same word if and only if all their key columns agree.

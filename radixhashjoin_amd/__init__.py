@@ -21,6 +21,9 @@ R in S, aligned with R: the first (or last) index in S, -1 where there is none, 
 ``unique_keys, counts, sums = Engine(0).group_by_columns(keys, weights)`` is GROUP BY on one key tensor: its distinct values, their
 counts and the per-group sums of the weight tensors (``rhj_group_sum_cols_dev``) -- with ``ops=["min", "max", "sum"]`` the per-group
 minimum, maximum or sum per weight tensor (``rhj_group_agg_cols_dev``);
+``unique_keys, counts, vals, rows = Engine(0).group_by_columns_arg(keys, [t], ["max"], ties="last")`` is which row holds each group's
+minimum or maximum -- the latest record per key -- and ``idx = Engine(0).drop_duplicates_columns(keys, keep="first")`` the rows
+pandas' drop_duplicates keeps (``rhj_group_arg_cols_dev``);
 ``keys, count, sums_R, sums_S = Engine(0).join_group_by_columns(keys_R, keys_S, weights_R, weights_S, how="inner")`` is the join
 with GROUP BY on the key: per join value COUNT(*) and the SUMs of both sides' weights over its pairs, without the pairs
 (``rhj_group_join_cols_dev``); ``ops_R`` / ``ops_S`` make a column a minimum or maximum there too (``rhj_group_join_agg_cols_dev``).
@@ -35,12 +38,20 @@ from .binding import (  # noqa: F401
     AGG_MIN_U64,
     AGG_SUM,
     ANTI,
+    ARG_MAX_I64,
+    ARG_MAX_U64,
+    ARG_MIN_I64,
+    ARG_MIN_U64,
+    ARG_ROW,
+    ARG_TIE_FIRST,
+    ARG_TIE_LAST,
     PAIR,
     TUPLE,
     DeviceBuffer,
     Engine,
     GJ_INNER,
     GJ_LEFT,
+    GROUP_ARG_MAX_COLS,
     GROUP_JOIN_MAX_COLS,
     GROUP_MAX_COLS,
     KEYS_DICT,
@@ -68,5 +79,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS"]
 __version__ = "0.1.0"

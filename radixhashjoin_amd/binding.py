@@ -129,6 +129,10 @@ SYMBOLS = {
     "rhj_group_join_agg_ids_dev": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _P(_vp), _P(C.c_uint32), C.c_uint32, _u64, _P(_vp), _P(C.c_uint32),
                                              C.c_uint32, _u64, C.c_int, _P(Opts), _vp, _vp, _vp, _P(_vp), _P(_vp), _u64, _P(_u64),
                                              _vp, _u64, _vp, _u64]),
+    "rhj_group_arg_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, _u64, _P(Opts), _vp, _vp,
+                                         _P(_vp), _P(_vp), _u64, _P(_u64)]),
+    "rhj_group_arg_dev": (C.c_int, [_vp, _vp, _u64, _P(_vp), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, _u64, _P(Opts), _vp, _vp, _P(_vp),
+                                    _P(_vp), _u64, _P(_u64)]),
     "rhj_keys_layout": (C.c_int, [C.c_uint32, _P(C.c_uint8), _u64, _P(KeysLayout)]),
     "rhj_keys_pack_dev": (C.c_int, [_vp, C.c_uint32, _P(_vp), _u64, _P(_vp), _u64, C.c_uint32, _vp, _vp, _P(_vp)]),
     "rhj_keys_unpack_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp)]),
@@ -253,6 +257,35 @@ def _agg_ops(ops, n, name):
         if o not in _AGG_BY_NAME:
             raise ValueError(f"{name}[{i}]: 'sum', 'min' or 'max', not {o!r}")
     return [_AGG_BY_NAME[o] for o in ops]
+# include/rhj.h RHJ_ARG_*: what a column of a group_arg_* call orders, RHJ_ARG_TIE_*: which of the rows that tie, and the columns per call
+ARG_MIN_U64, ARG_MAX_U64, ARG_MIN_I64, ARG_MAX_I64, ARG_ROW = 0, 1, 2, 3, 4
+ARG_TIE_FIRST, ARG_TIE_LAST = 0, 1
+GROUP_ARG_MAX_COLS = 4
+# ... by name (group_by_columns_arg): "min" / "max" order int64 tensors as signed words
+_ARG_BY_NAME = {"min": ARG_MIN_I64, "max": ARG_MAX_I64, "min_u64": ARG_MIN_U64, "max_u64": ARG_MAX_U64, "row": ARG_ROW}
+_TIE_BY_NAME = {"first": ARG_TIE_FIRST, "last": ARG_TIE_LAST}
+
+
+def _arg_ops(by, ops, ties):
+    """(RHJ_ARG_* words, RHJ_ARG_TIE_* words) of a group_by_columns_arg call from their names; ValueError on a wrong length, name, a
+    column too many or a value op without a tensor -- nothing here touches a device"""
+    by, ops = list(by), list(ops)
+    if len(by) > GROUP_ARG_MAX_COLS:
+        raise ValueError(f"at most {GROUP_ARG_MAX_COLS} columns per call, not {len(by)}")
+    if len(ops) != len(by):
+        raise ValueError(f"ops: {len(ops)} ops for {len(by)} columns")
+    ties = [ties] * len(by) if isinstance(ties, str) else list(ties)
+    if len(ties) != len(by):
+        raise ValueError(f"ties: {len(ties)} ties for {len(by)} columns")
+    for i, o in enumerate(ops):
+        if not isinstance(o, str) or o not in _ARG_BY_NAME:
+            raise ValueError(f"ops[{i}]: 'min', 'max', 'min_u64', 'max_u64' or 'row', not {o!r}")
+        if o != "row" and by[i] is None:
+            raise ValueError(f"by[{i}]: {o!r} needs a tensor; None goes with 'row' only")
+    for i, t in enumerate(ties):
+        if not isinstance(t, str) or t not in _TIE_BY_NAME:
+            raise ValueError(f"ties[{i}]: 'first' or 'last', not {t!r}")
+    return [_ARG_BY_NAME[o] for o in ops], [_TIE_BY_NAME[t] for t in ties]
 # include/rhj.h RHJ_KEYS_*: key columns per pack call; the flag of a pack that keeps no dictionaries; the kind of a column; fold ids
 KEYS_MAX_COLS, KEYS_NO_UNPACK, KEYS_RANGE, KEYS_DICT, KEYS_MAX_FOLDS, KEYS_FOLD0 = 4, 1, 0, 1, 2, 4
 SEMI, ANTI = 0, 1                                        # include/rhj.h RHJ_SEMI / RHJ_ANTI: the kind of a semi_join_* call
@@ -698,6 +731,49 @@ class Engine:
         self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
         return n.value
 
+    def _group_arg_args(self, d_cols, ops, ties, d_out_vals, d_out_rows):
+        """the five host arrays of a group_arg_* call (a missing pointer goes in as NULL: the library answers)"""
+        ncols = len(ops)
+        k = max(ncols, 1)
+
+        def ptrs(xs):
+            xs = list(xs)[:ncols]
+            return (_vp * k)(*[_addr(x) for x in xs + [None] * (ncols - len(xs))])
+        if ties is not None and len(ties) != ncols:
+            raise ValueError(f"{len(ties)} ties for {ncols} columns")
+        return (ptrs(d_cols), (C.c_uint32 * k)(*ops), None if ties is None else (C.c_uint32 * k)(*ties), ptrs(d_out_vals),
+                ptrs(d_out_rows))
+
+    def group_arg_cols_dev(self, d_valR, d_idR, nR, d_cols=(), ops=(), ties=None, col_rows=0, d_out_keys=None, d_out_counts=None,
+                           d_out_vals=(), d_out_rows=(), capacity=0, opts=None, allow_overflow=False):
+        """rhj_group_arg_cols_dev: the group-by of group_agg_cols_dev with the ROW of every extreme -- ops[j] one of ARG_MIN_U64,
+        ARG_MAX_U64, ARG_MIN_I64, ARG_MAX_I64 (d_out_vals[j][g] the extreme of d_cols[j][rowID] over group g, d_out_rows[j][g] the
+        rowID of a tuple of the group that holds it: the smallest under ties[j] == ARG_TIE_FIRST, the largest under ARG_TIE_LAST) or
+        ARG_ROW (no column: d_out_rows[j][g] the smallest / largest rowID of the group; d_cols[j] and d_out_vals[j] may be None).
+        ties None: every column ARG_TIE_FIRST.  The number of columns is len(ops), at most GROUP_ARG_MAX_COLS.  Everything else as
+        group_agg_cols_dev.  Costs: two sweeps and two gathers per value column, one global atomic per tuple that holds its group's
+        extreme; a row column one sweep in LDS."""
+        n = _u64()
+        ops = list(ops)
+        cols, opw, tiew, vals, rows = self._group_arg_args(d_cols, ops, None if ties is None else list(ties), d_out_vals, d_out_rows)
+        rc = self.lib.rhj_group_arg_cols_dev(self.ctx, _addr(d_valR), _addr(d_idR), nR, cols, opw, tiew, len(ops), col_rows,
+                                             C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_counts),
+                                             vals, rows, capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
+    def group_arg_dev(self, d_R, nR, d_cols=(), ops=(), ties=None, col_rows=0, d_out_keys=None, d_out_counts=None, d_out_vals=(),
+                      d_out_rows=(), capacity=0, opts=None, allow_overflow=False):
+        """rhj_group_arg_dev: group_arg_cols_dev on 16-byte tuples (value = .payload, rowID = .key)"""
+        n = _u64()
+        ops = list(ops)
+        cols, opw, tiew, vals, rows = self._group_arg_args(d_cols, ops, None if ties is None else list(ties), d_out_vals, d_out_rows)
+        rc = self.lib.rhj_group_arg_dev(self.ctx, _addr(d_R), nR, cols, opw, tiew, len(ops), col_rows,
+                                        C.byref(opts) if opts is not None else None, _addr(d_out_keys), _addr(d_out_counts), vals, rows,
+                                        capacity, C.byref(n))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return n.value
+
     def group_join_cols_dev(self, d_valR, d_idR, nR, d_valS, d_idS, nS, d_colsR=(), colR_rows=0, d_colsS=(), colS_rows=0, mode=GJ_INNER,
                             d_out_keys=None, d_out_cntR=None, d_out_cntS=None, d_out_sumsR=(), d_out_sumsS=(), capacity=0, opts=None,
                             allow_overflow=False):
@@ -1135,6 +1211,46 @@ class Engine:
         if return_inverse:
             return out_keys[:groups], counts[:groups], [s[:groups] for s in sums], inverse
         return out_keys[:groups], counts[:groups], [s[:groups] for s in sums]
+
+    def group_by_columns_arg(self, keys, by, ops, ties="first"):
+        """(unique_keys, counts, vals, rows): group_by_columns with the ROW that holds every minimum / maximum (pandas groupby.idxmin /
+        idxmax; SELECT DISTINCT ON (key) .. ORDER BY key, t DESC; the latest record per key) -- vals[k][g] the extreme of by[k] over
+        group g, rows[k][g] the index i of a row of the group with by[k][i] == vals[k][g]; int64 tensors, groups in no particular
+        order.  by: up to GROUP_ARG_MAX_COLS contiguous 1-D 64-bit integer tensors as long as keys (the same tensor may be given
+        several times), None where the op is "row".  ops: per tensor "min" | "max" (the int64 values), "min_u64" | "max_u64" (the
+        words as unsigned), or "row": no tensor, rows[k][g] the first / last row of the group and vals[k] None.  ties: "first" |
+        "last", one for all or one per column: among the rows that hold the extreme the smallest / the largest index.  A wrong name
+        or length, or a column too many: ValueError before any device use.  Everything else as group_by_columns
+        (rhj_group_arg_cols_dev: two sweeps per value column).
+        Composite keys: a list of 1 to KEYS_MAX_COLS key tensors is packed first (pack_keys); unique_keys is then a list of as many tensors."""
+        import torch
+        by = list(by)
+        opw, tiew = _arg_ops(by, ops, ties)
+        if isinstance(keys, (list, tuple)):
+            packed, _, plan = self.pack_keys(keys)
+            out = self.group_by_columns_arg(packed, by, ops, ties)
+            uniques = plan.unpack(out[0])
+            plan.close()
+            return (uniques,) + out[1:]
+        with self._on_torch_stream(keys, keys, tuple(b for b in by if b is not None)) as dev:
+            n = keys.numel()
+            out_keys = torch.empty(n, dtype=torch.int64, device=dev)
+            counts = torch.empty(n, dtype=torch.int64, device=dev)
+            vals = [None if b is None else torch.empty(n, dtype=torch.int64, device=dev) for b in by]
+            rows = [torch.empty(n, dtype=torch.int64, device=dev) for _ in by]
+            groups = self.group_arg_cols_dev(keys, None, n, by, opw, tiew, n, out_keys, counts, vals, rows, n) if n else 0
+        return out_keys[:groups], counts[:groups], [None if v is None else v[:groups] for v in vals], [r[:groups] for r in rows]
+
+    def drop_duplicates_columns(self, keys, keep="first"):
+        """idx: pandas drop_duplicates(keep="first" | "last") -- the int64 indices of the rows kept, one per distinct value of keys (its
+        first or its last row), SORTED ASCENDING, so keys[idx] is in the original order.  One group_by_columns_arg call with a single
+        "row" column and one torch.sort over the groups.  keep other than "first" / "last": ValueError before any device use.  keys as
+        group_by_columns_arg (composite keys: a list of tensors; index idx into each)."""
+        import torch
+        if not isinstance(keep, str) or keep not in _TIE_BY_NAME:
+            raise ValueError(f"keep: 'first' or 'last', not {keep!r}")
+        rows = self.group_by_columns_arg(keys, [None], ["row"], keep)[3][0]
+        return torch.sort(rows).values
 
     def factorize_columns(self, keys):
         """(codes, uniques): pandas.factorize without the ordering promise -- uniques the distinct values of keys in no particular

@@ -254,6 +254,8 @@ struct rhj_ctx {
     u64 *group_sums[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
     u64 group_cap = 0;
     u32 group_ops = 0;                 // the columns' packed op words (AGG_OP_*; a group-by join's: both sides'); 0: every column a sum
+    u64 *group_rows[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};   // rhj_group_arg_*: the rows arrays (group_sums: the values) ...
+    bool group_arg = false;            // ... and that group_ops holds ARG_OP_* words: group_phase launches k_group_bkt<., GB_ARG>
     int last_group_rounds = 0;         // "last.group_rounds": table builds of the busiest task of the last group-by or group-by join (0: another call)
     // a group-by join's arguments beyond the group-by's (R's side: agg_cols / agg_ncols / agg_col_rows, group_keys, group_counts = cntR,
     // group_sums, group_cap; device words: agg_out's [0] groups, [5] u32 GJOIN_BAD_ROW_R / _S)
@@ -1883,7 +1885,8 @@ int group_phase(rhj_ctx *ctx, u64 *out_groups)
                      ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, ctx->agg_cols, ctx->agg_ncols, ctx->agg_col_rows,
                      ctx->group_keys, ctx->group_counts, ctx->group_sums, ctx->group_cap, d_agg, (u32 *)(d_agg + AGG_MAX_COLS + 1),
                      d_count + 7, narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                     narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops, ctx->gid[0] != nullptr);
+                     narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops, ctx->gid[0] != nullptr,
+                     ctx->group_arg ? ctx->group_rows : nullptr);
     }
     RHJCHK(check_launch(ctx, "group-by phase"));
     u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, -, -, -, -, most table builds of a task (if > 1)
@@ -2867,6 +2870,9 @@ static u32 pack_ops(const uint32_t *ops, u32 ncols, u32 first, u32 *packed)
     return ncols;
 }
 
+static int group_run(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, u32 packed, u32 nsum, uint64_t col_rows,
+                     const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
+                     uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups, uint64_t *d_out_gid, uint64_t gid_rows);
 static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, const uint32_t *ops, uint32_t ncols,
                         uint64_t col_rows, const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
                         uint64_t *const *d_out_sums, uint64_t out_capacity, uint64_t *out_groups, uint64_t *d_out_gid = nullptr,
@@ -2882,13 +2888,26 @@ static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *c
     if (nsum && (!d_cols || !d_out_sums)) return fail(ctx, RHJ_E_INVALID, "null weight column array or d_out_sums");
     for (u32 j = 0; j < nsum; j++)
         if (!d_cols[j] || !d_out_sums[j]) return fail(ctx, RHJ_E_INVALID, "null weight column or sum column");
+    return group_run(ctx, d_R, nR, d_cols, packed, nsum, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, nullptr, out_capacity,
+                     out_groups, d_out_gid, gid_rows);
+}
+
+// The checked arguments of a group-by entry into the context, the one-sided partition phase and group_phase, and out of it again.
+// nsum: the columns the kernel sweeps (0 in a count-only call); packed: their op words -- AGG_OP_*, or with d_out_rows (DESIGN 4.23:
+// nsum rows arrays beside the nsum value arrays) ARG_OP_*.
+static int group_run(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, u32 packed, u32 nsum, uint64_t col_rows,
+                     const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
+                     uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups, uint64_t *d_out_gid, uint64_t gid_rows)
+{
     if (nR == 0) return join_nothing(ctx);
     rhj_opts plan;
     if (resolve_plan(nR, nR, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
     for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
         ctx->agg_cols[j] = j < nsum ? (const u64 *)d_cols[j] : nullptr;
         ctx->group_sums[j] = j < nsum ? (u64 *)d_out_sums[j] : nullptr;
+        ctx->group_rows[j] = j < nsum && d_out_rows ? (u64 *)d_out_rows[j] : nullptr;
     }
+    ctx->group_arg = d_out_rows != nullptr && nsum != 0;
     ctx->agg_ncols = nsum;
     ctx->agg_col_rows = nsum ? col_rows : ~0ull;
     ctx->group_keys = (u64 *)d_out_keys;
@@ -2906,7 +2925,8 @@ static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *c
     ctx->group_ops = 0;
     ctx->group_keys = ctx->group_counts = nullptr;
     ctx->group_cap = 0;
-    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) { ctx->agg_cols[j] = nullptr; ctx->group_sums[j] = nullptr; }
+    ctx->group_arg = false;
+    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) { ctx->agg_cols[j] = nullptr; ctx->group_sums[j] = nullptr; ctx->group_rows[j] = nullptr; }
     RHJCHK(rc);
     if (d_out_keys && *out_groups > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffers too small");
     return RHJ_OK;
@@ -3007,6 +3027,81 @@ int rhj_group_agg_ids_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint6
     ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
     const int rc = group_common(ctx, nullptr, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity,
                                 out_groups, d_out_gid, gid_rows);
+    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
+    return rc;
+}
+
+// ... with the row of every extreme: the same host path; the checks are this entry's own -- a row column has neither a
+// column nor a value array --, the op and tie words travel as ARG_OP_* words, the rows arrays beside the value arrays.  Nothing is
+// filled here: the kernel seeds the rows word of every group it emits below the capacity.
+static_assert(RHJ_GROUP_ARG_MAX_COLS == AGG_MAX_COLS, "rhj.h and rhj_internal.h disagree");
+static int group_arg_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, const uint32_t *ops,
+                            const uint32_t *ties, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts, uint64_t *d_out_keys,
+                            uint64_t *d_out_counts, uint64_t *const *d_out_vals, uint64_t *const *d_out_rows, uint64_t out_capacity,
+                            uint64_t *out_groups)
+{
+    static const u32 word[RHJ_ARG_ROW + 1] = {AGG_OP_MIN, AGG_OP_MAX, AGG_OP_MIN | AGG_OP_SIGNED, AGG_OP_MAX | AGG_OP_SIGNED, ARG_OP_ROW};
+    static_assert(RHJ_ARG_MIN_U64 == 0 && RHJ_ARG_MAX_U64 == 1 && RHJ_ARG_MIN_I64 == 2 && RHJ_ARG_MAX_I64 == 3 && RHJ_ARG_ROW == 4, "word[]");
+    if (ncols > RHJ_GROUP_ARG_MAX_COLS) return fail(ctx, RHJ_E_INVALID, "ncols is above RHJ_GROUP_ARG_MAX_COLS");
+    if (ncols && !ops) return fail(ctx, RHJ_E_INVALID, "ops is null with ncols > 0");
+    u32 packed = 0;
+    bool value_op = false;
+    for (u32 j = 0; j < ncols; j++) {
+        if (ops[j] > RHJ_ARG_ROW)
+            return fail(ctx, RHJ_E_INVALID, "ops[" + std::to_string(j) + "] = " + std::to_string(ops[j]) + " of column " + std::to_string(j) +
+                                                " is above RHJ_ARG_ROW");
+        if (ties && ties[j] > RHJ_ARG_TIE_LAST)
+            return fail(ctx, RHJ_E_INVALID, "ties[" + std::to_string(j) + "] = " + std::to_string(ties[j]) + " of column " + std::to_string(j) +
+                                                " is above RHJ_ARG_TIE_LAST");
+        packed |= (word[ops[j]] | (ties && ties[j] == RHJ_ARG_TIE_LAST ? ARG_OP_LAST : 0u)) << (ARG_OP_BITS * j);
+        value_op = value_op || ops[j] != RHJ_ARG_ROW;
+    }
+    if (!d_out_keys && out_capacity) return fail(ctx, RHJ_E_INVALID, "d_out_keys is null with out_capacity > 0");
+    const u32 nsum = d_out_keys && out_capacity ? ncols : 0;      // count only: no sweep, no array is read
+    if (nsum && !d_out_rows) return fail(ctx, RHJ_E_INVALID, "d_out_rows is null with out_capacity > 0");
+    for (u32 j = 0; j < nsum; j++) {
+        if (!d_out_rows[j]) return fail(ctx, RHJ_E_INVALID, "d_out_rows[" + std::to_string(j) + "] of column " + std::to_string(j) + " is null");
+        if (ops[j] != RHJ_ARG_ROW && (!d_cols || !d_cols[j] || !d_out_vals || !d_out_vals[j]))
+            return fail(ctx, RHJ_E_INVALID, "d_cols[" + std::to_string(j) + "] or d_out_vals[" + std::to_string(j) + "] of column " +
+                                                std::to_string(j) + " is null under a value op");
+    }
+    const uint64_t *cols[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};   // (a row column's two pointers are never read: null)
+    uint64_t *vals[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    for (u32 j = 0; j < nsum; j++)
+        if (ops[j] != RHJ_ARG_ROW) { cols[j] = d_cols[j]; vals[j] = d_out_vals[j]; }
+    return group_run(ctx, d_R, nR, cols, packed, nsum, value_op ? col_rows : ~0ull, opts, d_out_keys, d_out_counts, vals, d_out_rows,
+                     out_capacity, out_groups, nullptr, 0);
+}
+
+int rhj_group_arg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
+                      const uint64_t *const *d_cols, const uint32_t *ops, const uint32_t *ties, uint32_t ncols, uint64_t col_rows,
+                      const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                      uint64_t *const *d_out_vals, uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    return group_arg_common(ctx, d_R, nR, d_cols, ops, ties, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_vals, d_out_rows,
+                            out_capacity, out_groups);
+}
+
+int rhj_group_arg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
+                           const uint64_t *const *d_cols, const uint32_t *ops, const uint32_t *ties, uint32_t ncols, uint64_t col_rows,
+                           const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
+                           uint64_t *const *d_out_vals, uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
+    *out_groups = 0;
+    prof_reset(ctx);
+    if (nR && !d_valR) return fail(ctx, RHJ_E_INVALID, "null value column");
+    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
+    ctx->cols_in[1] = ColsIn();
+    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
+    const int rc = group_arg_common(ctx, nullptr, nR, d_cols, ops, ties, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_vals,
+                                    d_out_rows, out_capacity, out_groups);
     ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
     return rc;
 }

@@ -321,6 +321,15 @@ static_assert(2 * AGG_MAX_COLS * AGG_OP_BITS <= 32, "a call's op words fit one u
 constexpr size_t group_lds_bytes() { return mult_lds_bytes(true) + GROUP_LDS_EXTRA; }
 static_assert(group_lds_bytes() <= 160 * 1024 && mult_lds_bytes(true) % 8 == 0 && AGG_FILL + AGG_BUILD_TILE <= (1u << AGG_SLOT_BITS) &&
               (1u << AGG_SLOT_BITS) % AGG_THREADS == 0, "k_group_bkt's geometry");
+// The row of a group's extreme (k_group_bkt<., GB_ARG>): ARG_OP_BITS bits per column -- AGG_OP_MIN or AGG_OP_MAX and
+// AGG_OP_SIGNED as above, or ARG_OP_ROW (no column: the rowIDs are what is ordered), and ARG_OP_LAST (among the tuples that hold the
+// extreme the largest rowID; clear: the smallest).  Column j at bit ARG_OP_BITS * j of one u32.  The instantiation keeps four more
+// pointers in LDS than its siblings -- the rows arrays, behind the word of op words -- and has its own LDS size for them.
+constexpr u32 ARG_OP_ROW = 8, ARG_OP_LAST = 16, ARG_OP_BITS = 8;
+static_assert(AGG_MAX_COLS * ARG_OP_BITS <= 32 && (ARG_OP_ROW & (AGG_OP_KIND | AGG_OP_SIGNED)) == 0 && ARG_OP_LAST < (1u << ARG_OP_BITS),
+              "a call's arg op words fit one u32");
+constexpr size_t group_arg_lds_bytes() { return group_lds_bytes() + (size_t)AGG_MAX_COLS * 8; }
+static_assert(group_arg_lds_bytes() <= 160 * 1024 && group_arg_lds_bytes() % 8 == 0, "k_group_bkt<., GB_ARG>'s geometry");
 // The task list is launch_make_semi_tasks with anti = 1, a zeroed boundary array of S and split = 2^32 - 1: one task per non-empty
 // partition of R, the whole partition (its S range is empty and never read).  mixed: the partitions hold rhj_mix64 of the caller's
 // values (keys are unmixed on the way out).  d_cols / d_out_sums: HOST arrays of ncols (<= AGG_MAX_COLS) device columns; ncols == 0:
@@ -332,10 +341,13 @@ static_assert(group_lds_bytes() <= 160 * 1024 && mult_lds_bytes(true) % 8 == 0 &
 // ids: the same kernel with an id sweep behind the last column sweep of every class (k_group_bkt<., . | GB_IDS>);
 // d_ngroups is then FIVE words, the four behind the counter written by launch_group_id_words before this launch (the second pair
 // unused); d_bad is OR-ed with 2 when a rowID >= gid_rows was met (never stored to).  false: the launch is the one it was.
+// d_out_rows: a HOST array of ncols device columns of capacity words, and ops are then ARG_OP_* words: with ncols != 0
+// k_group_bkt<., GB_ARG>, which fills d_out_sums[j] with the extremes and d_out_rows[j] with their rows (d_cols[j] / d_out_sums[j] of an
+// ARG_OP_ROW column are never touched); ids must be false.  null: the launch is the one it was.
 void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits, bool mixed,
                   const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_out_keys, u64 *d_out_counts, u64 *const *d_out_sums,
                   u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip, u32 ops,
-                  bool ids = false);
+                  bool ids = false, u64 *const *d_out_rows = nullptr);
 // The id arrays of a launch with ids (either may be null: no sweep of that side) and their lengths in words, into d_ngroups[1 .. 4].
 void launch_group_id_words(hipStream_t st, u64 *d_ngroups, u64 *d_gidR, u64 gidR_rows, u64 *d_gidS, u64 gidS_rows);
 // ---- the group-by join kernel (k_gjoin_bkt): k_group_bkt's table and class walk over R, looked up by S ---------------

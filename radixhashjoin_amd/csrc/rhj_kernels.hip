@@ -3249,6 +3249,26 @@ enum : int { GB_COUNT = 0, GB_SUMS = 1, GB_OPS = 2, GB_KIND = 3, GB_IDS = 4 };
 // row beyond is never written: *bad).  No atomic; an id is never compared with the capacity.  The id arrays and their lengths are not
 // kernel arguments (the walk has no SGPR to hold them in and LDS no word): they wait in the words behind the group counter,
 // ngroups[1 .. 4] = gidR, gidR_rows, gidS, gidS_rows (launch_group_id_words; a null array gets no sweep; k_group_bkt reads the first two).
+// GB_ARG, the fourth value of the GB_KIND field: per column the group's minimum or maximum AND the rowID of a tuple
+// that holds it (the smallest or the largest such rowID), or -- ARG_OP_ROW -- the smallest / largest rowID of the group and no value.
+//   * a value column is GB_OPS's minimum / maximum sweep word for word; the owners emit the extreme, seed rows[g] with the tie's
+//     identity (all ones: first, 0: last) and leave the group index in the slot word, as the id sweep does.  A second sweep over the
+//     class's tuples then reads the group of every tuple, loads the extreme back from the column this workgroup has just emitted (a
+//     group belongs to one workgroup: the barrier between makes the words visible), gathers the column word again and, where the two
+//     are equal, takes a non-returning global minimum / maximum on rows[g] with the rowID.  That sweep skips no word: a group whose
+//     extreme is the op's identity has a row like any other.  Nothing at or past the capacity is stored to or taken an atomic on.
+//   * a row column is one sweep, all in LDS: the accumulators start from the tie's identity and take the minimum / maximum of the
+//     rowIDs; no column is read, so there is no row guard.
+// The op words travel eight bits per column (ARG_OP_BITS: AGG_OP_MIN / _MAX, AGG_OP_SIGNED, ARG_OP_ROW, ARG_OP_LAST) and wait in LDS
+// where GB_OPS's wait; the pointers of the rows arrays are the four words behind them (group_arg_lds_bytes()).
+constexpr int GB_ARG = 3;
+static_assert(GB_ARG == GB_KIND, "the fourth value of the two-bit field");
+struct GroupArgOuts { u64 *c[AGG_MAX_COLS]; u64 *r[AGG_MAX_COLS]; };       // GB_ARG: the value columns and the rows columns of the result
+// (selected by a bool spelt with literals: an expression over the unnamed enum above would put that enum's compiler-made name into
+// the kernels' symbols, and the host and the device compilation number unnamed types differently -- the launch stub's name would
+// match no kernel of the code object)
+template <bool ARG> struct GroupOuts { typedef GroupSums type; };
+template <> struct GroupOuts<true> { typedef GroupArgOuts type; };
 using AggAdd = std::integral_constant<u32, AGG_OP_ADD>;
 using AggMin = std::integral_constant<u32, AGG_OP_MIN>;
 using AggMax = std::integral_constant<u32, AGG_OP_MAX>;
@@ -3263,12 +3283,14 @@ __device__ __forceinline__ void lds_agg(u64 *w, u64 v)
 template <bool NARROW, int AGG>
 __global__ void __launch_bounds__(AGG_THREADS, 4)
 k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__restrict__ ntasks, int radix_bits, int mixed,
-            AggCols cols, u32 ncols, u64 col_rows, u64 *__restrict__ out_keys, u64 *__restrict__ out_counts, GroupSums out_sums,
+            AggCols cols, u32 ncols, u64 col_rows, u64 *__restrict__ out_keys, u64 *__restrict__ out_counts,
+            typename GroupOuts<(AGG & 3) == 3>::type out_sums,
             u64 capacity, u64 *__restrict__ ngroups, u32 *__restrict__ bad, u64 *__restrict__ max_rounds, const u32 *__restrict__ skip,
             u32 ops)
 {
     constexpr int KIND = AGG & GB_KIND;
     constexpr bool SUMS = KIND != GB_COUNT, IDS = (AGG & GB_IDS) != 0;
+    static_assert(KIND != GB_ARG || !IDS, "the rows of the extremes and the ids of the rows are two calls");
     if (skip != nullptr && *skip != 0) return;
     if (blockIdx.x >= *ntasks) return;
     constexpr int THREADS = AGG_THREADS;
@@ -3297,6 +3319,11 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
 #pragma unroll
             for (int j = 0; j < AGG_MAX_COLS; j++) { colp[j] = (u64)cols.c[j]; colp[AGG_MAX_COLS + j] = (u64)out_sums.c[j]; }
             if constexpr (KIND == GB_OPS) colp[2 * AGG_MAX_COLS] = ops;       // GB_OPS: the op words behind the pointers
+            if constexpr (KIND == GB_ARG) {                                  // GB_ARG: ... and the rows arrays behind the op words
+                colp[2 * AGG_MAX_COLS] = ops;
+#pragma unroll
+                for (int j = 0; j < AGG_MAX_COLS; j++) colp[2 * AGG_MAX_COLS + 1 + j] = (u64)out_sums.r[j];
+            }
         }                                                                    // (read behind the barriers of the first build)
     u32 d = 0, rounds = 0;                                                   // the class (d, p); table builds so far
     u64 p = 0;
@@ -3411,6 +3438,105 @@ k_group_bkt(RelView<NARROW> R, const JoinTask *__restrict__ tasks, const u32 *__
             for (u32 c = 0; c < ncols; c++) {
                 const u64 *__restrict__ col = reinterpret_cast<const u64 *>(colp[c]);
                 u64 *__restrict__ dst = reinterpret_cast<u64 *>(colp[AGG_MAX_COLS + c]);
+                if constexpr (KIND == GB_ARG) {                              // the extreme and the row that holds it
+                    const u32 op = (u32)__builtin_amdgcn_readfirstlane((int)((u32)colp[2 * AGG_MAX_COLS] >> (ARG_OP_BITS * c)));
+                    u64 *rows = reinterpret_cast<u64 *>(colp[2 * AGG_MAX_COLS + 1 + c]);
+                    u64 tie = op & ARG_OP_LAST ? 0ull : ~0ull;               // the tie's identity: where a rows word starts
+                    asm volatile("" : "+v"(tie));
+                    if (op & ARG_OP_ROW) {                                   // the rowIDs themselves: one sweep, all LDS, no column, no guard
+                        __syncthreads();                                     // the accumulators have been emitted
+                        for (u32 i = tid; i < SLOTS; i += THREADS) acc[i] = tie;
+                        if (tid == 0) *ones = tie;
+                        __syncthreads();
+                        auto sweep = [&](auto kind) {
+                            Both t = Rv.buf(0u, np < (u32)THREADS ? np : (u32)THREADS).both(0u, (u32)tid), t_next = t;
+                            for (u32 tb = 0; tb < np; tb += THREADS) {
+                                const u32 left = np - tb;
+                                if (left > (u32)THREADS)
+                                    t_next = Rv.buf(tb + (u32)THREADS, left - THREADS < (u32)THREADS ? left - THREADS : (u32)THREADS).both(0u, (u32)tid);
+                                if ((u32)tid < left && in_class(t.payload)) agg_on(t.payload, (u64)t.key, kind);
+                                t = t_next;
+                            }
+                        };
+                        if (op & ARG_OP_LAST) sweep(AggMax{});
+                        else sweep(AggMin{});
+                        __syncthreads();
+                        u64 g = g0;
+#pragma unroll 1
+                        for (u32 j = 0; j < SPT; j++)
+                            if (occ >> j & 1u) {
+                                if (g < capacity) rows[g] = acc[(u32)tid * SPT + j];
+                                g++;
+                            }
+                        if (tid == 0 && ho) {
+                            const u64 g1 = *base_s + filled;
+                            if (g1 < capacity) rows[g1] = *ones;
+                        }
+                        continue;
+                    }
+                    const u64 *colv = reinterpret_cast<const u64 *>(colp[c]);                  // (no __restrict__: the row sweep reads
+                    u64 *vals = reinterpret_cast<u64 *>(colp[AGG_MAX_COLS + c]);               // back what the owners store through vals)
+                    u64 init = (op & AGG_OP_KIND) == AGG_OP_MIN ? ~0ull : 0ull;   // GB_OPS's value sweep: identity start word, skip, bias
+                    u64 bias = op & AGG_OP_SIGNED ? 1ull << 63 : 0ull;
+                    asm volatile("" : "+v"(init), "+v"(bias));
+                    __syncthreads();                                         // the accumulators have been emitted
+                    for (u32 i = tid; i < SLOTS; i += THREADS) acc[i] = init;
+                    if (tid == 0) *ones = init;
+                    __syncthreads();
+                    auto sweep = [&](auto kind) {
+                        Both t = Rv.buf(0u, np < (u32)THREADS ? np : (u32)THREADS).both(0u, (u32)tid), t_next = t;
+                        for (u32 tb = 0; tb < np; tb += THREADS) {
+                            const u32 left = np - tb;
+                            if (left > (u32)THREADS)
+                                t_next = Rv.buf(tb + (u32)THREADS, left - THREADS < (u32)THREADS ? left - THREADS : (u32)THREADS).both(0u, (u32)tid);
+                            if ((u32)tid < left) {
+                                if ((u64)t.key >= col_rows) wild = true;
+                                else if (in_class(t.payload)) {
+                                    const u64 v = colv[(u64)t.key] ^ bias;
+                                    if (v != init) agg_on(t.payload, v, kind);
+                                }
+                            }
+                            t = t_next;
+                        }
+                    };
+                    if ((op & AGG_OP_KIND) == AGG_OP_MIN) sweep(AggMin{});
+                    else sweep(AggMax{});
+                    __syncthreads();
+                    {                                                        // the extremes out, the rows words seeded, the slot words: the groups
+                        u64 g = g0;
+#pragma unroll 1
+                        for (u32 j = 0; j < SPT; j++)
+                            if (occ >> j & 1u) {
+                                if (g < capacity) { vals[g] = acc[(u32)tid * SPT + j] ^ bias; rows[g] = tie; }
+                                acc[(u32)tid * SPT + j] = g++;
+                            }
+                        if (tid == 0 && ho) {
+                            const u64 g1 = *base_s + filled;
+                            if (g1 < capacity) { vals[g1] = *ones ^ bias; rows[g1] = tie; }
+                            *ones = g1;
+                        }
+                    }
+                    __syncthreads();                                         // (and the stores above are visible to this workgroup)
+                    auto row_sweep = [&](auto kind) {                        // no v != init skip here: every group has a row
+                        Both t = Rv.buf(0u, np < (u32)THREADS ? np : (u32)THREADS).both(0u, (u32)tid), t_next = t;
+                        for (u32 tb = 0; tb < np; tb += THREADS) {
+                            const u32 left = np - tb;
+                            if (left > (u32)THREADS)
+                                t_next = Rv.buf(tb + (u32)THREADS, left - THREADS < (u32)THREADS ? left - THREADS : (u32)THREADS).both(0u, (u32)tid);
+                            if ((u32)tid < left && (u64)t.key < col_rows && in_class(t.payload)) {
+                                const u64 g = word_of(t.payload);            // (all ones -- not there -- is past every capacity)
+                                if (g < capacity && colv[(u64)t.key] == vals[g]) {
+                                    if constexpr (decltype(kind)::value == AGG_OP_MIN) atomicMin((unsigned long long *)&rows[g], (unsigned long long)t.key);
+                                    else atomicMax((unsigned long long *)&rows[g], (unsigned long long)t.key);
+                                }
+                            }
+                            t = t_next;
+                        }
+                    };
+                    if (op & ARG_OP_LAST) row_sweep(AggMax{});
+                    else row_sweep(AggMin{});
+                    continue;
+                }
                 if constexpr (KIND == GB_OPS) {                               // the column's op word decides start, skip, atomic and bias
                     const u32 op = (u32)__builtin_amdgcn_readfirstlane((int)((u32)colp[2 * AGG_MAX_COLS] >> (AGG_OP_BITS * c)));
                     u64 init = (op & AGG_OP_KIND) == AGG_OP_MIN ? ~0ull : 0ull;   // the op's identity: where a word starts, what a sweep may skip
@@ -4628,6 +4754,8 @@ static void allow_big_lds()
     SET_LDS((k_group_bkt<false, GB_SUMS | GB_IDS>), group_lds_bytes());
     SET_LDS((k_group_bkt<true, GB_OPS | GB_IDS>), group_lds_bytes());
     SET_LDS((k_group_bkt<false, GB_OPS | GB_IDS>), group_lds_bytes());
+    SET_LDS((k_group_bkt<true, GB_ARG>), group_arg_lds_bytes());
+    SET_LDS((k_group_bkt<false, GB_ARG>), group_arg_lds_bytes());
     SET_LDS((k_gjoin_bkt<true, GB_COUNT | GB_IDS>), gjoin_lds_bytes());
     SET_LDS((k_gjoin_bkt<false, GB_COUNT | GB_IDS>), gjoin_lds_bytes());
     SET_LDS((k_gjoin_bkt<true, GB_SUMS | GB_IDS>), gjoin_lds_bytes());
@@ -5340,10 +5468,26 @@ void launch_lookup_join(hipStream_t st, const void *d_R, const void *d_S, const 
 
 void launch_group(hipStream_t st, const void *d_R, const JoinTask *d_tasks, const u32 *d_ntasks, u32 grid, int radix_bits, bool mixed,
                   const u64 *const *d_cols, u32 ncols, u64 col_rows, u64 *d_out_keys, u64 *d_out_counts, u64 *const *d_out_sums,
-                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip, u32 ops, bool ids)
+                  u64 capacity, u64 *d_ngroups, u32 *d_bad, u64 *d_max_rounds, const u32 *d_RK, const u32 *d_skip, u32 ops, bool ids,
+                  u64 *const *d_out_rows)
 {
     if (grid == 0) return;
     allow_big_lds();
+    if (d_out_rows != nullptr && ncols != 0) {                               // the rows of the extremes: its own instantiation and LDS size
+        AggCols cols;
+        GroupArgOuts outs;
+        for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
+            cols.c[j] = j < ncols ? d_cols[j] : nullptr; outs.c[j] = j < ncols ? d_out_sums[j] : nullptr; outs.r[j] = j < ncols ? d_out_rows[j] : nullptr;
+        }
+        auto go = [&](auto kernel, auto Rv) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(AGG_THREADS), group_arg_lds_bytes(), st, Rv, d_tasks, d_ntasks, radix_bits,
+                               mixed ? 1 : 0, cols, ncols, col_rows, d_out_keys, d_out_counts, outs, capacity, d_ngroups, d_bad, d_max_rounds,
+                               d_skip, ops);
+        };
+        if (d_RK != nullptr) go(k_group_bkt<true, GB_ARG>, RelView<true>{(const u64 *)d_R, d_RK});
+        else go(k_group_bkt<false, GB_ARG>, RelView<false>{(const Tup *)d_R});
+        return;
+    }
     AggCols cols;
     GroupSums sums;
     for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) { cols.c[j] = j < ncols ? d_cols[j] : nullptr; sums.c[j] = j < ncols ? d_out_sums[j] : nullptr; }

@@ -227,7 +227,7 @@ void launch_lookup_join(hipStream_t st, const void *, const void *, const JoinTa
     fake_enqueue(st, [=] { if (out_rows) d_out[0] = 0; *d_matched += out_rows ? 1 : 0; });
 }
 void launch_group(hipStream_t st, const void *, const JoinTask *, const u32 *, u32, int, bool, const u64 *const *, u32, u64, u64 *, u64 *,
-                  u64 *const *, u64, u64 *d_ngroups, u32 *, u64 *, const u32 *, const u32 *, u32, bool)
+                  u64 *const *, u64, u64 *d_ngroups, u32 *, u64 *, const u32 *, const u32 *, u32, bool, u64 *const *)
 {
     fake_enqueue(st, [=] { *d_ngroups += FAKE_PAIRS; });
 }

@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from cf_cases import build_side, probe_side                       # (moved: tests/cf_cases.py, where d2 can be set as well)
 from oracle.pyoracle import TUPLE
 from radixhashjoin_amd import Engine, Opts, mix64, unmix64
 
@@ -45,69 +46,11 @@ def unit_len(n):
     return max(TILE, -(-per // TILE) * TILE)
 
 
-def digit_plan(rng, n):
-    """-> the pass-1 digit (low 8 bits of h) of every input position: inside unit u the digits (u + j) % 256, j < len(SPECIAL),
-    get exactly SPECIAL[j] tuples, the other digits share the rest evenly; shuffled inside the unit"""
-    L = unit_len(n)
-    special = SPECIAL[L]
-    d1 = np.empty(n, dtype=np.int64)
-    for u in range(-(-n // L)):
-        lens = np.zeros(256, dtype=np.int64)
-        rest = [d for d in range(256) if (d - u) % 256 >= len(special)]
-        for j, s in enumerate(special):
-            lens[(u + j) % 256] = s
-        left = L - sum(special)
-        lens[rest] = left // len(rest)
-        lens[rest[: left % len(rest)]] += 1
-        assert lens.sum() == L and lens.max() <= CAP[L]
-        unit = np.repeat(np.arange(256), lens)
-        rng.shuffle(unit)
-        d1[u * L: (u + 1) * L] = unit[: min(L, n - u * L)]    # (the last unit may be cut short)
-    return d1
-
-
 def piece_lengths(t):
     """run lengths per (pass-1 unit, digit), from the relation as the library sees it"""
     n, L = len(t), unit_len(len(t))
     d1 = (mix64(t["payload"]) & U64(255)).astype(np.int64)
     return np.bincount((np.arange(n) // L) * 256 + d1, minlength=-(-n // L) * 256)
-
-
-def build_side(rng, n, kind):
-    """R: n distinct mixed values whose low 8 bits follow digit_plan"""
-    i = np.arange(n, dtype=U64)
-    d1 = digit_plan(rng, n).astype(U64)
-    d2 = rng.integers(0, 256, n).astype(U64)
-    if kind == "lowdup":      # low word: 4 values of its upper half -> at most 2^18 low words in all; high word: distinct
-        lo = (U64(0x5A5A) + (i & U64(3))) << U64(16) | d2 << U64(8) | d1
-        hi = ((i + U64(1)) * U64(0x9E3779B1)) & U64(0xFFFFFFFF)
-    else:                     # high word: one per 65,536 rows; low word: its upper half distinct inside a high word
-        assert n <= 1 << 24
-        lo = (i & U64(0xFFFF)) << U64(16) | d2 << U64(8) | d1
-        hi = U64(0xC0FFEE00) | ((i >> U64(16)) & U64(0xFF))
-    h = hi << U64(32) | lo
-    assert len(np.unique(h)) == n
-    return h
-
-
-def probe_side(rng, hR, n):
-    """S: position p takes a build value of the digit digit_plan gives p (so S's piece lengths are set too); a fifth of the rows
-    then change the high word, another fifth the upper half of the low word: same partition, no match (unless the changed
-    value happens to be another build value, which the oracle knows as well)"""
-    d1 = digit_plan(rng, n)
-    dR = (hR & U64(255)).astype(np.int64)
-    order = np.argsort(dR, kind="stable")
-    start = np.searchsorted(dR[order], np.arange(257))
-    cnt = np.diff(start)
-    assert cnt[d1].min() > 0
-    pick = order[start[d1] + (rng.integers(0, 1 << 62, n) % cnt[d1])]
-    h = hR[pick].copy()
-    r = rng.random(n)
-    flip_hi = r < 0.2
-    flip_lo = (r >= 0.2) & (r < 0.4)
-    h[flip_hi] ^= rng.integers(1, 1 << 32, int(flip_hi.sum())).astype(U64) << U64(32)
-    h[flip_lo] ^= rng.integers(1, 1 << 16, int(flip_lo.sum())).astype(U64) << U64(16)
-    return h
 
 
 def rel(rng, h):

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import cf_cases
 from oracle.pyoracle import TUPLE
 from radixhashjoin_amd import Engine, Opts, RhjError, SUM_MAX_COLS, unmix64
 from radixhashjoin_amd.binding import RHJ_E_INVALID, plan as resolve_plan
@@ -210,12 +211,14 @@ def test_partitions_beyond_one_table(eng):
 # ---- the repeats inside a call -----------------------------------------------------------------------------------------------
 def test_count_free_overflow_repeats_S(inputs):
     R, S, mult, W = inputs("quarter", 3_000_000)
+    # R fits its count-free regions (its largest pass-1 piece is 36 or 37 of 64 slots), S does not: R stands, "last.countfree_R" is 1
+    assert int(cf_cases.piece_lengths(R).max()) <= cf_cases.cap(cf_cases.unit_len(len(R)), 8) < int(cf_cases.piece_lengths(S).max())
     e = Engine(0)
     try:
         e.set_option("partition.narrow", 2)
         e.set_option("partition.countfree", 1)
         run_cols(e, R, S, mult, W, 4, ids=False, opts=PLAN)
-        assert e.info("last.narrow") == 2 and e.info("last.countfree_S") == 2 and e.info("last.countfree_R") in (1, 0)
+        assert e.info("last.narrow") == 2 and e.info("last.countfree_S") == 2 and e.info("last.countfree_R") == 1
         assert e.info("last.join_kernel") == JK_AGG
     finally:
         e.close()

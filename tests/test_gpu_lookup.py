@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import cf_cases
 import keyed_table_cases as K
 from oracle.pyoracle import TUPLE
 from radixhashjoin_amd import LOOKUP_FIRST, LOOKUP_LAST, LOOKUP_MAX_COLS, NO_ROW, SEMI, Engine, Opts, RhjError, unmix64
@@ -344,12 +345,14 @@ def test_a_row_at_out_rows_is_refused_and_the_context_goes_on(eng, inputs, n, wh
 @which_ids
 def test_count_free_overflow_repeats_S_and_starts_from_nothing(inputs, which):
     R, S = inputs("quarter", 3_000_000)
+    # R fits its count-free regions (its largest pass-1 piece is 36 or 37 of 64 slots), S does not: R stands, "last.countfree_R" is 1
+    assert int(cf_cases.piece_lengths(R).max()) <= cf_cases.cap(cf_cases.unit_len(len(R)), 8) < int(cf_cases.piece_lengths(S).max())
     e = Engine(0)
     try:
         e.set_option("partition.narrow", 2)
         e.set_option("partition.countfree", 1)
         run_cols(e, R, S, which, ids_R=False, ids_S=False, opts=PLAN)
-        assert e.info("last.narrow") == 2 and e.info("last.countfree_S") == 2 and e.info("last.countfree_R") in (1, 0)
+        assert e.info("last.narrow") == 2 and e.info("last.countfree_S") == 2 and e.info("last.countfree_R") == 1
         assert e.info("last.join_kernel") == JK_LOOKUP
     finally:
         e.close()

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+import cf_cases
 from oracle.pyoracle import TUPLE
 from radixhashjoin_amd import ANTI, NO_ROW, OUTER_FULL, OUTER_LEFT, OUTER_RIGHT, PAIR, Engine, Opts, RhjError
 from radixhashjoin_amd.binding import RHJ_E_INVALID, RHJ_E_OVERFLOW, mix64, plan as resolve_plan, unmix64
@@ -389,12 +390,14 @@ def test_invalid_arguments(eng, inputs):
 # ---- the repeats inside a call -----------------------------------------------------------------------------------------------
 def test_count_free_overflow_repeats_S(inputs):
     R, S, exp = inputs("quarter", 3_000_000, ids=False)
+    # R fits its count-free regions (its largest pass-1 piece is 36 or 37 of 64 slots), S does not: R stands, "last.countfree_R" is 1
+    assert int(cf_cases.piece_lengths(R).max()) <= cf_cases.cap(cf_cases.unit_len(len(R)), 8) < int(cf_cases.piece_lengths(S).max())
     e = Engine(0)
     try:
         e.set_option("partition.narrow", 2)
 
         def after(how):
-            assert e.info("last.narrow") == 2 and e.info("last.countfree_S") == 2 and e.info("last.countfree_R") in (1, 0)
+            assert e.info("last.narrow") == 2 and e.info("last.countfree_S") == 2 and e.info("last.countfree_R") == 1
             assert e.info("last.outer_sweeps") == SWEEPS[how]
             e.set_option("partition.countfree", 1)                         # re-arm the back-off for the next mode
         e.set_option("partition.countfree", 1)

@@ -131,7 +131,10 @@ int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
  * "join.sniff": -1 automatic (= 1 unless RHJ_SNIFF=0), 1: a partitioned join samples the join values of both relations for
  * duplicates while it counts them, and where the two sides of a partition are within 1/16 of each other in size the side with
  * fewer duplicates becomes the hash table (the reference builds on the smaller bucket, S on a tie: JobScheduler.cpp:187; a table
- * without duplicates answers every probe tuple with one match); 0: the first relation wins such a tie.  Same pairs either way. */
+ * without duplicates answers every probe tuple with one match); 0: the first relation wins such a tie.  Same pairs either way;
+ * "sort.max_units": -1 automatic (2048), 1 .. 2048: the most units -- workgroups per launch -- the sort entries cut their input into;
+ * a unit is a whole number of tiles of "sort.tile_rows" rows, so 1 makes one workgroup walk every tile (tests: several tiles per unit
+ * at a few thousand rows).  Same order either way. */
 int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
 /* what the last join did: "last.narrow" (0 / 1 / 2, see above), "last.countfree_R" / "last.countfree_S" (pass 1 of that side:
  * 0 exact cursors, 1 count-free, 2 count-free tried and repeated with exact cursors), "last.countfree2_R" / "last.countfree2_S" (pass 2 of
@@ -156,6 +159,10 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * that had tuples to report on; 0 after every other call.  After an outer join "last.semi_tables" is the largest number of tables any
  * task of those sweeps built -- 0 when no sweep ran a task --, and "last.join_kernel" the pair kernel as rhj_join_cols_dev reports it,
  * 12 when an empty side left only a sweep to run, -1 when nothing ran),
+ * "last.sort_bits" / "last.sort_passes" (the key width the last rhj_sort_cols_dev / rhj_sort_dev found and the scatter passes it ran; 0
+ * after every other call; "last.join_kernel" is -1 after a sort), "last.sort_units" (the units -- workgroups per launch -- those passes
+ * were cut into, each a whole number of tiles; 0 when no pass ran), "sort.tile_rows" (a constant of the build: the rows one workgroup
+ * of the sort's scatter ranks at once),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -751,6 +758,50 @@ int rhj_keys_unpack_dev(rhj_ctx *ctx, const rhj_keyplan *plan, const uint64_t *d
 int rhj_keys_plan_info(const rhj_keyplan *plan, rhj_keys_layout_t *out);
 /* frees the plan and its dictionaries; a NULL plan is fine */
 int rhj_keys_plan_free(rhj_ctx *ctx, rhj_keyplan *plan);
+
+/* ---- sort: a stable radix sort of one 64-bit key column with rowIDs (ORDER BY, argsort; the ordered half of what the operators above
+ * return "in no particular order").
+ * Tuple i is (d_keys[i], d_rows[i]); with d_rows == NULL the rowID is the position i.  Output position p holds the tuple of rank p:
+ * d_out_keys[p] its key word, the original word bit for bit, d_out_rows[p] its rowID.  Ascending order is by key word in the chosen
+ * view: unsigned 64-bit by default, two's-complement int64 under RHJ_SORT_I64 (an all-ones word is then -1, not the maximum).
+ * RHJ_SORT_DESC reverses the key order only.  Ties keep their input order in both directions: tuples with equal keys come out in the
+ * order they went in, ascending or descending -- torch.sort(stable=True, descending=..), np.argsort(kind="stable").  The result is
+ * bit-identical from run to run.
+ * Rows: with implicit rowIDs d_out_rows is the argsort permutation.  Explicit d_rows are opaque 64-bit payloads -- duplicates and
+ * values >= 2^32 are fine: rows are carried, never compared and never used as indices.  That is what makes ORDER BY a, b work, as a
+ * chain of stable sorts, last key first:
+ *     rhj_sort_cols_dev(ctx, b, NULL, n, fb, NULL, perm1);              -- perm1 = argsort of b
+ *     rhj_gather_u64(ctx, a, perm1, n, a1);                             -- a in that order
+ *     rhj_sort_cols_dev(ctx, a1, perm1, n, fa, a_sorted, perm);         -- ties of a keep the order of b; perm[p] = the row of rank p
+ * Outputs: either output may be NULL -- a keys-only sort (no d_out_rows; d_rows is then not read) or an argsort (no d_out_keys).  Both
+ * outputs NULL with n > 0 is RHJ_E_INVALID.  Inputs are neither modified nor retained; outputs must not overlap inputs.  Pointers need
+ * 8-byte alignment only (16 bytes everywhere lets every launch use 16-byte accesses; the kernels of this build use 8- and 4-byte ones).
+ * n == 0: RHJ_OK, no launch.  RHJ_E_INVALID, before any launch: unknown flag bits; NULL d_keys with n > 0; both outputs NULL with
+ * n > 0.  The call synchronises.  It honours rhj_set_stream and rhj_set_profiling (spans RHJ_K_HIST / RHJ_K_SCAN / RHJ_K_SCATTER per
+ * pass, RHJ_K_AUX for the probes and the copy).
+ * How: one probe launch finds the minimum and maximum of the column in the view; the width w is 0 when max == min, else 64 - clz(max -
+ * min), and the keys are sorted as t(v) - t(min) (descending: t(max) - t(v)), t the order transform -- an int64 column of -3 .. 3 is 3
+ * bits wide, a column of dense ids bits(groups - 1).  Digits are 8 bits from bit 0 of that word; a second probe launch (only when w > 8)
+ * finds the digits in which every key agrees, and their passes are skipped.  Each remaining pass is three launches ordered on the
+ * stream -- histogram per unit and digit, scan, stable scatter --; no workgroup waits on another inside a kernel.  The first pass reads
+ * the caller's column and applies the transform, the last pass writes the caller's outputs with the key words restored; w == 0 runs no
+ * pass: the outputs are copies (one launch).
+ * rhj_get_info: "last.sort_bits" is w, "last.sort_passes" the scatter passes that ran, "last.sort_units" the units they were cut into; all are 0 after every other call.  After a
+ * sort "last.join_kernel" is -1.  "sort.tile_rows": the rows one workgroup ranks at once, a constant of the build.
+ * Costs: passes <= ceil(w / 8), however many rows repeat a key -- the sort has no skew case.  Bytes per pass and tuple, histogram
+ * read + scatter read + scatter write:  keys only (no d_out_rows) 8 + 8 + 8 = 24;  narrow (implicit rowIDs, n <= 2^32: positions are
+ * carried as 4 bytes between passes, not read in the first pass, widened to 8 in the last) 8 + 12 + 12 = 32;  wide (explicit d_rows,
+ * or n > 2^32) 8 + 16 + 16 = 40.  An argsort's last pass stores no key: 8 bytes less.  Plus 8 bytes per tuple for each probe.
+ * Memory: the ping-pong buffers live in the context's workspace, grown on demand and kept until rhj_release_workspace: nothing for
+ * one pass, one set of n x (8 + 0 / 4 / 8) bytes for two, and from three passes on a second set only for the parts that are not a
+ * plain output array of the call (a NULL output, the 16-byte form) -- the output arrays serve as the other side; plus 3 KiB of tables
+ * per unit (at most 2048 units). */
+#define RHJ_SORT_I64   1u   /* flags bit 0: order the words as two's-complement int64 (default: unsigned 64-bit) */
+#define RHJ_SORT_DESC  2u   /* flags bit 1: descending */
+int rhj_sort_cols_dev(rhj_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_rows, uint64_t n, uint32_t flags,
+                      uint64_t *d_out_keys, uint64_t *d_out_rows);
+/* ... on 16-byte tuples in and out (value = .payload, rowID = .key; the wide form, words at a stride of two) */
+int rhj_sort_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t n, uint32_t flags, rhj_tuple *d_out);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:

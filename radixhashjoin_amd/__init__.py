@@ -30,6 +30,9 @@ with GROUP BY on the key: per join value COUNT(*) and the SUMs of both sides' we
 Composite keys: every one of these takes a list of up to four key tensors per side wherever it takes a key tensor (``ON r.a = s.a
 AND r.b = s.b``, ``GROUP BY a, b``); ``packed_R, packed_S, plan = Engine(0).pack_keys([a, b], [c, d])`` is the step they share -- one
 exact 64-bit key per row (``rhj_keys_pack_dev``), and ``plan.unpack(packed)`` gives the columns back (``rhj_keys_unpack_dev``).
+Order: ``sorted_keys, perm, gathered = Engine(0).sort_columns(keys, values, descending=False)`` is ORDER BY on a key tensor -- a stable
+radix sort, ``perm`` the stable argsort, ``values[k][perm]`` beside it; a list of key tensors is ``ORDER BY k0, k1, ..``;
+``Engine(0).argsort_columns(keys)`` returns ``perm`` alone (``rhj_sort_cols_dev``).
 """
 from .binding import (  # noqa: F401
     AGG_MAX_I64,
@@ -70,6 +73,8 @@ from .binding import (  # noqa: F401
     Opts,
     RhjError,
     SEMI,
+    SORT_DESC,
+    SORT_I64,
     SUM_MAX_COLS,
     Timings,
     lib_path,
@@ -79,5 +84,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS", "SORT_I64", "SORT_DESC"]
 __version__ = "0.1.0"

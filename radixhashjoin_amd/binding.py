@@ -138,6 +138,8 @@ SYMBOLS = {
     "rhj_keys_unpack_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp)]),
     "rhj_keys_plan_info": (C.c_int, [_vp, _P(KeysLayout)]),
     "rhj_keys_plan_free": (C.c_int, [_vp, _vp]),
+    "rhj_sort_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _vp, _vp]),
+    "rhj_sort_dev": (C.c_int, [_vp, _vp, _u64, C.c_uint32, _vp]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -293,6 +295,7 @@ OUTER_LEFT, OUTER_RIGHT, OUTER_FULL = 1, 2, 3           # include/rhj.h RHJ_OUTE
 NO_ROW = 0xFFFFFFFFFFFFFFFF                              # include/rhj.h RHJ_NO_ROW: the missing side of an unmatched row (-1 as int64)
 LOOKUP_FIRST, LOOKUP_LAST = 0, 1                         # include/rhj.h RHJ_LOOKUP_*: the smallest / largest rowID of S among the partners
 LOOKUP_MAX_COLS = 4                                      # include/rhj.h RHJ_LOOKUP_MAX_COLS: columns of a gather_cols_fill call
+SORT_I64, SORT_DESC = 1, 2                               # include/rhj.h RHJ_SORT_*: flags of the sort entries
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
 
@@ -453,8 +456,8 @@ class Engine:
         self._chk(self.lib.rhj_set_option(self.ctx, name.encode(), int(value)))
 
     def info(self, name):
-        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.outer_sweeps", "last.group_rounds";
-        include/rhj.h)"""
+        """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.outer_sweeps", "last.group_rounds",
+        "last.sort_bits", "last.sort_passes", "last.sort_units"; include/rhj.h) and constants of the build ("sort.tile_rows")"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
         return v.value
@@ -1251,6 +1254,107 @@ class Engine:
             raise ValueError(f"keep: 'first' or 'last', not {keep!r}")
         rows = self.group_by_columns_arg(keys, [None], ["row"], keep)[3][0]
         return torch.sort(rows).values
+
+    def sort_cols_dev(self, d_keys, d_rows, n, flags=0, d_out_keys=None, d_out_rows=None):
+        """rhj_sort_cols_dev: the stable sort of the tuples (d_keys[i], d_rows[i]) -- d_rows None: rowID = i -- by key word, unsigned
+        or (SORT_I64) as int64, ascending or (SORT_DESC) descending, ties in input order either way; d_out_keys / d_out_rows:
+        uint64[n] in HBM, either may be None (a keys-only sort, an argsort)"""
+        self._chk(self.lib.rhj_sort_cols_dev(self.ctx, _addr(d_keys), _addr(d_rows), n, flags, _addr(d_out_keys), _addr(d_out_rows)))
+
+    def sort_dev(self, d_R, n, flags=0, d_out=None):
+        """rhj_sort_dev: ... of n 16-byte tuples (value = .payload, rowID = .key) into d_out"""
+        self._chk(self.lib.rhj_sort_dev(self.ctx, _addr(d_R), n, flags, _addr(d_out)))
+
+    @staticmethod
+    def _sort_args(keys, descending, unsigned, values=()):
+        """(key tensors, one descending flag per tensor, value tensors) of sort_columns / argsort_columns; ValueError before any device use"""
+        many = isinstance(keys, (list, tuple))
+        cols = list(keys) if many else [keys]
+        if not cols:
+            raise ValueError("keys: an empty sequence of key tensors")
+        if len(cols) > KEYS_MAX_COLS:
+            raise ValueError(f"keys: at most {KEYS_MAX_COLS} key tensors, not {len(cols)}")
+        if isinstance(descending, bool):
+            desc = [descending] * len(cols)
+        elif many and isinstance(descending, (list, tuple)) and all(isinstance(d, bool) for d in descending):
+            if len(descending) != len(cols):
+                raise ValueError(f"descending: one bool, or one per key tensor ({len(cols)}), not {len(descending)}")
+            desc = list(descending)
+        else:
+            raise ValueError(f"descending: a bool{', or one bool per key tensor,' if many else ''} is needed, not {descending!r}")
+        if not isinstance(unsigned, bool):
+            raise ValueError(f"unsigned: a bool is needed, not {unsigned!r}")
+        values = tuple(values)
+        if len(values) > LOOKUP_MAX_COLS:
+            raise ValueError(f"at most {LOOKUP_MAX_COLS} value tensors per call, not {len(values)}")
+        return cols, desc, values
+
+    def _sort_tensors(self, cols, values, many):
+        """the tensors of a sort under the names the caller gave them: ValueError for one that is not a contiguous 1-D 64-bit integer
+        tensor on the engine's device, or not as long as the first key tensor (_on_torch_stream would say keys_R / weights[i])"""
+        import torch
+        ints = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)
+        named = [(f"keys[{i}]" if many else "keys", c) for i, c in enumerate(cols)] + [(f"values[{i}]", v) for i, v in enumerate(values)]
+        for name, k in named:
+            if not isinstance(k, torch.Tensor) or k.dtype not in ints or k.dim() != 1:
+                raise ValueError(f"{name}: a 1-D torch tensor of 64-bit integers is needed")
+            if k.device.type != "cuda" or (k.device.index or 0) != self.device:
+                raise ValueError(f"{name}: the tensor must live on the engine's device (cuda:{self.device}), not {k.device}")
+            if not k.is_contiguous():
+                raise ValueError(f"{name}: the tensor must be contiguous")
+            if k.numel() != cols[0].numel():
+                raise ValueError(f"{name}: {k.numel()} elements, {named[0][0]} has {cols[0].numel()}")
+
+    def _sort_chain(self, cols, desc, unsigned, values, want_keys):
+        """ORDER BY cols[0], cols[1], ..: a chain of stable sorts, last key first, each later one over the key gathered through the
+        permutation so far, with that permutation as its rows.  (sorted key tensors or None, perm, gathered values)"""
+        import torch
+        with self._on_torch_stream(cols[0], cols[0], tuple(cols[1:]) + values) as dev:       # (the tensors: checked by _sort_tensors)
+            n = cols[0].numel()
+            view = 0 if unsigned else SORT_I64
+            perm, first = None, None
+            for j in range(len(cols) - 1, -1, -1):
+                src = cols[j]
+                if perm is not None and n:
+                    src = torch.empty(n, dtype=cols[j].dtype, device=dev)
+                    self.gather_u64(cols[j], perm, n, src)
+                nxt = torch.empty(n, dtype=torch.int64, device=dev)
+                if j == 0 and want_keys:
+                    first = torch.empty(n, dtype=cols[0].dtype, device=dev)
+                if n:
+                    self.sort_cols_dev(src, perm, n, view | (SORT_DESC if desc[j] else 0), first if j == 0 else None, nxt)
+                perm = nxt
+            out_keys = None
+            if want_keys:
+                out_keys = [first] + [torch.empty(n, dtype=c.dtype, device=dev) for c in cols[1:]]
+                if n and len(cols) > 1:
+                    self.gather_cols_fill(cols[1:], n, perm, n, [0] * (len(cols) - 1), out_keys[1:])
+            gathered = [torch.empty(n, dtype=v.dtype, device=dev) for v in values]
+            if n and values:
+                self.gather_cols_fill(values, n, perm, n, [0] * len(values), gathered)
+        return out_keys, perm, gathered
+
+    def sort_columns(self, keys, values=(), descending=False, unsigned=False):
+        """(sorted_keys, perm, gathered_values): ORDER BY on a key tensor -- sorted_keys = keys[perm] in ascending (descending=True:
+        descending) order, perm the STABLE argsort as an int64 tensor (rows with equal keys keep their input order in both
+        directions, as torch.sort(stable=True, descending=..)), gathered_values one tensor per tensor of values: values[k][perm].
+        keys: a contiguous 1-D 64-bit integer tensor on the engine's device, ordered as int64 (unsigned=True: the words as uint64);
+        values: up to LOOKUP_MAX_COLS tensors of the same kind and length (rhj_gather_cols_fill).  A stable LSD radix sort whose number of passes
+        follows the width of the key's value range, not 64 bits (rhj_sort_cols_dev).
+        A list of 1 to KEYS_MAX_COLS key tensors is ORDER BY k0, k1, ..: descending is then one bool or one per tensor, sorted_keys a list
+        of as many tensors; it runs as a chain of stable sorts, last key first.  A wrong descending length, more than KEYS_MAX_COLS
+        key tensors, too many values or a non-bool flag: ValueError before any device use.  Streams and completion as join_columns."""
+        cols, desc, values = self._sort_args(keys, descending, unsigned, values)
+        self._sort_tensors(cols, values, isinstance(keys, (list, tuple)))
+        out_keys, perm, gathered = self._sort_chain(cols, desc, unsigned, values, True)
+        return (out_keys if isinstance(keys, (list, tuple)) else out_keys[0]), perm, gathered
+
+    def argsort_columns(self, keys, descending=False, unsigned=False):
+        """perm: sort_columns' permutation alone (torch.argsort(stable=True)); no key output is passed, so the last pass stores 8
+        bytes per row.  Arguments and errors as sort_columns."""
+        cols, desc, _ = self._sort_args(keys, descending, unsigned)
+        self._sort_tensors(cols, (), isinstance(keys, (list, tuple)))
+        return self._sort_chain(cols, desc, unsigned, (), False)[1]
 
     def factorize_columns(self, keys):
         """(codes, uniques): pandas.factorize without the ordering promise -- uniques the distinct values of keys in no particular

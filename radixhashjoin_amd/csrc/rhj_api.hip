@@ -232,6 +232,10 @@ struct rhj_ctx {
     u64 last_max_part[2] = {0, 0};     // largest partition of R / S the last task list saw (0: direct join)
     int last_semi_tables = 0;          // "last.semi_tables": LDS tables the busiest task of the last semi / anti join built (0: another call)
     int last_outer_sweeps = 0;         // "last.outer_sweeps": anti sweeps the last outer join ran behind its pair join (0: another call)
+    int last_sort_bits = 0, last_sort_passes = 0;   // "last.sort_bits" / "last.sort_passes": the width the last sort's probe found, the scatter passes it ran (0: another call)
+    int last_sort_units = 0;           // "last.sort_units": the units -- workgroups per launch -- of those passes (0: no pass ran)
+    DevBuf sort_ws;                    // the sort's tables and ping-pong buffers (rhj_sort.hip)
+    int opt_sort_units = -1;           // "sort.max_units": -1 automatic, else the most units a sort cuts its input into
     int outer_how = 0;                 // an outer join's RHJ_OUTER_* bits, for the length of the call
     u64 outer_sections[3] = {0, 0, 0}; // ... and its {matched, R-only, S-only} rows, as outer_phase leaves them
     bool counters_clean = false;       // the 64-byte join counters are zero (cleared by the partition phase's first launch)
@@ -497,6 +501,7 @@ void prof_reset(rhj_ctx *ctx)
     ctx->last_semi_tables = 0;                      // "last.semi_tables": ... and semi_phase this one
     ctx->last_group_rounds = 0;                     // "last.group_rounds": ... and group_phase this one
     ctx->last_outer_sweeps = 0;                     // "last.outer_sweeps": ... and outer_phase this one
+    ctx->last_sort_bits = ctx->last_sort_passes = ctx->last_sort_units = 0;   // "last.sort_*": ... and the sort entries these
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -2219,6 +2224,27 @@ void *rhj_internal_counters(rhj_ctx *ctx)
     ctx->counters_clean = false;                     // the caller is about to use them as scratch
     return ensure(ctx, ctx->counters, 64) == RHJ_OK ? ctx->counters.p : nullptr;
 }
+// ... and for rhj_sort.hip
+void rhj_internal_sort_begin(rhj_ctx *ctx)
+{
+    prof_reset(ctx);
+    ctx->last_join_kind = -1;                        // no join kernel runs
+}
+void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units)
+{
+    ctx->last_sort_bits = bits;
+    ctx->last_sort_passes = passes;
+    ctx->last_sort_units = units;
+}
+int rhj_internal_sort_workspace(rhj_ctx *ctx, size_t bytes, void **out)
+{
+    RHJCHK(ensure(ctx, ctx->sort_ws, bytes));
+    *out = ctx->sort_ws.p;
+    return RHJ_OK;
+}
+int rhj_internal_sort_max_units(rhj_ctx *ctx) { return ctx->opt_sort_units; }
+void *rhj_internal_span_open(rhj_ctx *ctx, int kind) { return new Span(ctx, kind); }
+void rhj_internal_span_close(void *span) { delete (Span *)span; }
 
 // =================================================================================================
 // C-ABI
@@ -2308,7 +2334,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->agg_out, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
                      &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cf2_end[0], &ctx->cf2_end[1], &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
-                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1]};
+                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
     ctx->small_hdr_clean = false;
@@ -2383,6 +2409,7 @@ int rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value)
     }
     if (n == "join.fused" && value >= -1 && value <= 1) { ctx->opt_fused = (int)value; return RHJ_OK; }
     if (n == "join.sniff" && value >= -1 && value <= 1) { ctx->opt_sniff = (int)value; return RHJ_OK; }
+    if (n == "sort.max_units" && (value == -1 || (value >= 1 && value <= 2048))) { ctx->opt_sort_units = (int)value; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_set_option: unknown option or value: " + n);
 }
 
@@ -2404,6 +2431,10 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.semi_tables") { *value = ctx->last_semi_tables; return RHJ_OK; }
     if (n == "last.group_rounds") { *value = ctx->last_group_rounds; return RHJ_OK; }
     if (n == "last.outer_sweeps") { *value = ctx->last_outer_sweeps; return RHJ_OK; }
+    if (n == "last.sort_bits") { *value = ctx->last_sort_bits; return RHJ_OK; }
+    if (n == "last.sort_passes") { *value = ctx->last_sort_passes; return RHJ_OK; }
+    if (n == "last.sort_units") { *value = ctx->last_sort_units; return RHJ_OK; }
+    if (n == "sort.tile_rows") { *value = SORT_TILE; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }

@@ -469,3 +469,10 @@ void launch_scatter_ranges_n2a(hipStream_t st, const void *d_in, void *d_out, u6
                                const u32 *d_skip);
 size_t scan_tmp_bytes(int bits);
 size_t part_lds_bytes(int bits);
+// ---- the sort kernels (rhj_sort.hip): one geometry -----------------------------------------------------------------
+// A stable LSD radix sort by 8-bit digits.  One workgroup of 512 threads ranks a tile of 4096 rows at once ("sort.tile_rows"): eight
+// rows per lane, the ranked tile staged in LDS (8-byte keys, 0 / 4 / 8-byte rows) beside the per-wave digit counts.
+constexpr int SORT_THREADS = 512;
+constexpr int SORT_TPT = 8;                       // rows per thread per tile
+constexpr int SORT_TILE = SORT_THREADS * SORT_TPT;
+constexpr int SORT_DIGIT_BITS = 8;

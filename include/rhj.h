@@ -134,7 +134,9 @@ int  rhj_set_profiling(rhj_ctx *ctx, int enabled);
  * without duplicates answers every probe tuple with one match); 0: the first relation wins such a tie.  Same pairs either way;
  * "sort.max_units": -1 automatic (2048), 1 .. 2048: the most units -- workgroups per launch -- the sort entries cut their input into;
  * a unit is a whole number of tiles of "sort.tile_rows" rows, so 1 makes one workgroup walk every tile (tests: several tiles per unit
- * at a few thousand rows).  Same order either way. */
+ * at a few thousand rows).  Same order either way;
+ * "topk.max_candidates": -1 automatic (max(k, "topk.auto_candidates")), 1 .. 2^31 - 1: the top-k entries go on selecting digits
+ * while more rows than this are tied with the threshold (tests: 1 runs down every digit).  Same result either way. */
 int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
 /* what the last join did: "last.narrow" (0 / 1 / 2, see above), "last.countfree_R" / "last.countfree_S" (pass 1 of that side:
  * 0 exact cursors, 1 count-free, 2 count-free tried and repeated with exact cursors), "last.countfree2_R" / "last.countfree2_S" (pass 2 of
@@ -163,6 +165,8 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * after every other call; "last.join_kernel" is -1 after a sort), "last.sort_units" (the units -- workgroups per launch -- those passes
  * were cut into, each a whole number of tiles; 0 when no pass ran), "sort.tile_rows" (a constant of the build: the rows one workgroup
  * of the sort's scatter ranks at once),
+ * "last.topk_bits" / "last.topk_passes" / "last.topk_candidates" / "last.topk_sorted_rows" (what the last rhj_topk_cols_dev /
+ * rhj_topk_dev did, see there; 0 after every other call), "topk.auto_candidates" (a constant of the build),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -802,6 +806,52 @@ int rhj_sort_cols_dev(rhj_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_ro
                       uint64_t *d_out_keys, uint64_t *d_out_rows);
 /* ... on 16-byte tuples in and out (value = .payload, rowID = .key; the wide form, words at a stride of two) */
 int rhj_sort_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t n, uint32_t flags, rhj_tuple *d_out);
+
+/* ---- top-k and k-th value: a radix select in front of the sort (ORDER BY .. LIMIT k, the k largest, a median, a quantile).
+ * With m = min(k, n) the outputs hold the first m tuples of what rhj_sort_cols_dev / rhj_sort_dev would write for the same (keys,
+ * rows, n, flags), bit for bit, in the same positions: the result is sorted and the key words are the original words.  d_rows NULL:
+ * rowID = index; explicit rows are opaque payloads, never compared and never used as indices.  flags: RHJ_SORT_I64 and RHJ_SORT_DESC
+ * (RHJ_SORT_DESC: the k largest).  Ties keep their input order in both directions, also at the cut: where the k-th key repeats, the
+ * tuples earliest in the input are the ones taken.  The result is bit-identical from run to run.
+ * Outputs: arrays of m words (m tuples); no word at or past m is written.  out_kth is a HOST pointer to two words, or NULL: it
+ * receives {key word, row word} of the tuple of rank m - 1 -- the k-th value, with k = (n + 1) / 2 a median, a quantile.  Either
+ * device output may be NULL.  Both device outputs NULL is allowed if and only if out_kth is given: a pure selection, nothing of size
+ * k is materialised.  Both device outputs NULL with out_kth NULL and n, k > 0 is RHJ_E_INVALID.  Inputs are neither modified nor
+ * retained; outputs must not overlap inputs; pointers need 8-byte alignment.
+ * n == 0 or k == 0: RHJ_OK, no launch, nothing written, out_kth untouched.  k >= n: the call is the sort, with the same launches and
+ * the same "last.sort_*" (when out_kth is asked for and a device output is missing, the selection below runs with k = n instead).
+ * RHJ_E_INVALID, before any launch: unknown flag bits; NULL d_keys with n > 0.  The call synchronises; it honours rhj_set_stream and
+ * rhj_set_profiling (RHJ_K_HIST: the select histograms and the count; RHJ_K_SCAN; RHJ_K_SCATTER: the compaction; the inner sort's
+ * spans add to the same call).
+ * How: the sort's probe gives the width w and the sort key < 2^w (w == 0: the first m rows of the input, one copy launch, no pass).
+ * Select: from the top 8-bit digit of w downward, on the sort's digit grid, one histogram launch per digit over the rows whose higher
+ * digits equal the threshold's, and a one-workgroup launch that picks the digit in which rank m - 1 falls; the rows of smaller digits
+ * are SURE to be in the result (M of them, M <= m - 1), the c rows of the picked digit are the CANDIDATES.  The host reads the 32-byte
+ * state after each digit and stops when c <= "topk.max_candidates" or digit 0 is done (n <= "topk.max_candidates": no select pass at
+ * all).  Keep: a count per unit, a scan over the units and a compaction write the sure rows and the candidates, raw key words and
+ * 64-bit rows, in INPUT ORDER into the workspace -- positions come from ballots, per-wave counts, running cursors and the scan, never
+ * from atomics, which is what makes the cut stable and the result deterministic.  When the digits ran out every candidate holds the
+ * k-th key itself and only the first m - M of them are kept (a 16-value column hands the sort m rows, not n / 16).  In a pure selection
+ * no sure row is kept, only the candidates (of such a run: one).  Order: the sort runs over the kept rows, straight into the caller's
+ * arrays when exactly m rows were kept, else into the workspace, and a copy launch emits the first m.  No workgroup waits on another.
+ * Costs: passes <= ceil(w / 8).  Bytes per tuple of the INPUT: a probe of 8, one to three select passes of 8 each (full-range keys
+ * under the automatic cap: two), a count of 8 and a compaction read of 8 = 32 .. 48, once, against 112 .. 272 for the sort (96 .. 256
+ * in its passes plus 16 in its probes); plus the sort of the kept rows.  (A tie run at the threshold that is longer than the cap
+ * only ends when the digits do: up to ceil(w / 8) select passes, after which exactly m rows are sorted.)  The bound: "last.topk_sorted_rows" <= m + "topk.max_candidates"
+ * (from M <= m - 1); in a pure selection <= "topk.max_candidates", or 1 when the digits ran out.
+ * rhj_get_info: "last.topk_bits" is w, "last.topk_passes" the select histograms that ran, "last.topk_candidates" the tuples still tied
+ * with the threshold's digits when selection stopped, "last.topk_sorted_rows" the rows handed to the inner sort; all four are 0 after
+ * every other call.  On the select path "last.sort_*" stay 0 and "last.join_kernel" is -1.  "topk.auto_candidates": a constant of the
+ * build -- the automatic "topk.max_candidates" is max(k, "topk.auto_candidates").
+ * rhj_set_option: "topk.max_candidates": -1 automatic, 1 .. 2^31 - 1: selection goes on while more rows than this are tied (a test
+ * knob like "sort.max_units": the result never depends on it).  "sort.max_units" also caps the units of the histogram, count and
+ * compact launches.
+ * Memory: the select state, the tables and the kept rows live in a workspace buffer of their own (the inner sort regrows the sort's),
+ * kept until rhj_release_workspace: up to 4 x 8 bytes per kept row. */
+int rhj_topk_cols_dev(rhj_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_rows, uint64_t n, uint64_t k, uint32_t flags,
+                      uint64_t *d_out_keys, uint64_t *d_out_rows, uint64_t *out_kth);
+/* ... on 16-byte tuples in and out (value = .payload, rowID = .key); out_kth[0] is the value, out_kth[1] the rowID */
+int rhj_topk_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t n, uint64_t k, uint32_t flags, rhj_tuple *d_out, uint64_t *out_kth);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:

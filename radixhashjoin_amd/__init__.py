@@ -33,6 +33,9 @@ exact 64-bit key per row (``rhj_keys_pack_dev``), and ``plan.unpack(packed)`` gi
 Order: ``sorted_keys, perm, gathered = Engine(0).sort_columns(keys, values, descending=False)`` is ORDER BY on a key tensor -- a stable
 radix sort, ``perm`` the stable argsort, ``values[k][perm]`` beside it; a list of key tensors is ``ORDER BY k0, k1, ..``;
 ``Engine(0).argsort_columns(keys)`` returns ``perm`` alone (``rhj_sort_cols_dev``).
+``top_keys, idx, gathered = Engine(0).topk_columns(keys, k, values, descending=False)`` is ORDER BY .. LIMIT k -- the first k entries of
+that sort without sorting the column (a radix select in front of the sort), and ``value, row = Engine(0).kth_value_columns(keys, k)``
+the k-th smallest key and its row, a median or a quantile, with nothing of size k written (``rhj_topk_cols_dev``).
 """
 from .binding import (  # noqa: F401
     AGG_MAX_I64,

@@ -140,6 +140,8 @@ SYMBOLS = {
     "rhj_keys_plan_free": (C.c_int, [_vp, _vp]),
     "rhj_sort_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _vp, _vp]),
     "rhj_sort_dev": (C.c_int, [_vp, _vp, _u64, C.c_uint32, _vp]),
+    "rhj_topk_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _u64, C.c_uint32, _vp, _vp, _P(_u64)]),
+    "rhj_topk_dev": (C.c_int, [_vp, _vp, _u64, _u64, C.c_uint32, _vp, _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -457,7 +459,8 @@ class Engine:
 
     def info(self, name):
         """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.outer_sweeps", "last.group_rounds",
-        "last.sort_bits", "last.sort_passes", "last.sort_units"; include/rhj.h) and constants of the build ("sort.tile_rows")"""
+        "last.sort_bits", "last.sort_passes", "last.sort_units", "last.topk_bits", "last.topk_passes", "last.topk_candidates",
+        "last.topk_sorted_rows"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates")"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
         return v.value
@@ -1355,6 +1358,76 @@ class Engine:
         cols, desc, _ = self._sort_args(keys, descending, unsigned)
         self._sort_tensors(cols, (), isinstance(keys, (list, tuple)))
         return self._sort_chain(cols, desc, unsigned, (), False)[1]
+
+    def topk_cols_dev(self, d_keys, d_rows, n, k, flags=0, d_out_keys=None, d_out_rows=None, want_kth=False):
+        """rhj_topk_cols_dev: the first min(k, n) tuples of what sort_cols_dev would write, ties in input order also at the cut;
+        d_out_keys / d_out_rows: uint64[min(k, n)] in HBM, either may be None, both only with want_kth (a pure selection).
+        want_kth: returns (key word, row word) of the tuple of rank min(k, n) - 1, or None when n or k is 0; else returns None"""
+        kth = (_u64 * 2)() if want_kth else None
+        self._chk(self.lib.rhj_topk_cols_dev(self.ctx, _addr(d_keys), _addr(d_rows), n, k, flags, _addr(d_out_keys), _addr(d_out_rows), kth))
+        return (kth[0], kth[1]) if want_kth and n and k else None
+
+    def topk_dev(self, d_R, n, k, flags=0, d_out=None, want_kth=False):
+        """rhj_topk_dev: ... of n 16-byte tuples (value = .payload, rowID = .key) into d_out; the k-th tuple as (value, rowID)"""
+        kth = (_u64 * 2)() if want_kth else None
+        self._chk(self.lib.rhj_topk_dev(self.ctx, _addr(d_R), n, k, flags, _addr(d_out), kth))
+        return (kth[0], kth[1]) if want_kth and n and k else None
+
+    @staticmethod
+    def _topk_args(keys, k, descending, unsigned, values=()):
+        """ValueError before any device use: the arguments of topk_columns / kth_value_columns that are not tensors"""
+        if isinstance(keys, (list, tuple)):
+            raise ValueError("keys: one key tensor is needed, not a list -- ORDER BY k0, k1, .. LIMIT k is sort_columns(keys, ..) and a slice")
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise ValueError(f"k: an int is needed, not {k!r}")
+        if k < 0:
+            raise ValueError(f"k: a count of rows is needed, not {k}")
+        if not isinstance(descending, bool):
+            raise ValueError(f"descending: a bool is needed, not {descending!r}")
+        if not isinstance(unsigned, bool):
+            raise ValueError(f"unsigned: a bool is needed, not {unsigned!r}")
+        values = tuple(values)
+        if len(values) > LOOKUP_MAX_COLS:
+            raise ValueError(f"at most {LOOKUP_MAX_COLS} value tensors per call, not {len(values)}")
+        return values
+
+    def topk_columns(self, keys, k, values=(), descending=False, unsigned=False):
+        """(top_keys, idx, gathered_values): ORDER BY keys LIMIT k -- the first min(k, len(keys)) entries of what sort_columns returns
+        for the same arguments, without sorting the column: top_keys sorted ascending (descending=True: the k largest, descending),
+        idx their rows as an int64 tensor, ties in input order also at the cut (torch.sort(stable=True)[:k]), gathered_values one
+        tensor per tensor of values: values[j][idx].  A radix select, a stable compaction and a sort of what is left
+        (rhj_topk_cols_dev).  keys: ONE contiguous 1-D 64-bit integer tensor on the engine's device (a list: ValueError, see
+        sort_columns); k: an int >= 0.  Every ValueError comes before any device use.  Streams and completion as join_columns."""
+        import torch
+        values = self._topk_args(keys, k, descending, unsigned, values)
+        self._sort_tensors([keys], values, False)
+        with self._on_torch_stream(keys, keys, values) as dev:
+            n = keys.numel()
+            m = min(k, n)
+            top = torch.empty(m, dtype=keys.dtype, device=dev)
+            idx = torch.empty(m, dtype=torch.int64, device=dev)
+            if m:
+                self.topk_cols_dev(keys, None, n, k, (0 if unsigned else SORT_I64) | (SORT_DESC if descending else 0), top, idx)
+            gathered = [torch.empty(m, dtype=v.dtype, device=dev) for v in values]
+            if m and values:
+                self.gather_cols_fill(values, n, idx, m, [0] * len(values), gathered)
+        return top, idx, gathered
+
+    def kth_value_columns(self, keys, k, descending=False, unsigned=False):
+        """(value, row): the k-th smallest (descending=True: k-th largest) key and the row that holds it, as Python ints -- k is
+        1-based as in torch.kthvalue; among equal keys the row is the one a stable sort puts at rank k - 1.  A pure selection: nothing
+        of size k is written (rhj_topk_cols_dev with out_kth alone).  value is an int64 value unless unsigned.  k < 1 or k > len(keys):
+        ValueError; every ValueError comes before any device use."""
+        self._topk_args(keys, k, descending, unsigned)
+        if k < 1:
+            raise ValueError(f"k: a rank from 1 (as torch.kthvalue) is needed, not {k}")
+        self._sort_tensors([keys], (), False)
+        if k > keys.numel():
+            raise ValueError(f"k: 1 .. {keys.numel()} (the length of keys) is needed, not {k}")
+        with self._on_torch_stream(keys, keys, ()):
+            value, row = self.topk_cols_dev(keys, None, keys.numel(), k, (0 if unsigned else SORT_I64) | (SORT_DESC if descending else 0),
+                                            None, None, want_kth=True)
+        return (value if unsigned or value < 1 << 63 else value - (1 << 64)), row
 
     def factorize_columns(self, keys):
         """(codes, uniques): pandas.factorize without the ordering promise -- uniques the distinct values of keys in no particular

@@ -236,6 +236,10 @@ struct rhj_ctx {
     int last_sort_units = 0;           // "last.sort_units": the units -- workgroups per launch -- of those passes (0: no pass ran)
     DevBuf sort_ws;                    // the sort's tables and ping-pong buffers (rhj_sort.hip)
     int opt_sort_units = -1;           // "sort.max_units": -1 automatic, else the most units a sort cuts its input into
+    int last_topk_bits = 0, last_topk_passes = 0;   // "last.topk_bits" / "last.topk_passes": the width the last top-k's probe found, the select histograms it ran (0: another call)
+    u64 last_topk_cand = 0, last_topk_sorted = 0;   // "last.topk_candidates" / "last.topk_sorted_rows": the rows tied with the threshold's digits when selection stopped, the rows its inner sort took
+    DevBuf topk_ws;                    // top-k's select state, tables and kept rows (rhj_sort.hip): not sort_ws, which the inner sort regrows
+    int64_t opt_topk_cand = -1;        // "topk.max_candidates": -1 automatic, else selection goes on while more rows than this are tied
     int outer_how = 0;                 // an outer join's RHJ_OUTER_* bits, for the length of the call
     u64 outer_sections[3] = {0, 0, 0}; // ... and its {matched, R-only, S-only} rows, as outer_phase leaves them
     bool counters_clean = false;       // the 64-byte join counters are zero (cleared by the partition phase's first launch)
@@ -502,6 +506,8 @@ void prof_reset(rhj_ctx *ctx)
     ctx->last_group_rounds = 0;                     // "last.group_rounds": ... and group_phase this one
     ctx->last_outer_sweeps = 0;                     // "last.outer_sweeps": ... and outer_phase this one
     ctx->last_sort_bits = ctx->last_sort_passes = ctx->last_sort_units = 0;   // "last.sort_*": ... and the sort entries these
+    ctx->last_topk_bits = ctx->last_topk_passes = 0;                          // "last.topk_*": ... and the top-k entries these
+    ctx->last_topk_cand = ctx->last_topk_sorted = 0;
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -2243,6 +2249,20 @@ int rhj_internal_sort_workspace(rhj_ctx *ctx, size_t bytes, void **out)
     return RHJ_OK;
 }
 int rhj_internal_sort_max_units(rhj_ctx *ctx) { return ctx->opt_sort_units; }
+void rhj_internal_topk_report(rhj_ctx *ctx, int bits, int passes, u64 candidates, u64 sorted_rows)
+{
+    ctx->last_topk_bits = bits;
+    ctx->last_topk_passes = passes;
+    ctx->last_topk_cand = candidates;
+    ctx->last_topk_sorted = sorted_rows;
+}
+int rhj_internal_topk_workspace(rhj_ctx *ctx, size_t bytes, void **out)
+{
+    RHJCHK(ensure(ctx, ctx->topk_ws, bytes));
+    *out = ctx->topk_ws.p;
+    return RHJ_OK;
+}
+int64_t rhj_internal_topk_max_candidates(rhj_ctx *ctx) { return ctx->opt_topk_cand; }
 void *rhj_internal_span_open(rhj_ctx *ctx, int kind) { return new Span(ctx, kind); }
 void rhj_internal_span_close(void *span) { delete (Span *)span; }
 
@@ -2334,7 +2354,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->agg_out, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
                      &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cf2_end[0], &ctx->cf2_end[1], &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
-                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws};
+                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
     ctx->small_hdr_clean = false;
@@ -2410,6 +2430,7 @@ int rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value)
     if (n == "join.fused" && value >= -1 && value <= 1) { ctx->opt_fused = (int)value; return RHJ_OK; }
     if (n == "join.sniff" && value >= -1 && value <= 1) { ctx->opt_sniff = (int)value; return RHJ_OK; }
     if (n == "sort.max_units" && (value == -1 || (value >= 1 && value <= 2048))) { ctx->opt_sort_units = (int)value; return RHJ_OK; }
+    if (n == "topk.max_candidates" && (value == -1 || (value >= 1 && value <= 0x7FFFFFFF))) { ctx->opt_topk_cand = value; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_set_option: unknown option or value: " + n);
 }
 
@@ -2435,6 +2456,11 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.sort_passes") { *value = ctx->last_sort_passes; return RHJ_OK; }
     if (n == "last.sort_units") { *value = ctx->last_sort_units; return RHJ_OK; }
     if (n == "sort.tile_rows") { *value = SORT_TILE; return RHJ_OK; }
+    if (n == "last.topk_bits") { *value = ctx->last_topk_bits; return RHJ_OK; }
+    if (n == "last.topk_passes") { *value = ctx->last_topk_passes; return RHJ_OK; }
+    if (n == "last.topk_candidates") { *value = (int64_t)ctx->last_topk_cand; return RHJ_OK; }
+    if (n == "last.topk_sorted_rows") { *value = (int64_t)ctx->last_topk_sorted; return RHJ_OK; }
+    if (n == "topk.auto_candidates") { *value = TOPK_AUTO_CANDIDATES; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }

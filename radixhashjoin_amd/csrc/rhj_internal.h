@@ -476,3 +476,6 @@ constexpr int SORT_THREADS = 512;
 constexpr int SORT_TPT = 8;                       // rows per thread per tile
 constexpr int SORT_TILE = SORT_THREADS * SORT_TPT;
 constexpr int SORT_DIGIT_BITS = 8;
+// top-k: the automatic "topk.max_candidates" is max(k, this) -- selection stops once so few rows are tied with the
+// threshold's digits that sorting them costs less than another read of the column ("topk.auto_candidates")
+constexpr int TOPK_AUTO_CANDIDATES = 1 << 16;

@@ -162,6 +162,45 @@ struct CopyPool {
     }
 };
 
+// The operator arguments of one entry call, as its phase reads them from the context.  The *_common function of the entry opens a
+// CallScope, fills in what its operator takes, and the scope puts CallArgs() back on every way out: nothing here outlives the call,
+// and a field added here needs no line elsewhere to be cleared.
+struct CallArgs {
+    int outer_how = 0;                 // an outer join's RHJ_OUTER_* bits
+    // an aggregating join's weight columns (device), and where agg_phase leaves the ncols sums (host); device words: agg_out's
+    const u64 *agg_cols[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    u32 agg_ncols = 0;
+    u64 agg_col_rows = 0;
+    u64 *agg_sums_out = nullptr;
+    // a multiplicity join's arguments (its device words are agg_out's: [0] total, [5] u32 MULT_BAD_ROW_*)
+    const u64 *mult_w = nullptr;       // weights by S's rowID (device), or null
+    u64 mult_w_rows = 0;
+    u64 *mult_out = nullptr;           // out_rows words (device)
+    u64 mult_out_rows = 0;
+    int lookup_which = 0;              // a lookup join's RHJ_LOOKUP_* (its output words are mult_out / mult_out_rows, its device words agg_out's: [0] matched, [5] u32 LOOKUP_BAD_ROW_*)
+    // a group-by's arguments (input columns: agg_cols / agg_ncols / agg_col_rows; device words: agg_out's [0] groups, [5] u32 a rowID
+    // >= col_rows was met)
+    bool one_sided = false;            // partition_phase partitions R alone: no kernel touches a buffer of S, part_S does not grow
+    u64 *group_keys = nullptr, *group_counts = nullptr;   // capacity words each (device; counts may be null)
+    u64 *group_sums[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    u64 group_cap = 0;
+    u32 group_ops = 0;                 // the columns' packed op words (AGG_OP_*; a group-by join's: both sides'); 0: every column a sum
+    u64 *group_rows[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};   // rhj_group_arg_*: the rows arrays (group_sums: the values) ...
+    bool group_arg = false;            // ... and that group_ops holds ARG_OP_* words: group_phase launches k_group_bkt<., GB_ARG>
+    // a group-by join's arguments beyond the group-by's (R's side: agg_cols / agg_ncols / agg_col_rows, group_keys, group_counts = cntR,
+    // group_sums, group_cap; device words: agg_out's [0] groups, [5] u32 GJOIN_BAD_ROW_R / _S)
+    const u64 *gjoin_colsS[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    u32 gjoin_ncolsS = 0;
+    u64 gjoin_colS_rows = 0;
+    u64 *gjoin_cntS = nullptr;         // capacity words (device; may be null)
+    u64 *gjoin_sumsS[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    bool gjoin_left = false;           // RHJ_GJ_LEFT
+    // the id arrays of a group-by ([0]) or group-by join ([0] R's, [1] S's) with ids: device arrays of gid_rows[.] words
+    // indexed by the side's rowID, null: none; device words: agg_out's [1 .. 4], flag bits GROUP_BAD_GID / GJOIN_BAD_GID_*
+    u64 *gid[2] = {nullptr, nullptr};
+    u64 gid_rows[2] = {0, 0};
+};
+
 struct rhj_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -240,45 +279,13 @@ struct rhj_ctx {
     u64 last_topk_cand = 0, last_topk_sorted = 0;   // "last.topk_candidates" / "last.topk_sorted_rows": the rows tied with the threshold's digits when selection stopped, the rows its inner sort took
     DevBuf topk_ws;                    // top-k's select state, tables and kept rows (rhj_sort.hip): not sort_ws, which the inner sort regrows
     int64_t opt_topk_cand = -1;        // "topk.max_candidates": -1 automatic, else selection goes on while more rows than this are tied
-    int outer_how = 0;                 // an outer join's RHJ_OUTER_* bits, for the length of the call
-    u64 outer_sections[3] = {0, 0, 0}; // ... and its {matched, R-only, S-only} rows, as outer_phase leaves them
+    CallArgs call;                     // the operator arguments of the entry in progress (CallScope)
+    u64 outer_sections[3] = {0, 0, 0}; // an outer join's {matched, R-only, S-only} rows, as outer_phase leaves them
     bool counters_clean = false;       // the 64-byte join counters are zero (cleared by the partition phase's first launch)
     int cur_narrow = 0;                // partitions are in the narrow {payload, rowID} format (k_scatter_wcn); 2: so was the intermediate
     DevBuf agg_out;                    // an aggregating join's words: [0] count, [1 .. 4] sums, [5] u32 a rowID >= col_rows was met
-    const u64 *agg_cols[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};   // ... its weight columns (device), for the length of the call
-    u32 agg_ncols = 0;
-    u64 agg_col_rows = 0;
-    u64 *agg_sums_out = nullptr;       // ... and where agg_phase leaves the ncols sums (host)
-    // a multiplicity join's arguments, for the length of the call (its device words are agg_out's: [0] total, [5] u32 MULT_BAD_ROW_*)
-    const u64 *mult_w = nullptr;       // weights by S's rowID (device), or null
-    u64 mult_w_rows = 0;
-    u64 *mult_out = nullptr;           // out_rows words (device)
-    u64 mult_out_rows = 0;
-    int lookup_which = 0;              // a lookup join's RHJ_LOOKUP_* (its output words are mult_out / mult_out_rows, its device words agg_out's: [0] matched, [5] u32 LOOKUP_BAD_ROW_*)
-    // a group-by's arguments, for the length of the call (input columns: agg_cols / agg_ncols / agg_col_rows; device words: agg_out's
-    // [0] groups, [5] u32 a rowID >= col_rows was met)
-    bool one_sided = false;            // partition_phase partitions R alone: no kernel touches a buffer of S, part_S does not grow
-    u64 *group_keys = nullptr, *group_counts = nullptr;   // capacity words each (device; counts may be null)
-    u64 *group_sums[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
-    u64 group_cap = 0;
-    u32 group_ops = 0;                 // the columns' packed op words (AGG_OP_*; a group-by join's: both sides'); 0: every column a sum
-    u64 *group_rows[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};   // rhj_group_arg_*: the rows arrays (group_sums: the values) ...
-    bool group_arg = false;            // ... and that group_ops holds ARG_OP_* words: group_phase launches k_group_bkt<., GB_ARG>
     int last_group_rounds = 0;         // "last.group_rounds": table builds of the busiest task of the last group-by or group-by join (0: another call)
-    // a group-by join's arguments beyond the group-by's (R's side: agg_cols / agg_ncols / agg_col_rows, group_keys, group_counts = cntR,
-    // group_sums, group_cap; device words: agg_out's [0] groups, [5] u32 GJOIN_BAD_ROW_R / _S)
-    const u64 *gjoin_colsS[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
-    u32 gjoin_ncolsS = 0;
-    u64 gjoin_colS_rows = 0;
-    u64 *gjoin_cntS = nullptr;         // capacity words (device; may be null)
-    u64 *gjoin_sumsS[AGG_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
-    bool gjoin_left = false;           // RHJ_GJ_LEFT
-    // the id arrays of a group-by ([0]) or group-by join ([0] R's, [1] S's) with ids, for the length of the call: device
-    // arrays of gid_rows[.] words indexed by the side's rowID, null: none; device words: agg_out's [1 .. 4], flag bits GROUP_BAD_GID /
-    // GJOIN_BAD_GID_*
-    u64 *gid[2] = {nullptr, nullptr};
-    u64 gid_rows[2] = {0, 0};
-    DevBuf narrow_flag;                // u32: a rowID >= 2^32 met a narrow scatter -> the join re-runs in the 16-byte format
+    DevBuf narrow_flag;               // u32: a rowID >= 2^32 met a narrow scatter -> the join re-runs in the 16-byte format
     // ... the next join tries the narrow format again; consecutive fall-backs make the context skip the attempt for the next
     // 2, 4, ... 32 eligible joins (a caller whose rowIDs are always wide pays one extra histogram per relation now and then)
     u32 narrow_fail_streak = 0, narrow_skip = 0;
@@ -517,6 +524,12 @@ int check_launch(rhj_ctx *ctx, const char *what)
         return fail(ctx, RHJ_E_HIP, std::string(what) + ": " + attr);
     if (e != hipSuccess) return fail(ctx, RHJ_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
     return RHJ_OK;
+}
+
+// the rowID array of narrow partitions: the u32 words behind the payloads of n tuples (or slots, where a side lies in regions with gaps)
+const u32 *narrow_ids(const void *base, u64 n_or_slots)
+{
+    return (const u32 *)((const unsigned char *)base + narrow_k_offset(n_or_slots));
 }
 
 // tuning environment variables: unset, empty or non-numeric -> the default; numeric values are clamped to [lo, hi]
@@ -1043,7 +1056,7 @@ int partition_relation_narrow2(rhj_ctx *ctx, const void *d_in, u64 n, int b1, in
             Span s(ctx, RHJ_K_SCATTER);
             void *out = pass ? d_out : ctx->part_tmp.p;
             launch_scatter_units_narrow_any(ctx->stream, pass ? ctx->part_tmp.p : d_in,
-                                            pass ? (const u32 *)((const unsigned char *)ctx->part_tmp.p + narrow_k_offset(n)) : d_inK,
+                                            pass ? narrow_ids(ctx->part_tmp.p, n) : d_inK,
                                             out, (u32 *)((unsigned char *)out + narrow_k_offset(n)), g, seg_start, unit_start,
                                             (const u64 *)ctx->unit_base.p, wide);
         }
@@ -1260,7 +1273,7 @@ int cols_to_aos(rhj_ctx *ctx, u64 nR, const void *&d_R, u64 nS, const void *&d_S
 // before_S (optional, consumed by the first call that gets it): invoked once, after the kernels that partition R have been
 // enqueued and before anything reads S -- rhj_join uploads S there, so that S crosses PCIe while R is being partitioned
 // (plans that push both relations through the same launches call it first).
-// ctx->one_sided (a group-by): R alone is partitioned, under the plan, the format and the count-free choice of a join of (nR, nS = nR)
+// ctx->call.one_sided (a group-by): R alone is partitioned, under the plan, the format and the count-free choice of a join of (nR, nS = nR)
 // -- S is skipped explicitly: no kernel reads or writes a buffer of S, part_S is not grown, nothing is sampled (one side has no tie
 // to break), R takes the one-stream path and, under a one-pass plan, run_pass instead of the paired launches.  cur_S is null.
 // gaps_ok: the consumer is the pair join's join_phase, which takes partitions in regions with gaps (cf2_end_for); every other
@@ -1268,7 +1281,7 @@ int cols_to_aos(rhj_ctx *ctx, u64 nR, const void *&d_R, u64 nS, const void *&d_S
 int partition_phase(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u64 nS, const rhj_opts &plan,
                     std::function<int()> *before_S = nullptr, bool gaps_ok = false)
 {
-    const bool one = ctx->one_sided;
+    const bool one = ctx->call.one_sided;
     ctx->sniff_ready = false;
     auto s_ready = [&]() -> int {
         if (!before_S || !*before_S) return RHJ_OK;
@@ -1467,8 +1480,8 @@ int join_phase_on(rhj_ctx *ctx, const void *d_Rp, const u64 *d_psR, u64 nR, cons
             Span s(ctx, RHJ_K_JOIN);
             launch_join(ctx->stream, d_Rp, d_psR, d_Sp, d_psS, (const JoinTask *)ctx->tasks.p, d_ntasks, max_tasks,
                         radix_bits, d_out, d_out ? cap : 0, d_count, kind,
-                        narrow ? (const u32 *)((const unsigned char *)d_Rp + narrow_k_offset(slotsR ? slotsR : nR)) : nullptr,
-                        narrow ? (const u32 *)((const unsigned char *)d_Sp + narrow_k_offset(slotsS ? slotsS : nS)) : nullptr,
+                        narrow ? narrow_ids(d_Rp, slotsR ? slotsR : nR) : nullptr,
+                        narrow ? narrow_ids(d_Sp, slotsS ? slotsS : nS) : nullptr,
                         d_tag_base, narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
         }
     }
@@ -1512,110 +1525,158 @@ int join_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
 // OUT_LOOKUP: one partner rowID of S per row of R, the smallest or the largest (lookup_phase).
 enum JoinOutput { OUT_PAIRS = -1, OUT_SEMI = RHJ_SEMI, OUT_ANTI = RHJ_ANTI, OUT_SUMS = 2, OUT_MULT = 3, OUT_GROUP = 4, OUT_GJOIN = 5, OUT_OUTER = 6, OUT_LOOKUP = 7 };
 
-// Semi / anti join phase on the partitions partition_phase left (DESIGN 4.12): k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
-// Reads the skip word behind its kernel and answers with the retry codes of join_phase_on.
-int semi_phase(rhj_ctx *ctx, JoinOutput what, void *d_out, u64 cap, u64 *out_count)
+// ---- the scaffold of the keyed-table phases: semi_phase, outer_sweep, agg_phase, mult_phase, lookup_phase, group_phase, gjoin_phase ----
+// Each builds a task list with k_make_semi_tasks over the partitions ctx->cur_* describe, launches its own kernel over it and reads
+// the join counters back.  keyed_begin is everything in front of the kernel, keyed_finish everything behind it up to the words the
+// phase interprets itself.  Stream order: counters, agg_out, the empty boundaries of a missing table side, the operator's fill, the
+// single segments, the task list, the kernel.
+constexpr u32 NEVER_CUT = 0xffffffffu;                 // a split cap: a partition is never cut -- its keys would be emitted twice
+enum KeyedClear {
+    CLEAR_COUNTERS,                                    // the 64 counter bytes, unless a paired partition pass has cleared them already
+    CLEAR_COUNTERS_AGG,                                // ... and agg_out's 64, on EVERY attempt: a repeat (count-free overflow, wide rowID) starts from nothing
+    CLEAR_TAIL                                         // counter words 1..7: word 0, the result counter, goes on (outer_sweep; cf. join_phase_on's keep_count)
+};
+struct Keyed {                                         // what keyed_begin leaves for the launch and for keyed_finish
+    KeyedClear clear;
+    bool narrow;
+    u32 max_tasks;
+    const JoinTask *tasks;
+    const u32 *ntasks;                                 // counters[1]
+    u64 *count, *max_tables;                           // counters[0], counters[7]
+    u64 *agg;                                          // agg_out's words (CLEAR_COUNTERS_AGG, else null) ...
+    u32 *bad;                                          // ... and the guard flags among them
+    const u32 *skip;                                   // the narrow flag word, or null
+};
+
+// split_cap: the most probe tuples per task the kernel takes (the context's probe split counts below it), or NEVER_CUT; rows: the probe
+// side's tuples, which bound the task list; psP / psT: the boundaries of the probe side and of the table side -- psT null: there is no
+// table side, its boundary array is ctx->ps_S, zeroed here (every partition empty, at 0); fill: the operator's own work between the
+// clears and the task builder, inside the clears' span.
+int keyed_begin(rhj_ctx *ctx, Keyed &k, KeyedClear clear, int kind, u32 split_cap, u64 rows, int anti, const u64 *psP, const u64 *psT,
+                const std::function<int()> &fill = nullptr)
 {
-    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
-    const bool narrow = ctx->cur_narrow != 0;
-    u32 split = ctx->cur_probe_split;
-    if (split == 0 || split > SEMI_MAX_SPLIT) split = SEMI_MAX_SPLIT;        // a task's match bits: 4 KiB of LDS
-    const u64 max_tasks64 = nparts + nR / split + 1;
+    const u64 nparts = ctx->cur_nparts;
+    u32 split = split_cap;
+    if (split_cap != NEVER_CUT) {
+        split = ctx->cur_probe_split ? ctx->cur_probe_split : 32768;
+        if (split > split_cap) split = split_cap;
+    }
+    const u64 max_tasks64 = nparts + rows / split + 1;
     if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
-    const u32 max_tasks = (u32)max_tasks64;
-    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
-    RHJCHK(ensure(ctx, ctx->counters, 64));
-    u64 *d_count = (u64 *)ctx->counters.p;
-    if (!ctx->counters_clean) {                        // (a paired partition pass has cleared them already)
+    const bool no_T = psT == nullptr;
+    const size_t empty_bytes = (size_t)(nparts + 1) * 8;
+    k.clear = clear;
+    k.narrow = ctx->cur_narrow != 0;
+    k.max_tasks = (u32)max_tasks64;
+    RHJCHK(ensure(ctx, ctx->tasks, (size_t)k.max_tasks * sizeof(JoinTask)));
+    if (clear != CLEAR_TAIL) RHJCHK(ensure(ctx, ctx->counters, 64));
+    if (clear == CLEAR_COUNTERS_AGG) RHJCHK(ensure(ctx, ctx->agg_out, 64));
+    if (no_T) { RHJCHK(ensure(ctx, ctx->ps_S, empty_bytes)); psT = (const u64 *)ctx->ps_S.p; }
+    k.tasks = (const JoinTask *)ctx->tasks.p;
+    k.count = (u64 *)ctx->counters.p;
+    k.ntasks = (const u32 *)(k.count + 1);
+    k.max_tables = k.count + 7;
+    k.agg = clear == CLEAR_COUNTERS_AGG ? (u64 *)ctx->agg_out.p : nullptr;
+    k.bad = k.agg ? (u32 *)(k.agg + AGG_MAX_COLS + 1) : nullptr;
+    k.skip = k.narrow ? (const u32 *)ctx->narrow_flag.p : nullptr;
+    if (clear != CLEAR_COUNTERS || !ctx->counters_clean) {
         Span s(ctx, RHJ_K_AUX);
-        HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+        if (clear == CLEAR_TAIL) HIPCHK(ctx, hipMemsetAsync((unsigned char *)ctx->counters.p + 8, 0, 56, ctx->stream));
+        else if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+        if (k.agg) HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
+        if (no_T) HIPCHK(ctx, hipMemsetAsync(ctx->ps_S.p, 0, empty_bytes, ctx->stream));
+        if (fill) RHJCHK(fill());
     }
-    ctx->counters_clean = false;
-    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
-        Span s(ctx, RHJ_K_AUX);
-        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
-        launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+    if (clear != CLEAR_TAIL) {                         // (a sweep runs behind a phase that has done all this)
+        ctx->counters_clean = false;
+        if (ctx->cur_radix_bits == 0) {                // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
+            Span s(ctx, RHJ_K_AUX);
+            launch_init_single_segment(ctx->stream, ctx->cur_nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
+            if (!no_T) launch_init_single_segment(ctx->stream, ctx->cur_nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
+        }
+        ctx->last_join_kind = kind;
+        ctx->sniff_ready = false;                      // (the samples of the partition phase are not asked)
     }
-    ctx->last_join_kind = JK_SEMI;
-    ctx->sniff_ready = false;                          // (the samples of the partition phase are not asked)
-    {
-        Span s(ctx, RHJ_K_TASKS);
-        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, ctx->cur_psS, nparts, split, what == OUT_ANTI, (JoinTask *)ctx->tasks.p,
-                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
-    }
-    {
-        Span s(ctx, RHJ_K_JOIN);
-        launch_semi_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
-                         ctx->cur_radix_bits, what == OUT_ANTI, (u64 *)d_out, d_out ? cap : 0, d_count, d_count + 7,
-                         narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                         narrow ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
-                         narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
-    }
-    RHJCHK(check_launch(ctx, "semi join phase"));
-    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // count, ntasks, max |R_k|, max |S_k|, -, oversized table side, -, most tables of a task (if > 1)
+    Span s(ctx, RHJ_K_TASKS);
+    launch_make_semi_tasks(ctx->stream, psP, psT, nparts, split, anti, (JoinTask *)ctx->tasks.p, (u32 *)(k.count + 1), k.max_tasks, k.count + 2);
+    return RHJ_OK;
+}
+
+// Behind the phase's kernel: the launch check, the counters (host[8]: count, ntasks, max |R_k|, max |S_k|, -, oversized table side, -,
+// most tables or rounds of a task if > 1), agg_out's words (agg[8], where the phase has them) and the narrow flag in one synchronisation;
+// the retry codes of join_phase_on; "last.ntasks" and "last.max_part_*".  A sweep (CLEAR_TAIL) gets its counters and adds them up itself.
+int keyed_finish(rhj_ctx *ctx, const Keyed &k, const char *what, u64 *host, u64 *agg = nullptr)
+{
+    RHJCHK(check_launch(ctx, what));
     u32 wide_rowid = 0;
-    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    memset(host, 0, 64);
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, 64, hipMemcpyDeviceToHost, ctx->stream));
+    if (k.agg) {
+        memset(agg, 0, 64);
+        HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, 64, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (k.narrow && k.clear != CLEAR_TAIL) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (k.clear == CLEAR_TAIL) return RHJ_OK;
     if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
     if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
-    *out_count = host[0];
     ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
-    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
-    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
-    ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
-    if (host[5])
-        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    ctx->last_max_part[0] = ctx->cur_nparts > 1 ? host[2] : 0;
+    ctx->last_max_part[1] = ctx->cur_nparts > 1 ? host[3] : 0;
+    return RHJ_OK;
+}
+
+// "last.semi_tables" / "last.group_rounds" of a task list: the kernels report only a task that built more than one
+int keyed_rounds(const u64 *host, u32 ntasks) { return host[7] ? (int)host[7] : (ntasks ? 1 : 0); }
+
+int part_too_large(rhj_ctx *ctx, const char *side, u64 n)
+{
+    return fail(ctx, RHJ_E_INVALID, std::string("a partition of ") + side + " has " + std::to_string(n) + " tuples (>= 2^32): use more radix bits");
+}
+
+// Semi / anti join phase on the partitions partition_phase left (DESIGN 4.12): k_make_semi_tasks + k_semi_bkt.  d_out: u64 rowIDs.
+// A task's match bits are 4 KiB of LDS: SEMI_MAX_SPLIT tuples of R at most.
+int semi_phase(rhj_ctx *ctx, JoinOutput what, void *d_out, u64 cap, u64 *out_count)
+{
+    Keyed k;
+    RHJCHK(keyed_begin(ctx, k, CLEAR_COUNTERS, JK_SEMI, SEMI_MAX_SPLIT, ctx->cur_nR, what == OUT_ANTI, ctx->cur_psR, ctx->cur_psS));
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        launch_semi_join(ctx->stream, ctx->cur_R, ctx->cur_S, k.tasks, k.ntasks, k.max_tasks, ctx->cur_radix_bits, what == OUT_ANTI, (u64 *)d_out,
+                         d_out ? cap : 0, k.count, k.max_tables, k.narrow ? narrow_ids(ctx->cur_R, ctx->cur_nR) : nullptr,
+                         k.narrow ? narrow_ids(ctx->cur_S, ctx->cur_nS) : nullptr, k.skip);
+    }
+    u64 host[8];
+    RHJCHK(keyed_finish(ctx, k, "semi join phase", host));
+    *out_count = host[0];
+    ctx->last_semi_tables = keyed_rounds(host, (u32)ctx->last.ntasks);
+    if (host[5]) return part_too_large(ctx, "S", host[5]);
     return RHJ_OK;
 }
 
 // One anti sweep of an outer join over the partitions ctx->cur_* describe: the tuples of the preserved side -- R
 // (side 0: the tables on S's partitions) or S (side 1: the roles exchanged, the tables on R's partitions) -- without a partner, as
-// {rowID, NO_ROW} / {NO_ROW, rowID} behind whatever the result counter already counts.  Counter words 1..7 start from zero, word 0
-// goes on (cf. join_phase_on's keep_count).  *out_total: the counter after the sweep.
+// {rowID, NO_ROW} / {NO_ROW, rowID} behind whatever the result counter already counts.  *out_total: the counter after the sweep.
 int outer_sweep(rhj_ctx *ctx, int side, void *d_out, u64 cap, u64 *out_total)
 {
-    const u64 nP = side ? ctx->cur_nS : ctx->cur_nR, nT = side ? ctx->cur_nR : ctx->cur_nS, nparts = ctx->cur_nparts;
+    const u64 nP = side ? ctx->cur_nS : ctx->cur_nR, nT = side ? ctx->cur_nR : ctx->cur_nS;
     const void *d_P = side ? ctx->cur_S : ctx->cur_R, *d_T = side ? ctx->cur_R : ctx->cur_S;
-    const u64 *d_psP = side ? ctx->cur_psS : ctx->cur_psR, *d_psT = side ? ctx->cur_psR : ctx->cur_psS;
-    const bool narrow = ctx->cur_narrow != 0;
-    u32 split = ctx->cur_probe_split;
-    if (split == 0 || split > SEMI_MAX_SPLIT) split = SEMI_MAX_SPLIT;        // a task's match bits: 4 KiB of LDS
-    const u64 max_tasks64 = nparts + nP / split + 1;
-    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
-    const u32 max_tasks = (u32)max_tasks64;
-    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
-    u64 *d_count = (u64 *)ctx->counters.p;
-    {
-        Span s(ctx, RHJ_K_AUX);
-        HIPCHK(ctx, hipMemsetAsync((unsigned char *)ctx->counters.p + 8, 0, 56, ctx->stream));
-    }
-    {
-        Span s(ctx, RHJ_K_TASKS);
-        launch_make_semi_tasks(ctx->stream, d_psP, d_psT, nparts, split, 1, (JoinTask *)ctx->tasks.p, (u32 *)(d_count + 1), max_tasks,
-                               d_count + 2);
-    }
+    Keyed k;
+    RHJCHK(keyed_begin(ctx, k, CLEAR_TAIL, JK_SEMI, SEMI_MAX_SPLIT, nP, 1, side ? ctx->cur_psS : ctx->cur_psR, side ? ctx->cur_psR : ctx->cur_psS));
     {
         Span s(ctx, RHJ_K_JOIN);
-        launch_outer_sweep(ctx->stream, d_P, d_T, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
-                           ctx->cur_radix_bits, side, d_out, d_out ? cap : 0, d_count, d_count + 7,
-                           narrow ? (const u32 *)((const unsigned char *)d_P + narrow_k_offset(nP)) : nullptr,
-                           narrow ? (const u32 *)((const unsigned char *)d_T + narrow_k_offset(nT)) : nullptr,
-                           narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+        launch_outer_sweep(ctx->stream, d_P, d_T, k.tasks, k.ntasks, k.max_tasks, ctx->cur_radix_bits, side, d_out, d_out ? cap : 0, k.count,
+                           k.max_tables, k.narrow ? narrow_ids(d_P, nP) : nullptr, k.narrow ? narrow_ids(d_T, nT) : nullptr, k.skip);
     }
-    RHJCHK(check_launch(ctx, "outer join sweep"));
-    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // count, ntasks, max |P_k|, max |T_k|, -, oversized table side, -, most tables of a task (if > 1)
-    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    u64 host[8];
+    RHJCHK(keyed_finish(ctx, k, "outer join sweep", host));
     *out_total = host[0];
     const u32 ntasks = (u32)(host[1] & 0xffffffffu);
     ctx->last.ntasks += ntasks;
-    const int tables = host[7] ? (int)host[7] : (ntasks ? 1 : 0);
+    const int tables = keyed_rounds(host, ntasks);
     if (tables > ctx->last_semi_tables) ctx->last_semi_tables = tables;
     ctx->last_outer_sweeps++;
-    if (host[5])
-        return fail(ctx, RHJ_E_INVALID, std::string("a partition of ") + (side ? "R" : "S") + " has " + std::to_string(host[5]) +
-                                        " tuples (>= 2^32): use more radix bits");
+    if (host[5]) return part_too_large(ctx, side ? "R" : "S", host[5]);
     return RHJ_OK;
 }
 
@@ -1639,7 +1700,7 @@ int outer_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
     }
     u64 before = *out_count;
     for (int side = 0; side < 2; side++) {
-        if (!(ctx->outer_how & (1 << side))) continue;
+        if (!(ctx->call.outer_how & (1 << side))) continue;
         u64 total = before;
         RHJCHK(outer_sweep(ctx, side, d_out, cap, &total));
         ctx->outer_sections[1 + side] = total - before;
@@ -1651,133 +1712,49 @@ int outer_phase(rhj_ctx *ctx, void *d_out, u64 cap, u64 *out_count)
 }
 
 // Aggregating join phase on the partitions partition_phase left: k_make_semi_tasks (anti = 0) + k_agg_bkt over the
-// weight columns the entry point left in the context.  EVERY attempt zeroes the sums words and the guard flag before its kernel: a
-// repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes as semi_phase.
+// weight columns of the call.  Retry codes as semi_phase.
 int agg_phase(rhj_ctx *ctx, u64 *out_count)
 {
-    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
-    const bool narrow = ctx->cur_narrow != 0;
-    u32 split = ctx->cur_probe_split;
-    if (split == 0) split = 32768;
-    if (split > AGG_MAX_SPLIT) split = AGG_MAX_SPLIT;
-    const u64 max_tasks64 = nparts + nR / split + 1;
-    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
-    const u32 max_tasks = (u32)max_tasks64;
-    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
-    RHJCHK(ensure(ctx, ctx->counters, 64));
-    RHJCHK(ensure(ctx, ctx->agg_out, 64));
-    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
-    {
-        Span s(ctx, RHJ_K_AUX);
-        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));   // (a paired partition pass has cleared them already)
-        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
-    }
-    ctx->counters_clean = false;
-    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
-        Span s(ctx, RHJ_K_AUX);
-        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
-        launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
-    }
-    ctx->last_join_kind = JK_AGG;
-    ctx->sniff_ready = false;                          // (the samples of the partition phase are not asked)
-    {
-        Span s(ctx, RHJ_K_TASKS);
-        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, ctx->cur_psS, nparts, split, 0, (JoinTask *)ctx->tasks.p,
-                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
-    }
+    const CallArgs &a = ctx->call;
+    Keyed k;
+    RHJCHK(keyed_begin(ctx, k, CLEAR_COUNTERS_AGG, JK_AGG, AGG_MAX_SPLIT, ctx->cur_nR, 0, ctx->cur_psR, ctx->cur_psS));
     {
         Span s(ctx, RHJ_K_JOIN);
-        launch_agg_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
-                        ctx->cur_radix_bits, ctx->agg_cols, ctx->agg_ncols, ctx->agg_col_rows, d_agg, (u32 *)(d_agg + AGG_MAX_COLS + 1),
-                        d_count + 7,
-                        narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                        narrow ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
-                        narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+        launch_agg_join(ctx->stream, ctx->cur_R, ctx->cur_S, k.tasks, k.ntasks, k.max_tasks, ctx->cur_radix_bits, a.agg_cols, a.agg_ncols,
+                        a.agg_col_rows, k.agg, k.bad, k.max_tables, k.narrow ? narrow_ids(ctx->cur_R, ctx->cur_nR) : nullptr,
+                        k.narrow ? narrow_ids(ctx->cur_S, ctx->cur_nS) : nullptr, k.skip);
     }
-    RHJCHK(check_launch(ctx, "aggregating join phase"));
-    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, oversized table side, -, most tables of a task (if > 1)
-    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // count, sums, guard flag
-    u32 wide_rowid = 0;
-    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
-    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
-    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
-    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
-    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
-    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
-    ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
-    if (host[5])
-        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    u64 host[8], agg[8];                               // agg: count, sums, guard flag
+    RHJCHK(keyed_finish(ctx, k, "aggregating join phase", host, agg));
+    ctx->last_semi_tables = keyed_rounds(host, (u32)ctx->last.ntasks);
+    if (host[5]) return part_too_large(ctx, "S", host[5]);
     if ((u32)agg[AGG_MAX_COLS + 1])
         return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= col_rows: the weight columns have no such row");
     *out_count = agg[0];
-    for (u32 j = 0; j < ctx->agg_ncols; j++) ctx->agg_sums_out[j] = agg[1 + j];
+    for (u32 j = 0; j < a.agg_ncols; j++) a.agg_sums_out[j] = agg[1 + j];
     return RHJ_OK;
 }
 
 // Multiplicity join phase on the partitions partition_phase left: k_make_semi_tasks (anti = 0) + k_mult_bkt over the
-// weights and the output words the entry point left in the context.  EVERY attempt zeroes the output words, the total and the
-// guard flags before its kernel: a repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes as semi_phase.
+// weights and the output words of the call.  EVERY attempt zeroes the output words too.  Retry codes as semi_phase.
 int mult_phase(rhj_ctx *ctx, u64 *out_total)
 {
-    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
-    const bool narrow = ctx->cur_narrow != 0;
-    u32 split = ctx->cur_probe_split;
-    if (split == 0) split = 32768;
-    if (split > AGG_MAX_SPLIT) split = AGG_MAX_SPLIT;
-    const u64 max_tasks64 = nparts + nR / split + 1;
-    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
-    const u32 max_tasks = (u32)max_tasks64;
-    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
-    RHJCHK(ensure(ctx, ctx->counters, 64));
-    RHJCHK(ensure(ctx, ctx->agg_out, 64));
-    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
-    {
-        Span s(ctx, RHJ_K_AUX);
-        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));   // (a paired partition pass has cleared them already)
-        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
-        if (ctx->mult_out_rows) HIPCHK(ctx, hipMemsetAsync(ctx->mult_out, 0, ctx->mult_out_rows * 8, ctx->stream));
-    }
-    ctx->counters_clean = false;
-    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
-        Span s(ctx, RHJ_K_AUX);
-        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
-        launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
-    }
-    ctx->last_join_kind = JK_MULT;
-    ctx->sniff_ready = false;                          // (the samples of the partition phase are not asked)
-    {
-        Span s(ctx, RHJ_K_TASKS);
-        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, ctx->cur_psS, nparts, split, 0, (JoinTask *)ctx->tasks.p,
-                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
-    }
+    const CallArgs &a = ctx->call;
+    Keyed k;
+    RHJCHK(keyed_begin(ctx, k, CLEAR_COUNTERS_AGG, JK_MULT, AGG_MAX_SPLIT, ctx->cur_nR, 0, ctx->cur_psR, ctx->cur_psS, [&]() -> int {
+        if (a.mult_out_rows) HIPCHK(ctx, hipMemsetAsync(a.mult_out, 0, a.mult_out_rows * 8, ctx->stream));
+        return RHJ_OK;
+    }));
     {
         Span s(ctx, RHJ_K_JOIN);
-        launch_mult_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
-                         ctx->cur_radix_bits, ctx->mult_w, ctx->mult_w_rows, ctx->mult_out, ctx->mult_out_rows, d_agg,
-                         (u32 *)(d_agg + AGG_MAX_COLS + 1), d_count + 7,
-                         narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                         narrow ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
-                         narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+        launch_mult_join(ctx->stream, ctx->cur_R, ctx->cur_S, k.tasks, k.ntasks, k.max_tasks, ctx->cur_radix_bits, a.mult_w, a.mult_w_rows,
+                         a.mult_out, a.mult_out_rows, k.agg, k.bad, k.max_tables, k.narrow ? narrow_ids(ctx->cur_R, ctx->cur_nR) : nullptr,
+                         k.narrow ? narrow_ids(ctx->cur_S, ctx->cur_nS) : nullptr, k.skip);
     }
-    RHJCHK(check_launch(ctx, "multiplicity join phase"));
-    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, oversized table side, -, most tables of a task (if > 1)
-    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // total, -, -, -, -, guard flags
-    u32 wide_rowid = 0;
-    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
-    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
-    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
-    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
-    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
-    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
-    ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
-    if (host[5])
-        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    u64 host[8], agg[8];                               // agg: total, -, -, -, -, guard flags
+    RHJCHK(keyed_finish(ctx, k, "multiplicity join phase", host, agg));
+    ctx->last_semi_tables = keyed_rounds(host, (u32)ctx->last.ntasks);
+    if (host[5]) return part_too_large(ctx, "S", host[5]);
     const u32 bad = (u32)agg[AGG_MAX_COLS + 1];
     if (bad & MULT_BAD_ROW_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= out_rows: d_out has no such word");
     if (bad & MULT_BAD_ROW_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= wS_rows: the weight column has no such row");
@@ -1786,67 +1763,25 @@ int mult_phase(rhj_ctx *ctx, u64 *out_total)
 }
 
 // Lookup join phase on the partitions partition_phase left: k_make_semi_tasks (anti = 0) + k_lookup_bkt over the output
-// words the entry point left in the context.  EVERY attempt fills the output words with all ones (RHJ_NO_ROW) and zeroes the matched
-// word and the guard flags before its kernel: a repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes as
-// semi_phase.
+// words of the call.  EVERY attempt fills the output words with all ones (RHJ_NO_ROW).  Retry codes as semi_phase.
 int lookup_phase(rhj_ctx *ctx, u64 *out_matched)
 {
-    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
-    const bool narrow = ctx->cur_narrow != 0;
-    u32 split = ctx->cur_probe_split;
-    if (split == 0) split = 32768;
-    if (split > AGG_MAX_SPLIT) split = AGG_MAX_SPLIT;
-    const u64 max_tasks64 = nparts + nR / split + 1;
-    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
-    const u32 max_tasks = (u32)max_tasks64;
-    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
-    RHJCHK(ensure(ctx, ctx->counters, 64));
-    RHJCHK(ensure(ctx, ctx->agg_out, 64));
-    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
-    {
-        Span s(ctx, RHJ_K_AUX);
-        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));   // (a paired partition pass has cleared them already)
-        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
-        if (ctx->mult_out_rows) HIPCHK(ctx, hipMemsetAsync(ctx->mult_out, 0xFF, ctx->mult_out_rows * 8, ctx->stream));
-    }
-    ctx->counters_clean = false;
-    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
-        Span s(ctx, RHJ_K_AUX);
-        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
-        launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
-    }
-    ctx->last_join_kind = JK_LOOKUP;
-    ctx->sniff_ready = false;                          // (the samples of the partition phase are not asked)
-    {
-        Span s(ctx, RHJ_K_TASKS);
-        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, ctx->cur_psS, nparts, split, 0, (JoinTask *)ctx->tasks.p,
-                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
-    }
+    const CallArgs &a = ctx->call;
+    Keyed k;
+    RHJCHK(keyed_begin(ctx, k, CLEAR_COUNTERS_AGG, JK_LOOKUP, AGG_MAX_SPLIT, ctx->cur_nR, 0, ctx->cur_psR, ctx->cur_psS, [&]() -> int {
+        if (a.mult_out_rows) HIPCHK(ctx, hipMemsetAsync(a.mult_out, 0xFF, a.mult_out_rows * 8, ctx->stream));
+        return RHJ_OK;
+    }));
     {
         Span s(ctx, RHJ_K_JOIN);
-        launch_lookup_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
-                           ctx->cur_radix_bits, ctx->lookup_which, ctx->mult_out, ctx->mult_out_rows, d_agg,
-                           (u32 *)(d_agg + AGG_MAX_COLS + 1), d_count + 7,
-                           narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                           narrow ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
-                           narrow ? (const u32 *)ctx->narrow_flag.p : nullptr);
+        launch_lookup_join(ctx->stream, ctx->cur_R, ctx->cur_S, k.tasks, k.ntasks, k.max_tasks, ctx->cur_radix_bits, a.lookup_which, a.mult_out,
+                           a.mult_out_rows, k.agg, k.bad, k.max_tables, k.narrow ? narrow_ids(ctx->cur_R, ctx->cur_nR) : nullptr,
+                           k.narrow ? narrow_ids(ctx->cur_S, ctx->cur_nS) : nullptr, k.skip);
     }
-    RHJCHK(check_launch(ctx, "lookup join phase"));
-    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, oversized table side, -, most tables of a task (if > 1)
-    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // matched, -, -, -, -, guard flags
-    u32 wide_rowid = 0;
-    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
-    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
-    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
-    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
-    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
-    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
-    ctx->last_semi_tables = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
-    if (host[5])
-        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    u64 host[8], agg[8];                               // agg: matched, -, -, -, -, guard flags
+    RHJCHK(keyed_finish(ctx, k, "lookup join phase", host, agg));
+    ctx->last_semi_tables = keyed_rounds(host, (u32)ctx->last.ntasks);
+    if (host[5]) return part_too_large(ctx, "S", host[5]);
     const u32 bad = (u32)agg[AGG_MAX_COLS + 1];
     if (bad & LOOKUP_BAD_ROW_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= out_rows: d_out has no such word");
     if (bad & LOOKUP_BAD_ROW_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= 2^63: RHJ_LOOKUP_LAST orders rowIDs as signed words");
@@ -1855,66 +1790,28 @@ int lookup_phase(rhj_ctx *ctx, u64 *out_matched)
 }
 
 // Group-by phase on the partitions of R that a one-sided partition_phase left: k_make_semi_tasks with anti = 1 over a
-// ZEROED boundary array of S and split = 2^32 - 1 -- one task per non-empty partition of R, the whole partition -- then k_group_bkt
-// over the columns and outputs the entry point left in the context.  EVERY attempt zeroes the group counter and the guard flag
-// before its kernel: a repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes as semi_phase.
+// ZEROED boundary array of S and a split that never cuts -- one task per non-empty partition of R, the whole partition -- then
+// k_group_bkt over the columns and outputs of the call.  Retry codes as semi_phase.
 int group_phase(rhj_ctx *ctx, u64 *out_groups)
 {
-    const u64 nR = ctx->cur_nR, nparts = ctx->cur_nparts;
-    const bool narrow = ctx->cur_narrow != 0;
-    const u32 split = 0xffffffffu;                     // a partition is never cut: its keys would be emitted twice
-    const u64 max_tasks64 = nparts + nR / split + 1;
-    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
-    const u32 max_tasks = (u32)max_tasks64;
-    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
-    RHJCHK(ensure(ctx, ctx->counters, 64));
-    RHJCHK(ensure(ctx, ctx->agg_out, 64));
-    RHJCHK(ensure(ctx, ctx->ps_S, (size_t)(nparts + 1) * 8));
-    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
-    {
-        Span s(ctx, RHJ_K_AUX);
-        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(ctx->ps_S.p, 0, (size_t)(nparts + 1) * 8, ctx->stream));   // every partition of S: empty, at 0
-        if (ctx->gid[0]) launch_group_id_words(ctx->stream, d_agg, ctx->gid[0], ctx->gid_rows[0], nullptr, 0);
-    }
-    ctx->counters_clean = false;
-    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
-        Span s(ctx, RHJ_K_AUX);
-        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
-    }
-    ctx->last_join_kind = JK_GROUP;
-    ctx->sniff_ready = false;
-    {
-        Span s(ctx, RHJ_K_TASKS);
-        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, (const u64 *)ctx->ps_S.p, nparts, split, 1, (JoinTask *)ctx->tasks.p,
-                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
-    }
+    const CallArgs &a = ctx->call;
+    Keyed k;
+    RHJCHK(keyed_begin(ctx, k, CLEAR_COUNTERS_AGG, JK_GROUP, NEVER_CUT, ctx->cur_nR, 1, ctx->cur_psR, nullptr, [&]() -> int {
+        if (a.gid[0]) launch_group_id_words(ctx->stream, k.agg, a.gid[0], a.gid_rows[0], nullptr, 0);
+        return RHJ_OK;
+    }));
     {
         Span s(ctx, RHJ_K_JOIN);
-        launch_group(ctx->stream, ctx->cur_R, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks, ctx->cur_radix_bits,
-                     ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, ctx->agg_cols, ctx->agg_ncols, ctx->agg_col_rows,
-                     ctx->group_keys, ctx->group_counts, ctx->group_sums, ctx->group_cap, d_agg, (u32 *)(d_agg + AGG_MAX_COLS + 1),
-                     d_count + 7, narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                     narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops, ctx->gid[0] != nullptr,
-                     ctx->group_arg ? ctx->group_rows : nullptr);
+        launch_group(ctx->stream, ctx->cur_R, k.tasks, k.ntasks, k.max_tasks, ctx->cur_radix_bits,
+                     ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, a.agg_cols, a.agg_ncols, a.agg_col_rows, a.group_keys, a.group_counts,
+                     a.group_sums, a.group_cap, k.agg, k.bad, k.max_tables, k.narrow ? narrow_ids(ctx->cur_R, ctx->cur_nR) : nullptr, k.skip,
+                     a.group_ops, a.gid[0] != nullptr, a.group_arg ? a.group_rows : nullptr);
     }
-    RHJCHK(check_launch(ctx, "group-by phase"));
-    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, -, -, -, -, most table builds of a task (if > 1)
-    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // groups, -, -, -, -, guard flag
-    u32 wide_rowid = 0;
-    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
-    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
-    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
-    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
-    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
+    u64 host[8], agg[8];                               // agg: groups, -, -, -, -, guard flag
+    RHJCHK(keyed_finish(ctx, k, "group-by phase", host, agg));
     ctx->last_max_part[1] = 0;
-    ctx->last_group_rounds = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
-    if (host[2] >> 32)                                           // (such a partition was cut in two: its groups are not the result)
-        return fail(ctx, RHJ_E_INVALID, "a partition of R has " + std::to_string(host[2]) + " tuples (>= 2^32): use more radix bits");
+    ctx->last_group_rounds = keyed_rounds(host, (u32)ctx->last.ntasks);
+    if (host[2] >> 32) return part_too_large(ctx, "R", host[2]);   // (such a partition was cut in two: its groups are not the result)
     if ((u32)agg[AGG_MAX_COLS + 1] & GROUP_BAD_ROW)
         return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= col_rows: the weight columns have no such row");
     if ((u32)agg[AGG_MAX_COLS + 1] & GROUP_BAD_GID)
@@ -1927,83 +1824,40 @@ int group_phase(rhj_ctx *ctx, u64 *out_groups)
 static int fill_no_group(rhj_ctx *ctx)
 {
     for (int side = 0; side < 2; side++)
-        if (ctx->gid[side] && ctx->gid_rows[side])
-            HIPCHK(ctx, hipMemsetAsync(ctx->gid[side], 0xff, (size_t)ctx->gid_rows[side] * 8, ctx->stream));
+        if (ctx->call.gid[side] && ctx->call.gid_rows[side])
+            HIPCHK(ctx, hipMemsetAsync(ctx->call.gid[side], 0xff, (size_t)ctx->call.gid_rows[side] * 8, ctx->stream));
     return RHJ_OK;
 }
 
 // Group-by join phase on the partitions partition_phase left: k_make_semi_tasks over the boundary arrays of R and S with
-// split = 2^32 - 1 -- a partition is never cut -- and anti = 1 under RHJ_GJ_LEFT (a task wherever R_k is non-empty), 0 under
-// RHJ_GJ_INNER (R_k and S_k non-empty), then k_gjoin_bkt over the columns and outputs the entry point left in the context.  After a
-// one-sided partition_phase (LEFT with an empty S) S's boundary array is a zeroed one, as in group_phase.  EVERY attempt zeroes the
-// group counter and the guard flags before its kernel: a repeat (count-free overflow, wide rowID) starts from nothing.  Retry codes
-// as semi_phase.
+// a split that never cuts and anti = 1 under RHJ_GJ_LEFT (a task wherever R_k is non-empty), 0 under RHJ_GJ_INNER (R_k and S_k
+// non-empty), then k_gjoin_bkt over the columns and outputs of the call.  After a one-sided partition_phase (LEFT with an empty S) S's
+// boundary array is a zeroed one, as in group_phase.  Retry codes as semi_phase.
 int gjoin_phase(rhj_ctx *ctx, u64 *out_groups)
 {
-    const u64 nR = ctx->cur_nR, nS = ctx->cur_nS, nparts = ctx->cur_nparts;
-    const bool narrow = ctx->cur_narrow != 0, one = ctx->one_sided, ids = ctx->gid[0] != nullptr || ctx->gid[1] != nullptr;
-    const u32 split = 0xffffffffu;                     // a partition is never cut: its keys would be emitted twice
-    const u64 max_tasks64 = nparts + nR / split + 1;
-    if (max_tasks64 > 0x7fffffffull) return fail(ctx, RHJ_E_INVALID, "too many join tasks");
-    const u32 max_tasks = (u32)max_tasks64;
-    RHJCHK(ensure(ctx, ctx->tasks, (size_t)max_tasks * sizeof(JoinTask)));
-    RHJCHK(ensure(ctx, ctx->counters, 64));
-    RHJCHK(ensure(ctx, ctx->agg_out, 64));
-    if (one) RHJCHK(ensure(ctx, ctx->ps_S, (size_t)(nparts + 1) * 8));
-    u64 *d_count = (u64 *)ctx->counters.p, *d_agg = (u64 *)ctx->agg_out.p;
-    {
-        Span s(ctx, RHJ_K_AUX);
-        if (!ctx->counters_clean) HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(ctx->agg_out.p, 0, 64, ctx->stream));
-        if (one) HIPCHK(ctx, hipMemsetAsync(ctx->ps_S.p, 0, (size_t)(nparts + 1) * 8, ctx->stream));   // every partition of S: empty, at 0
-        if (ids) {                                     // "no group" everywhere, on every attempt: the kernel stores group indices only
-            RHJCHK(fill_no_group(ctx));
-            launch_group_id_words(ctx->stream, d_agg, ctx->gid[0], ctx->gid_rows[0], ctx->gid[1], ctx->gid_rows[1]);
-        }
-    }
-    ctx->counters_clean = false;
-    if (ctx->cur_radix_bits == 0) {                    // unpartitioned: partition_phase writes the boundaries {0, n} for some sizes only
-        Span s(ctx, RHJ_K_AUX);
-        launch_init_single_segment(ctx->stream, nR, PART_TILE, (u64 *)ctx->ps_R.p, (u32 *)((u64 *)ctx->ps_R.p + 4));
-        if (!one) launch_init_single_segment(ctx->stream, nS, PART_TILE, (u64 *)ctx->ps_S.p, (u32 *)((u64 *)ctx->ps_S.p + 4));
-    }
-    ctx->last_join_kind = JK_GJOIN;
-    ctx->sniff_ready = false;
-    const u64 *psS = one ? (const u64 *)ctx->ps_S.p : ctx->cur_psS;
-    {
-        Span s(ctx, RHJ_K_TASKS);
-        launch_make_semi_tasks(ctx->stream, ctx->cur_psR, psS, nparts, split, ctx->gjoin_left ? 1 : 0, (JoinTask *)ctx->tasks.p,
-                               (u32 *)(d_count + 1), max_tasks, d_count + 2);
-    }
+    const CallArgs &a = ctx->call;
+    const bool ids = a.gid[0] != nullptr || a.gid[1] != nullptr;
+    Keyed k;
+    RHJCHK(keyed_begin(ctx, k, CLEAR_COUNTERS_AGG, JK_GJOIN, NEVER_CUT, ctx->cur_nR, a.gjoin_left ? 1 : 0, ctx->cur_psR,
+                       a.one_sided ? nullptr : ctx->cur_psS, [&]() -> int {
+        if (!ids) return RHJ_OK;                       // "no group" everywhere, on every attempt: the kernel stores group indices only
+        RHJCHK(fill_no_group(ctx));
+        launch_group_id_words(ctx->stream, k.agg, a.gid[0], a.gid_rows[0], a.gid[1], a.gid_rows[1]);
+        return RHJ_OK;
+    }));
     {
         Span s(ctx, RHJ_K_JOIN);
-        launch_group_join(ctx->stream, ctx->cur_R, ctx->cur_S, (const JoinTask *)ctx->tasks.p, (const u32 *)(d_count + 1), max_tasks,
-                          ctx->cur_radix_bits, ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, ctx->gjoin_left, ctx->agg_cols,
-                          ctx->agg_ncols, ctx->agg_col_rows, ctx->gjoin_colsS, ctx->gjoin_ncolsS, ctx->gjoin_colS_rows, ctx->group_keys,
-                          ctx->group_counts, ctx->gjoin_cntS, ctx->group_sums, ctx->gjoin_sumsS, ctx->group_cap, d_agg,
-                          (u32 *)(d_agg + AGG_MAX_COLS + 1), d_count + 7,
-                          narrow ? (const u32 *)((const unsigned char *)ctx->cur_R + narrow_k_offset(nR)) : nullptr,
-                          narrow && ctx->cur_S ? (const u32 *)((const unsigned char *)ctx->cur_S + narrow_k_offset(nS)) : nullptr,
-                          narrow ? (const u32 *)ctx->narrow_flag.p : nullptr, ctx->group_ops, ids);
+        launch_group_join(ctx->stream, ctx->cur_R, ctx->cur_S, k.tasks, k.ntasks, k.max_tasks, ctx->cur_radix_bits,
+                          ctx->cur_radix_bits != 0 && join_mix(ctx) != MIX_NONE, a.gjoin_left, a.agg_cols, a.agg_ncols, a.agg_col_rows,
+                          a.gjoin_colsS, a.gjoin_ncolsS, a.gjoin_colS_rows, a.group_keys, a.group_counts, a.gjoin_cntS, a.group_sums,
+                          a.gjoin_sumsS, a.group_cap, k.agg, k.bad, k.max_tables, k.narrow ? narrow_ids(ctx->cur_R, ctx->cur_nR) : nullptr,
+                          k.narrow && ctx->cur_S ? narrow_ids(ctx->cur_S, ctx->cur_nS) : nullptr, k.skip, a.group_ops, ids);
     }
-    RHJCHK(check_launch(ctx, "group-by join phase"));
-    u64 host[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // -, ntasks, max |R_k|, max |S_k|, -, an |S_k| >= 2^32, -, most table builds of a task (if > 1)
-    u64 agg[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // groups, -, -, -, -, guard flags
-    u32 wide_rowid = 0;
-    HIPCHK(ctx, hipMemcpyAsync(host, ctx->counters.p, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(agg, ctx->agg_out.p, sizeof(agg), hipMemcpyDeviceToHost, ctx->stream));
-    if (narrow) HIPCHK(ctx, hipMemcpyAsync(&wide_rowid, ctx->narrow_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (wide_rowid & 1u) return RHJ_RETRY_WIDE;                  // a rowID did not fit 32 bits: nothing of this run is valid
-    if (wide_rowid) { ctx->cf_over = wide_rowid; return RHJ_RETRY_CF; }   // a count-free pass 1 met a run longer than its region
-    ctx->last.ntasks = (u32)(host[1] & 0xffffffffu);
-    ctx->last_max_part[0] = nparts > 1 ? host[2] : 0;
-    ctx->last_max_part[1] = nparts > 1 ? host[3] : 0;
-    ctx->last_group_rounds = host[7] ? (int)host[7] : (ctx->last.ntasks ? 1 : 0);
-    if (host[2] >> 32)                                           // (such a partition was cut in two: its groups are not the result)
-        return fail(ctx, RHJ_E_INVALID, "a partition of R has " + std::to_string(host[2]) + " tuples (>= 2^32): use more radix bits");
-    if (host[5])
-        return fail(ctx, RHJ_E_INVALID, "a partition of S has " + std::to_string(host[5]) + " tuples (>= 2^32): use more radix bits");
+    u64 host[8], agg[8];                               // agg: groups, -, -, -, -, guard flags
+    RHJCHK(keyed_finish(ctx, k, "group-by join phase", host, agg));
+    ctx->last_group_rounds = keyed_rounds(host, (u32)ctx->last.ntasks);
+    if (host[2] >> 32) return part_too_large(ctx, "R", host[2]);   // (such a partition was cut in two: its groups are not the result)
+    if (host[5]) return part_too_large(ctx, "S", host[5]);
     const u32 bad = (u32)agg[AGG_MAX_COLS + 1];
     if (bad & GJOIN_BAD_ROW_R) return fail(ctx, RHJ_E_INVALID, "a rowID of R is >= colR_rows: the weight columns of R have no such row");
     if (bad & GJOIN_BAD_ROW_S) return fail(ctx, RHJ_E_INVALID, "a rowID of S is >= colS_rows: the weight columns of S have no such row");
@@ -2150,11 +2004,18 @@ int partition_and_join(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S, u
     if (what == OUT_PAIRS && fused_one_pass_ok(ctx, nR, nS, plan))
         return join_one_pass_fused(ctx, d_R, nR, d_S, nS, plan, d_out, cap, out_count, before_S);
     auto after_partition = [&]() {
-        return what == OUT_PAIRS ? join_phase(ctx, d_out, cap, out_count) : what == OUT_SUMS ? agg_phase(ctx, out_count) :
-               what == OUT_MULT ? mult_phase(ctx, out_count) : what == OUT_GROUP ? group_phase(ctx, out_count) :
-               what == OUT_GJOIN ? gjoin_phase(ctx, out_count) : what == OUT_LOOKUP ? lookup_phase(ctx, out_count) :
-               what == OUT_OUTER ? outer_phase(ctx, d_out, cap, out_count) :
-               semi_phase(ctx, what, d_out, cap, out_count);
+        switch (what) {
+        case OUT_PAIRS: return join_phase(ctx, d_out, cap, out_count);
+        case OUT_SEMI:
+        case OUT_ANTI: return semi_phase(ctx, what, d_out, cap, out_count);
+        case OUT_SUMS: return agg_phase(ctx, out_count);
+        case OUT_MULT: return mult_phase(ctx, out_count);
+        case OUT_GROUP: return group_phase(ctx, out_count);
+        case OUT_GJOIN: return gjoin_phase(ctx, out_count);
+        case OUT_OUTER: return outer_phase(ctx, d_out, cap, out_count);
+        case OUT_LOOKUP: return lookup_phase(ctx, out_count);
+        }
+        return fail(ctx, RHJ_E_INVALID, "no phase for this output");
     };
     const bool gaps_ok = what == OUT_PAIRS;                  // the pair join's task builder reads boundaries with gaps
     int rc = partition_phase(ctx, d_R, nR, d_S, nS, plan, before_S, gaps_ok);
@@ -2551,6 +2412,53 @@ int rhj_reserve(rhj_ctx *ctx, uint64_t nR, uint64_t nS, const rhj_opts *opts)
     return RHJ_OK;
 }
 
+// ---- the scaffold of the device entries, rhj_join_dev through rhj_group_join_agg_ids_cols_dev ---------------------------------------
+// Every entry starts here: the device, the out word -- named as the entry names it -- checked and zeroed, the profile and the
+// "last.*" state reset.
+static int entry_begin(rhj_ctx *ctx, uint64_t *out_word, const char *name)
+{
+    RHJCHK(use_device(ctx));
+    if (!out_word) return fail(ctx, RHJ_E_INVALID, std::string(name) + " is null");
+    *out_word = 0;
+    prof_reset(ctx);
+    return RHJ_OK;
+}
+
+// The relations of a columnar entry, in the context for the length of the call: partition_phase and the one-pass join hand them to the
+// kernels that read columns (fused_input) or convert the side they need (cols_to_aos), also when a join repeats itself (count-free
+// overflow: columns again; wide rowID: the 16-byte copy).  No valS: no S, or an empty one; no idS: rowID = index.
+struct ColsScope {
+    rhj_ctx *c;
+    ColsScope(rhj_ctx *ctx, const uint64_t *valR, const uint64_t *idR, const uint64_t *valS = nullptr, const uint64_t *idS = nullptr) : c(ctx)
+    {
+        c->cols_in[0].val = (const u64 *)valR; c->cols_in[0].id = (const u64 *)idR;
+        c->cols_in[1].val = (const u64 *)valS; c->cols_in[1].id = (const u64 *)idS;
+        c->cols_aos_done[0] = c->cols_aos_done[1] = false;
+    }
+    ~ColsScope() { c->cols_in[0] = c->cols_in[1] = ColsIn(); }
+};
+
+// The operator arguments of an entry (ctx->call) go back to CallArgs() on every way out of its *_common function.
+struct CallScope {
+    rhj_ctx *c;
+    explicit CallScope(rhj_ctx *ctx) : c(ctx) {}
+    ~CallScope() { c->call = CallArgs(); }
+};
+
+// the caller's options as the plan of a device-resident join
+static int entry_plan(rhj_ctx *ctx, u64 nR, u64 nS, const rhj_opts *opts, rhj_opts *plan)
+{
+    if (resolve_plan(nR, nS, opts, plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+    return RHJ_OK;
+}
+
+// the end of an entry that writes rows: more of them than the caller's arrays hold (a count-only call has no array)
+static int check_capacity(rhj_ctx *ctx, const void *d_out, u64 rows, u64 capacity, const char *what = "result buffer")
+{
+    if (d_out && rows > capacity) return fail(ctx, RHJ_E_OVERFLOW, std::string(what) + " too small");
+    return RHJ_OK;
+}
+
 // a join with an empty input runs no kernel: "last.join_kernel" / "last.narrow" say so instead of describing the join before it
 static int join_nothing(rhj_ctx *ctx)
 {
@@ -2559,45 +2467,52 @@ static int join_nothing(rhj_ctx *ctx)
     return RHJ_OK;
 }
 
-int rhj_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
-                 const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count)
+// What a partition phase would leave for a join whose one side is empty: the other side (`side`, d_P) unpartitioned, its one partition
+// standing for both sides -- no tuple of the empty side is read.
+static int one_partition(rhj_ctx *ctx, u64 nR, u64 nS, int side, const void *d_P)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
-    *out_count = 0;
-    prof_reset(ctx);
-    if (nR == 0 || nS == 0) return join_nothing(ctx);  // nothing to schedule (Result.cpp:101 never fires)
-    if (!d_R || !d_S) return fail(ctx, RHJ_E_INVALID, "null input relation");
-    rhj_opts plan;
-    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
-    RHJCHK(partition_and_join(ctx, d_R, nR, d_S, nS, plan, d_out, d_out ? out_capacity : 0, (u64 *)out_count));
-    if (d_out && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
+    ctx->cur_nR = nR;
+    ctx->cur_nS = nS;
+    ctx->cur_probe_split = 0;
+    ctx->cur_narrow = 0;
+    ctx->last_cf[0] = ctx->last_cf[1] = 0;
+    clear_gaps(ctx);
+    RHJCHK(cols_to_aos(ctx, side, side ? nS : nR, d_P));
+    RHJCHK(ensure(ctx, ctx->ps_R, 64));
+    RHJCHK(ensure(ctx, ctx->ps_S, 64));
+    ctx->cur_R = ctx->cur_S = d_P;
+    ctx->cur_psR = (const u64 *)ctx->ps_R.p;
+    ctx->cur_psS = (const u64 *)ctx->ps_S.p;
+    ctx->cur_nparts = 1;
+    ctx->cur_radix_bits = 0;
     return RHJ_OK;
 }
 
-// rhj_join_dev on relations given as columns.  The columns stay in the context for the length of the call: partition_phase and
-// the one-pass join hand them to the kernels that read columns (fused_input) or convert the side they need (cols_to_aos), also
-// when a join repeats itself (count-free overflow: columns again; wide rowID: the 16-byte copy).
+int rhj_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
+                 const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count)
+{
+    RHJCHK(entry_begin(ctx, out_count, "out_count"));
+    if (nR == 0 || nS == 0) return join_nothing(ctx);  // nothing to schedule (Result.cpp:101 never fires)
+    if (!d_R || !d_S) return fail(ctx, RHJ_E_INVALID, "null input relation");
+    rhj_opts plan;
+    RHJCHK(entry_plan(ctx, nR, nS, opts, &plan));
+    RHJCHK(partition_and_join(ctx, d_R, nR, d_S, nS, plan, d_out, d_out ? out_capacity : 0, (u64 *)out_count));
+    return check_capacity(ctx, d_out, *out_count, out_capacity);
+}
+
+// rhj_join_dev on relations given as columns
 int rhj_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR, const uint64_t *d_valS,
                       const uint64_t *d_idS, uint64_t nS, const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity,
                       uint64_t *out_count)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
-    *out_count = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_count, "out_count"));
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
     if (nR == 0 || nS == 0) return join_nothing(ctx);
     rhj_opts plan;
-    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
-    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = partition_and_join(ctx, nullptr, nR, nullptr, nS, plan, d_out, d_out ? out_capacity : 0, (u64 *)out_count);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    RHJCHK(rc);
-    if (d_out && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
-    return RHJ_OK;
+    RHJCHK(entry_plan(ctx, nR, nS, opts, &plan));
+    ColsScope cols(ctx, d_valR, d_idR, d_valS, d_idS);
+    RHJCHK(partition_and_join(ctx, nullptr, nR, nullptr, nS, plan, d_out, d_out ? out_capacity : 0, (u64 *)out_count));
+    return check_capacity(ctx, d_out, *out_count, out_capacity);
 }
 
 // Semi / anti join: the partition phase and the repeat ladder of rhj_join_dev / rhj_join_cols_dev, then semi_phase.
@@ -2609,40 +2524,23 @@ static int semi_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d
     if (nR == 0 || (nS == 0 && kind == RHJ_SEMI)) return join_nothing(ctx);
     const u64 cap = d_out_ids ? out_capacity : 0;
     if (nS == 0) {
-        ctx->cur_nR = nR;
-        ctx->cur_nS = 0;
-        ctx->cur_probe_split = 0;
-        ctx->cur_narrow = 0;
         ctx->counters_clean = false;
-        ctx->last_cf[0] = ctx->last_cf[1] = 0;
-        clear_gaps(ctx);
-        RHJCHK(cols_to_aos(ctx, 0, nR, d_R));
-        RHJCHK(ensure(ctx, ctx->ps_R, 64));
-        RHJCHK(ensure(ctx, ctx->ps_S, 64));
-        ctx->cur_R = ctx->cur_S = d_R;                 // (no tuple of S is read)
-        ctx->cur_psR = (const u64 *)ctx->ps_R.p;
-        ctx->cur_psS = (const u64 *)ctx->ps_S.p;
-        ctx->cur_nparts = 1;
-        ctx->cur_radix_bits = 0;
+        RHJCHK(one_partition(ctx, nR, 0, 0, d_R));
         const int rc = semi_phase(ctx, OUT_ANTI, d_out_ids, cap, (u64 *)out_count);
         if (rc != RHJ_OK) return rc > 0 ? fail(ctx, RHJ_E_HIP, "semi join: a repeat was asked for without a partition phase") : rc;
     } else {
         rhj_opts plan;
-        if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+        RHJCHK(entry_plan(ctx, nR, nS, opts, &plan));
         RHJCHK(partition_and_join(ctx, d_R, nR, d_S, nS, plan, d_out_ids, cap, (u64 *)out_count, nullptr,
                                   kind == RHJ_ANTI ? OUT_ANTI : OUT_SEMI));
     }
-    if (d_out_ids && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
-    return RHJ_OK;
+    return check_capacity(ctx, d_out_ids, *out_count, out_capacity);
 }
 
 int rhj_semi_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, int kind,
                       const rhj_opts *opts, uint64_t *d_out_ids, uint64_t out_capacity, uint64_t *out_count)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
-    *out_count = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_count, "out_count"));
     if (kind != RHJ_SEMI && kind != RHJ_ANTI) return fail(ctx, RHJ_E_INVALID, "kind is neither RHJ_SEMI nor RHJ_ANTI");
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return semi_join_common(ctx, d_R, nR, d_S, nS, kind, opts, d_out_ids, out_capacity, out_count);
@@ -2652,18 +2550,11 @@ int rhj_semi_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
                            uint64_t nS, int kind, const rhj_opts *opts, uint64_t *d_out_ids, uint64_t out_capacity,
                            uint64_t *out_count)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
-    *out_count = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_count, "out_count"));
     if (kind != RHJ_SEMI && kind != RHJ_ANTI) return fail(ctx, RHJ_E_INVALID, "kind is neither RHJ_SEMI nor RHJ_ANTI");
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
-    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = nullptr;      // S has no id column: rowID = index, never reported
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = semi_join_common(ctx, nullptr, nR, nullptr, nS, kind, opts, d_out_ids, out_capacity, out_count);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR, d_valS);        // S has no id column: rowID = index, never reported
+    return semi_join_common(ctx, nullptr, nR, nullptr, nS, kind, opts, d_out_ids, out_capacity, out_count);
 }
 
 // Outer join: the partition phase and the repeat ladder of rhj_join_dev / rhj_join_cols_dev, then outer_phase.
@@ -2673,27 +2564,14 @@ static int outer_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *
                              rhj_pair *d_out, u64 out_capacity, uint64_t *out_count, uint64_t *out_sections)
 {
     const u64 cap = d_out ? out_capacity : 0;
-    ctx->outer_how = how;
+    CallScope call(ctx);
+    ctx->call.outer_how = how;
     ctx->outer_sections[0] = ctx->outer_sections[1] = ctx->outer_sections[2] = 0;
     if (nR == 0 || nS == 0) {
         const int side = nR == 0 ? 1 : 0;              // the side that may have tuples
         if ((nR == 0 && nS == 0) || !(how & (1 << side))) return join_nothing(ctx);
-        ctx->cur_nR = nR;
-        ctx->cur_nS = nS;
-        ctx->cur_probe_split = 0;
-        ctx->cur_narrow = 0;
-        ctx->last_cf[0] = ctx->last_cf[1] = 0;
-        clear_gaps(ctx);
-        const void *d_P = side ? d_S : d_R;
-        RHJCHK(cols_to_aos(ctx, side, side ? nS : nR, d_P));
-        RHJCHK(ensure(ctx, ctx->ps_R, 64));
-        RHJCHK(ensure(ctx, ctx->ps_S, 64));
+        RHJCHK(one_partition(ctx, nR, nS, side, side ? d_S : d_R));
         RHJCHK(ensure(ctx, ctx->counters, 64));
-        ctx->cur_R = ctx->cur_S = d_P;                 // (no tuple of the empty side is read)
-        ctx->cur_psR = (const u64 *)ctx->ps_R.p;
-        ctx->cur_psS = (const u64 *)ctx->ps_S.p;
-        ctx->cur_nparts = 1;
-        ctx->cur_radix_bits = 0;
         {
             Span s(ctx, RHJ_K_AUX);
             HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
@@ -2708,23 +2586,26 @@ static int outer_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *
         ctx->outer_sections[1 + side] = *out_count;
     } else {
         rhj_opts plan;
-        if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
+        RHJCHK(entry_plan(ctx, nR, nS, opts, &plan));
         RHJCHK(partition_and_join(ctx, d_R, nR, d_S, nS, plan, d_out, cap, (u64 *)out_count, nullptr, OUT_OUTER));
     }
     if (out_sections) for (int i = 0; i < 3; i++) out_sections[i] = ctx->outer_sections[i];
-    if (d_out && *out_count > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffer too small");
+    return check_capacity(ctx, d_out, *out_count, out_capacity);
+}
+
+// the prologue of the two outer-join entries: entry_begin, the sections zeroed beside the out word, `how`
+static int outer_begin(rhj_ctx *ctx, int how, uint64_t *out_count, uint64_t *out_sections)
+{
+    RHJCHK(entry_begin(ctx, out_count, "out_count"));
+    if (out_sections) out_sections[0] = out_sections[1] = out_sections[2] = 0;
+    if (how < RHJ_OUTER_LEFT || how > RHJ_OUTER_FULL) return fail(ctx, RHJ_E_INVALID, "how is none of RHJ_OUTER_LEFT, RHJ_OUTER_RIGHT, RHJ_OUTER_FULL");
     return RHJ_OK;
 }
 
 int rhj_outer_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, int how,
                        const rhj_opts *opts, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count, uint64_t *out_sections)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
-    *out_count = 0;
-    if (out_sections) out_sections[0] = out_sections[1] = out_sections[2] = 0;
-    prof_reset(ctx);
-    if (how < RHJ_OUTER_LEFT || how > RHJ_OUTER_FULL) return fail(ctx, RHJ_E_INVALID, "how is none of RHJ_OUTER_LEFT, RHJ_OUTER_RIGHT, RHJ_OUTER_FULL");
+    RHJCHK(outer_begin(ctx, how, out_count, out_sections));
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return outer_join_common(ctx, d_R, nR, d_S, nS, how, opts, d_out, out_capacity, out_count, out_sections);
 }
@@ -2733,19 +2614,10 @@ int rhj_outer_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t
                             const uint64_t *d_idS, uint64_t nS, int how, const rhj_opts *opts, rhj_pair *d_out,
                             uint64_t out_capacity, uint64_t *out_count, uint64_t *out_sections)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
-    *out_count = 0;
-    if (out_sections) out_sections[0] = out_sections[1] = out_sections[2] = 0;
-    prof_reset(ctx);
-    if (how < RHJ_OUTER_LEFT || how > RHJ_OUTER_FULL) return fail(ctx, RHJ_E_INVALID, "how is none of RHJ_OUTER_LEFT, RHJ_OUTER_RIGHT, RHJ_OUTER_FULL");
+    RHJCHK(outer_begin(ctx, how, out_count, out_sections));
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
-    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = outer_join_common(ctx, nullptr, nR, nullptr, nS, how, opts, d_out, out_capacity, out_count, out_sections);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR, d_valS, d_idS);
+    return outer_join_common(ctx, nullptr, nR, nullptr, nS, how, opts, d_out, out_capacity, out_count, out_sections);
 }
 
 // Aggregating join: the partition phase and the repeat ladder of rhj_join_dev / rhj_join_cols_dev, then agg_phase.
@@ -2761,25 +2633,21 @@ static int join_sum_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_
     }
     if (nR == 0 || nS == 0) return join_nothing(ctx);
     rhj_opts plan;
-    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
-    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) ctx->agg_cols[j] = j < ncols ? (const u64 *)d_cols[j] : nullptr;
-    ctx->agg_ncols = ncols;
-    ctx->agg_col_rows = ncols ? col_rows : ~0ull;
-    ctx->agg_sums_out = (u64 *)out_sums;
-    const int rc = partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_count, nullptr, OUT_SUMS);
-    ctx->agg_ncols = 0;
-    ctx->agg_sums_out = nullptr;
-    return rc;
+    RHJCHK(entry_plan(ctx, nR, nS, opts, &plan));
+    CallScope call(ctx);
+    CallArgs &a = ctx->call;
+    for (u32 j = 0; j < ncols; j++) a.agg_cols[j] = (const u64 *)d_cols[j];
+    a.agg_ncols = ncols;
+    a.agg_col_rows = ncols ? col_rows : ~0ull;
+    a.agg_sums_out = (u64 *)out_sums;
+    return partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_count, nullptr, OUT_SUMS);
 }
 
 int rhj_join_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                      const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows,
                      const rhj_opts *opts, uint64_t *out_count, uint64_t *out_sums)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
-    *out_count = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_count, "out_count"));
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return join_sum_common(ctx, d_R, nR, d_S, nS, d_cols, ncols, col_rows, opts, out_count, out_sums);
 }
@@ -2788,17 +2656,20 @@ int rhj_join_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *
                           const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
                           uint64_t *out_count, uint64_t *out_sums)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_count) return fail(ctx, RHJ_E_INVALID, "out_count is null");
-    *out_count = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_count, "out_count"));
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
-    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = nullptr;      // S has no id column: rowID = index, never looked at
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = join_sum_common(ctx, nullptr, nR, nullptr, nS, d_cols, ncols, col_rows, opts, out_count, out_sums);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR, d_valS);        // S has no id column: rowID = index, never looked at
+    return join_sum_common(ctx, nullptr, nR, nullptr, nS, d_cols, ncols, col_rows, opts, out_count, out_sums);
+}
+
+// The words of a multiplicity or lookup join with an empty input -- all `byte` -- complete when the call returns.
+static int fill_out_words(rhj_ctx *ctx, uint64_t *d_out, uint64_t out_rows, int byte)
+{
+    if (out_rows) {
+        HIPCHK(ctx, hipMemsetAsync(d_out, byte, out_rows * 8, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return join_nothing(ctx);
 }
 
 // Multiplicity join: the partition phase and the repeat ladder of rhj_join_dev / rhj_join_cols_dev, then mult_phase.
@@ -2807,34 +2678,22 @@ static int join_mult_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d
                             const rhj_opts *opts, uint64_t *d_out, uint64_t out_rows, uint64_t *out_total)
 {
     if (out_rows && !d_out) return fail(ctx, RHJ_E_INVALID, "d_out is null");
-    if (nR == 0 || nS == 0) {                          // all zero, and complete when the call returns
-        if (out_rows) {
-            HIPCHK(ctx, hipMemsetAsync(d_out, 0, out_rows * 8, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        return join_nothing(ctx);
-    }
+    if (nR == 0 || nS == 0) return fill_out_words(ctx, d_out, out_rows, 0);
     rhj_opts plan;
-    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
-    ctx->mult_w = (const u64 *)d_wS;
-    ctx->mult_w_rows = d_wS ? wS_rows : 0;
-    ctx->mult_out = (u64 *)d_out;
-    ctx->mult_out_rows = out_rows;
-    const int rc = partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_total, nullptr, OUT_MULT);
-    ctx->mult_w = nullptr;
-    ctx->mult_out = nullptr;
-    ctx->mult_w_rows = ctx->mult_out_rows = 0;
-    return rc;
+    RHJCHK(entry_plan(ctx, nR, nS, opts, &plan));
+    CallScope call(ctx);
+    ctx->call.mult_w = (const u64 *)d_wS;
+    ctx->call.mult_w_rows = d_wS ? wS_rows : 0;
+    ctx->call.mult_out = (u64 *)d_out;
+    ctx->call.mult_out_rows = out_rows;
+    return partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_total, nullptr, OUT_MULT);
 }
 
 int rhj_join_mult_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
                       const uint64_t *d_wS, uint64_t wS_rows, const rhj_opts *opts,
                       uint64_t *d_out, uint64_t out_rows, uint64_t *out_total)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_total) return fail(ctx, RHJ_E_INVALID, "out_total is null");
-    *out_total = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_total, "out_total"));
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return join_mult_common(ctx, d_R, nR, d_S, nS, d_wS, wS_rows, opts, d_out, out_rows, out_total);
 }
@@ -2844,17 +2703,10 @@ int rhj_join_mult_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
                            const uint64_t *d_wS, uint64_t wS_rows, const rhj_opts *opts,
                            uint64_t *d_out, uint64_t out_rows, uint64_t *out_total)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_total) return fail(ctx, RHJ_E_INVALID, "out_total is null");
-    *out_total = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_total, "out_total"));
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
-    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;   // S's rowIDs name its weights
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = join_mult_common(ctx, nullptr, nR, nullptr, nS, d_wS, wS_rows, opts, d_out, out_rows, out_total);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR, d_valS, d_idS);  // S's rowIDs name its weights
+    return join_mult_common(ctx, nullptr, nR, nullptr, nS, d_wS, wS_rows, opts, d_out, out_rows, out_total);
 }
 
 // Lookup join: the partition phase and the repeat ladder of rhj_join_mult_dev / rhj_join_mult_cols_dev, then
@@ -2865,31 +2717,20 @@ static int lookup_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *d_S,
 {
     if (which != RHJ_LOOKUP_FIRST && which != RHJ_LOOKUP_LAST) return fail(ctx, RHJ_E_INVALID, "which is neither RHJ_LOOKUP_FIRST nor RHJ_LOOKUP_LAST");
     if (out_rows && !d_out) return fail(ctx, RHJ_E_INVALID, "d_out is null");
-    if (nR == 0 || nS == 0) {                          // all ones, and complete when the call returns
-        if (out_rows) {
-            HIPCHK(ctx, hipMemsetAsync(d_out, 0xFF, out_rows * 8, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        return join_nothing(ctx);
-    }
+    if (nR == 0 || nS == 0) return fill_out_words(ctx, d_out, out_rows, 0xFF);
     rhj_opts plan;
-    if (resolve_plan(nR, nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
-    ctx->mult_out = (u64 *)d_out;
-    ctx->mult_out_rows = out_rows;
-    ctx->lookup_which = which;
-    const int rc = partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_matched, nullptr, OUT_LOOKUP);
-    ctx->mult_out = nullptr;
-    ctx->mult_out_rows = 0;
-    return rc;
+    RHJCHK(entry_plan(ctx, nR, nS, opts, &plan));
+    CallScope call(ctx);
+    ctx->call.mult_out = (u64 *)d_out;
+    ctx->call.mult_out_rows = out_rows;
+    ctx->call.lookup_which = which;
+    return partition_and_join(ctx, d_R, nR, d_S, nS, plan, nullptr, 0, (u64 *)out_matched, nullptr, OUT_LOOKUP);
 }
 
 int rhj_lookup_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS, int which,
                    const rhj_opts *opts, uint64_t *d_out, uint64_t out_rows, uint64_t *out_matched)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_matched) return fail(ctx, RHJ_E_INVALID, "out_matched is null");
-    *out_matched = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_matched, "out_matched"));
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return lookup_common(ctx, d_R, nR, d_S, nS, which, opts, d_out, out_rows, out_matched);
 }
@@ -2898,17 +2739,10 @@ int rhj_lookup_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_
                         const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS, int which, const rhj_opts *opts,
                         uint64_t *d_out, uint64_t out_rows, uint64_t *out_matched)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_matched) return fail(ctx, RHJ_E_INVALID, "out_matched is null");
-    *out_matched = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_matched, "out_matched"));
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;
-    ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS;   // S's rowIDs are the answer
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = lookup_common(ctx, nullptr, nR, nullptr, nS, which, opts, d_out, out_rows, out_matched);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR, d_valS, d_idS);  // S's rowIDs are the answer
+    return lookup_common(ctx, nullptr, nR, nullptr, nS, which, opts, d_out, out_rows, out_matched);
 }
 
 // Group-by: R alone through the partition phase and the repeat ladder of the joins (one-sided, planned as an aggregating
@@ -2949,7 +2783,7 @@ static int group_common(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *c
                      out_groups, d_out_gid, gid_rows);
 }
 
-// The checked arguments of a group-by entry into the context, the one-sided partition phase and group_phase, and out of it again.
+// The checked arguments of a group-by entry into the context, the one-sided partition phase and group_phase.
 // nsum: the columns the kernel sweeps (0 in a count-only call); packed: their op words -- AGG_OP_*, or with d_out_rows (DESIGN 4.23:
 // nsum rows arrays beside the nsum value arrays) ARG_OP_*.
 static int group_run(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *const *d_cols, u32 packed, u32 nsum, uint64_t col_rows,
@@ -2958,35 +2792,26 @@ static int group_run(rhj_ctx *ctx, const void *d_R, u64 nR, const uint64_t *cons
 {
     if (nR == 0) return join_nothing(ctx);
     rhj_opts plan;
-    if (resolve_plan(nR, nR, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
-    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
-        ctx->agg_cols[j] = j < nsum ? (const u64 *)d_cols[j] : nullptr;
-        ctx->group_sums[j] = j < nsum ? (u64 *)d_out_sums[j] : nullptr;
-        ctx->group_rows[j] = j < nsum && d_out_rows ? (u64 *)d_out_rows[j] : nullptr;
+    RHJCHK(entry_plan(ctx, nR, nR, opts, &plan));
+    CallScope call(ctx);
+    CallArgs &a = ctx->call;
+    for (u32 j = 0; j < nsum; j++) {
+        a.agg_cols[j] = (const u64 *)d_cols[j];
+        a.group_sums[j] = (u64 *)d_out_sums[j];
+        a.group_rows[j] = d_out_rows ? (u64 *)d_out_rows[j] : nullptr;
     }
-    ctx->group_arg = d_out_rows != nullptr && nsum != 0;
-    ctx->agg_ncols = nsum;
-    ctx->agg_col_rows = nsum ? col_rows : ~0ull;
-    ctx->group_keys = (u64 *)d_out_keys;
-    ctx->group_counts = d_out_keys ? (u64 *)d_out_counts : nullptr;
-    ctx->group_cap = d_out_keys ? out_capacity : 0;
-    ctx->group_ops = packed;
-    ctx->gid[0] = (u64 *)d_out_gid;
-    ctx->gid_rows[0] = d_out_gid ? gid_rows : 0;
-    ctx->one_sided = true;
-    const int rc = partition_and_join(ctx, d_R, nR, nullptr, nR, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GROUP);
-    ctx->one_sided = false;
-    ctx->gid[0] = nullptr;
-    ctx->gid_rows[0] = 0;
-    ctx->agg_ncols = 0;
-    ctx->group_ops = 0;
-    ctx->group_keys = ctx->group_counts = nullptr;
-    ctx->group_cap = 0;
-    ctx->group_arg = false;
-    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) { ctx->agg_cols[j] = nullptr; ctx->group_sums[j] = nullptr; ctx->group_rows[j] = nullptr; }
-    RHJCHK(rc);
-    if (d_out_keys && *out_groups > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffers too small");
-    return RHJ_OK;
+    a.group_arg = d_out_rows != nullptr && nsum != 0;
+    a.agg_ncols = nsum;
+    a.agg_col_rows = nsum ? col_rows : ~0ull;
+    a.group_keys = (u64 *)d_out_keys;
+    a.group_counts = d_out_keys ? (u64 *)d_out_counts : nullptr;
+    a.group_cap = d_out_keys ? out_capacity : 0;
+    a.group_ops = packed;
+    a.gid[0] = (u64 *)d_out_gid;
+    a.gid_rows[0] = d_out_gid ? gid_rows : 0;
+    a.one_sided = true;
+    RHJCHK(partition_and_join(ctx, d_R, nR, nullptr, nR, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GROUP));
+    return check_capacity(ctx, d_out_keys, *out_groups, out_capacity, "result buffers");
 }
 
 int rhj_group_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
@@ -2994,31 +2819,22 @@ int rhj_group_sum_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
                       uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
                       uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return group_common(ctx, d_R, nR, d_cols, nullptr, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity, out_groups);
 }
 
+// (in the columnar twins the ids travel with the values, also with ncols == 0)
 int rhj_group_sum_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
                            const uint64_t *const *d_cols, uint32_t ncols, uint64_t col_rows, const rhj_opts *opts,
                            uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_sums,
                            uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if (nR && !d_valR) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
-    ctx->cols_in[1] = ColsIn();
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_common(ctx, nullptr, nR, d_cols, nullptr, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity,
-                                out_groups);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR);
+    return group_common(ctx, nullptr, nR, d_cols, nullptr, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_sums, out_capacity,
+                        out_groups);
 }
 
 // ... with an aggregate per column: the same host path, the columns' ops beside them
@@ -3027,10 +2843,7 @@ int rhj_group_agg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
                       uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_aggs,
                       uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return group_common(ctx, d_R, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity, out_groups);
 }
@@ -3040,18 +2853,11 @@ int rhj_group_agg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
                            uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_aggs,
                            uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if (nR && !d_valR) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
-    ctx->cols_in[1] = ColsIn();
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_common(ctx, nullptr, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity,
-                                out_groups);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR);
+    return group_common(ctx, nullptr, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity,
+                        out_groups);
 }
 
 // ... with the group of every row: the same host path, the id array beside the outputs; a null array: the entry above
@@ -3060,10 +2866,7 @@ int rhj_group_agg_ids_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
                           uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_aggs,
                           uint64_t out_capacity, uint64_t *out_groups, uint64_t *d_out_gid, uint64_t gid_rows)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return group_common(ctx, d_R, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity, out_groups,
                         d_out_gid, gid_rows);
@@ -3074,18 +2877,11 @@ int rhj_group_agg_ids_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint6
                                uint64_t *d_out_keys, uint64_t *d_out_counts, uint64_t *const *d_out_aggs,
                                uint64_t out_capacity, uint64_t *out_groups, uint64_t *d_out_gid, uint64_t gid_rows)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if (nR && !d_valR) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
-    ctx->cols_in[1] = ColsIn();
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_common(ctx, nullptr, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity,
-                                out_groups, d_out_gid, gid_rows);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR);
+    return group_common(ctx, nullptr, nR, d_cols, ops, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_aggs, out_capacity,
+                        out_groups, d_out_gid, gid_rows);
 }
 
 // ... with the row of every extreme: the same host path; the checks are this entry's own -- a row column has neither a
@@ -3135,10 +2931,7 @@ int rhj_group_arg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
                       const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
                       uint64_t *const *d_out_vals, uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if (nR && !d_R) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return group_arg_common(ctx, d_R, nR, d_cols, ops, ties, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_vals, d_out_rows,
                             out_capacity, out_groups);
@@ -3149,18 +2942,11 @@ int rhj_group_arg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t 
                            const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
                            uint64_t *const *d_out_vals, uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if (nR && !d_valR) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with ncols == 0)
-    ctx->cols_in[1] = ColsIn();
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_arg_common(ctx, nullptr, nR, d_cols, ops, ties, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_vals,
-                                    d_out_rows, out_capacity, out_groups);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR);
+    return group_arg_common(ctx, nullptr, nR, d_cols, ops, ties, ncols, col_rows, opts, d_out_keys, d_out_counts, d_out_vals,
+                            d_out_rows, out_capacity, out_groups);
 }
 
 // Group-by join: the two-sided partition phase and the repeat ladder of rhj_join_mult_dev / rhj_join_mult_cols_dev,
@@ -3192,48 +2978,33 @@ static int group_join_common(rhj_ctx *ctx, const void *d_R, u64 nR, const void *
         if (!d_colsR[j] || !d_out_sumsR[j]) return fail(ctx, RHJ_E_INVALID, "null weight column or sum column of R");
     for (u32 j = 0; j < nsumS; j++)
         if (!d_colsS[j] || !d_out_sumsS[j]) return fail(ctx, RHJ_E_INVALID, "null weight column or sum column of S");
-    ctx->gid[0] = (u64 *)d_out_gidR; ctx->gid_rows[0] = d_out_gidR ? gidR_rows : 0;
-    ctx->gid[1] = (u64 *)d_out_gidS; ctx->gid_rows[1] = d_out_gidS ? gidS_rows : 0;
-    struct GidReset { rhj_ctx *c; ~GidReset() { c->gid[0] = c->gid[1] = nullptr; c->gid_rows[0] = c->gid_rows[1] = 0; } } gid_reset{ctx};
+    CallScope call(ctx);
+    CallArgs &a = ctx->call;
+    a.gid[0] = (u64 *)d_out_gidR; a.gid_rows[0] = d_out_gidR ? gidR_rows : 0;
+    a.gid[1] = (u64 *)d_out_gidS; a.gid_rows[1] = d_out_gidS ? gidS_rows : 0;
     if (nR == 0 || (nS == 0 && mode == RHJ_GJ_INNER)) {    // no group, no kernel: every id word says so when the call returns
         RHJCHK(fill_no_group(ctx));
-        if (ctx->gid[0] || ctx->gid[1]) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (a.gid[0] || a.gid[1]) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return join_nothing(ctx);
     }
     const bool one = nS == 0;                          // LEFT over an empty S: the group-by of R with zero S fields
     rhj_opts plan;
-    if (resolve_plan(nR, one ? nR : nS, opts, &plan, true, default_join_kernels(ctx)) != RHJ_OK) return fail(ctx, RHJ_E_INVALID, "bad rhj_opts");
-    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
-        ctx->agg_cols[j] = j < nsumR ? (const u64 *)d_colsR[j] : nullptr;
-        ctx->group_sums[j] = j < nsumR ? (u64 *)d_out_sumsR[j] : nullptr;
-        ctx->gjoin_colsS[j] = j < nsumS ? (const u64 *)d_colsS[j] : nullptr;
-        ctx->gjoin_sumsS[j] = j < nsumS ? (u64 *)d_out_sumsS[j] : nullptr;
-    }
-    ctx->agg_ncols = nsumR;
-    ctx->agg_col_rows = nsumR ? colR_rows : ~0ull;
-    ctx->gjoin_ncolsS = nsumS;
-    ctx->gjoin_colS_rows = nsumS ? colS_rows : ~0ull;
-    ctx->group_keys = (u64 *)d_out_keys;
-    ctx->group_counts = d_out_keys ? (u64 *)d_out_cntR : nullptr;
-    ctx->gjoin_cntS = d_out_keys ? (u64 *)d_out_cntS : nullptr;
-    ctx->group_cap = d_out_keys ? out_capacity : 0;
-    ctx->gjoin_left = mode == RHJ_GJ_LEFT;
-    ctx->group_ops = packed;
-    ctx->one_sided = one;
-    const int rc = partition_and_join(ctx, d_R, nR, one ? nullptr : d_S, one ? nR : nS, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GJOIN);
-    ctx->one_sided = false;
-    ctx->gjoin_left = false;
-    ctx->group_ops = 0;
-    ctx->agg_ncols = ctx->gjoin_ncolsS = 0;
-    ctx->group_keys = ctx->group_counts = ctx->gjoin_cntS = nullptr;
-    ctx->group_cap = 0;
-    for (u32 j = 0; j < (u32)AGG_MAX_COLS; j++) {
-        ctx->agg_cols[j] = ctx->gjoin_colsS[j] = nullptr;
-        ctx->group_sums[j] = ctx->gjoin_sumsS[j] = nullptr;
-    }
-    RHJCHK(rc);
-    if (d_out_keys && *out_groups > out_capacity) return fail(ctx, RHJ_E_OVERFLOW, "result buffers too small");
-    return RHJ_OK;
+    RHJCHK(entry_plan(ctx, nR, one ? nR : nS, opts, &plan));
+    for (u32 j = 0; j < nsumR; j++) { a.agg_cols[j] = (const u64 *)d_colsR[j]; a.group_sums[j] = (u64 *)d_out_sumsR[j]; }
+    for (u32 j = 0; j < nsumS; j++) { a.gjoin_colsS[j] = (const u64 *)d_colsS[j]; a.gjoin_sumsS[j] = (u64 *)d_out_sumsS[j]; }
+    a.agg_ncols = nsumR;
+    a.agg_col_rows = nsumR ? colR_rows : ~0ull;
+    a.gjoin_ncolsS = nsumS;
+    a.gjoin_colS_rows = nsumS ? colS_rows : ~0ull;
+    a.group_keys = (u64 *)d_out_keys;
+    a.group_counts = d_out_keys ? (u64 *)d_out_cntR : nullptr;
+    a.gjoin_cntS = d_out_keys ? (u64 *)d_out_cntS : nullptr;
+    a.group_cap = d_out_keys ? out_capacity : 0;
+    a.gjoin_left = mode == RHJ_GJ_LEFT;
+    a.group_ops = packed;
+    a.one_sided = one;
+    RHJCHK(partition_and_join(ctx, d_R, nR, one ? nullptr : d_S, one ? nR : nS, plan, nullptr, 0, (u64 *)out_groups, nullptr, OUT_GJOIN));
+    return check_capacity(ctx, d_out_keys, *out_groups, out_capacity, "result buffers");
 }
 
 int rhj_group_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rhj_tuple *d_S, uint64_t nS,
@@ -3244,15 +3015,13 @@ int rhj_group_join_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, const rh
                        uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS,
                        uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return group_join_common(ctx, d_R, nR, d_S, nS, d_colsR, nullptr, ncolsR, colR_rows, d_colsS, nullptr, ncolsS, colS_rows, mode, opts,
                              d_out_keys, d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
 }
 
+// (in the columnar twins the ids travel with the values, also with no column; an empty S has no columns)
 int rhj_group_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t *d_idR, uint64_t nR,
                             const uint64_t *d_valS, const uint64_t *d_idS, uint64_t nS,
                             const uint64_t *const *d_colsR, uint32_t ncolsR, uint64_t colR_rows,
@@ -3262,19 +3031,11 @@ int rhj_group_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint64_t
                             uint64_t *const *d_out_sumsR, uint64_t *const *d_out_sumsS,
                             uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with no column)
-    if (nS) { ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS; }
-    else ctx->cols_in[1] = ColsIn();
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, nullptr, ncolsR, colR_rows, d_colsS, nullptr, ncolsS, colS_rows,
-                                     mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR, nS ? d_valS : nullptr, nS ? d_idS : nullptr);
+    return group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, nullptr, ncolsR, colR_rows, d_colsS, nullptr, ncolsS, colS_rows,
+                             mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_sumsR, d_out_sumsS, out_capacity, out_groups);
 }
 
 // ... with an aggregate per column: the same host path, each side's ops beside its columns
@@ -3286,10 +3047,7 @@ int rhj_group_join_agg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, cons
                            uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
                            uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return group_join_common(ctx, d_R, nR, d_S, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows, mode, opts,
                              d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups);
@@ -3304,19 +3062,11 @@ int rhj_group_join_agg_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const uint
                                 uint64_t *const *d_out_aggsR, uint64_t *const *d_out_aggsS,
                                 uint64_t out_capacity, uint64_t *out_groups)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with no column)
-    if (nS) { ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS; }
-    else ctx->cols_in[1] = ColsIn();
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows,
-                                     mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR, nS ? d_valS : nullptr, nS ? d_idS : nullptr);
+    return group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows,
+                             mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups);
 }
 
 // ... with the group of every row of either side: the same host path, the id arrays beside the outputs
@@ -3329,10 +3079,7 @@ int rhj_group_join_agg_ids_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR, 
                                uint64_t out_capacity, uint64_t *out_groups,
                                uint64_t *d_out_gidR, uint64_t gidR_rows, uint64_t *d_out_gidS, uint64_t gidS_rows)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if ((nR && !d_R) || (nS && !d_S)) return fail(ctx, RHJ_E_INVALID, "null input relation");
     return group_join_common(ctx, d_R, nR, d_S, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows, mode, opts,
                              d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups,
@@ -3349,21 +3096,14 @@ int rhj_group_join_agg_ids_cols_dev(rhj_ctx *ctx, const uint64_t *d_valR, const 
                                     uint64_t out_capacity, uint64_t *out_groups,
                                     uint64_t *d_out_gidR, uint64_t gidR_rows, uint64_t *d_out_gidS, uint64_t gidS_rows)
 {
-    RHJCHK(use_device(ctx));
-    if (!out_groups) return fail(ctx, RHJ_E_INVALID, "out_groups is null");
-    *out_groups = 0;
-    prof_reset(ctx);
+    RHJCHK(entry_begin(ctx, out_groups, "out_groups"));
     if ((nR && !d_valR) || (nS && !d_valS)) return fail(ctx, RHJ_E_INVALID, "null value column");
-    ctx->cols_in[0].val = (const u64 *)d_valR; ctx->cols_in[0].id = (const u64 *)d_idR;   // (ids travel with the values, also with no column)
-    if (nS) { ctx->cols_in[1].val = (const u64 *)d_valS; ctx->cols_in[1].id = (const u64 *)d_idS; }
-    else ctx->cols_in[1] = ColsIn();
-    ctx->cols_aos_done[0] = ctx->cols_aos_done[1] = false;
-    const int rc = group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows,
-                                     mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups,
-                                     d_out_gidR, gidR_rows, d_out_gidS, gidS_rows);
-    ctx->cols_in[0] = ctx->cols_in[1] = ColsIn();
-    return rc;
+    ColsScope cols(ctx, d_valR, d_idR, nS ? d_valS : nullptr, nS ? d_idS : nullptr);
+    return group_join_common(ctx, nullptr, nR, nullptr, nS, d_colsR, opsR, ncolsR, colR_rows, d_colsS, opsS, ncolsS, colS_rows,
+                             mode, opts, d_out_keys, d_out_cntR, d_out_cntS, d_out_aggsR, d_out_aggsS, out_capacity, out_groups,
+                             d_out_gidR, gidR_rows, d_out_gidS, gidS_rows);
 }
+
 
 namespace {
 

@@ -167,6 +167,8 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * of the sort's scatter ranks at once),
  * "last.topk_bits" / "last.topk_passes" / "last.topk_candidates" / "last.topk_sorted_rows" (what the last rhj_topk_cols_dev /
  * rhj_topk_dev did, see there; 0 after every other call), "topk.auto_candidates" (a constant of the build),
+ * "last.window_units" / "last.window_sorts" / "last.window_partitions" (what the last rhj_window_cols_dev did, see there; 0 after
+ * every other call), "window.tile_rows" (a constant of the build),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -852,6 +854,75 @@ int rhj_topk_cols_dev(rhj_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_ro
                       uint64_t *d_out_keys, uint64_t *d_out_rows, uint64_t *out_kth);
 /* ... on 16-byte tuples in and out (value = .payload, rowID = .key); out_kth[0] is the value, out_kth[1] the rowID */
 int rhj_topk_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t n, uint64_t k, uint32_t flags, rhj_tuple *d_out, uint64_t *out_kth);
+
+/* ---- window functions: a value per row from the rows before it in its partition (ROW_NUMBER / RANK / DENSE_RANK() OVER (PARTITION BY
+ * k ORDER BY t), a running SUM / MIN / MAX, LAG / LEAD; pandas groupby.cumcount / rank / cumsum / cummin / cummax / shift; top-k per
+ * group is ROW_NUMBER <= k).
+ * Rows are the indices 0 .. n - 1.  d_part, d_order and every d_cols[j] are device columns of n words; ops, args, the two pointer
+ * arrays and out_partitions are HOST memory.  A PARTITION is the set of rows with the same d_part word -- the word is compared for
+ * equality only; d_part == NULL: one partition.  Inside a partition the rows are ordered by their d_order word under flags:
+ * RHJ_SORT_I64 and RHJ_SORT_DESC, with the sort entry's meaning.  Ties keep their input order in both directions, so every result is
+ * defined, and bit-identical from run to run.  d_order == NULL: input order, and every row is its own peer; a non-zero flags with
+ * d_order == NULL is RHJ_E_INVALID.  Rows with equal order words in one partition are PEERS.
+ * Ops: for row i at 0-based position q of its partition P, d_outs[j][i] receives -- the outputs are aligned with the input rows, not
+ * in sorted order --
+ *     RHJ_WIN_ROW_NUMBER   q + 1
+ *     RHJ_WIN_RANK         1 + the rows of P whose order key is strictly before i's
+ *     RHJ_WIN_DENSE_RANK   1 + the distinct order keys of P strictly before i's
+ *     RHJ_WIN_LAG_ROW      the row at position q - off of P, RHJ_NO_ROW where there is none
+ *     RHJ_WIN_LEAD_ROW     the row at position q + off of P, RHJ_NO_ROW where there is none
+ *     RHJ_WIN_CUMSUM       the sum mod 2^64 of d_cols[j][r] over the rows r of P at positions <= q
+ *     RHJ_WIN_CUMMIN_U64 / RHJ_WIN_CUMMAX_U64 / RHJ_WIN_CUMMIN_I64 / RHJ_WIN_CUMMAX_I64
+ *                          the minimum / maximum of those words, unsigned or as two's-complement int64: bit for bit a column word
+ * off = args[j] >= 1 for the two row ops; args == NULL: offset 1; args[j] is ignored for the other ops, d_cols[j] for the ops
+ * without a column (d_cols may then be NULL).  The running aggregates use the frame ROWS UNBOUNDED PRECEDING -- every row up to and
+ * including the current one, peers behind it excluded --, not SQL's default RANGE frame, under which peers share a value.  The same
+ * column may be given several times; two equal output pointers are undefined.  Lag and lead of a PAYLOAD go through
+ * rhj_gather_cols_fill, which reads RHJ_NO_ROW as "fill":
+ *     ops = {RHJ_WIN_LAG_ROW}; rhj_window_cols_dev(ctx, k, t, n, RHJ_SORT_I64, ops, NULL, NULL, 1, &prev, NULL);   -- prev[i] = the row before i
+ *     rhj_gather_cols_fill(ctx, &x, 1, n, prev, n, &fill, &x_lag);                                           -- x_lag[i] = x[prev[i]] or fill
+ * A multi-column order is the sort entry's chain first (ORDER BY a, b), then this call on the columns gathered in that order with
+ * d_order == NULL.
+ * *out_partitions receives the number of partitions; it may be NULL.  n == 0: RHJ_OK, no launch, 0 partitions.  RHJ_E_INVALID,
+ * before any launch, with a message naming the argument: unknown flag bits; flags without d_order; nops 0 or above
+ * RHJ_WINDOW_MAX_OPS; NULL ops, d_outs or d_outs[j]; an op above RHJ_WIN_CUMMAX_I64; a lag or lead offset of 0; a NULL d_cols[j] for
+ * a column op with n > 0.  Inputs are neither modified nor retained; outputs must not overlap inputs.  The call synchronises; it
+ * honours rhj_set_stream and rhj_set_profiling (the inner sorts' spans; RHJ_K_AUX: heads, gather, the row ops; per scan RHJ_K_HIST,
+ * RHJ_K_SCAN, RHJ_K_SCATTER).
+ * How: the order (partition, order key, input position) from the stable sort -- d_order argsorted under flags, d_part gathered
+ * through that permutation and sorted with the permutation as its rows; one sort when either column is NULL, none when both are (a
+ * column of dense ids or a narrow range is few passes: the sort's probe).  One launch marks, per sorted position, whether it heads a
+ * partition (its partition word differs from its predecessor's) and whether it heads a run of peers (or its order word does).  Every
+ * result is then a scan over the sorted positions that restarts at heads, three launches ordered on the stream on the sort's units
+ * ("sort.max_units" caps them here too): a reduce per unit -- "has a head" and the aggregate since the unit's last head --, a
+ * one-workgroup carry over the at most 2048 unit summaries, an apply per unit that scans tile by tile from its carry-in and stores
+ * out[perm[p]].  No workgroup waits on another inside a kernel, and no position or value comes from an atomic.  ROW_NUMBER, RANK,
+ * LAG_ROW and LEAD_ROW follow from the partition start and the peer start of each position -- inclusive maximum scans of (head ?
+ * position : 0), materialised once per call -- in one further launch; DENSE_RANK is the running count of peer heads; signed minimum
+ * and maximum go through the 1 << 63 bias.
+ * Costs in bytes per row: the sorts (see there) plus 24 for the gather between two of them; heads 9 .. 25; each start 1 + 1 + 8; the
+ * row ops together 8 .. 40 read and one scattered 8-byte store each; each other op 2 x (1 + 8) read, for a column op two gathered
+ * 8-byte loads more, and one scattered 8-byte store.
+ * rhj_get_info: "last.window_units" the units the scans were cut into, "last.window_sorts" the inner sorts that ran (0, 1 or 2),
+ * "last.window_partitions" the partitions; all three are 0 after every other call.  After a window call "last.join_kernel" is -1 and
+ * "last.sort_*" / "last.topk_*" are 0.  "window.tile_rows": the positions one workgroup scans at once, a constant of the build.
+ * Memory: a workspace buffer of its own (the inner sorts regrow the sort's), kept until rhj_release_workspace: up to 4 x 8 + 1 bytes
+ * per row.
+ * There is no 16-byte tuple form: two key columns do not fit a {key, payload} tuple. */
+#define RHJ_WINDOW_MAX_OPS   4
+#define RHJ_WIN_ROW_NUMBER   0   /* no column */
+#define RHJ_WIN_RANK         1   /* no column */
+#define RHJ_WIN_DENSE_RANK   2   /* no column */
+#define RHJ_WIN_LAG_ROW      3   /* no column; args[j] = offset >= 1 */
+#define RHJ_WIN_LEAD_ROW     4   /* no column; args[j] = offset >= 1 */
+#define RHJ_WIN_CUMSUM       5   /* column; mod 2^64 */
+#define RHJ_WIN_CUMMIN_U64   6
+#define RHJ_WIN_CUMMAX_U64   7
+#define RHJ_WIN_CUMMIN_I64   8
+#define RHJ_WIN_CUMMAX_I64   9
+int rhj_window_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_order, uint64_t n, uint32_t flags,
+                        const uint32_t *ops, const uint64_t *args, const uint64_t *const *d_cols, uint32_t nops,
+                        uint64_t *const *d_outs, uint64_t *out_partitions);
 
 /* ---- stage entry points (device pointers), one per reference job body ---------------------
  * rhj_histogram: HistogramJob::run over the whole relation + the reduction of structs.cpp:168-173:

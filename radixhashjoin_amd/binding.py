@@ -142,6 +142,7 @@ SYMBOLS = {
     "rhj_sort_dev": (C.c_int, [_vp, _vp, _u64, C.c_uint32, _vp]),
     "rhj_topk_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _u64, C.c_uint32, _vp, _vp, _P(_u64)]),
     "rhj_topk_dev": (C.c_int, [_vp, _vp, _u64, _u64, C.c_uint32, _vp, _P(_u64)]),
+    "rhj_window_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -298,6 +299,60 @@ NO_ROW = 0xFFFFFFFFFFFFFFFF                              # include/rhj.h RHJ_NO_
 LOOKUP_FIRST, LOOKUP_LAST = 0, 1                         # include/rhj.h RHJ_LOOKUP_*: the smallest / largest rowID of S among the partners
 LOOKUP_MAX_COLS = 4                                      # include/rhj.h RHJ_LOOKUP_MAX_COLS: columns of a gather_cols_fill call
 SORT_I64, SORT_DESC = 1, 2                               # include/rhj.h RHJ_SORT_*: flags of the sort entries
+# include/rhj.h RHJ_WIN_*: the ops of a window_cols_dev call, and how many one call takes
+WINDOW_MAX_OPS = 4
+WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_LAG_ROW, WIN_LEAD_ROW = 0, 1, 2, 3, 4
+WIN_CUMSUM, WIN_CUMMIN_U64, WIN_CUMMAX_U64, WIN_CUMMIN_I64, WIN_CUMMAX_I64 = 5, 6, 7, 8, 9
+# ... by name (window_columns): "cummin" / "cummax" order int64 tensors as signed words
+_WIN_BY_NAME = {"row_number": WIN_ROW_NUMBER, "rank": WIN_RANK, "dense_rank": WIN_DENSE_RANK, "lag": WIN_LAG_ROW, "lead": WIN_LEAD_ROW,
+                "cumsum": WIN_CUMSUM, "cummin": WIN_CUMMIN_I64, "cummax": WIN_CUMMAX_I64, "cummin_u64": WIN_CUMMIN_U64,
+                "cummax_u64": WIN_CUMMAX_U64}
+
+
+def _window_args(order_by, values, ops, descending, unsigned, offsets, fill):
+    """(RHJ_WIN_* words, value tensors or None, offsets) of a window_columns call; ValueError on a wrong name, length, flag or offset --
+    nothing here touches a device"""
+    if isinstance(ops, str):
+        raise ValueError(f"ops: a sequence of op names is needed, not the string {ops!r}")
+    ops = list(ops)
+    if not ops:
+        raise ValueError("ops: at least one op is needed")
+    if len(ops) > WINDOW_MAX_OPS:
+        raise ValueError(f"ops: at most {WINDOW_MAX_OPS} ops per call, not {len(ops)}")
+    for i, o in enumerate(ops):
+        if not isinstance(o, str) or o not in _WIN_BY_NAME:
+            raise ValueError(f"ops[{i}]: one of {', '.join(repr(k) for k in _WIN_BY_NAME)}, not {o!r}")
+    values = list(values) if values is not None else []
+    if not values:
+        values = [None] * len(ops)
+    if len(values) != len(ops):
+        raise ValueError(f"values: {len(values)} entries for {len(ops)} ops (None for an op without a column)")
+    if offsets is None:
+        offs = [1] * len(ops)
+    else:
+        offs = list(offsets)
+        if len(offs) != len(ops):
+            raise ValueError(f"offsets: {len(offs)} entries for {len(ops)} ops")
+    if not isinstance(descending, bool):
+        raise ValueError(f"descending: a bool is needed, not {descending!r}")
+    if not isinstance(unsigned, bool):
+        raise ValueError(f"unsigned: a bool is needed, not {unsigned!r}")
+    if descending and order_by is None:
+        raise ValueError("descending: True needs an order_by tensor; without one the order is the input order")
+    if isinstance(order_by, (list, tuple)):
+        raise ValueError("order_by: one tensor or None -- for ORDER BY a, b run sort_columns([k, a, b]) first and pass order_by=None")
+    for i, o in enumerate(ops):
+        if o in ("lag", "lead"):
+            if isinstance(offs[i], bool) or not isinstance(offs[i], int) or offs[i] < 1:
+                raise ValueError(f"offsets[{i}]: an int >= 1 is needed for {o!r}, not {offs[i]!r}")
+        elif o in ("row_number", "rank", "dense_rank"):
+            if values[i] is not None:
+                raise ValueError(f"values[{i}]: {o!r} takes no column; None is needed")
+        elif values[i] is None:
+            raise ValueError(f"values[{i}]: {o!r} needs a tensor")
+    if isinstance(fill, bool) or not isinstance(fill, int):
+        raise ValueError(f"fill: an int is needed, not {fill!r}")
+    return [_WIN_BY_NAME[o] for o in ops], values, [o if isinstance(o, int) and not isinstance(o, bool) else 1 for o in offs]
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
 
@@ -460,7 +515,8 @@ class Engine:
     def info(self, name):
         """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.outer_sweeps", "last.group_rounds",
         "last.sort_bits", "last.sort_passes", "last.sort_units", "last.topk_bits", "last.topk_passes", "last.topk_candidates",
-        "last.topk_sorted_rows"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates")"""
+        "last.topk_sorted_rows", "last.window_units", "last.window_sorts", "last.window_partitions"; include/rhj.h) and constants of
+        the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows")"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
         return v.value
@@ -1428,6 +1484,86 @@ class Engine:
             value, row = self.topk_cols_dev(keys, None, keys.numel(), k, (0 if unsigned else SORT_I64) | (SORT_DESC if descending else 0),
                                             None, None, want_kth=True)
         return (value if unsigned or value < 1 << 63 else value - (1 << 64)), row
+
+    def window_cols_dev(self, d_part, d_order, n, flags=0, ops=(), args=None, d_cols=None, d_outs=()):
+        """rhj_window_cols_dev: per row a value from the rows before it in its partition (rows with the same d_part word; None: one
+        partition), ordered by d_order under flags (SORT_I64, SORT_DESC; None: input order), ties in input order -- ops[j] one of
+        WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_LAG_ROW / WIN_LEAD_ROW (args[j]: the offset >= 1; args None: 1; NO_ROW where
+        there is no such row), WIN_CUMSUM, WIN_CUMMIN_U64 / WIN_CUMMAX_U64 / WIN_CUMMIN_I64 / WIN_CUMMAX_I64 (of d_cols[j], over the
+        rows up to and including this one: ROWS UNBOUNDED PRECEDING).  d_outs[j]: uint64[n] in HBM, aligned with the rows.  The
+        number of ops is len(ops), at most WINDOW_MAX_OPS.  Returns the number of partitions.  (A sequence that is None goes in as
+        NULL: the library answers.)"""
+        k = len(ops) if ops is not None else 0
+        opw = (C.c_uint32 * max(k, 1))(*[int(o) for o in ops]) if ops is not None else None
+        argw = (_u64 * max(k, 1))(*[int(a) for a in args]) if args is not None else None
+        cols = (_vp * max(k, 1))(*[_addr(c) for c in d_cols]) if d_cols is not None else None
+        outs = (_vp * max(k, 1))(*[_addr(o) for o in d_outs]) if d_outs is not None else None
+        parts = _u64()
+        self._chk(self.lib.rhj_window_cols_dev(self.ctx, _addr(d_part), _addr(d_order), n, flags, opw, argw, cols, k, outs, C.byref(parts)))
+        return parts.value
+
+    def window_columns(self, partition_by, order_by=None, values=(), ops=("row_number",), descending=False, unsigned=False, offsets=None,
+                       fill=0):
+        """[out_0, out_1, ..]: window functions over the rows of a table -- one int64 tensor per op, ALIGNED WITH THE ROWS (not in
+        sorted order).  Rows with equal partition_by form a partition; inside it they are ordered by order_by as int64 (unsigned=True:
+        the words as uint64), ascending (descending=True: descending), rows with equal order keys in input order in both directions --
+        every result is defined and the same from run to run.  order_by None: input order.  partition_by: None (one partition), a
+        contiguous 1-D 64-bit integer tensor on the engine's device, or a list of 1 to KEYS_MAX_COLS of them (packed first, as
+        group_by_columns does).  ops, with q the 0-based position of a row in its partition:
+          "row_number"  q + 1 (pandas groupby.cumcount() + 1)            "rank"  1 + the rows with a strictly earlier order key (rank(method="min"))
+          "dense_rank"  1 + the distinct earlier order keys               "cumsum"  the running sum mod 2^64 of values[j]
+          "cummin" / "cummax"  the running minimum / maximum of values[j] as int64;  "cummin_u64" / "cummax_u64": of the words as uint64
+          "lag" / "lead"  values[j] None: the index of the row offsets[j] (default 1) positions before / behind in the partition, -1
+                          where there is none; values[j] a tensor: that tensor at that row, fill where there is none (groupby.shift)
+        The running aggregates cover the rows up to and including the current one (ROWS UNBOUNDED PRECEDING), not its later peers.
+        values[j] is None for an op without a column (values=() : every op without one).  At most WINDOW_MAX_OPS ops per call.
+        ORDER BY a, b inside the partitions: _, perm, (k2, ..) = sort_columns([k, a, b], values=[k, ..]) first, then window_columns(k2,
+        None, ..) on the gathered tensors -- the results are then aligned with the sorted rows; out[perm] = result puts them back.
+        An unknown op, more than WINDOW_MAX_OPS ops, a length mismatch among values / ops / offsets, a non-bool flag, an offset < 1,
+        descending=True without order_by: ValueError before any device use.  One rhj_window_cols_dev call, and one rhj_gather_cols_fill
+        per lagged payload.  Streams and completion as join_columns."""
+        import torch
+        opw, values, offs = _window_args(order_by, values, ops, descending, unsigned, offsets, fill)
+        if isinstance(partition_by, (list, tuple)):
+            packed, _, plan = self.pack_keys(partition_by, keep_dictionaries=False)
+            plan.close()
+            partition_by = packed
+        named = [("partition_by", partition_by), ("order_by", order_by)] + [(f"values[{j}]", v) for j, v in enumerate(values)]
+        named = [(name, t) for name, t in named if t is not None]
+        if not named:
+            raise ValueError("partition_by, order_by and values are all None: the number of rows is unknown")
+        ints = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)
+        for name, t in named:
+            if not isinstance(t, torch.Tensor) or t.dtype not in ints or t.dim() != 1:
+                raise ValueError(f"{name}: a 1-D torch tensor of 64-bit integers is needed")
+            if t.numel() != named[0][1].numel():
+                raise ValueError(f"{name}: {t.numel()} elements, {named[0][0]} has {named[0][1].numel()}")
+        tensors = [t for _, t in named]
+        flags = 0 if order_by is None else (0 if unsigned else SORT_I64) | (SORT_DESC if descending else 0)
+        with self._on_torch_stream(tensors[0], tensors[0], tuple(tensors[1:])) as dev:
+            n = tensors[0].numel()
+            outs = [torch.empty(n, dtype=torch.int64, device=dev) for _ in opw]
+            if n:
+                cols = [v if o >= WIN_CUMSUM else None for o, v in zip(opw, values)]
+                self.window_cols_dev(partition_by, order_by, n, flags, opw, offs, cols, outs)
+                for j, o in enumerate(opw):
+                    if o in (WIN_LAG_ROW, WIN_LEAD_ROW) and values[j] is not None:
+                        got = torch.empty(n, dtype=values[j].dtype, device=dev)
+                        self.gather_cols_fill([values[j]], n, outs[j], n, [fill], [got])
+                        outs[j] = got
+        return outs
+
+    def topk_per_group_columns(self, partition_by, order_by, k, descending=False, unsigned=False):
+        """idx: the rows with ROW_NUMBER() OVER (PARTITION BY partition_by ORDER BY order_by) <= k -- the first k rows of every partition
+        in that order (descending=True: the k largest per group), ties in input order also at the cut -- as an int64 tensor SORTED
+        ASCENDING.  One window_columns call and one torch.nonzero.  k: an int >= 0; the other arguments and errors as window_columns."""
+        import torch
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise ValueError(f"k: an int is needed, not {k!r}")
+        if k < 0:
+            raise ValueError(f"k: a count of rows is needed, not {k}")
+        number = self.window_columns(partition_by, order_by, (), ("row_number",), descending, unsigned)[0]
+        return torch.nonzero(number <= k).reshape(-1)
 
     def factorize_columns(self, keys):
         """(codes, uniques): pandas.factorize without the ordering promise -- uniques the distinct values of keys in no particular

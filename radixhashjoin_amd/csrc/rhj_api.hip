@@ -279,6 +279,9 @@ struct rhj_ctx {
     u64 last_topk_cand = 0, last_topk_sorted = 0;   // "last.topk_candidates" / "last.topk_sorted_rows": the rows tied with the threshold's digits when selection stopped, the rows its inner sort took
     DevBuf topk_ws;                    // top-k's select state, tables and kept rows (rhj_sort.hip): not sort_ws, which the inner sort regrows
     int64_t opt_topk_cand = -1;        // "topk.max_candidates": -1 automatic, else selection goes on while more rows than this are tied
+    int last_window_units = 0, last_window_sorts = 0;   // "last.window_units" / "last.window_sorts": the units the last window call's scans were cut into, its inner sorts (0: another call)
+    u64 last_window_parts = 0;         // "last.window_partitions": the partitions it found
+    DevBuf window_ws;                  // the window entry's permutation, sorted words, flags, starts and unit tables (rhj_window.hip): not sort_ws, which the inner sorts regrow
     CallArgs call;                     // the operator arguments of the entry in progress (CallScope)
     u64 outer_sections[3] = {0, 0, 0}; // an outer join's {matched, R-only, S-only} rows, as outer_phase leaves them
     bool counters_clean = false;       // the 64-byte join counters are zero (cleared by the partition phase's first launch)
@@ -515,6 +518,8 @@ void prof_reset(rhj_ctx *ctx)
     ctx->last_sort_bits = ctx->last_sort_passes = ctx->last_sort_units = 0;   // "last.sort_*": ... and the sort entries these
     ctx->last_topk_bits = ctx->last_topk_passes = 0;                          // "last.topk_*": ... and the top-k entries these
     ctx->last_topk_cand = ctx->last_topk_sorted = 0;
+    ctx->last_window_units = ctx->last_window_sorts = 0;                      // "last.window_*": ... and the window entry these
+    ctx->last_window_parts = 0;
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -2124,6 +2129,19 @@ int rhj_internal_topk_workspace(rhj_ctx *ctx, size_t bytes, void **out)
     return RHJ_OK;
 }
 int64_t rhj_internal_topk_max_candidates(rhj_ctx *ctx) { return ctx->opt_topk_cand; }
+// ... and for rhj_window.hip
+void rhj_internal_window_report(rhj_ctx *ctx, int units, int sorts, u64 partitions)
+{
+    ctx->last_window_units = units;
+    ctx->last_window_sorts = sorts;
+    ctx->last_window_parts = partitions;
+}
+int rhj_internal_window_workspace(rhj_ctx *ctx, size_t bytes, void **out)
+{
+    RHJCHK(ensure(ctx, ctx->window_ws, bytes));
+    *out = ctx->window_ws.p;
+    return RHJ_OK;
+}
 void *rhj_internal_span_open(rhj_ctx *ctx, int kind) { return new Span(ctx, kind); }
 void rhj_internal_span_close(void *span) { delete (Span *)span; }
 
@@ -2215,7 +2233,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->agg_out, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
                      &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cf2_end[0], &ctx->cf2_end[1], &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
-                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws};
+                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws, &ctx->window_ws};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
     ctx->small_hdr_clean = false;
@@ -2322,6 +2340,10 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.topk_candidates") { *value = (int64_t)ctx->last_topk_cand; return RHJ_OK; }
     if (n == "last.topk_sorted_rows") { *value = (int64_t)ctx->last_topk_sorted; return RHJ_OK; }
     if (n == "topk.auto_candidates") { *value = TOPK_AUTO_CANDIDATES; return RHJ_OK; }
+    if (n == "last.window_units") { *value = ctx->last_window_units; return RHJ_OK; }
+    if (n == "last.window_sorts") { *value = ctx->last_window_sorts; return RHJ_OK; }
+    if (n == "last.window_partitions") { *value = (int64_t)ctx->last_window_parts; return RHJ_OK; }
+    if (n == "window.tile_rows") { *value = WINDOW_TILE; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }

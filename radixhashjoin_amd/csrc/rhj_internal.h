@@ -479,3 +479,6 @@ constexpr int SORT_DIGIT_BITS = 8;
 // top-k: the automatic "topk.max_candidates" is max(k, this) -- selection stops once so few rows are tied with the
 // threshold's digits that sorting them costs less than another read of the column ("topk.auto_candidates")
 constexpr int TOPK_AUTO_CANDIDATES = 1 << 16;
+// the window scans (rhj_window.hip) run on the sort's units and tiles: one workgroup of SORT_THREADS scans a tile of
+// this many sorted positions at once ("window.tile_rows")
+constexpr int WINDOW_TILE = SORT_TILE;

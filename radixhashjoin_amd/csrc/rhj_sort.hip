@@ -932,6 +932,14 @@ int topk_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
 
 }  // namespace
 
+// hooks for rhj_window.hip: the sort proper on plain columns, under the caller's entry name and "last.*", and the unit
+// geometry its passes use
+int rhj_internal_sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, const u64 *rows, u64 n, u32 flags, u64 *okeys, u64 *orows)
+{
+    return sort_run(ctx, who, keys, 1, rows, 1, n, flags, okeys, 1, orows, 1);
+}
+void rhj_internal_sort_units(rhj_ctx *ctx, u64 n, u64 *L, u32 *U) { sort_units(ctx, n, L, U); }
+
 extern "C" {
 
 int rhj_sort_cols_dev(rhj_ctx *ctx, const uint64_t *d_keys, const uint64_t *d_rows, uint64_t n, uint32_t flags,

@@ -169,6 +169,8 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * rhj_topk_dev did, see there; 0 after every other call), "topk.auto_candidates" (a constant of the build),
  * "last.window_units" / "last.window_sorts" / "last.window_partitions" (what the last rhj_window_cols_dev did, see there; 0 after
  * every other call), "window.tile_rows" (a constant of the build),
+ * "last.asof_units" / "last.asof_sorts" / "last.asof_matched" (what the last rhj_asof_cols_dev did, see there; 0 after every other
+ * call), "asof.tile_rows" (a constant of the build),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -764,6 +766,69 @@ int rhj_keys_unpack_dev(rhj_ctx *ctx, const rhj_keyplan *plan, const uint64_t *d
 int rhj_keys_plan_info(const rhj_keyplan *plan, rhj_keys_layout_t *out);
 /* frees the plan and its dictionaries; a NULL plan is fine */
 int rhj_keys_plan_free(rhj_ctx *ctx, rhj_keyplan *plan);
+
+/* ---- as-of join: for every row of R the nearest row of S of its partition at or before it -- "for every trade the latest quote of
+ * the same symbol at or before the trade's time" (pandas.merge_asof, ASOF JOIN, the point-in-time lookup against a slowly changing
+ * dimension).
+ * Rows are the indices 0 .. n - 1 of their table.  d_byR / d_onR are device columns of nR words, d_byS / d_onS of nS words, d_out_rowS
+ * a device column of nR words; out_matched is a HOST pointer and may be NULL.  Neither table needs to be sorted: pandas requires
+ * sorted inputs, this entry does not.
+ * Partitions: a row of R can only match rows of S whose `by` word is bit-equal -- the word is compared for equality only.
+ * d_byR == NULL && d_byS == NULL: one partition.  Exactly one of the two NULL with both tables non-empty is RHJ_E_INVALID.
+ * Candidates: the `on` words are ordered in the chosen view, unsigned 64-bit by default, two's-complement int64 under RHJ_ASOF_I64 (as
+ * RHJ_SORT_I64).  For row i of R the candidates are the rows j of S in its partition with
+ *     onS[j] <= onR[i]     backward (the default)              onS[j] <  onR[i]     backward under RHJ_ASOF_STRICT
+ *     onS[j] >= onR[i]     forward (RHJ_ASOF_FORWARD)          onS[j] >  onR[i]     forward under RHJ_ASOF_STRICT
+ * (RHJ_ASOF_STRICT is pandas' allow_exact_matches=False.)  Under RHJ_ASOF_TOLERANCE a candidate must also satisfy |onR[i] - onS[j]| <=
+ * tolerance, a comparison of exact integers, not mod 2^64: in the int64 view the distance between INT64_MIN and INT64_MAX is 2^64 - 1
+ * and still fits the word (it is computed as a difference of the order-transformed words).  tolerance 0 means equal words only;
+ * together with RHJ_ASOF_STRICT that matches nothing, and it is legal.  Without the bit `tolerance` is ignored.
+ * Result: d_out_rowS[i] is the candidate whose `on` is nearest to onR[i] -- the largest `on` for backward, the smallest for forward.
+ * Among candidates that share that `on` word, backward takes the LARGEST row index and forward takes the SMALLEST (pandas: the last,
+ * respectively the first, of the duplicates).  With no candidate the output is RHJ_NO_ROW.  The outputs are aligned with R, 8 bytes
+ * per row, no pair set is written.  *out_matched receives the number of rows of R with a partner.  The result is bit-identical from
+ * run to run.
+ * Payloads of S go through rhj_gather_cols_fill, which reads RHJ_NO_ROW as "fill":
+ *     rhj_asof_cols_dev(ctx, symR, timeR, nR, symS, timeS, nS, RHJ_ASOF_I64, 0, rowS, NULL);        -- rowS[i] = the latest quote of trade i
+ *     rhj_gather_cols_fill(ctx, &bid, 1, nS, rowS, nR, &fill, &bid_R);                              -- bid_R[i] = bid[rowS[i]] or fill
+ * Empty tables: nR == 0: RHJ_OK, no launch, *out_matched = 0.  nS == 0 with nR > 0: every output is RHJ_NO_ROW (one fill launch) and
+ * matched is 0.
+ * RHJ_E_INVALID, before any launch, with a message naming the argument: unknown flag bits (also when both tables are empty); NULL
+ * d_onR with nR > 0; NULL d_onS with nS > 0; NULL d_out_rowS with nR > 0; the one-sided `by`.  *out_matched is then untouched.
+ * Inputs are neither modified nor retained; outputs must not overlap inputs; pointers need 8-byte alignment.  The call synchronises;
+ * it honours rhj_set_stream and rhj_set_profiling (the inner sorts' spans; RHJ_K_AUX: concatenation, gather, heads, fill; the scan
+ * RHJ_K_HIST, RHJ_K_SCAN, RHJ_K_SCATTER).
+ * How: one launch concatenates the `on` words (and the `by` words) of both tables into columns of n = nR + nS words, [S ; R], under
+ * RHJ_ASOF_STRICT [R ; S]; the side of a concatenated position follows from its index.  The order (by, on, concatenated position) comes
+ * from the stable sort -- `on` argsorted in the view, descending for RHJ_ASOF_FORWARD, then `by` gathered through that permutation and
+ * sorted with the permutation as its rows; one sort without `by`.  Equal `on` words keep the concatenation's order, so the candidates
+ * of a row of R are exactly the rows of S before it in its partition, and the nearest is the last of them.  One launch marks, per
+ * sorted position, whether it heads a partition, whether it is a row of S, and whether the scan may land on it: backward every row
+ * of S, forward only the head of a run of rows of S with one `on` word (the smallest index of the run).  The scan is the window
+ * entry's, three launches ordered on the stream on the sort's units ("sort.max_units" caps them here too; the result never depends on
+ * it): a reduce per unit, a one-workgroup carry over the at most 2048 unit summaries, an apply per unit.  It carries the maximum of
+ * (landing position + 1) and restarts at partition heads; the apply maps the position to its row of S through the permutation, tests
+ * the tolerance with two gathered loads under the flag only, and stores out[row of R] at every position of R, RHJ_NO_ROW included.
+ * No workgroup waits on another inside a kernel, and no position, value or count comes from an atomic: the matches are counted per
+ * unit and summed on the host.
+ * Costs in bytes per row of nR + nS: the concatenation 16 (32 with `by`); the sorts (see there) plus 24 for the gather between two of
+ * them; heads 8 + 1, 8 more with `by`, a gathered 8 more for forward; reduce 1; apply 1 + 8 and, per row of R, one gathered 8-byte
+ * load and one scattered 8-byte store (two gathered loads more under the tolerance flag).
+ * rhj_get_info: "last.asof_units" the units the scan was cut into, "last.asof_sorts" the inner sorts that ran (1 without `by`, else
+ * 2; 0 when a table was empty), "last.asof_matched" the matched rows; all three are 0 after every other call.  After an as-of call
+ * "last.join_kernel" is -1 and "last.sort_*" / "last.topk_*" / "last.window_*" are 0.  "asof.tile_rows": the positions one workgroup
+ * scans at once, a constant of the build.
+ * Memory: a workspace buffer of its own (the inner sorts regrow the sort's), kept until rhj_release_workspace: 2 x 8 + 1 bytes per row
+ * of nR + nS, 5 x 8 + 1 with `by`.
+ * Out of scope: direction "nearest" is not part of this entry -- a backward call, a forward call and a caller-side comparison of the
+ * two distances give it.  There is no 16-byte tuple form: a table here has two key columns. */
+#define RHJ_ASOF_I64        1u   /* order the `on` words as two's-complement int64 (default: unsigned), as RHJ_SORT_I64 */
+#define RHJ_ASOF_FORWARD    2u   /* the nearest row of S at or AFTER (default: at or before) */
+#define RHJ_ASOF_STRICT     4u   /* exclude equal `on` words (pandas allow_exact_matches=False) */
+#define RHJ_ASOF_TOLERANCE  8u   /* only partners whose distance is <= tolerance; without the bit `tolerance` is ignored */
+int rhj_asof_cols_dev(rhj_ctx *ctx, const uint64_t *d_byR, const uint64_t *d_onR, uint64_t nR,
+                      const uint64_t *d_byS, const uint64_t *d_onS, uint64_t nS, uint32_t flags, uint64_t tolerance,
+                      uint64_t *d_out_rowS, uint64_t *out_matched);
 
 /* ---- sort: a stable radix sort of one 64-bit key column with rowIDs (ORDER BY, argsort; the ordered half of what the operators above
  * return "in no particular order").

@@ -39,6 +39,10 @@ the k-th smallest key and its row, a median or a quantile, with nothing of size 
 Window functions: ``number, running = Engine(0).window_columns(k, t, [None, x], ["row_number", "cumsum"])`` is ROW_NUMBER() and a
 running SUM(x) OVER (PARTITION BY k ORDER BY t), one tensor per op aligned with the rows -- also rank, dense_rank, cummin / cummax and
 lag / lead (``rhj_window_cols_dev``); ``Engine(0).topk_per_group_columns(k, t, 3)`` the rows with ROW_NUMBER <= 3.
+As-of join: ``idx_S, matched, values = Engine(0).asof_join_columns(t_R, t_S, by_R=sym_R, by_S=sym_S, values_S=[bid])`` is, for every
+row of R, the row of S with the same ``by`` whose ``on`` is the nearest at or before it (``direction="forward"``: at or after), -1
+where there is none, aligned with R -- ``pandas.merge_asof`` on unsorted tensors, with ``allow_exact_matches`` and ``tolerance``
+(``rhj_asof_cols_dev``).
 """
 from .binding import (  # noqa: F401
     AGG_MAX_I64,
@@ -54,6 +58,10 @@ from .binding import (  # noqa: F401
     ARG_ROW,
     ARG_TIE_FIRST,
     ARG_TIE_LAST,
+    ASOF_FORWARD,
+    ASOF_I64,
+    ASOF_STRICT,
+    ASOF_TOLERANCE,
     PAIR,
     TUPLE,
     DeviceBuffer,
@@ -101,5 +109,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS", "SORT_I64", "SORT_DESC", "WINDOW_MAX_OPS", "WIN_ROW_NUMBER", "WIN_RANK", "WIN_DENSE_RANK", "WIN_LAG_ROW", "WIN_LEAD_ROW", "WIN_CUMSUM", "WIN_CUMMIN_U64", "WIN_CUMMAX_U64", "WIN_CUMMIN_I64", "WIN_CUMMAX_I64"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS", "SORT_I64", "SORT_DESC", "WINDOW_MAX_OPS", "WIN_ROW_NUMBER", "WIN_RANK", "WIN_DENSE_RANK", "WIN_LAG_ROW", "WIN_LEAD_ROW", "WIN_CUMSUM", "WIN_CUMMIN_U64", "WIN_CUMMAX_U64", "WIN_CUMMIN_I64", "WIN_CUMMAX_I64", "ASOF_I64", "ASOF_FORWARD", "ASOF_STRICT", "ASOF_TOLERANCE"]
 __version__ = "0.1.0"

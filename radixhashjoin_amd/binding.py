@@ -138,6 +138,7 @@ SYMBOLS = {
     "rhj_keys_unpack_dev": (C.c_int, [_vp, _vp, _vp, _u64, _P(_vp)]),
     "rhj_keys_plan_info": (C.c_int, [_vp, _P(KeysLayout)]),
     "rhj_keys_plan_free": (C.c_int, [_vp, _vp]),
+    "rhj_asof_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, C.c_uint32, _u64, _vp, _P(_u64)]),
     "rhj_sort_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _vp, _vp]),
     "rhj_sort_dev": (C.c_int, [_vp, _vp, _u64, C.c_uint32, _vp]),
     "rhj_topk_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _u64, C.c_uint32, _vp, _vp, _P(_u64)]),
@@ -353,6 +354,45 @@ def _window_args(order_by, values, ops, descending, unsigned, offsets, fill):
     if isinstance(fill, bool) or not isinstance(fill, int):
         raise ValueError(f"fill: an int is needed, not {fill!r}")
     return [_WIN_BY_NAME[o] for o in ops], values, [o if isinstance(o, int) and not isinstance(o, bool) else 1 for o in offs]
+
+
+# include/rhj.h RHJ_ASOF_*: flags of an asof_cols_dev call -- the int64 view, at or after, equal words excluded, the distance bound
+ASOF_I64, ASOF_FORWARD, ASOF_STRICT, ASOF_TOLERANCE = 1, 2, 4, 8
+
+
+def _asof_args(by_R, by_S, values_S, direction, allow_exact_matches, tolerance, unsigned, fill):
+    """(flags, tolerance word, value tensors, fills) of an asof_join_columns call; ValueError on a wrong direction, flag, tolerance, `by`
+    or number of tensors -- nothing here touches a device"""
+    if direction == "nearest":
+        raise ValueError("direction: 'nearest' is not supported -- run 'backward' and 'forward' and keep the closer partner per row")
+    if not isinstance(direction, str) or direction not in ("backward", "forward"):
+        raise ValueError(f"direction: 'backward' or 'forward' is needed ('nearest' is not supported), not {direction!r}")
+    if not isinstance(allow_exact_matches, bool):
+        raise ValueError(f"allow_exact_matches: a bool is needed, not {allow_exact_matches!r}")
+    if not isinstance(unsigned, bool):
+        raise ValueError(f"unsigned: a bool is needed, not {unsigned!r}")
+    if tolerance is not None and (isinstance(tolerance, bool) or not isinstance(tolerance, int) or not 0 <= tolerance <= NO_ROW):
+        raise ValueError(f"tolerance: an int >= 0 (below 2^64) or None is needed, not {tolerance!r}")
+    if (by_R is None) != (by_S is None):
+        raise ValueError(f"{'by_S' if by_S is None else 'by_R'}: None, but the other side has a `by`: both sides or neither")
+    if by_R is not None:
+        counts = [len(b) if isinstance(b, (list, tuple)) else 1 for b in (by_R, by_S)]
+        for name, k in zip(("by_R", "by_S"), counts):
+            if not 1 <= k <= KEYS_MAX_COLS:
+                raise ValueError(f"{name}: 1 to {KEYS_MAX_COLS} tensors are needed, not {k}")
+        if counts[0] != counts[1]:
+            raise ValueError(f"by_S: {counts[1]} tensors, by_R has {counts[0]}")
+    values_S = tuple(values_S)
+    if len(values_S) > LOOKUP_MAX_COLS:
+        raise ValueError(f"values_S: at most {LOOKUP_MAX_COLS} value tensors per call, not {len(values_S)}")
+    fills = [fill] * len(values_S) if isinstance(fill, int) else list(fill) if isinstance(fill, (list, tuple)) else [None]
+    if len(fills) != len(values_S) or not all(isinstance(f, int) and not isinstance(f, bool) for f in fills):
+        raise ValueError(f"fill: an int, or one int per tensor of values_S ({len(values_S)}), is needed")
+    flags = ((0 if unsigned else ASOF_I64) | (ASOF_FORWARD if direction == "forward" else 0) | (0 if allow_exact_matches else ASOF_STRICT) |
+             (ASOF_TOLERANCE if tolerance is not None else 0))
+    return flags, tolerance or 0, values_S, fills
+
+
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
 
@@ -515,8 +555,9 @@ class Engine:
     def info(self, name):
         """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.outer_sweeps", "last.group_rounds",
         "last.sort_bits", "last.sort_passes", "last.sort_units", "last.topk_bits", "last.topk_passes", "last.topk_candidates",
-        "last.topk_sorted_rows", "last.window_units", "last.window_sorts", "last.window_partitions"; include/rhj.h) and constants of
-        the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows")"""
+        "last.topk_sorted_rows", "last.window_units", "last.window_sorts", "last.window_partitions", "last.asof_units", "last.asof_sorts",
+        "last.asof_matched"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows",
+        "asof.tile_rows")"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
         return v.value
@@ -1564,6 +1605,48 @@ class Engine:
             raise ValueError(f"k: a count of rows is needed, not {k}")
         number = self.window_columns(partition_by, order_by, (), ("row_number",), descending, unsigned)[0]
         return torch.nonzero(number <= k).reshape(-1)
+
+    def asof_cols_dev(self, d_byR, d_onR, nR, d_byS, d_onS, nS, flags=0, tolerance=0, d_out_rowS=None):
+        """rhj_asof_cols_dev: d_out_rowS[i] = the row of S nearest to row i of R among the rows with a bit-equal `by` word (d_byR and
+        d_byS None: one partition) whose `on` word is at or before onR[i] -- flags: ASOF_I64 (the words as int64), ASOF_FORWARD (at or
+        after), ASOF_STRICT (equal words excluded), ASOF_TOLERANCE (only within tolerance; ignored without the bit) --, NO_ROW where
+        there is none; among equal `on` words backward takes the largest row of S, forward the smallest.  d_out_rowS: uint64[nR] in
+        HBM, aligned with R.  Returns the number of rows of R with a partner."""
+        matched = _u64()
+        self._chk(self.lib.rhj_asof_cols_dev(self.ctx, _addr(d_byR), _addr(d_onR), nR, _addr(d_byS), _addr(d_onS), nS, flags, tolerance,
+                                             _addr(d_out_rowS), C.byref(matched)))
+        return matched.value
+
+    def asof_join_columns(self, on_R, on_S, by_R=None, by_S=None, values_S=(), direction="backward", allow_exact_matches=True, tolerance=None,
+                          unsigned=False, fill=0):
+        """(idx_S, matched, values): the as-of join, pandas.merge_asof(R, S, on=.., by=..) as indices -- idx_S[i] = the row of S whose
+        on_S is the nearest at or before on_R[i] (direction="forward": at or after) among the rows of S with by_S equal to by_R[i],
+        -1 where there is none; an int64 tensor of len(on_R) on the tensors' device, aligned with R.  matched = how many rows of R found
+        a partner, a Python int; values = one int64 tensor of len(on_R) per tensor of values_S: values[k][i] = values_S[k][idx_S[i]], or
+        fill where idx_S[i] == -1 (shaped as lookup_columns returns them).  on_R / on_S: contiguous 1-D 64-bit integer tensors on the
+        engine's device, ordered as int64 (unsigned=True: the words as uint64); NEITHER needs to be sorted.  by_R / by_S: None (one
+        partition), a tensor per side, or a list of 1 to KEYS_MAX_COLS tensors per side (packed first, pack_keys).
+        allow_exact_matches=False excludes equal on values; tolerance: None, or an int >= 0 -- only partners with |on_R[i] - on_S[j]|
+        <= tolerance, as exact integers.  Where S repeats a (by, on), backward returns the LAST of the duplicates and forward the
+        FIRST, as pandas does.  values_S: up to LOOKUP_MAX_COLS tensors of len(on_S); fill: an int, or one per tensor.
+        direction="nearest" is not supported (a backward call, a forward call and a comparison of the two distances give it).  A wrong
+        direction, a non-bool flag, a negative, bool or float tolerance, `by` on one side only, a different number of `by` tensors per
+        side, more than KEYS_MAX_COLS of them, too many value tensors: ValueError before any device use.  One rhj_asof_cols_dev call
+        and one rhj_gather_cols_fill.  Streams and completion as join_columns."""
+        import torch
+        flags, tol, values_S, fills = _asof_args(by_R, by_S, values_S, direction, allow_exact_matches, tolerance, unsigned, fill)
+        if isinstance(by_R, (list, tuple)) or isinstance(by_S, (list, tuple)):
+            by_R, by_S, plan = self.pack_keys(by_R if isinstance(by_R, (list, tuple)) else [by_R],
+                                              by_S if isinstance(by_S, (list, tuple)) else [by_S], keep_dictionaries=False)
+            plan.close()                           # (a join needs no dictionary: the plan holds nothing)
+        with self._on_torch_stream(on_R, on_S, () if by_R is None else (by_R,), weights_S=values_S + (() if by_S is None else (by_S,))) as dev:
+            nR, nS = on_R.numel(), on_S.numel()
+            idx_S = torch.empty(nR, dtype=torch.int64, device=dev)
+            matched = self.asof_cols_dev(by_R, on_R, nR, by_S, on_S, nS, flags, tol, idx_S if nR else None)
+            values = [torch.empty(nR, dtype=torch.int64, device=dev) for _ in values_S]
+            if values and nR:
+                self.gather_cols_fill(values_S, nS, idx_S, nR, fills, values)
+        return idx_S, matched, values
 
     def factorize_columns(self, keys):
         """(codes, uniques): pandas.factorize without the ordering promise -- uniques the distinct values of keys in no particular

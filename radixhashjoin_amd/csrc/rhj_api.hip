@@ -281,6 +281,9 @@ struct rhj_ctx {
     int64_t opt_topk_cand = -1;        // "topk.max_candidates": -1 automatic, else selection goes on while more rows than this are tied
     int last_window_units = 0, last_window_sorts = 0;   // "last.window_units" / "last.window_sorts": the units the last window call's scans were cut into, its inner sorts (0: another call)
     u64 last_window_parts = 0;         // "last.window_partitions": the partitions it found
+    int last_asof_units = 0, last_asof_sorts = 0;       // "last.asof_units" / "last.asof_sorts": the units the last as-of call's scan was cut into, its inner sorts (0: another call)
+    u64 last_asof_matched = 0;         // "last.asof_matched": the rows of R that found a partner
+    DevBuf asof_ws;                    // the as-of entry's concatenation, permutation, flags and unit tables (rhj_asof.hip): not sort_ws, which the inner sorts regrow
     DevBuf window_ws;                  // the window entry's permutation, sorted words, flags, starts and unit tables (rhj_window.hip): not sort_ws, which the inner sorts regrow
     CallArgs call;                     // the operator arguments of the entry in progress (CallScope)
     u64 outer_sections[3] = {0, 0, 0}; // an outer join's {matched, R-only, S-only} rows, as outer_phase leaves them
@@ -520,6 +523,8 @@ void prof_reset(rhj_ctx *ctx)
     ctx->last_topk_cand = ctx->last_topk_sorted = 0;
     ctx->last_window_units = ctx->last_window_sorts = 0;                      // "last.window_*": ... and the window entry these
     ctx->last_window_parts = 0;
+    ctx->last_asof_units = ctx->last_asof_sorts = 0;                          // "last.asof_*": ... and the as-of entry these
+    ctx->last_asof_matched = 0;
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -2142,6 +2147,19 @@ int rhj_internal_window_workspace(rhj_ctx *ctx, size_t bytes, void **out)
     *out = ctx->window_ws.p;
     return RHJ_OK;
 }
+// ... and for rhj_asof.hip
+void rhj_internal_asof_report(rhj_ctx *ctx, int units, int sorts, u64 matched)
+{
+    ctx->last_asof_units = units;
+    ctx->last_asof_sorts = sorts;
+    ctx->last_asof_matched = matched;
+}
+int rhj_internal_asof_workspace(rhj_ctx *ctx, size_t bytes, void **out)
+{
+    RHJCHK(ensure(ctx, ctx->asof_ws, bytes));
+    *out = ctx->asof_ws.p;
+    return RHJ_OK;
+}
 void *rhj_internal_span_open(rhj_ctx *ctx, int kind) { return new Span(ctx, kind); }
 void rhj_internal_span_close(void *span) { delete (Span *)span; }
 
@@ -2233,7 +2251,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->agg_out, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
                      &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cf2_end[0], &ctx->cf2_end[1], &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
-                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws, &ctx->window_ws};
+                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws, &ctx->window_ws, &ctx->asof_ws};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
     ctx->small_hdr_clean = false;
@@ -2344,6 +2362,10 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.window_sorts") { *value = ctx->last_window_sorts; return RHJ_OK; }
     if (n == "last.window_partitions") { *value = (int64_t)ctx->last_window_parts; return RHJ_OK; }
     if (n == "window.tile_rows") { *value = WINDOW_TILE; return RHJ_OK; }
+    if (n == "last.asof_units") { *value = ctx->last_asof_units; return RHJ_OK; }
+    if (n == "last.asof_sorts") { *value = ctx->last_asof_sorts; return RHJ_OK; }
+    if (n == "last.asof_matched") { *value = (int64_t)ctx->last_asof_matched; return RHJ_OK; }
+    if (n == "asof.tile_rows") { *value = ASOF_TILE; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }

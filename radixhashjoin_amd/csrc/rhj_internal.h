@@ -482,3 +482,5 @@ constexpr int TOPK_AUTO_CANDIDATES = 1 << 16;
 // the window scans (rhj_window.hip) run on the sort's units and tiles: one workgroup of SORT_THREADS scans a tile of
 // this many sorted positions at once ("window.tile_rows")
 constexpr int WINDOW_TILE = SORT_TILE;
+// ... and so does the as-of scan (rhj_asof.hip; "asof.tile_rows")
+constexpr int ASOF_TILE = SORT_TILE;

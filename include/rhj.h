@@ -682,6 +682,81 @@ int rhj_group_arg_dev(rhj_ctx *ctx, const rhj_tuple *d_R, uint64_t nR,
                       const rhj_opts *opts, uint64_t *d_out_keys, uint64_t *d_out_counts,
                       uint64_t *const *d_out_vals, uint64_t *const *d_out_rows, uint64_t out_capacity, uint64_t *out_groups);
 
+/* ---- framed window aggregates: a value per row from a ROWS frame around it in its partition (SUM / MIN / MAX / COUNT / FIRST_VALUE /
+ * LAST_VALUE OVER [PARTITION BY k ORDER BY t ROWS BETWEEN a PRECEDING AND b FOLLOWING]; pandas groupby.rolling(w).sum / min / max,
+ * groupby.transform("size" / "first" / "last")).  The window entry below computes over the rows BEFORE a row; this one
+ * computes over a sliding or whole-partition frame, and a sliding MIN / MAX costs the same for every frame width.
+ * Partitions, order and ties are the window entry's, word for word: rows are the indices 0 .. n - 1; d_part, d_order and every
+ * d_cols[j] are device columns of n words; ops, preceding, following, the two pointer arrays and out_partitions are HOST memory.  A
+ * PARTITION is the set of rows with the same d_part word -- the word is compared for equality only; d_part == NULL: one partition.
+ * Inside a partition the rows are ordered by their d_order word under flags: RHJ_SORT_I64 and RHJ_SORT_DESC, with the sort entry's
+ * meaning.  Ties keep their input order in both directions, so every result is defined, and bit-identical from run to run.
+ * d_order == NULL: input order; a non-zero flags with d_order == NULL is RHJ_E_INVALID.  The outputs are aligned with the input rows,
+ * not in sorted order.
+ * The frame: for row i at 0-based position q of its partition P of m rows, the frame of op j is the positions
+ *     [max(0, q - preceding[j]), min(m - 1, q + following[j])]  of P,
+ * computed without wrap-around: q + following[j] saturates.  RHJ_FRAME_UNBOUNDED (all ones) on either side means "to the partition's
+ * edge".  preceding == NULL: unbounded for every op; following == NULL: 0 for every op -- together the running frame ROWS UNBOUNDED
+ * PRECEDING of the window entry.  The frame always contains the current row; frames that end before or start after the current row,
+ * and value-based RANGE frames, are not part of this entry.  Each op has its own frame.
+ * Ops: d_outs[j][i] receives
+ *     RHJ_FRAME_COUNT       the rows in the frame; with both sides unbounded the partition's size (COUNT(*) OVER (PARTITION BY k))
+ *     RHJ_FRAME_SUM         the sum mod 2^64 of d_cols[j][r] over the rows r in the frame
+ *     RHJ_FRAME_MIN_U64 / RHJ_FRAME_MAX_U64 / RHJ_FRAME_MIN_I64 / RHJ_FRAME_MAX_I64
+ *                           the minimum / maximum of those words, unsigned or as two's-complement int64: bit for bit a column word
+ *     RHJ_FRAME_FIRST_ROW / RHJ_FRAME_LAST_ROW
+ *                           the row at the frame's first / last position; the frame holds the current row, so there is never RHJ_NO_ROW
+ * d_cols[j] is ignored for the ops without a column (d_cols may then be NULL).  The same column may be given several times; two equal
+ * output pointers are undefined.  FIRST_VALUE / LAST_VALUE of a PAYLOAD is rhj_gather_u64 through the row:
+ *     ops = {RHJ_FRAME_FIRST_ROW}; pre = {9}; rhj_frame_cols_dev(ctx, k, t, n, RHJ_SORT_I64, ops, pre, NULL, NULL, 1, &first, NULL);
+ *     rhj_gather_u64(ctx, x, first, n, x_first);                              -- x_first[i] = x at the frame's first row
+ * Each row's share of its partition: with ROW_NUMBER rn and RANK rk from rhj_window_cols_dev and the partition's size m from
+ * RHJ_FRAME_COUNT with both sides unbounded, NTILE(b) is -- big = m % b, small = m / b -- rn <= big * (small + 1) ? (rn - 1) / (small
+ * + 1) + 1 : big + (rn - 1 - big * (small + 1)) / small + 1; PERCENT_RANK is m > 1 ? (rk - 1) / (m - 1) : 0; CUME_DIST is (the
+ * RHJ_FRAME_COUNT of a frame reaching to the last peer) / m -- over distinct order keys rn_of_last_peer / m.  Two calls, so two sets
+ * of sorts.
+ * *out_partitions receives the number of partitions; it may be NULL.  n == 0: RHJ_OK, no launch, 0 partitions.  RHJ_E_INVALID,
+ * before any launch, with a message naming the argument: unknown flag bits; flags without d_order; nops 0 or above
+ * RHJ_FRAME_MAX_OPS; NULL ops, d_outs or d_outs[j]; an op above RHJ_FRAME_LAST_ROW; a NULL d_cols[j] for a column op with n > 0.
+ * Inputs are neither modified nor retained; outputs must not overlap inputs.  The call synchronises; it honours rhj_set_stream and
+ * rhj_set_profiling (the inner sorts' spans; RHJ_K_AUX: heads, gather, emit; per scan RHJ_K_HIST, RHJ_K_SCAN, RHJ_K_SCATTER).
+ * How: the order (partition, order key, input position) from the stable sort, as the window entry's -- 0, 1 or 2 inner sorts.  One
+ * launch marks the partition heads.  Every position's partition start and end are a forward maximum scan of (head ? position : 0) and
+ * a backward minimum scan of (tail ? position : all ones); lo and hi of every op are then arithmetic, and COUNT, FIRST_ROW and
+ * LAST_ROW need nothing else.  Value scans are stored BY SORTED POSITION.  SUM: one forward scan S that restarts at partition heads;
+ * the answer is S[hi] - (lo above the start ? S[lo - 1] : 0), exact mod 2^64.  MIN / MAX of width w = preceding + following + 1: the
+ * positions are cut into blocks of w, aligned to multiples of w of the global position; F is the forward scan that restarts at
+ * partition heads and block starts, B the backward scan that restarts at partition tails and block ends; a frame is never wider than
+ * a block, so it is F[hi], B[lo] or op(B[lo], F[hi]) -- two stored words at most, whatever w.  A side that is unbounded or reaches n -
+ * 1 positions needs one scan without blocks (F for preceding, B for following); otherwise two, with blocks when w < n.  A backward
+ * scan is the forward fold over the mirrored position n - 1 - p.  Each scan is three launches ordered on the stream on the sort's
+ * units ("sort.max_units" caps them here too; the result never depends on it): a reduce per unit, a one-workgroup carry over the at
+ * most 2048 unit summaries, an apply per unit.  One emit launch per call reads the arrays at lo / hi and stores out[perm[p]].  No
+ * workgroup waits on another inside a kernel, and no position, value or count comes from an atomic.
+ * Costs in bytes per row: the sorts (see there) plus 24 for the gather between two of them; heads 8 + 1; each bound 1 + 1 + 8; each
+ * value scan 2 x (1 + 8) read and two gathered 8-byte loads, 8 written; emit 8 .. 24 read, per op up to two gathered 8-byte loads
+ * and one scattered 8-byte store.
+ * rhj_get_info: "last.frame_units" the units the scans were cut into, "last.frame_sorts" the inner sorts that ran (0, 1 or 2),
+ * "last.frame_partitions" the partitions, "last.frame_scans" the value scans: 1 per SUM, 1 or 2 per MIN / MAX, 0 for the other ops;
+ * all four are 0 after every other call.  After a frame call "last.join_kernel" is -1 and "last.sort_*" / "last.topk_*" /
+ * "last.window_*" / "last.asof_*" are 0.
+ * Memory: a workspace buffer of its own (the inner sorts regrow the sort's), kept until rhj_release_workspace: 4 x 8 + 1 bytes per
+ * row for the order and the bounds, and 8 per value scan -- up to 12 x 8 + 1.
+ * There is no 16-byte tuple form. */
+#define RHJ_FRAME_MAX_OPS    4
+#define RHJ_FRAME_UNBOUNDED  0xFFFFFFFFFFFFFFFFull   /* preceding[j] / following[j]: to the partition's edge */
+#define RHJ_FRAME_COUNT      0   /* no column */
+#define RHJ_FRAME_SUM        1   /* column; mod 2^64 */
+#define RHJ_FRAME_MIN_U64    2
+#define RHJ_FRAME_MAX_U64    3
+#define RHJ_FRAME_MIN_I64    4
+#define RHJ_FRAME_MAX_I64    5
+#define RHJ_FRAME_FIRST_ROW  6   /* no column */
+#define RHJ_FRAME_LAST_ROW   7   /* no column */
+int rhj_frame_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_order, uint64_t n, uint32_t flags,
+                       const uint32_t *ops, const uint64_t *preceding, const uint64_t *following,
+                       const uint64_t *const *d_cols, uint32_t nops, uint64_t *const *d_outs, uint64_t *out_partitions);
+
 /* ---- composite keys: up to four key columns per relation packed into ONE 64-bit key column (JOIN .. ON r.a = s.a AND r.b = s.b; GROUP
  * BY a, b; torch.unique(dim=0); merge(on=[..])).  Every operator above compares 64-bit values by bit pattern, so what it needs is an
  * EXACT surrogate: a 64-bit word per row such that two rows of R u S get the same word if and only if all their key columns agree.

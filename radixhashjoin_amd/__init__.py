@@ -43,6 +43,10 @@ As-of join: ``idx_S, matched, values = Engine(0).asof_join_columns(t_R, t_S, by_
 row of R, the row of S with the same ``by`` whose ``on`` is the nearest at or before it (``direction="forward"``: at or after), -1
 where there is none, aligned with R -- ``pandas.merge_asof`` on unsorted tensors, with ``allow_exact_matches`` and ``tolerance``
 (``rhj_asof_cols_dev``).
+Framed window aggregates: ``moving, size = Engine(0).frame_columns(k, t, [x, None], ["max", "count"], [9, None], [0, None])`` is
+MAX(x) over the last ten rows of each partition and the partition's size, aligned with the rows -- sliding ROWS frames for count, sum,
+min / max and the frame's first / last row, a sliding min / max at the same cost for every width (``rhj_frame_cols_dev``);
+``Engine(0).ntile_columns(k, t, 4)`` is NTILE(4).
 """
 from .binding import (  # noqa: F401
     AGG_MAX_I64,
@@ -66,6 +70,16 @@ from .binding import (  # noqa: F401
     TUPLE,
     DeviceBuffer,
     Engine,
+    FRAME_COUNT,
+    FRAME_FIRST_ROW,
+    FRAME_LAST_ROW,
+    FRAME_MAX_I64,
+    FRAME_MAX_OPS,
+    FRAME_MAX_U64,
+    FRAME_MIN_I64,
+    FRAME_MIN_U64,
+    FRAME_SUM,
+    FRAME_UNBOUNDED,
     GJ_INNER,
     GJ_LEFT,
     GROUP_ARG_MAX_COLS,
@@ -109,5 +123,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS", "SORT_I64", "SORT_DESC", "WINDOW_MAX_OPS", "WIN_ROW_NUMBER", "WIN_RANK", "WIN_DENSE_RANK", "WIN_LAG_ROW", "WIN_LEAD_ROW", "WIN_CUMSUM", "WIN_CUMMIN_U64", "WIN_CUMMAX_U64", "WIN_CUMMIN_I64", "WIN_CUMMAX_I64", "ASOF_I64", "ASOF_FORWARD", "ASOF_STRICT", "ASOF_TOLERANCE"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS", "SORT_I64", "SORT_DESC", "WINDOW_MAX_OPS", "WIN_ROW_NUMBER", "WIN_RANK", "WIN_DENSE_RANK", "WIN_LAG_ROW", "WIN_LEAD_ROW", "WIN_CUMSUM", "WIN_CUMMIN_U64", "WIN_CUMMAX_U64", "WIN_CUMMIN_I64", "WIN_CUMMAX_I64", "ASOF_I64", "ASOF_FORWARD", "ASOF_STRICT", "ASOF_TOLERANCE", "FRAME_MAX_OPS", "FRAME_UNBOUNDED", "FRAME_COUNT", "FRAME_SUM", "FRAME_MIN_U64", "FRAME_MAX_U64", "FRAME_MIN_I64", "FRAME_MAX_I64", "FRAME_FIRST_ROW", "FRAME_LAST_ROW"]
 __version__ = "0.1.0"

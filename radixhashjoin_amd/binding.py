@@ -144,6 +144,7 @@ SYMBOLS = {
     "rhj_topk_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, _u64, C.c_uint32, _vp, _vp, _P(_u64)]),
     "rhj_topk_dev": (C.c_int, [_vp, _vp, _u64, _u64, C.c_uint32, _vp, _P(_u64)]),
     "rhj_window_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
+    "rhj_frame_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -393,6 +394,59 @@ def _asof_args(by_R, by_S, values_S, direction, allow_exact_matches, tolerance, 
     return flags, tolerance or 0, values_S, fills
 
 
+# include/rhj.h RHJ_FRAME_*: the ops of a frame_cols_dev call, how many one call takes, and "to the partition's edge"
+FRAME_MAX_OPS = 4
+FRAME_UNBOUNDED = 0xFFFFFFFFFFFFFFFF
+FRAME_COUNT, FRAME_SUM, FRAME_MIN_U64, FRAME_MAX_U64, FRAME_MIN_I64, FRAME_MAX_I64, FRAME_FIRST_ROW, FRAME_LAST_ROW = range(8)
+_FRAME_NAMES = ("count", "sum", "min", "max", "first_row", "last_row")
+
+
+def _frame_args(order, cols, ops, preceding, following, descending, unsigned):
+    """(RHJ_FRAME_* words, column tensors or None, preceding words, following words) of a frame_columns call; ValueError on a wrong
+    name, length, bound or flag -- nothing here touches a device"""
+    if isinstance(ops, str):
+        raise ValueError(f"ops: a sequence of op names is needed, not the string {ops!r}")
+    ops = list(ops) if ops is not None else []
+    if not ops:
+        raise ValueError("ops: at least one op is needed")
+    if len(ops) > FRAME_MAX_OPS:
+        raise ValueError(f"ops: at most {FRAME_MAX_OPS} ops per call, not {len(ops)}")
+    for i, o in enumerate(ops):
+        if not isinstance(o, str) or o not in _FRAME_NAMES:
+            raise ValueError(f"ops[{i}]: one of {', '.join(repr(k) for k in _FRAME_NAMES)}, not {o!r}")
+    cols = list(cols) if cols is not None else []
+    if not cols:
+        cols = [None] * len(ops)
+    if len(cols) != len(ops):
+        raise ValueError(f"cols: {len(cols)} entries for {len(ops)} ops (None for an op without a column)")
+    bounds = []
+    for name, b in (("preceding", preceding), ("following", following)):
+        side = list(b) if isinstance(b, (list, tuple)) else [b] * len(ops)
+        if len(side) != len(ops):
+            raise ValueError(f"{name}: {len(side)} entries for {len(ops)} ops")
+        for i, x in enumerate(side):
+            if x is not None and (isinstance(x, bool) or not isinstance(x, int) or not 0 <= x <= FRAME_UNBOUNDED):
+                raise ValueError(f"{name}{f'[{i}]' if isinstance(b, (list, tuple)) else ''}: an int >= 0 (below 2^64) or None (unbounded) is needed, not {x!r}")
+        bounds.append([FRAME_UNBOUNDED if x is None else x for x in side])
+    if not isinstance(descending, bool):
+        raise ValueError(f"descending: a bool is needed, not {descending!r}")
+    if not isinstance(unsigned, bool):
+        raise ValueError(f"unsigned: a bool is needed, not {unsigned!r}")
+    if descending and order is None:
+        raise ValueError("descending: True needs an order tensor; without one the order is the input order")
+    if isinstance(order, (list, tuple)):
+        raise ValueError("order: one tensor or None -- for ORDER BY a, b run sort_columns([k, a, b]) first and pass order=None")
+    for i, o in enumerate(ops):
+        if o in ("count", "first_row", "last_row"):
+            if cols[i] is not None:
+                raise ValueError(f"cols[{i}]: {o!r} takes no column; None is needed")
+        elif cols[i] is None:
+            raise ValueError(f"cols[{i}]: {o!r} needs a tensor")
+    words = {"count": FRAME_COUNT, "sum": FRAME_SUM, "min": FRAME_MIN_U64 if unsigned else FRAME_MIN_I64,
+             "max": FRAME_MAX_U64 if unsigned else FRAME_MAX_I64, "first_row": FRAME_FIRST_ROW, "last_row": FRAME_LAST_ROW}
+    return [words[o] for o in ops], cols, bounds[0], bounds[1]
+
+
 SHARD_TAGGED, SHARD_GLOBAL16, SHARD_PLAIN = 1, 2, 3      # include/rhj.h: how the receiver restores global rowIDs
 
 
@@ -556,7 +610,7 @@ class Engine:
         """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.outer_sweeps", "last.group_rounds",
         "last.sort_bits", "last.sort_passes", "last.sort_units", "last.topk_bits", "last.topk_passes", "last.topk_candidates",
         "last.topk_sorted_rows", "last.window_units", "last.window_sorts", "last.window_partitions", "last.asof_units", "last.asof_sorts",
-        "last.asof_matched"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows",
+        "last.asof_matched", "last.frame_units", "last.frame_sorts", "last.frame_scans", "last.frame_partitions"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows",
         "asof.tile_rows")"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
@@ -1605,6 +1659,83 @@ class Engine:
             raise ValueError(f"k: a count of rows is needed, not {k}")
         number = self.window_columns(partition_by, order_by, (), ("row_number",), descending, unsigned)[0]
         return torch.nonzero(number <= k).reshape(-1)
+
+    def frame_cols_dev(self, d_part, d_order, n, flags=0, ops=(), preceding=None, following=None, d_cols=None, d_outs=()):
+        """rhj_frame_cols_dev: per row a value over the ROWS frame [q - preceding[j], q + following[j]] around its position q in its
+        partition (rows with the same d_part word; None: one partition), ordered by d_order under flags (SORT_I64, SORT_DESC; None:
+        input order), ties in input order -- ops[j] one of FRAME_COUNT, FRAME_SUM, FRAME_MIN_U64 / FRAME_MAX_U64 / FRAME_MIN_I64 /
+        FRAME_MAX_I64 (of d_cols[j]), FRAME_FIRST_ROW / FRAME_LAST_ROW (the row at the frame's first / last position).  preceding /
+        following: one word per op, FRAME_UNBOUNDED: to the partition's edge; preceding None: unbounded for every op, following None:
+        0 for every op.  d_outs[j]: uint64[n] in HBM, aligned with the rows.  The number of ops is len(ops), at most FRAME_MAX_OPS.
+        Returns the number of partitions.  (A sequence that is None goes in as NULL: the library answers.)"""
+        k = len(ops) if ops is not None else 0
+        opw = (C.c_uint32 * max(k, 1))(*[int(o) for o in ops]) if ops is not None else None
+        pre = (_u64 * max(k, 1))(*[int(a) for a in preceding]) if preceding is not None else None
+        fol = (_u64 * max(k, 1))(*[int(a) for a in following]) if following is not None else None
+        cols = (_vp * max(k, 1))(*[_addr(c) for c in d_cols]) if d_cols is not None else None
+        outs = (_vp * max(k, 1))(*[_addr(o) for o in d_outs]) if d_outs is not None else None
+        parts = _u64()
+        self._chk(self.lib.rhj_frame_cols_dev(self.ctx, _addr(d_part), _addr(d_order), n, flags, opw, pre, fol, cols, k, outs, C.byref(parts)))
+        return parts.value
+
+    def frame_columns(self, part, order, cols, ops, preceding=None, following=0, descending=False, unsigned=False):
+        """[out_0, out_1, ..]: framed window aggregates over the rows of a table -- one int64 tensor per op, ALIGNED WITH THE ROWS.
+        Partitions, order and ties as window_columns: rows with equal part form a partition (None: one partition; a list of 1 to
+        KEYS_MAX_COLS tensors is packed first), ordered inside it by order as int64 (unsigned=True: as uint64), ascending
+        (descending=True: descending), equal order keys in input order; order None: input order.  For the row at 0-based position q of
+        a partition of m rows the frame of op j is the positions [max(0, q - preceding[j]), min(m - 1, q + following[j])] -- ROWS
+        BETWEEN preceding PRECEDING AND following FOLLOWING.  preceding / following: an int >= 0, None (unbounded: to the partition's
+        edge), or a list with one of those per op.  The defaults are the running frame of window_columns.  ops:
+          "count"  the rows in the frame; with both sides None the partition's size (groupby.transform("size"))
+          "sum"    the sum mod 2^64 of cols[j] over the frame (groupby.rolling(w).sum() is preceding=w - 1)
+          "min" / "max"  the minimum / maximum of cols[j] over the frame as int64 (unsigned=True: of the words as uint64); its cost does
+                   not depend on the frame's width
+          "first_row" / "last_row"  the index of the row at the frame's first / last position; x[out] is FIRST_VALUE / LAST_VALUE(x)
+        cols[j] is None for an op without a column (cols=() or None: every op without one).  At most FRAME_MAX_OPS ops per call.
+        An unknown op, too many ops, a length mismatch, a negative, bool or float bound, a non-bool flag, descending=True without
+        order: ValueError before any device use.  One rhj_frame_cols_dev call.  Streams and completion as join_columns."""
+        import torch
+        opw, cols, pre, fol = _frame_args(order, cols, ops, preceding, following, descending, unsigned)
+        if isinstance(part, (list, tuple)):
+            packed, _, plan = self.pack_keys(part, keep_dictionaries=False)
+            plan.close()
+            part = packed
+        named = [("part", part), ("order", order)] + [(f"cols[{j}]", v) for j, v in enumerate(cols)]
+        named = [(name, t) for name, t in named if t is not None]
+        if not named:
+            raise ValueError("part, order and cols are all None: the number of rows is unknown")
+        ints = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)
+        for name, t in named:
+            if not isinstance(t, torch.Tensor) or t.dtype not in ints or t.dim() != 1:
+                raise ValueError(f"{name}: a 1-D torch tensor of 64-bit integers is needed")
+            if t.numel() != named[0][1].numel():
+                raise ValueError(f"{name}: {t.numel()} elements, {named[0][0]} has {named[0][1].numel()}")
+        tensors = [t for _, t in named]
+        flags = 0 if order is None else (0 if unsigned else SORT_I64) | (SORT_DESC if descending else 0)
+        with self._on_torch_stream(tensors[0], tensors[0], tuple(tensors[1:])) as dev:
+            n = tensors[0].numel()
+            outs = [torch.empty(n, dtype=torch.int64, device=dev) for _ in opw]
+            if n:
+                self.frame_cols_dev(part, order, n, flags, opw, pre, fol, cols, outs)
+        return outs
+
+    def ntile_columns(self, part, order, buckets, descending=False, unsigned=False):
+        """tile: NTILE(buckets) OVER (PARTITION BY part ORDER BY order) as an int64 tensor aligned with the rows -- the rows of a
+        partition of m rows, in order, dealt into buckets 1 .. buckets whose sizes differ by at most one, the m % buckets larger ones
+        first (SQL's rule; with m < buckets the rows get 1 .. m).  ROW_NUMBER from window_columns, the partition's size from
+        frame_columns(.., ["count"], None, None), the rule in torch: TWO calls, so two sets of sorts.  buckets: an int >= 1; the
+        other arguments and errors as window_columns."""
+        import torch
+        if isinstance(buckets, bool) or not isinstance(buckets, int) or buckets < 1:
+            raise ValueError(f"buckets: an int >= 1 is needed, not {buckets!r}")
+        number = self.window_columns(part, order, (), ("row_number",), descending, unsigned)[0]
+        size = self.frame_columns(part, order, (), ["count"], None, None, descending, unsigned)[0]
+        small = torch.div(size, buckets, rounding_mode="floor")
+        big = size - small * buckets                      # that many buckets hold small + 1 rows, and they come first
+        cut = big * (small + 1)
+        q = number - 1
+        return torch.where(q < cut, torch.div(q, small + 1, rounding_mode="floor"),
+                           big + torch.div(q - cut, torch.clamp(small, min=1), rounding_mode="floor")) + 1
 
     def asof_cols_dev(self, d_byR, d_onR, nR, d_byS, d_onS, nS, flags=0, tolerance=0, d_out_rowS=None):
         """rhj_asof_cols_dev: d_out_rowS[i] = the row of S nearest to row i of R among the rows with a bit-equal `by` word (d_byR and

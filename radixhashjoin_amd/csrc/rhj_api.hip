@@ -283,6 +283,9 @@ struct rhj_ctx {
     u64 last_window_parts = 0;         // "last.window_partitions": the partitions it found
     int last_asof_units = 0, last_asof_sorts = 0;       // "last.asof_units" / "last.asof_sorts": the units the last as-of call's scan was cut into, its inner sorts (0: another call)
     u64 last_asof_matched = 0;         // "last.asof_matched": the rows of R that found a partner
+    int last_frame_units = 0, last_frame_sorts = 0, last_frame_scans = 0;   // "last.frame_units" / "last.frame_sorts" / "last.frame_scans": the units the last frame call's scans were cut into, its inner sorts, its value scans (0: another call)
+    u64 last_frame_parts = 0;          // "last.frame_partitions": the partitions it found
+    DevBuf frame_ws;                   // the frame entry's permutation, sorted words, flags, bounds, by-position scans and unit tables (rhj_frame.hip): not sort_ws, which the inner sorts regrow
     DevBuf asof_ws;                    // the as-of entry's concatenation, permutation, flags and unit tables (rhj_asof.hip): not sort_ws, which the inner sorts regrow
     DevBuf window_ws;                  // the window entry's permutation, sorted words, flags, starts and unit tables (rhj_window.hip): not sort_ws, which the inner sorts regrow
     CallArgs call;                     // the operator arguments of the entry in progress (CallScope)
@@ -525,6 +528,8 @@ void prof_reset(rhj_ctx *ctx)
     ctx->last_window_parts = 0;
     ctx->last_asof_units = ctx->last_asof_sorts = 0;                          // "last.asof_*": ... and the as-of entry these
     ctx->last_asof_matched = 0;
+    ctx->last_frame_units = ctx->last_frame_sorts = ctx->last_frame_scans = 0;   // "last.frame_*": ... and the frame entry these
+    ctx->last_frame_parts = 0;
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -2160,6 +2165,20 @@ int rhj_internal_asof_workspace(rhj_ctx *ctx, size_t bytes, void **out)
     *out = ctx->asof_ws.p;
     return RHJ_OK;
 }
+// ... and for rhj_frame.hip
+void rhj_internal_frame_report(rhj_ctx *ctx, int units, int sorts, int scans, u64 partitions)
+{
+    ctx->last_frame_units = units;
+    ctx->last_frame_sorts = sorts;
+    ctx->last_frame_scans = scans;
+    ctx->last_frame_parts = partitions;
+}
+int rhj_internal_frame_workspace(rhj_ctx *ctx, size_t bytes, void **out)
+{
+    RHJCHK(ensure(ctx, ctx->frame_ws, bytes));
+    *out = ctx->frame_ws.p;
+    return RHJ_OK;
+}
 void *rhj_internal_span_open(rhj_ctx *ctx, int kind) { return new Span(ctx, kind); }
 void rhj_internal_span_close(void *span) { delete (Span *)span; }
 
@@ -2251,7 +2270,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->agg_out, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
                      &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cf2_end[0], &ctx->cf2_end[1], &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
-                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws, &ctx->window_ws, &ctx->asof_ws};
+                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws, &ctx->window_ws, &ctx->asof_ws, &ctx->frame_ws};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
     ctx->small_hdr_clean = false;
@@ -2366,6 +2385,10 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.asof_sorts") { *value = ctx->last_asof_sorts; return RHJ_OK; }
     if (n == "last.asof_matched") { *value = (int64_t)ctx->last_asof_matched; return RHJ_OK; }
     if (n == "asof.tile_rows") { *value = ASOF_TILE; return RHJ_OK; }
+    if (n == "last.frame_units") { *value = ctx->last_frame_units; return RHJ_OK; }
+    if (n == "last.frame_sorts") { *value = ctx->last_frame_sorts; return RHJ_OK; }
+    if (n == "last.frame_scans") { *value = ctx->last_frame_scans; return RHJ_OK; }
+    if (n == "last.frame_partitions") { *value = (int64_t)ctx->last_frame_parts; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }

@@ -1,0 +1,641 @@
+// rhj_frame.hip -- the frame entry (include/rhj.h, "framed window aggregates"): a value per row from the ROWS frame
+// [q - preceding, q + following] around it in its partition -- COUNT, SUM, MIN / MAX, the frame's first / last row.  The order
+// (partition, order key, input position) comes from the stable sort of rhj_sort.hip, as in rhj_window.hip.  What is new here: scans
+// that are stored BY SORTED POSITION, run forward or backward (the same fold over the mirrored position n - 1 - p), and restart at
+// the starts of blocks of w consecutive positions beside the partition heads -- so that a sliding minimum or maximum of width w is
+// the fold of at most two stored words, whatever w (van Herk, Gil-Werman) --, and one emit launch that reads them at the frame's two
+// ends and stores out[perm[p]].  Per scan three launches ordered on the context's stream: a reduce per unit, a one-workgroup carry
+// over the unit summaries, an apply per unit.  No workgroup ever waits on another, and no position, value or count comes from an
+// atomic.
+#include "../../include/rhj.h"
+#include "rhj_internal.h"
+
+#include <string>
+#include <vector>
+
+// provided by rhj_api.hip
+int rhj_internal_use_device(rhj_ctx *ctx);
+hipStream_t rhj_internal_stream(rhj_ctx *ctx);
+int rhj_internal_fail(rhj_ctx *ctx, int code, const char *msg);
+void rhj_internal_sort_begin(rhj_ctx *ctx);     // the start of a call: timings and "last.*" as prof_reset leaves them, "last.join_kernel" -1
+void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units);
+int rhj_internal_frame_workspace(rhj_ctx *ctx, size_t bytes, void **out);       // the frame entry's own buffer (the inner sorts regrow the sort's), grown to >= bytes
+void rhj_internal_frame_report(rhj_ctx *ctx, int units, int sorts, int scans, u64 partitions);   // "last.frame_units" / "last.frame_sorts" / "last.frame_scans" / "last.frame_partitions"
+void *rhj_internal_span_open(rhj_ctx *ctx, int kind);
+void rhj_internal_span_close(void *span);
+// provided by rhj_sort.hip
+int rhj_internal_sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, const u64 *rows, u64 n, u32 flags, u64 *okeys, u64 *orows);
+void rhj_internal_sort_units(rhj_ctx *ctx, u64 n, u64 *L, u32 *U);              // units of L rows, a whole number of tiles, under "sort.max_units"
+
+namespace {
+
+constexpr u64 BIAS = 1ull << 63;
+constexpr int ST = SORT_THREADS, TPT = SORT_TPT, TILE = WINDOW_TILE, NW = ST / 64;
+constexpr u32 FRM_MAX_UNITS = 2048;              // the sort's: what one carry workgroup scans
+constexpr int RED_UNROLL = 4;
+constexpr int FLAT_THREADS = 256;
+constexpr u32 FLAT_MAX_GRID = 4096;
+static_assert(TILE == ST * TPT && ST % 64 == 0 && TILE % (NW * 64 * RED_UNROLL) == 0, "k_frm_reduce's and k_frm_apply's geometry");
+
+// ---- the scan's algebra ------------------------------------------------------------------------------------------------------------
+// An element is (f, v): f -- a head stands here, v -- its value.  (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2), the later
+// element on the right, + the op.  It is associative wherever the heads stand, so heads at block starts beside the
+// partition heads change nothing in the argument, and neither does the direction: a backward scan is this fold over the index
+// m = n - 1 - p, in which a partition's tail and a block's end are the heads.
+enum { OP_SUM = 0, OP_MIN = 1, OP_MAX = 2 };
+enum { VS_COL = 0, VS_POS = 1 };                 // the value: a column word through the permutation; head ? position : the identity
+
+template <int OP> __device__ __forceinline__ u64 ident() { return OP == OP_MIN ? ~0ull : 0ull; }
+template <int OP> __device__ __forceinline__ u64 comb(u64 a, u64 b)
+{
+    return OP == OP_SUM ? a + b : OP == OP_MIN ? (b < a ? b : a) : (b > a ? b : a);
+}
+
+// inclusive scan of (f, v) over the wave's lanes: __shfl_up with the head flag carried along
+template <int OP> __device__ __forceinline__ void wave_seg_scan(u32 &f, u64 &v, u32 lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const u64 ov = __shfl_up(v, off, 64);
+        const u32 of = __shfl_up(f, off, 64);
+        if (lane >= (u32)off) {
+            v = f ? v : comb<OP>(ov, v);
+            f |= of;
+        }
+    }
+}
+
+struct FrmScan {
+    const unsigned char *flags;                  // n bytes, by sorted position: non-zero where a partition starts
+    const u64 *perm;                             // perm[p] = the row at sorted position p; null: the identity
+    const u64 *col;                              // VS_COL: the caller's column, by row
+    u64 *out;                                    // BY SORTED POSITION p, in both directions
+    u64 n, L;
+    u32 U;
+    u64 bias;                                    // VS_COL: 1 << 63 for the signed minimum / maximum; the stored words keep it, k_frm_emit takes it off
+    u64 w, s64, stile;                           // BLK: the block length (1 <= w < n), 64 % w and TILE % w
+    u64 *usum_v;                                 // per unit: the aggregate since the unit's last head (the whole unit without one)
+    u32 *usum_f;                                 // ... and whether it has a head
+    u64 *carry;                                  // per unit: the aggregate since the last head before the unit
+};
+
+// The scans run over the index m: the position itself forward, n - 1 - p backward.  The block counter c(m) is m forward and n - m
+// (= p + 1) backward; a block head stands where c % w == 0: at a block's first position forward, at its last one backward.  A thread
+// takes ONE 64-bit remainder per launch and steps it by 64 % w per round and TILE % w per tile (both from the host): x, s < w <
+// n < 2^63, so nothing wraps.
+template <bool BACK> __device__ __forceinline__ u64 frm_pos(const FrmScan &a, u64 m) { return BACK ? a.n - 1 - m : m; }
+template <bool BACK> __device__ __forceinline__ u64 frm_rem0(const FrmScan &a, u64 m) { return m < a.n ? (BACK ? a.n - m : m) % a.w : 0; }
+template <bool BACK> __device__ __forceinline__ u64 frm_step(u64 x, u64 s, u64 w)
+{
+    if (BACK) return x >= s ? x - s : x + (w - s);
+    x += s;
+    return x >= w ? x - w : x;
+}
+// the partition head at m (m < n): position 0 or a flagged one forward; backward the last position, or one whose successor is flagged
+template <bool BACK> __device__ __forceinline__ u32 frm_head(const FrmScan &a, u64 m, u64 p)
+{
+    if (m == 0) return 1;
+    return a.flags[BACK ? p + 1 : p] ? 1 : 0;
+}
+template <int OP, int VS, bool BACK> __device__ __forceinline__ u64 frm_value(const FrmScan &a, u64 p, u32 head)
+{
+    if (VS == VS_POS) return head ? p : ident<OP>();
+    const u64 row = a.perm ? a.perm[p] : p;
+    return row < a.n ? a.col[row] ^ a.bias : ident<OP>();                 // (row < n always: perm is a permutation)
+}
+
+// ---- k_frm_heads: one flag byte per sorted position, and the partition heads per unit ----------------------------------------------
+// A position heads a partition when its sorted partition word differs from its predecessor's; position 0 always does.  Each lane
+// takes its predecessor's word from the lane below; lane 0 loads it.
+__global__ void __launch_bounds__(ST)
+k_frm_heads(const u64 *__restrict__ sp, u64 n, u64 L, unsigned char *__restrict__ flags, u64 *__restrict__ ucnt)
+{
+    __shared__ u64 ws[NW];
+    const u32 tid = threadIdx.x, lane = tid & 63, u = blockIdx.x;
+    const u64 beg = (u64)u * L, end = beg + L < n ? beg + L : n;
+    u64 cnt = 0;
+    for (u64 p0 = beg; p0 < end; p0 += ST) {
+        const u64 p = p0 + tid;
+        const bool valid = p < end;
+        u64 cp = 0;
+        if (valid && sp) cp = sp[p];
+        u64 pp = __shfl_up(cp, 1, 64);
+        if (valid && lane == 0 && p > 0 && sp) pp = sp[p - 1];
+        if (valid) {
+            const bool ph = p == 0 || (sp && cp != pp);
+            flags[p] = ph ? 1 : 0;
+            cnt += ph;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if (lane == 0) ws[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid != 0) return;
+    u64 s = 0;
+#pragma unroll
+    for (int w = 0; w < NW; w++) s += ws[w];
+    ucnt[u] = s;
+}
+
+// ---- k_frm_gather: dst[i] = src[idx[i]] -- the partition column in the order of the first inner sort ------------------------------
+__global__ void __launch_bounds__(FLAT_THREADS)
+k_frm_gather(const u64 *__restrict__ src, const u64 *__restrict__ idx, u64 n, u64 *__restrict__ dst)
+{
+    for (u64 i = (u64)blockIdx.x * FLAT_THREADS + threadIdx.x; i < n; i += (u64)gridDim.x * FLAT_THREADS) {
+        const u64 r = idx[i];
+        dst[i] = r < n ? src[r] : 0;                                  // (r < n always: idx is a permutation of 0 .. n - 1)
+    }
+}
+
+// ---- k_frm_reduce<OP, VS, BACK, BLK>: per unit "has a head" and the aggregate since the unit's last head --------------------------
+// One workgroup per unit of the index m.  Wave w walks the w-th eighth of the unit 64 indices at a time, RED_UNROLL rounds of loads
+// in flight.  A round with a head keeps only the lanes from its last head on and replaces the wave's running aggregate; one without
+// adds to it.  The eight wave summaries are folded in order.
+template <int OP, int VS, bool BACK, bool BLK>
+__global__ void __launch_bounds__(ST)
+k_frm_reduce(FrmScan a)
+{
+    __shared__ u64 wv[NW];
+    __shared__ u32 wf[NW];
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, u = blockIdx.x;
+    const u64 beg = (u64)u * a.L, end = beg + a.L < a.n ? beg + a.L : a.n;
+    const u64 chunk = a.L / NW;
+    u64 wb = beg + wave * chunk;
+    if (wb > end) wb = end;
+    const u64 we = wb + chunk < end ? wb + chunk : end;
+    u64 rem = BLK ? frm_rem0<BACK>(a, wb + lane) : 1;
+    u32 rf = 0;
+    u64 rv = ident<OP>();
+    for (u64 m0 = wb; m0 < we; m0 += 64 * RED_UNROLL) {
+        u32 fl[RED_UNROLL];
+        u64 v[RED_UNROLL];
+#pragma unroll
+        for (int j = 0; j < RED_UNROLL; j++) {
+            const u64 m = m0 + (u64)j * 64 + lane;
+            fl[j] = 0;
+            v[j] = ident<OP>();
+            if (m < we) {
+                const u64 p = frm_pos<BACK>(a, m);
+                const u32 ph = frm_head<BACK>(a, m, p);
+                fl[j] = ph | (BLK && rem == 0 ? 1u : 0u);
+                v[j] = frm_value<OP, VS, BACK>(a, p, ph);
+            }
+            if (BLK) rem = frm_step<BACK>(rem, a.s64, a.w);
+        }
+#pragma unroll
+        for (int j = 0; j < RED_UNROLL; j++) {
+            const u64 hb = __ballot(fl[j] != 0);
+            u64 x = v[j];
+            if (hb != 0 && lane < (u32)(63 - __clzll((long long)hb))) x = ident<OP>();
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) x = comb<OP>(x, __shfl_xor(x, off, 64));
+            rv = hb != 0 ? x : comb<OP>(rv, x);
+            rf |= hb != 0;
+        }
+    }
+    if (lane == 0) { wv[wave] = rv; wf[wave] = rf; }
+    __syncthreads();
+    if (tid != 0) return;
+    u32 f = 0;
+    u64 v = ident<OP>();
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+        v = wf[w] ? wv[w] : comb<OP>(v, wv[w]);
+        f |= wf[w];
+    }
+    a.usum_v[u] = v;
+    a.usum_f[u] = f;
+}
+
+// ---- k_frm_carry<OP>: one workgroup -- the exclusive scan of at most 2048 unit summaries -------------------------------------------
+// Thread t folds its run of ceil(U / 512) consecutive units, the runs are scanned over the workgroup (wave scan, per-wave totals
+// through LDS), and the thread walks its run again from its carry-in.
+template <int OP>
+__global__ void __launch_bounds__(ST)
+k_frm_carry(const u64 *__restrict__ usum_v, const u32 *__restrict__ usum_f, u32 U, u64 *__restrict__ carry)
+{
+    __shared__ u64 wv[NW];
+    __shared__ u32 wf[NW];
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u32 per = (U + ST - 1) / ST;
+    const u32 b = tid * per < U ? tid * per : U, e = b + per < U ? b + per : U;
+    u32 sf = 0;
+    u64 sv = ident<OP>();
+    for (u32 u = b; u < e; u++) {
+        const u32 fu = usum_f[u];
+        const u64 vu = usum_v[u];
+        sv = fu ? vu : comb<OP>(sv, vu);
+        sf |= fu;
+    }
+    wave_seg_scan<OP>(sf, sv, lane);
+    if (lane == 63) { wv[wave] = sv; wf[wave] = sf; }
+    __syncthreads();
+    u64 pv = ident<OP>();
+#pragma unroll
+    for (int w = 0; w < NW; w++)
+        if ((u32)w < wave) pv = wf[w] ? wv[w] : comb<OP>(pv, wv[w]);
+    u64 ev = __shfl_up(sv, 1, 64);
+    u32 ef = __shfl_up(sf, 1, 64);
+    if (lane == 0) { ev = ident<OP>(); ef = 0; }
+    u64 cur = ef ? ev : comb<OP>(pv, ev);
+    for (u32 u = b; u < e; u++) {
+        carry[u] = cur;
+        const u32 fu = usum_f[u];
+        const u64 vu = usum_v[u];
+        cur = fu ? vu : comb<OP>(cur, vu);
+    }
+}
+
+// ---- k_frm_apply<OP, VS, BACK, BLK>: the scan itself, stored by position -------------------------------------------------------------
+// One workgroup per unit, tile by tile, in the order (wave, round, lane): wave w of a tile owns the indices [w * 64 * TPT, (w + 1) *
+// 64 * TPT) of it.  Per round a wave scan, continued from the wave's running aggregate (lane 63 of the round before); per tile the
+// waves' totals through LDS, folded onto the tile's carry-in -- the unit's from k_frm_carry, then the running one.  An index behind a
+// head of its own wave is final after the wave's rounds; any other takes the fold of the carry and the waves before.
+template <int OP, int VS, bool BACK, bool BLK>
+__global__ void __launch_bounds__(ST)
+k_frm_apply(FrmScan a)
+{
+    __shared__ u64 wv[NW];
+    __shared__ u32 wf[NW];
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, u = blockIdx.x;
+    const u64 beg = (u64)u * a.L, end = beg + a.L < a.n ? beg + a.L : a.n;
+    u64 rem_t = BLK ? frm_rem0<BACK>(a, beg + wave * (64 * TPT) + lane) : 1;     // of this thread's first index of the tile
+    u64 cv = a.carry[u];
+    for (u64 tb = beg; tb < end; tb += TILE) {
+        const u32 tn = end - tb < (u64)TILE ? (u32)(end - tb) : (u32)TILE;
+        u64 v[TPT];
+        u32 hd = 0;                                                      // one bit per round: a head at or before this index, in its wave's part
+        u64 rem = rem_t;
+        const u64 pb = frm_pos<BACK>(a, tb + wave * (64 * TPT) + lane);     // the position of this thread's first index of the tile; round r is r * 64 further on
+#pragma unroll
+        for (int r = 0; r < TPT; r++) {
+            const u32 li = wave * (64 * TPT) + r * 64 + lane;
+            v[r] = ident<OP>();
+            if (li < tn) {
+                const u64 p = BACK ? pb - (u64)(r * 64) : pb + (u64)(r * 64);
+                const u32 ph = frm_head<BACK>(a, tb + li, p);
+                hd |= (ph | (BLK && rem == 0 ? 1u : 0u)) << r;
+                v[r] = frm_value<OP, VS, BACK>(a, p, ph);
+            }
+            if (BLK) rem = frm_step<BACK>(rem, a.s64, a.w);
+        }
+        if (BLK) rem_t = frm_step<BACK>(rem_t, a.stile, a.w);
+        u32 rf = 0;
+        u64 rv = ident<OP>();
+#pragma unroll
+        for (int r = 0; r < TPT; r++) {
+            u32 f = (hd >> r) & 1;
+            u64 x = v[r];
+            wave_seg_scan<OP>(f, x, lane);
+            x = f ? x : comb<OP>(rv, x);
+            f |= rf;
+            v[r] = x;
+            hd = (hd & ~(1u << r)) | (f << r);
+            rv = __shfl(x, 63, 64);
+            rf = __shfl(f, 63, 64);
+        }
+        if (lane == 0) { wv[wave] = rv; wf[wave] = rf; }
+        __syncthreads();
+        u64 pre = cv, tot = cv;
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            tot = wf[w] ? wv[w] : comb<OP>(tot, wv[w]);
+            if ((u32)w < wave) pre = tot;
+        }
+#pragma unroll
+        for (int r = 0; r < TPT; r++) {
+            const u32 li = wave * (64 * TPT) + r * 64 + lane;
+            if (li >= tn) continue;                                      // (tb + li < end <= n: the store below is inside out[0 .. n))
+            a.out[BACK ? pb - (u64)(r * 64) : pb + (u64)(r * 64)] = ((hd >> r) & 1) ? v[r] : comb<OP>(pre, v[r]);
+        }
+        cv = tot;
+        __syncthreads();
+    }
+}
+
+// ---- k_frm_emit: every op's answer from the by-position arrays, and out[perm[p]] ------------------------------------------------------
+// pstart[p] / pend[p]: the first / last sorted position of p's partition (null: not needed by any op of the call -- every preceding /
+// following is 0 --, and p stands in).  lo = max(pstart, p - preceding), hi = min(pend, p + following), without wrap-around.
+//   COUNT hi - lo + 1;  FIRST_ROW perm[lo];  LAST_ROW perm[hi];  SUM S[hi] - (lo > pstart ? S[lo - 1] : 0)
+//   MIN / MAX  M_FWD: F[hi] (lo is the partition's start);  M_BACK: B[lo] (hi is its end);  M_BOTH: with bs the start of hi's block
+//              (0 without blocks) -- lo == max(bs, pstart): F[hi]; else lo >= bs: B[lo] (hi is the partition's end); else the two
+//              blocks are neighbours and the answer is op(B[lo], F[hi])  
+// One sweep of the positions per op (the bounds and the permutation are read again: 8 .. 24 coalesced bytes per row and op).
+enum { M_FWD = 0, M_BACK = 1, M_BOTH = 2 };
+struct FrmEmit {
+    u32 nops;
+    u32 op[RHJ_FRAME_MAX_OPS], mode[RHJ_FRAME_MAX_OPS];
+    u64 prec[RHJ_FRAME_MAX_OPS], fol[RHJ_FRAME_MAX_OPS];
+    u64 w[RHJ_FRAME_MAX_OPS], sgrid[RHJ_FRAME_MAX_OPS];               // M_BOTH with blocks: the block length and (grid stride) % w; w == 0: one block
+    u64 bias[RHJ_FRAME_MAX_OPS];
+    const u64 *F[RHJ_FRAME_MAX_OPS];                                  // SUM: S
+    const u64 *B[RHJ_FRAME_MAX_OPS];
+    u64 *out[RHJ_FRAME_MAX_OPS];
+};
+
+// one op over every position: its parameters stay uniform words for the length of its sweep, and the block offset p % w is ONE 64-bit
+// remainder per thread, stepped by (grid stride) % w
+__device__ __forceinline__ void frm_emit_op(const u64 *__restrict__ pstart, const u64 *__restrict__ pend, const u64 *__restrict__ perm, u64 n,
+                                            u32 op, u32 mode, u64 prec, u64 fol, u64 w, u64 sgrid, u64 bias, const u64 *__restrict__ F,
+                                            const u64 *__restrict__ B, u64 *__restrict__ out)
+{
+    const u64 p0 = (u64)blockIdx.x * FLAT_THREADS + threadIdx.x;
+    const bool mn = op == RHJ_FRAME_MIN_U64 || op == RHJ_FRAME_MIN_I64;
+    u64 rem = w != 0 ? p0 % w : 0;
+    for (u64 p = p0; p < n; p += (u64)gridDim.x * FLAT_THREADS) {
+        const u64 row = perm ? perm[p] : p;
+        u64 ps = pstart ? pstart[p] : p, pe = pend ? pend[p] : p;
+        if (ps > p) ps = p;                                              // (never: pstart <= p <= pend < n; the guards keep every index below inside [0, n))
+        if (pe < p || pe >= n) pe = p;
+        const u64 lo = prec >= p - ps ? ps : p - prec;
+        const u64 hi = fol >= pe - p ? pe : p + fol;
+        u64 val;
+        if (op == RHJ_FRAME_COUNT) {
+            val = hi - lo + 1;
+        } else if (op == RHJ_FRAME_FIRST_ROW) {
+            val = perm ? perm[lo] : lo;
+        } else if (op == RHJ_FRAME_LAST_ROW) {
+            val = perm ? perm[hi] : hi;
+        } else if (op == RHJ_FRAME_SUM) {
+            val = F[hi] - (lo > ps ? F[lo - 1] : 0);
+        } else {
+            if (mode == M_FWD) {
+                val = F[hi];
+            } else if (mode == M_BACK) {
+                val = B[lo];
+            } else {
+                u64 bs = 0;                                              // the start of hi's block: p's own, or the next one
+                if (w != 0) bs = hi - p < w - rem ? p - rem : p - rem + w;
+                if (lo == (bs > ps ? bs : ps)) {
+                    val = F[hi];
+                } else if (lo >= bs) {
+                    val = B[lo];
+                } else {
+                    const u64 x = B[lo], y = F[hi];
+                    val = mn ? (y < x ? y : x) : (y > x ? y : x);
+                }
+            }
+            val ^= bias;
+        }
+        if (row < n) out[row] = val;                                     // (row < n always: perm is a permutation)
+        if (w != 0) {
+            rem += sgrid;
+            if (rem >= w) rem -= w;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(FLAT_THREADS)
+k_frm_emit(const u64 *__restrict__ pstart, const u64 *__restrict__ pend, const u64 *__restrict__ perm, u64 n, FrmEmit e)
+{
+#pragma unroll
+    for (u32 j = 0; j < RHJ_FRAME_MAX_OPS; j++) {
+        if (j >= e.nops) break;
+        frm_emit_op(pstart, pend, perm, n, e.op[j], e.mode[j], e.prec[j], e.fol[j], e.w[j], e.sgrid[j], e.bias[j], e.F[j], e.B[j], e.out[j]);
+    }
+}
+
+int hip_fail(rhj_ctx *ctx, const char *what, hipError_t e)
+{
+    (void)hipGetLastError();
+    return rhj_internal_fail(ctx, e == hipErrorOutOfMemory ? RHJ_E_NOMEM : RHJ_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
+}
+
+int check(rhj_ctx *ctx, const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? RHJ_OK : hip_fail(ctx, what, e);
+}
+
+struct Span {
+    void *s;
+    Span(rhj_ctx *ctx, int kind) : s(rhj_internal_span_open(ctx, kind)) {}
+    ~Span() { rhj_internal_span_close(s); }
+};
+
+unsigned flat_grid(u64 n)
+{
+    u64 g = (n + FLAT_THREADS - 1) / FLAT_THREADS;
+    if (g > FLAT_MAX_GRID) g = FLAT_MAX_GRID;
+    return (unsigned)(g ? g : 1);
+}
+
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// one scan: reduce, carry, apply, ordered by the stream
+template <int OP, int VS, bool BACK, bool BLK>
+int scan_t(rhj_ctx *ctx, hipStream_t st, const FrmScan &a)
+{
+    int rc;
+    {
+        Span s(ctx, RHJ_K_HIST);
+        hipLaunchKernelGGL((k_frm_reduce<OP, VS, BACK, BLK>), dim3(a.U), dim3(ST), 0, st, a);
+    }
+    if ((rc = check(ctx, "k_frm_reduce")) != RHJ_OK) return rc;
+    {
+        Span s(ctx, RHJ_K_SCAN);
+        hipLaunchKernelGGL(k_frm_carry<OP>, dim3(1), dim3(ST), 0, st, (const u64 *)a.usum_v, (const u32 *)a.usum_f, a.U, a.carry);
+    }
+    if ((rc = check(ctx, "k_frm_carry")) != RHJ_OK) return rc;
+    {
+        Span s(ctx, RHJ_K_SCATTER);
+        hipLaunchKernelGGL((k_frm_apply<OP, VS, BACK, BLK>), dim3(a.U), dim3(ST), 0, st, a);
+    }
+    return check(ctx, "k_frm_apply");
+}
+
+template <int OP>
+int scan_col(rhj_ctx *ctx, hipStream_t st, const FrmScan &a, bool back, bool blk)
+{
+    if (back) return blk ? scan_t<OP, VS_COL, true, true>(ctx, st, a) : scan_t<OP, VS_COL, true, false>(ctx, st, a);
+    return blk ? scan_t<OP, VS_COL, false, true>(ctx, st, a) : scan_t<OP, VS_COL, false, false>(ctx, st, a);
+}
+
+bool is_col_op(u32 op) { return op >= RHJ_FRAME_SUM && op <= RHJ_FRAME_MAX_I64; }
+bool is_minmax(u32 op) { return op >= RHJ_FRAME_MIN_U64 && op <= RHJ_FRAME_MAX_I64; }
+
+int frame_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 flags, const u32 *ops, const u64 *preceding,
+              const u64 *following, const u64 *const *d_cols, u32 nops, u64 *const *d_outs, u64 *out_partitions)
+{
+    const std::string me("rhj_frame_cols_dev");
+    if (flags & ~(RHJ_SORT_I64 | RHJ_SORT_DESC)) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": unknown flags").c_str());
+    if (flags && !d_order) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": flags without d_order: they say how the order column is read").c_str());
+    if (nops == 0 || nops > RHJ_FRAME_MAX_OPS) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": nops must be 1 .. RHJ_FRAME_MAX_OPS").c_str());
+    if (!ops) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops is null").c_str());
+    if (!d_outs) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_outs is null").c_str());
+    for (u32 j = 0; j < nops; j++) {
+        const std::string at = "[" + std::to_string(j) + "]";
+        if (ops[j] > RHJ_FRAME_LAST_ROW) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops" + at + " is not an RHJ_FRAME_* op").c_str());
+        if (!d_outs[j]) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_outs" + at + " is null").c_str());
+        if (is_col_op(ops[j]) && n > 0 && (!d_cols || !d_cols[j]))
+            return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_cols" + at + " is null for a column op with a non-zero row count").c_str());
+    }
+    if (out_partitions) *out_partitions = 0;
+    if (n == 0) return RHJ_OK;
+
+    hipStream_t st = rhj_internal_stream(ctx);
+    hipError_t e;
+    int rc;
+    u64 L;
+    u32 U;
+    rhj_internal_sort_units(ctx, n, &L, &U);
+    if (U == 0 || U > FRM_MAX_UNITS) return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
+
+    // 1. the plan of every op: its frame, and for MIN / MAX which scans it needs.  A side that reaches n - 1 positions reaches every
+    //    partition's edge from every row: it is unbounded.  With preceding unbounded lo is the partition's start and F alone answers;
+    //    else with following unbounded hi is its end and B alone does; else w = preceding + following + 1 <= 2n - 3 does not wrap,
+    //    and blocks of w positions apply when w < n (with w >= n the one block needs no heads of its own)
+    FrmEmit em = {};
+    em.nops = nops;
+    bool need_ps = false, need_pe = false;
+    int scans = 0, arrays = 0;
+    const unsigned eg = flat_grid(n);
+    for (u32 j = 0; j < nops; j++) {
+        const u64 pr = preceding ? preceding[j] : RHJ_FRAME_UNBOUNDED, fo = following ? following[j] : 0;
+        em.op[j] = ops[j];
+        em.prec[j] = pr;
+        em.fol[j] = fo;
+        em.out[j] = d_outs[j];
+        need_pe |= fo != 0;
+        need_ps |= pr != 0 || ops[j] == RHJ_FRAME_SUM;
+        if (ops[j] == RHJ_FRAME_SUM) { scans += 1; arrays += 1; }
+        if (!is_minmax(ops[j])) continue;
+        em.bias[j] = (ops[j] == RHJ_FRAME_MIN_I64 || ops[j] == RHJ_FRAME_MAX_I64) ? BIAS : 0;
+        if (pr >= n - 1) {
+            em.mode[j] = M_FWD;
+        } else if (fo >= n - 1) {
+            em.mode[j] = M_BACK;
+        } else {
+            em.mode[j] = M_BOTH;
+            const u64 w = pr + fo + 1;
+            if (w < n) { em.w[j] = w; em.sgrid[j] = ((u64)eg * FLAT_THREADS) % w; }
+            need_ps = true;
+        }
+        scans += em.mode[j] == M_BOTH ? 2 : 1;
+        arrays += em.mode[j] == M_BOTH ? 2 : 1;
+    }
+
+    // 2. the workspace: the sorted words and the permutation, two arrays for the first of two sorts (then the two bounds), one array
+    //    per value scan, the flag bytes, the unit tables
+    const int sorts = (d_part ? 1 : 0) + (d_order ? 1 : 0);
+    const size_t nb = up256((size_t)n * 8), ub = up256((size_t)U * 8);
+    const bool need_ab = sorts == 2 || need_ps || need_pe;
+    const size_t bytes = (need_ab ? 2 * nb : 0) + (sorts ? 2 * nb : 0) + (size_t)arrays * nb + up256((size_t)n) + 4 * ub;
+    void *ws = nullptr;
+    if ((rc = rhj_internal_frame_workspace(ctx, bytes, &ws)) != RHJ_OK) return rc;
+    unsigned char *p = (unsigned char *)ws;
+    u64 *bufA = nullptr, *bufB = nullptr, *skey = nullptr, *perm = nullptr;
+    if (need_ab) { bufA = (u64 *)p; p += nb; bufB = (u64 *)p; p += nb; }
+    if (sorts) { skey = (u64 *)p; p += nb; perm = (u64 *)p; p += nb; }
+    u64 *d_arr = (u64 *)p; p += (size_t)arrays * nb;
+    unsigned char *d_flags = p; p += up256((size_t)n);
+    u64 *d_usum_v = (u64 *)p; p += ub;
+    u32 *d_usum_f = (u32 *)p; p += ub;
+    u64 *d_carry = (u64 *)p; p += ub;
+    u64 *d_ucnt = (u64 *)p; p += ub;
+
+    // 3. the order (partition, order key, input position), exactly as the window entry's
+    const u64 *sp = nullptr;
+    if (sorts == 2) {
+        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, nullptr, bufA)) != RHJ_OK) return rc;
+        {
+            Span s(ctx, RHJ_K_AUX);
+            hipLaunchKernelGGL(k_frm_gather, dim3(flat_grid(n)), dim3(FLAT_THREADS), 0, st, d_part, (const u64 *)bufA, n, bufB);
+        }
+        if ((rc = check(ctx, "k_frm_gather")) != RHJ_OK) return rc;
+        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), bufB, bufA, n, 0, skey, perm)) != RHJ_OK) return rc;
+        sp = skey;
+    } else if (d_part) {
+        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_part, nullptr, n, 0, skey, perm)) != RHJ_OK) return rc;
+        sp = skey;
+    } else if (d_order) {
+        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, skey, perm)) != RHJ_OK) return rc;
+    }
+    rhj_internal_sort_report(ctx, 0, 0, 0);                              // "last.sort_*" speak of the sort entries only
+
+    // 4. heads
+    {
+        Span s(ctx, RHJ_K_AUX);
+        hipLaunchKernelGGL(k_frm_heads, dim3(U), dim3(ST), 0, st, sp, n, L, d_flags, d_ucnt);
+    }
+    if ((rc = check(ctx, "k_frm_heads")) != RHJ_OK) return rc;
+
+    FrmScan a = {};
+    a.flags = d_flags; a.perm = perm; a.n = n; a.L = L; a.U = U; a.usum_v = d_usum_v; a.usum_f = d_usum_f; a.carry = d_carry;
+
+    // 5. the bounds: pstart the forward maximum scan of (head ? p : 0), pend the backward minimum scan of (tail ? p : all ones)
+    if (need_ps) {
+        FrmScan b = a;
+        b.out = bufA;
+        if ((rc = scan_t<OP_MAX, VS_POS, false, false>(ctx, st, b)) != RHJ_OK) return rc;
+    }
+    if (need_pe) {
+        FrmScan b = a;
+        b.out = bufB;
+        if ((rc = scan_t<OP_MIN, VS_POS, true, false>(ctx, st, b)) != RHJ_OK) return rc;
+    }
+
+    // 6. the value scans, by position
+    u64 *next = d_arr;
+    for (u32 j = 0; j < nops; j++) {
+        if (!is_col_op(ops[j])) continue;
+        FrmScan b = a;
+        b.col = d_cols[j];
+        b.bias = em.bias[j];
+        if (ops[j] == RHJ_FRAME_SUM) {
+            b.out = next; next += nb / 8;
+            em.F[j] = b.out;
+            if ((rc = scan_t<OP_SUM, VS_COL, false, false>(ctx, st, b)) != RHJ_OK) return rc;
+            continue;
+        }
+        const bool mn = ops[j] == RHJ_FRAME_MIN_U64 || ops[j] == RHJ_FRAME_MIN_I64, blk = em.w[j] != 0;
+        if (blk) { b.w = em.w[j]; b.s64 = 64 % b.w; b.stile = (u64)TILE % b.w; }
+        if (em.mode[j] != M_BACK) {
+            b.out = next; next += nb / 8;
+            em.F[j] = b.out;
+            if ((rc = mn ? scan_col<OP_MIN>(ctx, st, b, false, blk) : scan_col<OP_MAX>(ctx, st, b, false, blk)) != RHJ_OK) return rc;
+        }
+        if (em.mode[j] != M_FWD) {
+            b.out = next; next += nb / 8;
+            em.B[j] = b.out;
+            if ((rc = mn ? scan_col<OP_MIN>(ctx, st, b, true, blk) : scan_col<OP_MAX>(ctx, st, b, true, blk)) != RHJ_OK) return rc;
+        }
+    }
+
+    // 7. every op's answer, by row
+    {
+        Span s(ctx, RHJ_K_AUX);
+        hipLaunchKernelGGL(k_frm_emit, dim3(eg), dim3(FLAT_THREADS), 0, st, (const u64 *)(need_ps ? bufA : nullptr),
+                           (const u64 *)(need_pe ? bufB : nullptr), (const u64 *)perm, n, em);
+    }
+    if ((rc = check(ctx, "k_frm_emit")) != RHJ_OK) return rc;
+
+    // 8. the partitions: the heads' per-unit counts, summed on the host
+    std::vector<u64> cnt(U);
+    e = hipMemcpyAsync(cnt.data(), d_ucnt, (size_t)U * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(ctx, "rhj_frame_cols_dev", e);
+    u64 parts = 0;
+    for (u32 u = 0; u < U; u++) parts += cnt[u];
+    if (out_partitions) *out_partitions = parts;
+    rhj_internal_frame_report(ctx, (int)U, sorts, scans, parts);
+    return RHJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rhj_frame_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_order, uint64_t n, uint32_t flags,
+                       const uint32_t *ops, const uint64_t *preceding, const uint64_t *following,
+                       const uint64_t *const *d_cols, uint32_t nops, uint64_t *const *d_outs, uint64_t *out_partitions)
+{
+    const int rc = rhj_internal_use_device(ctx);
+    if (rc != RHJ_OK) return rc;
+    rhj_internal_sort_begin(ctx);
+    return frame_run(ctx, (const u64 *)d_part, (const u64 *)d_order, n, flags, ops, (const u64 *)preceding, (const u64 *)following,
+                     (const u64 *const *)d_cols, nops, (u64 *const *)d_outs, (u64 *)out_partitions);
+}
+
+}  // extern "C"

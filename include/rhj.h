@@ -757,6 +757,58 @@ int rhj_frame_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_o
                        const uint32_t *ops, const uint64_t *preceding, const uint64_t *following,
                        const uint64_t *const *d_cols, uint32_t nops, uint64_t *const *d_outs, uint64_t *out_partitions);
 
+/* ---- RANGE frames: the same aggregates over a VALUE distance on the order key (SUM / COUNT / MIN / MAX / FIRST_VALUE / LAST_VALUE
+ * OVER [PARTITION BY k ORDER BY t RANGE BETWEEN a PRECEDING AND b FOLLOWING]; "the same symbol's rows of the last 5 seconds"; pandas
+ * groupby.rolling("5s")).  The argument list, the RHJ_FRAME_* ops and RHJ_FRAME_UNBOUNDED are rhj_frame_cols_dev's.
+ * Partitions, the order inside them, ties and output alignment are the frame entry's, word for word: a PARTITION is the set of rows
+ * with a bit-equal d_part word (d_part == NULL: one partition); the rows are ordered by their d_order word under RHJ_SORT_I64 /
+ * RHJ_SORT_DESC; ties keep their input order in both directions; the outputs are aligned with the input rows; every result is
+ * bit-identical from run to run.  d_order == NULL is RHJ_E_INVALID: a value distance needs a value.
+ * The frame: let t be the row's order word in the chosen view (unsigned, or two's-complement int64).  Ascending, the frame of op j is
+ * every row of the partition whose order value lies in [t - preceding[j], t + following[j]]; under RHJ_SORT_DESC the interval is
+ * [t - following[j], t + preceding[j]] -- PRECEDING still means "earlier in the order".  Distances are exact integers; both ends
+ * saturate at the view's minimum and maximum, nothing wraps: a distance of 2^64 - 2 between INT64_MIN and INT64_MAX is honoured.
+ * RHJ_FRAME_UNBOUNDED (all ones) on a side is the partition's edge, which is also what a distance of 2^64 - 1 means.  preceding ==
+ * NULL: unbounded for every op; following == NULL: 0 for every op -- together SQL's default frame, RANGE UNBOUNDED PRECEDING to
+ * CURRENT ROW, under which peers share a value.  The frame is a contiguous run of sorted positions and always contains the current
+ * row and all its peers, also at distance 0: this is the difference from ROWS.  pandas' time-based rolling stops at the current row
+ * among peers, so the results agree with pandas exactly when the order keys are distinct within a partition.  Frames that exclude the
+ * current row are not part of this entry, nor are empty frames: there is never RHJ_NO_ROW.  Each op has its own frame.
+ * Ops: RHJ_FRAME_COUNT, RHJ_FRAME_SUM (the sum mod 2^64), RHJ_FRAME_MIN_U64 / RHJ_FRAME_MAX_U64 / RHJ_FRAME_MIN_I64 /
+ * RHJ_FRAME_MAX_I64 (bit for bit a column word), RHJ_FRAME_FIRST_ROW / RHJ_FRAME_LAST_ROW (the row at the frame's first / last
+ * sorted position, which the tie rule defines).  d_cols[j] is ignored for the ops without a column; the same column may be given
+ * several times; two equal output pointers are undefined.
+ * *out_partitions receives the number of partitions; it may be NULL.  n == 0: RHJ_OK, no launch, 0 partitions.  RHJ_E_INVALID,
+ * before any launch, with a message naming the argument: unknown flag bits; d_order == NULL with n > 0 or with flags; nops 0 or above
+ * RHJ_FRAME_MAX_OPS; NULL ops, d_outs or d_outs[j]; an op above RHJ_FRAME_LAST_ROW; a NULL d_cols[j] for a column op with n > 0.
+ * Inputs are neither modified nor retained; outputs must not overlap inputs.  The call synchronises; it honours rhj_set_stream and
+ * rhj_set_profiling (the inner sorts' spans; RHJ_K_AUX: heads, gathers; per scan RHJ_K_HIST, RHJ_K_SCAN, RHJ_K_SCATTER; RHJ_K_TASKS:
+ * the table levels; RHJ_K_JOIN: the searches and the answers, one launch).
+ * How: the order, the heads and every position's partition start and end as the frame entry's -- 1 or 2 inner sorts.  The order
+ * words by sorted position (the sorted keys after one sort, one gather through the permutation after two) are read as v = word ^
+ * (I64 ? 1 << 63 : 0), complemented under DESC: v is non-decreasing along a partition in all four views, and in both directions the
+ * frame is max(0, v - preceding) <= v_r <= min(2^64 - 1, v + following).  Per row and distinct frame two searches: lo gallops from
+ * the row's position towards the partition's start in doubling steps and bisects the bracket, hi the mirror -- about 2 log2(frame
+ * rows) dependent 8-byte loads each; an unbounded side needs none.  Every column is gathered once BY SORTED POSITION (V).  SUM: S[hi]
+ * - (lo above the start ? S[lo - 1] : 0).  MIN / MAX with an unbounded side: one scan, F[hi] or B[lo].  Otherwise the frame entry's
+ * block-restarting scans at the FIXED block length 64 and a sparse table over the summaries of the n / 64 whole blocks, T_0[k] = F[64 k
+ * + 63], T_l[k] = op(T_(l-1)[k], T_(l-1)[k + 2^(l-1)]), one small launch per level.  With bl = lo / 64 and bh = hi / 64: the same block
+ * -- F[hi] when lo is the block's or the partition's start, B[lo] when hi is the block's or the partition's end, else a walk over
+ * V[lo .. hi], at most 62 words --; different blocks -- op(B[lo], F[hi]), and with bh - bl >= 2 also op(T_l[bl + 1], T_l[bh - 2^l]), l =
+ * floor(log2(bh - bl - 1)).  Interior blocks lie wholly inside the frame, therefore inside one partition: table words that span a
+ * partition boundary are never read.  No workgroup waits on another inside a kernel, and no position, value or count comes from an
+ * atomic.
+ * rhj_get_info: "last.frame_range_units", "last.frame_range_sorts" (1 or 2), "last.frame_range_partitions", "last.frame_range_scans"
+ * the value scans: 1 per SUM, 1 or 2 per MIN / MAX; "last.frame_range_levels" the sparse-table levels built, 0 when no op needed
+ * them.  All five are 0 after every other call.  After this call "last.join_kernel" is -1 and every other entry's "last.*" (the
+ * frame entry's included) is 0.  "sort.max_units" caps the units here too; the result never depends on it.
+ * Memory: the frame entry's workspace buffer, kept until rhj_release_workspace: 4 x 8 + 1 bytes per row, 8 more after two sorts, 8
+ * per distinct column and per value scan, and 8 x (n / 64) per table level.
+ * There is no 16-byte tuple form. */
+int rhj_frame_range_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_order, uint64_t n, uint32_t flags,
+                             const uint32_t *ops, const uint64_t *preceding, const uint64_t *following,
+                             const uint64_t *const *d_cols, uint32_t nops, uint64_t *const *d_outs, uint64_t *out_partitions);
+
 /* ---- composite keys: up to four key columns per relation packed into ONE 64-bit key column (JOIN .. ON r.a = s.a AND r.b = s.b; GROUP
  * BY a, b; torch.unique(dim=0); merge(on=[..])).  Every operator above compares 64-bit values by bit pattern, so what it needs is an
  * EXACT surrogate: a 64-bit word per row such that two rows of R u S get the same word if and only if all their key columns agree.

@@ -47,6 +47,8 @@ Framed window aggregates: ``moving, size = Engine(0).frame_columns(k, t, [x, Non
 MAX(x) over the last ten rows of each partition and the partition's size, aligned with the rows -- sliding ROWS frames for count, sum,
 min / max and the frame's first / last row, a sliding min / max at the same cost for every width (``rhj_frame_cols_dev``);
 ``Engine(0).ntile_columns(k, t, 4)`` is NTILE(4).
+RANGE frames: ``Engine(0).frame_range_columns(sym, t, [x, None], ["sum", "count"], 5_000_000_000)`` is the sum and the count of the same
+symbol's rows of the last 5 seconds -- the frame a value distance on the order key, peers always inside (``rhj_frame_range_cols_dev``).
 """
 from .binding import (  # noqa: F401
     AGG_MAX_I64,

@@ -145,6 +145,7 @@ SYMBOLS = {
     "rhj_topk_dev": (C.c_int, [_vp, _vp, _u64, _u64, C.c_uint32, _vp, _P(_u64)]),
     "rhj_window_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
     "rhj_frame_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
+    "rhj_frame_range_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -610,7 +611,8 @@ class Engine:
         """what the last join did ("last.narrow", "last.countfree_R" / "_S", "last.cols_R" / "_S", "last.join_kernel", "last.semi_tables", "last.outer_sweeps", "last.group_rounds",
         "last.sort_bits", "last.sort_passes", "last.sort_units", "last.topk_bits", "last.topk_passes", "last.topk_candidates",
         "last.topk_sorted_rows", "last.window_units", "last.window_sorts", "last.window_partitions", "last.asof_units", "last.asof_sorts",
-        "last.asof_matched", "last.frame_units", "last.frame_sorts", "last.frame_scans", "last.frame_partitions"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows",
+        "last.asof_matched", "last.frame_units", "last.frame_sorts", "last.frame_scans", "last.frame_partitions", "last.frame_range_units", "last.frame_range_sorts",
+        "last.frame_range_scans", "last.frame_range_levels", "last.frame_range_partitions"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows",
         "asof.tile_rows")"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
@@ -1717,6 +1719,61 @@ class Engine:
             outs = [torch.empty(n, dtype=torch.int64, device=dev) for _ in opw]
             if n:
                 self.frame_cols_dev(part, order, n, flags, opw, pre, fol, cols, outs)
+        return outs
+
+    def frame_range_cols_dev(self, d_part, d_order, n, flags=0, ops=(), preceding=None, following=None, d_cols=None, d_outs=()):
+        """rhj_frame_range_cols_dev: frame_cols_dev with a RANGE frame -- per row a value over the rows of its partition whose d_order
+        value lies in [t - preceding[j], t + following[j]] around its own value t (under SORT_DESC [t - following[j], t +
+        preceding[j]]), saturating at the view's ends; the current row's peers are always inside.  d_order is needed.  preceding /
+        following: one distance per op, FRAME_UNBOUNDED: to the partition's edge; preceding None: unbounded for every op, following
+        None: 0 for every op -- SQL's default frame.  Everything else as frame_cols_dev.  Returns the number of partitions."""
+        k = len(ops) if ops is not None else 0
+        opw = (C.c_uint32 * max(k, 1))(*[int(o) for o in ops]) if ops is not None else None
+        pre = (_u64 * max(k, 1))(*[int(a) for a in preceding]) if preceding is not None else None
+        fol = (_u64 * max(k, 1))(*[int(a) for a in following]) if following is not None else None
+        cols = (_vp * max(k, 1))(*[_addr(c) for c in d_cols]) if d_cols is not None else None
+        outs = (_vp * max(k, 1))(*[_addr(o) for o in d_outs]) if d_outs is not None else None
+        parts = _u64()
+        self._chk(self.lib.rhj_frame_range_cols_dev(self.ctx, _addr(d_part), _addr(d_order), n, flags, opw, pre, fol, cols, k, outs, C.byref(parts)))
+        return parts.value
+
+    def frame_range_columns(self, part, order, cols, ops, preceding=None, following=0, descending=False, unsigned=False):
+        """[out_0, out_1, ..]: window aggregates over RANGE frames -- one int64 tensor per op, ALIGNED WITH THE ROWS.  As frame_columns,
+        but the frame is a VALUE distance on `order`, which is needed: for a row with order value t the frame of op j is every row of
+        its partition whose order value lies in [t - preceding[j], t + following[j]] (descending=True: [t - following[j], t +
+        preceding[j]]; preceding still means earlier in the order) -- RANGE BETWEEN preceding PRECEDING AND following FOLLOWING.  The
+        values are compared as int64 (unsigned=True: as uint64), distances are exact and saturate at the type's ends.  preceding /
+        following: an int >= 0, None (unbounded: to the partition's edge), or a list with one of those per op.  The defaults are SQL's
+        default frame, RANGE UNBOUNDED PRECEDING to CURRENT ROW: the running aggregate in which peers share a value.  The frame always
+        holds the current row and ALL its peers, also at distance 0; pandas' time-based rolling stops at the current row among peers,
+        so groupby.rolling("5s").sum() is preceding=4_999_999_999 (closed="both": 5_000_000_000) exactly when the order keys are
+        distinct within a partition.  part: a tensor, None (one partition), or a list of 1 to KEYS_MAX_COLS tensors, packed first.
+        ops and cols as frame_columns; the cost of "min" / "max" depends on the frame here.  An unknown op, too many ops, a length
+        mismatch, a negative, bool or float bound, a non-bool flag, order None or a list: ValueError before any device use.  One
+        rhj_frame_range_cols_dev call.  Streams and completion as join_columns."""
+        import torch
+        if order is None or isinstance(order, (list, tuple)):
+            raise ValueError("order: one tensor is needed -- a value distance needs a value")
+        opw, cols, pre, fol = _frame_args(order, cols, ops, preceding, following, descending, unsigned)
+        if isinstance(part, (list, tuple)):
+            packed, _, plan = self.pack_keys(part, keep_dictionaries=False)
+            plan.close()
+            part = packed
+        named = [("order", order), ("part", part)] + [(f"cols[{j}]", v) for j, v in enumerate(cols)]
+        named = [(name, t) for name, t in named if t is not None]
+        ints = tuple(t for t in (torch.int64, getattr(torch, "uint64", None)) if t is not None)
+        for name, t in named:
+            if not isinstance(t, torch.Tensor) or t.dtype not in ints or t.dim() != 1:
+                raise ValueError(f"{name}: a 1-D torch tensor of 64-bit integers is needed")
+            if t.numel() != order.numel():
+                raise ValueError(f"{name}: {t.numel()} elements, order has {order.numel()}")
+        tensors = [t for _, t in named]
+        flags = (0 if unsigned else SORT_I64) | (SORT_DESC if descending else 0)
+        with self._on_torch_stream(tensors[0], tensors[0], tuple(tensors[1:])) as dev:
+            n = order.numel()
+            outs = [torch.empty(n, dtype=torch.int64, device=dev) for _ in opw]
+            if n:
+                self.frame_range_cols_dev(part, order, n, flags, opw, pre, fol, cols, outs)
         return outs
 
     def ntile_columns(self, part, order, buckets, descending=False, unsigned=False):

@@ -285,6 +285,8 @@ struct rhj_ctx {
     u64 last_asof_matched = 0;         // "last.asof_matched": the rows of R that found a partner
     int last_frame_units = 0, last_frame_sorts = 0, last_frame_scans = 0;   // "last.frame_units" / "last.frame_sorts" / "last.frame_scans": the units the last frame call's scans were cut into, its inner sorts, its value scans (0: another call)
     u64 last_frame_parts = 0;          // "last.frame_partitions": the partitions it found
+    int last_frange_units = 0, last_frange_sorts = 0, last_frange_scans = 0, last_frange_levels = 0;   // "last.frame_range_units" / "_sorts" / "_scans" / "_levels": the same of the last RANGE frame call, and the sparse-table levels it built (0: another call)
+    u64 last_frange_parts = 0;         // "last.frame_range_partitions": the partitions it found
     DevBuf frame_ws;                   // the frame entry's permutation, sorted words, flags, bounds, by-position scans and unit tables (rhj_frame.hip): not sort_ws, which the inner sorts regrow
     DevBuf asof_ws;                    // the as-of entry's concatenation, permutation, flags and unit tables (rhj_asof.hip): not sort_ws, which the inner sorts regrow
     DevBuf window_ws;                  // the window entry's permutation, sorted words, flags, starts and unit tables (rhj_window.hip): not sort_ws, which the inner sorts regrow
@@ -530,6 +532,8 @@ void prof_reset(rhj_ctx *ctx)
     ctx->last_asof_matched = 0;
     ctx->last_frame_units = ctx->last_frame_sorts = ctx->last_frame_scans = 0;   // "last.frame_*": ... and the frame entry these
     ctx->last_frame_parts = 0;
+    ctx->last_frange_units = ctx->last_frange_sorts = ctx->last_frange_scans = ctx->last_frange_levels = 0;   // "last.frame_range_*": ... and the RANGE frame entry these
+    ctx->last_frange_parts = 0;
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -2173,6 +2177,14 @@ void rhj_internal_frame_report(rhj_ctx *ctx, int units, int sorts, int scans, u6
     ctx->last_frame_scans = scans;
     ctx->last_frame_parts = partitions;
 }
+void rhj_internal_frame_range_report(rhj_ctx *ctx, int units, int sorts, int scans, int levels, u64 partitions)
+{
+    ctx->last_frange_units = units;
+    ctx->last_frange_sorts = sorts;
+    ctx->last_frange_scans = scans;
+    ctx->last_frange_levels = levels;
+    ctx->last_frange_parts = partitions;
+}
 int rhj_internal_frame_workspace(rhj_ctx *ctx, size_t bytes, void **out)
 {
     RHJCHK(ensure(ctx, ctx->frame_ws, bytes));
@@ -2389,6 +2401,11 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.frame_sorts") { *value = ctx->last_frame_sorts; return RHJ_OK; }
     if (n == "last.frame_scans") { *value = ctx->last_frame_scans; return RHJ_OK; }
     if (n == "last.frame_partitions") { *value = (int64_t)ctx->last_frame_parts; return RHJ_OK; }
+    if (n == "last.frame_range_units") { *value = ctx->last_frange_units; return RHJ_OK; }
+    if (n == "last.frame_range_sorts") { *value = ctx->last_frange_sorts; return RHJ_OK; }
+    if (n == "last.frame_range_scans") { *value = ctx->last_frange_scans; return RHJ_OK; }
+    if (n == "last.frame_range_levels") { *value = ctx->last_frange_levels; return RHJ_OK; }
+    if (n == "last.frame_range_partitions") { *value = (int64_t)ctx->last_frange_parts; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }

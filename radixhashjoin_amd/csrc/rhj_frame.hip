@@ -7,6 +7,8 @@
 // ends and stores out[perm[p]].  Per scan three launches ordered on the context's stream: a reduce per unit, a one-workgroup carry
 // over the unit summaries, an apply per unit.  No workgroup ever waits on another, and no position, value or count comes from an
 // atomic.
+// The RANGE entry (include/rhj.h, "RANGE frames") stands behind it in this file and runs on the same kernels: its frames
+// are value distances on the order key, found by two searches per row in the order words by sorted position.
 #include "../../include/rhj.h"
 #include "rhj_internal.h"
 
@@ -21,6 +23,7 @@ void rhj_internal_sort_begin(rhj_ctx *ctx);     // the start of a call: timings 
 void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units);
 int rhj_internal_frame_workspace(rhj_ctx *ctx, size_t bytes, void **out);       // the frame entry's own buffer (the inner sorts regrow the sort's), grown to >= bytes
 void rhj_internal_frame_report(rhj_ctx *ctx, int units, int sorts, int scans, u64 partitions);   // "last.frame_units" / "last.frame_sorts" / "last.frame_scans" / "last.frame_partitions"
+void rhj_internal_frame_range_report(rhj_ctx *ctx, int units, int sorts, int scans, int levels, u64 partitions);   // "last.frame_range_*", as above and "last.frame_range_levels"
 void *rhj_internal_span_open(rhj_ctx *ctx, int kind);
 void rhj_internal_span_close(void *span);
 // provided by rhj_sort.hip
@@ -623,9 +626,406 @@ int frame_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
     return RHJ_OK;
 }
 
+// ==== the RANGE entry (include/rhj.h, "RANGE frames") ====================================================================
+// The frame of a row is a VALUE distance on the order key: every row of the partition whose order value lies in [t - preceding, t +
+// following].  The order, the heads and the two bounds are frame_run's.  New: the order words by sorted position, read through ONE
+// transform v (unsigned, non-decreasing along a partition in all four views), two galloping searches per row and distinct frame for
+// lo / hi, and for MIN / MAX -- a frame has no fixed width here -- the scans of above at the FIXED block length 64 with a sparse table
+// over the whole blocks' summaries between them.
+constexpr u64 RB = 64;                           // the block length of the MIN / MAX scans
+constexpr int RB_SHIFT = 6;
+
+// ---- k_frr_level: one level of the sparse table over the block summaries ---------------------------------------------------------
+// half == 0: dst[k] = F[64 k + 63], the summary of whole block k (valid where no partition head stands inside the block: the only
+// ones k_frr_emit reads).  Else dst[k] = op(src[k], src[k + half]), half = 2^(l - 1): blocks k .. k + 2^l - 1.
+__global__ void __launch_bounds__(FLAT_THREADS)
+k_frr_level(const u64 *__restrict__ src, u64 src_n, u64 cnt, u64 half, u32 mn, u64 *__restrict__ dst)
+{
+    for (u64 k = (u64)blockIdx.x * FLAT_THREADS + threadIdx.x; k < cnt; k += (u64)gridDim.x * FLAT_THREADS) {
+        if (half == 0) {
+            const u64 at = k * RB + (RB - 1);
+            dst[k] = at < src_n ? src[at] : 0;                            // (at < n always: cnt = n / 64)
+            continue;
+        }
+        if (k + half >= src_n) continue;                                 // (never: cnt + half is the length of the level below)
+        const u64 x = src[k], y = src[k + half];
+        dst[k] = mn ? (y < x ? y : x) : (y > x ? y : x);
+    }
+}
+
+struct FrrEmit {
+    u32 nops, nframes, levels, desc;
+    u64 flip;                                                         // 1 << 63 under RHJ_SORT_I64
+    u64 tstride, tcnt;                                                // words between two levels of a table; the whole blocks n / 64
+    u64 prec[RHJ_FRAME_MAX_OPS], fol[RHJ_FRAME_MAX_OPS];              // per distinct FRAME
+    u32 op[RHJ_FRAME_MAX_OPS], mode[RHJ_FRAME_MAX_OPS], frame[RHJ_FRAME_MAX_OPS];
+    u64 bias[RHJ_FRAME_MAX_OPS];
+    const u64 *F[RHJ_FRAME_MAX_OPS];                                  // SUM: S
+    const u64 *B[RHJ_FRAME_MAX_OPS];
+    const u64 *V[RHJ_FRAME_MAX_OPS];                                  // the column by sorted position
+    const u64 *T[RHJ_FRAME_MAX_OPS];                                  // M_BOTH: the table, level l at T + l * tstride
+    u64 *out[RHJ_FRAME_MAX_OPS];
+};
+
+__device__ __forceinline__ u64 frr_view(u64 word, u64 flip, u32 desc)
+{
+    const u64 v = word ^ flip;
+    return desc ? ~v : v;
+}
+
+// lo: the first position of [ps, p] whose v is >= tl (v[p] is).  Gallop away from p in doubling steps while the probe still
+// qualifies, then bisect the bracket: about 2 log2(p - lo) dependent loads.  Every index stays inside [ps, p].
+__device__ __forceinline__ u64 frr_search_lo(const u64 *__restrict__ vs, u64 flip, u32 desc, u64 ps, u64 p, u64 tl)
+{
+    u64 l = ps, b = p, step = 1;
+    while (b - l >= step) {
+        const u64 c = b - step;
+        if (frr_view(vs[c], flip, desc) >= tl) {
+            b = c;
+            step <<= 1;
+        } else {
+            l = c + 1;
+            break;
+        }
+    }
+    while (l < b) {
+        const u64 mid = l + ((b - l) >> 1);
+        if (frr_view(vs[mid], flip, desc) >= tl) b = mid;
+        else l = mid + 1;
+    }
+    return b;
+}
+
+// hi: the last position of [p, pe] whose v is <= th (v[p] is): the mirror of frr_search_lo.  Every index stays inside [p, pe].
+__device__ __forceinline__ u64 frr_search_hi(const u64 *__restrict__ vs, u64 flip, u32 desc, u64 p, u64 pe, u64 th)
+{
+    u64 g = p, h = pe, step = 1;
+    while (h - g >= step) {
+        const u64 c = g + step;
+        if (frr_view(vs[c], flip, desc) <= th) {
+            g = c;
+            step <<= 1;
+        } else {
+            h = c - 1;
+            break;
+        }
+    }
+    while (g < h) {
+        const u64 mid = g + ((h - g + 1) >> 1);
+        if (frr_view(vs[mid], flip, desc) <= th) g = mid;
+        else h = mid - 1;
+    }
+    return g;
+}
+
+// ---- k_frr_emit: the searches and every op's answer, out[perm[p]] -----------------------------------------------------------------
+// Per position: v = the order word in the transformed view; per distinct frame lo = first position with v_r >= max(0, v - preceding),
+// hi = last position with v_r <= min(2^64 - 1, v + following) (an all-ones side: the partition's edge, no search).  COUNT, FIRST_ROW,
+// LAST_ROW, SUM as k_frm_emit.  MIN / MAX: M_FWD F[hi], M_BACK B[lo]; M_BOTH with bl = lo / 64, bh = hi / 64 --
+//   bl == bh: lo at the block's or partition's start F[hi]; hi at the block's or partition's end B[lo]; else the walk V[lo .. hi]
+//   (at most 62 words);  bl < bh: op(B[lo], F[hi]), and with c = bh - bl - 1 >= 1 interior blocks, l = floor(log2 c), also
+//   op(T_l[bl + 1], T_l[bh - 2^l]).  Interior blocks lie inside the frame, so inside one partition: their summaries are valid.
+__global__ void __launch_bounds__(FLAT_THREADS)
+k_frr_emit(const u64 *__restrict__ pstart, const u64 *__restrict__ pend, const u64 *__restrict__ perm, const u64 *__restrict__ vs, u64 n, FrrEmit e)
+{
+    for (u64 p = (u64)blockIdx.x * FLAT_THREADS + threadIdx.x; p < n; p += (u64)gridDim.x * FLAT_THREADS) {
+        const u64 row = perm[p];
+        u64 ps = pstart[p], pe = pend[p];
+        if (ps > p) ps = p;                                              // (never: pstart <= p <= pend < n; the guards keep every index below inside [0, n))
+        if (pe < p || pe >= n) pe = p;
+        const u64 v = frr_view(vs[p], e.flip, e.desc);
+        u64 lo[RHJ_FRAME_MAX_OPS], hi[RHJ_FRAME_MAX_OPS];
+#pragma unroll
+        for (u32 f = 0; f < RHJ_FRAME_MAX_OPS; f++) {
+            lo[f] = ps;
+            hi[f] = pe;
+            if (f >= e.nframes) continue;
+            const u64 pr = e.prec[f], fo = e.fol[f];
+            if (pr != RHJ_FRAME_UNBOUNDED) lo[f] = frr_search_lo(vs, e.flip, e.desc, ps, p, v >= pr ? v - pr : 0);
+            if (fo != RHJ_FRAME_UNBOUNDED) hi[f] = frr_search_hi(vs, e.flip, e.desc, p, pe, fo > ~v ? ~0ull : v + fo);
+        }
+#pragma unroll
+        for (u32 j = 0; j < RHJ_FRAME_MAX_OPS; j++) {
+            if (j >= e.nops) continue;
+            const u32 fr = e.frame[j], op = e.op[j];
+            u64 l = lo[0], h = hi[0];
+#pragma unroll
+            for (u32 f = 1; f < RHJ_FRAME_MAX_OPS; f++)
+                if (fr == f) { l = lo[f]; h = hi[f]; }
+            u64 val;
+            if (op == RHJ_FRAME_COUNT) {
+                val = h - l + 1;
+            } else if (op == RHJ_FRAME_FIRST_ROW) {
+                val = perm[l];
+            } else if (op == RHJ_FRAME_LAST_ROW) {
+                val = perm[h];
+            } else if (op == RHJ_FRAME_SUM) {
+                val = e.F[j][h] - (l > ps ? e.F[j][l - 1] : 0);
+            } else {
+                const bool mn = op == RHJ_FRAME_MIN_U64 || op == RHJ_FRAME_MIN_I64;
+                const u64 *__restrict__ F = e.F[j], *__restrict__ B = e.B[j];
+                if (e.mode[j] == M_FWD) {
+                    val = F[h];
+                } else if (e.mode[j] == M_BACK) {
+                    val = B[l];
+                } else {
+                    const u64 bl = l >> RB_SHIFT, bh = h >> RB_SHIFT;
+                    if (bl == bh) {
+                        const u64 bs = bl << RB_SHIFT, be = bs + (RB - 1);
+                        if (l == (bs > ps ? bs : ps)) {
+                            val = F[h];
+                        } else if (h == (be < pe ? be : pe)) {
+                            val = B[l];
+                        } else {
+                            val = e.V[j][l] ^ e.bias[j];
+                            for (u64 q = l + 1; q <= h; q++) {
+                                const u64 y = e.V[j][q] ^ e.bias[j];
+                                val = mn ? (y < val ? y : val) : (y > val ? y : val);
+                            }
+                        }
+                    } else {
+                        const u64 x = B[l], y = F[h];
+                        val = mn ? (y < x ? y : x) : (y > x ? y : x);
+                        const u64 c = bh - bl - 1;
+                        if (c != 0) {
+                            const u32 lv = 63 - (u32)__clzll((long long)c);
+                            const u64 i0 = bl + 1, i1 = bh - (1ull << lv);
+                            if (lv < e.levels && i1 < e.tcnt && i0 <= i1) {       // (always: the levels reach floor(log2((n - 1) / 64 - 1)))
+                                const u64 *__restrict__ t = e.T[j] + (u64)lv * e.tstride;
+                                const u64 x2 = t[i0], y2 = t[i1];
+                                const u64 z = mn ? (y2 < x2 ? y2 : x2) : (y2 > x2 ? y2 : x2);
+                                val = mn ? (z < val ? z : val) : (z > val ? z : val);
+                            }
+                        }
+                    }
+                }
+                val ^= e.bias[j];
+            }
+            if (row < n) e.out[j][row] = val;                            // (row < n always: perm is a permutation)
+        }
+    }
+}
+
+// the sparse-table levels a call with a two-sided MIN / MAX builds: T_0 .. T_floor(log2 c), c = (n - 1) / 64 - 1 the most interior
+// blocks a frame can hold; 0 when no frame can hold one
+int range_levels(u64 n)
+{
+    const u64 last = (n - 1) >> RB_SHIFT;
+    if (last < 2) return 0;
+    int l = 0;
+    while ((2ull << l) <= last - 1) l++;
+    return l + 1;
+}
+
+int range_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 flags, const u32 *ops, const u64 *preceding,
+              const u64 *following, const u64 *const *d_cols, u32 nops, u64 *const *d_outs, u64 *out_partitions)
+{
+    const std::string me("rhj_frame_range_cols_dev");
+    if (flags & ~(RHJ_SORT_I64 | RHJ_SORT_DESC)) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": unknown flags").c_str());
+    if (!d_order && (n > 0 || flags)) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_order is null: a value distance needs a value").c_str());
+    if (nops == 0 || nops > RHJ_FRAME_MAX_OPS) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": nops must be 1 .. RHJ_FRAME_MAX_OPS").c_str());
+    if (!ops) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops is null").c_str());
+    if (!d_outs) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_outs is null").c_str());
+    for (u32 j = 0; j < nops; j++) {
+        const std::string at = "[" + std::to_string(j) + "]";
+        if (ops[j] > RHJ_FRAME_LAST_ROW) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops" + at + " is not an RHJ_FRAME_* op").c_str());
+        if (!d_outs[j]) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_outs" + at + " is null").c_str());
+        if (is_col_op(ops[j]) && n > 0 && (!d_cols || !d_cols[j]))
+            return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_cols" + at + " is null for a column op with a non-zero row count").c_str());
+    }
+    if (out_partitions) *out_partitions = 0;
+    if (n == 0) return RHJ_OK;
+
+    hipStream_t st = rhj_internal_stream(ctx);
+    hipError_t e;
+    int rc;
+    u64 L;
+    u32 U;
+    rhj_internal_sort_units(ctx, n, &L, &U);
+    if (U == 0 || U > FRM_MAX_UNITS) return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
+
+    // 1. the plan: the distinct frames (one pair of searches each), the distinct columns (one gather each), and per MIN / MAX the
+    //    scans: an all-ones preceding makes lo the partition's start and F alone answers, an all-ones following B alone; else both, in
+    //    blocks of 64 when n > 64, and the table when a frame can hold a whole block between its two ends
+    FrrEmit em = {};
+    em.nops = nops;
+    em.flip = (flags & RHJ_SORT_I64) ? BIAS : 0;
+    em.desc = (flags & RHJ_SORT_DESC) ? 1 : 0;
+    const bool blk = n > RB;
+    int scans = 0, arrays = 0, nboth = 0, ncols = 0;
+    const u64 *ucol[RHJ_FRAME_MAX_OPS] = {};
+    u32 colof[RHJ_FRAME_MAX_OPS] = {};
+    for (u32 j = 0; j < nops; j++) {
+        const u64 pr = preceding ? preceding[j] : RHJ_FRAME_UNBOUNDED, fo = following ? following[j] : 0;
+        u32 f = 0;
+        while (f < em.nframes && (em.prec[f] != pr || em.fol[f] != fo)) f++;
+        if (f == em.nframes) { em.prec[f] = pr; em.fol[f] = fo; em.nframes++; }
+        em.frame[j] = f;
+        em.op[j] = ops[j];
+        em.out[j] = d_outs[j];
+        if (!is_col_op(ops[j])) continue;
+        u32 c = 0;
+        while (c < (u32)ncols && ucol[c] != d_cols[j]) c++;
+        if (c == (u32)ncols) ucol[ncols++] = d_cols[j];
+        colof[j] = c;
+        if (ops[j] == RHJ_FRAME_SUM) { scans += 1; arrays += 1; continue; }
+        em.bias[j] = (ops[j] == RHJ_FRAME_MIN_I64 || ops[j] == RHJ_FRAME_MAX_I64) ? BIAS : 0;
+        em.mode[j] = pr == RHJ_FRAME_UNBOUNDED ? M_FWD : fo == RHJ_FRAME_UNBOUNDED ? M_BACK : M_BOTH;
+        nboth += em.mode[j] == M_BOTH;
+        scans += em.mode[j] == M_BOTH ? 2 : 1;
+        arrays += em.mode[j] == M_BOTH ? 2 : 1;
+    }
+    const int levels = nboth ? range_levels(n) : 0;
+    const u64 nblk = n >> RB_SHIFT;
+
+    // 2. the workspace: the two bounds, the sorted words and the permutation, the order words by position after two sorts, one array
+    //    per distinct column and per value scan, the tables, the flag bytes, the unit tables
+    const int sorts = (d_part ? 1 : 0) + 1;
+    const size_t nb = up256((size_t)n * 8), ub = up256((size_t)U * 8), tb = up256((size_t)nblk * 8);
+    const size_t bytes = 4 * nb + (sorts == 2 ? nb : 0) + (size_t)(ncols + arrays) * nb + (size_t)nboth * levels * tb + up256((size_t)n) + 4 * ub;
+    void *ws = nullptr;
+    if ((rc = rhj_internal_frame_workspace(ctx, bytes, &ws)) != RHJ_OK) return rc;
+    unsigned char *p = (unsigned char *)ws;
+    u64 *bufA = (u64 *)p; p += nb;
+    u64 *bufB = (u64 *)p; p += nb;
+    u64 *skey = (u64 *)p; p += nb;
+    u64 *perm = (u64 *)p; p += nb;
+    u64 *vs = skey;
+    if (sorts == 2) { vs = (u64 *)p; p += nb; }
+    u64 *d_V = (u64 *)p; p += (size_t)ncols * nb;
+    u64 *d_arr = (u64 *)p; p += (size_t)arrays * nb;
+    u64 *d_tab = (u64 *)p; p += (size_t)nboth * levels * tb;
+    unsigned char *d_flags = p; p += up256((size_t)n);
+    u64 *d_usum_v = (u64 *)p; p += ub;
+    u32 *d_usum_f = (u32 *)p; p += ub;
+    u64 *d_carry = (u64 *)p; p += ub;
+    u64 *d_ucnt = (u64 *)p; p += ub;
+    em.tstride = tb / 8;
+    em.tcnt = nblk;
+    em.levels = (u32)levels;
+
+    // 3. the order (partition, order key, input position), and the order words by sorted position
+    const u64 *sp = nullptr;
+    const unsigned fg = flat_grid(n);
+    if (sorts == 2) {
+        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, nullptr, bufA)) != RHJ_OK) return rc;
+        {
+            Span s(ctx, RHJ_K_AUX);
+            hipLaunchKernelGGL(k_frm_gather, dim3(fg), dim3(FLAT_THREADS), 0, st, d_part, (const u64 *)bufA, n, bufB);
+        }
+        if ((rc = check(ctx, "k_frm_gather")) != RHJ_OK) return rc;
+        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), bufB, bufA, n, 0, skey, perm)) != RHJ_OK) return rc;
+        sp = skey;
+        {
+            Span s(ctx, RHJ_K_AUX);
+            hipLaunchKernelGGL(k_frm_gather, dim3(fg), dim3(FLAT_THREADS), 0, st, d_order, (const u64 *)perm, n, vs);
+        }
+        if ((rc = check(ctx, "k_frm_gather")) != RHJ_OK) return rc;
+    } else {
+        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, skey, perm)) != RHJ_OK) return rc;
+    }
+    rhj_internal_sort_report(ctx, 0, 0, 0);                              // "last.sort_*" speak of the sort entries only
+
+    // 4. heads, and the two bounds
+    {
+        Span s(ctx, RHJ_K_AUX);
+        hipLaunchKernelGGL(k_frm_heads, dim3(U), dim3(ST), 0, st, sp, n, L, d_flags, d_ucnt);
+    }
+    if ((rc = check(ctx, "k_frm_heads")) != RHJ_OK) return rc;
+    FrmScan a = {};
+    a.flags = d_flags; a.n = n; a.L = L; a.U = U; a.usum_v = d_usum_v; a.usum_f = d_usum_f; a.carry = d_carry;
+    {
+        FrmScan b = a;
+        b.out = bufA;
+        if ((rc = scan_t<OP_MAX, VS_POS, false, false>(ctx, st, b)) != RHJ_OK) return rc;
+        b.out = bufB;
+        if ((rc = scan_t<OP_MIN, VS_POS, true, false>(ctx, st, b)) != RHJ_OK) return rc;
+    }
+
+    // 5. every distinct column by sorted position: the scans below and the walk read it in place (a.perm stays null)
+    for (int c = 0; c < ncols; c++) {
+        {
+            Span s(ctx, RHJ_K_AUX);
+            hipLaunchKernelGGL(k_frm_gather, dim3(fg), dim3(FLAT_THREADS), 0, st, ucol[c], (const u64 *)perm, n, d_V + (size_t)c * (nb / 8));
+        }
+        if ((rc = check(ctx, "k_frm_gather")) != RHJ_OK) return rc;
+    }
+
+    // 6. the value scans, and the tables
+    u64 *next = d_arr, *tnext = d_tab;
+    for (u32 j = 0; j < nops; j++) {
+        if (!is_col_op(ops[j])) continue;
+        FrmScan b = a;
+        b.col = d_V + (size_t)colof[j] * (nb / 8);
+        b.bias = em.bias[j];
+        em.V[j] = b.col;
+        if (ops[j] == RHJ_FRAME_SUM) {
+            b.out = next; next += nb / 8;
+            em.F[j] = b.out;
+            if ((rc = scan_t<OP_SUM, VS_COL, false, false>(ctx, st, b)) != RHJ_OK) return rc;
+            continue;
+        }
+        const bool mn = ops[j] == RHJ_FRAME_MIN_U64 || ops[j] == RHJ_FRAME_MIN_I64, both = em.mode[j] == M_BOTH, bk = both && blk;
+        if (bk) { b.w = RB; b.s64 = 0; b.stile = (u64)TILE % RB; }
+        if (em.mode[j] != M_BACK) {
+            b.out = next; next += nb / 8;
+            em.F[j] = b.out;
+            if ((rc = mn ? scan_col<OP_MIN>(ctx, st, b, false, bk) : scan_col<OP_MAX>(ctx, st, b, false, bk)) != RHJ_OK) return rc;
+        }
+        if (em.mode[j] != M_FWD) {
+            b.out = next; next += nb / 8;
+            em.B[j] = b.out;
+            if ((rc = mn ? scan_col<OP_MIN>(ctx, st, b, true, bk) : scan_col<OP_MAX>(ctx, st, b, true, bk)) != RHJ_OK) return rc;
+        }
+        if (!both || levels == 0) continue;
+        em.T[j] = tnext;
+        for (int l = 0; l < levels; l++) {
+            const u64 half = l ? 1ull << (l - 1) : 0, cnt = nblk - (1ull << l) + 1;
+            const u64 *src = l ? tnext + (size_t)(l - 1) * em.tstride : em.F[j];
+            const u64 src_n = l ? nblk - half + 1 : n;
+            {
+                Span s(ctx, RHJ_K_TASKS);
+                hipLaunchKernelGGL(k_frr_level, dim3(flat_grid(cnt)), dim3(FLAT_THREADS), 0, st, src, src_n, cnt, half, (u32)(mn ? 1 : 0),
+                                   tnext + (size_t)l * em.tstride);
+            }
+            if ((rc = check(ctx, "k_frr_level")) != RHJ_OK) return rc;
+        }
+        tnext += (size_t)levels * em.tstride;
+    }
+
+    // 7. the searches and every op's answer, by row
+    {
+        Span s(ctx, RHJ_K_JOIN);
+        hipLaunchKernelGGL(k_frr_emit, dim3(fg), dim3(FLAT_THREADS), 0, st, (const u64 *)bufA, (const u64 *)bufB, (const u64 *)perm, (const u64 *)vs, n, em);
+    }
+    if ((rc = check(ctx, "k_frr_emit")) != RHJ_OK) return rc;
+
+    // 8. the partitions: the heads' per-unit counts, summed on the host
+    std::vector<u64> cnt(U);
+    e = hipMemcpyAsync(cnt.data(), d_ucnt, (size_t)U * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(ctx, "rhj_frame_range_cols_dev", e);
+    u64 parts = 0;
+    for (u32 u = 0; u < U; u++) parts += cnt[u];
+    if (out_partitions) *out_partitions = parts;
+    rhj_internal_frame_range_report(ctx, (int)U, sorts, scans, levels, parts);
+    return RHJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rhj_frame_range_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_order, uint64_t n, uint32_t flags,
+                             const uint32_t *ops, const uint64_t *preceding, const uint64_t *following,
+                             const uint64_t *const *d_cols, uint32_t nops, uint64_t *const *d_outs, uint64_t *out_partitions)
+{
+    const int rc = rhj_internal_use_device(ctx);
+    if (rc != RHJ_OK) return rc;
+    rhj_internal_sort_begin(ctx);
+    return range_run(ctx, (const u64 *)d_part, (const u64 *)d_order, n, flags, ops, (const u64 *)preceding, (const u64 *)following,
+                     (const u64 *const *)d_cols, nops, (u64 *const *)d_outs, (u64 *)out_partitions);
+}
 
 int rhj_frame_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_order, uint64_t n, uint32_t flags,
                        const uint32_t *ops, const uint64_t *preceding, const uint64_t *following,

@@ -171,6 +171,9 @@ int  rhj_set_option(rhj_ctx *ctx, const char *name, int64_t value);
  * every other call), "window.tile_rows" (a constant of the build),
  * "last.asof_units" / "last.asof_sorts" / "last.asof_matched" (what the last rhj_asof_cols_dev did, see there; 0 after every other
  * call), "asof.tile_rows" (a constant of the build),
+ * "last.range_join_units" / "last.range_join_sorts" / "last.range_join_pairs" / "last.range_join_expand_tiles" (what the last
+ * rhj_range_join_cols_dev / rhj_range_expand_dev did, see there; 0 after every other call), "range_join.tile_rows" /
+ * "range_join.expand_tile" (constants of the build),
  * "last.pipelined" (the number
  * of S chunks the last rhj_join streamed through the device while finished pairs travelled home, also when no pair came of
  * them; 0: the plain path, which a join abandoned on the pipelined path -- a rowID that does not fit the narrow format, more pairs
@@ -808,6 +811,88 @@ int rhj_frame_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_o
 int rhj_frame_range_cols_dev(rhj_ctx *ctx, const uint64_t *d_part, const uint64_t *d_order, uint64_t n, uint32_t flags,
                              const uint32_t *ops, const uint64_t *preceding, const uint64_t *following,
                              const uint64_t *const *d_cols, uint32_t nops, uint64_t *const *d_outs, uint64_t *out_partitions);
+
+/* ---- range join: for every row of R the rows of S of its partition whose `on` word lies in the row's interval -- SELECT r.row, s.row
+ * FROM R JOIN S ON r.by = s.by AND s.t BETWEEN r.lo AND r.hi: "every quote of the same symbol within 5 s around each trade", "every
+ * event that falls inside each session", the band join |r.t - s.t| <= d, the point-in-interval join against validity ranges (DESIGN
+ * 4.31).  The as-of entry returns ONE partner per row, the RANGE frames look at one table and return aggregates; this entry returns the
+ * partner rows, as a compact CSR result over S in sorted order and as ordered pairs.
+ * Rows are the indices 0 .. n - 1 of their table.  d_byR / d_loR / d_hiR are device columns of nR words, d_byS / d_onS of nS words.
+ * Neither table needs to be sorted.
+ * Partitions: `by` is compared for bit-equality only.  d_byR == NULL && d_byS == NULL: one partition.  Exactly one of the two NULL
+ * with both tables non-empty is RHJ_E_INVALID.
+ * Partners: lo / hi / on are ordered in the chosen view, unsigned 64-bit by default, two's-complement int64 under RHJ_RANGE_I64 (as
+ * RHJ_SORT_I64).  Row j of S is a partner of row i of R iff the `by` words are equal and lo[i] <= on[j] <= hi[i] in the view;
+ * RHJ_RANGE_LO_OPEN turns the first <= into <, RHJ_RANGE_HI_OPEN the second.  An interval with lo > hi in the view has no partner
+ * and is legal; so is an open bound with lo == hi.
+ * Band form (RHJ_RANGE_BAND): d_loR holds R's own order word x and d_hiR must be NULL; lo = x - below and hi = x + above as exact
+ * integers that saturate at the view's ends, nothing wraps -- the rule of the RANGE frames' distances, so all ones is "to the end of
+ * the view".  Open flags apply to the saturated bound like to any other.  Without the bit `below` and `above` are ignored and d_hiR is
+ * required.
+ * Sorted S and the CSR form: rowsS is the rows of S ordered by (`by` word unsigned ascending, `on` in the view ascending, row index
+ * ascending).  The partners of row i are the contiguous run rowsS[first[i] .. first[i] + cnt[i]), cnt[i] = offsets[i + 1] -
+ * offsets[i].  d_out_offsets has nR + 1 words: the exclusive prefix of the counts, offsets[0] = 0 and offsets[nR] the total.
+ * d_out_first has nR words; where cnt[i] == 0, first[i] is any value <= nS.  d_out_rowsS has nS words.  Each of the three may be NULL.
+ * This compact result is 16 nR + 8 nS bytes however many pairs there are.
+ * Pairs: d_out[k] = {rowR, rowS}, ordered by rowR ascending, within one row of R in the order of rowsS: d_out[offsets[i] + q] = {i,
+ * rowsS[first[i] + q]}.  d_out == NULL with out_capacity == 0 writes no pairs; NULL with a non-zero capacity is RHJ_E_INVALID.  d_out
+ * needs 16-byte alignment.  *out_count is a HOST pointer and may be NULL; it always receives the exact total.  When the total exceeds
+ * out_capacity the return is RHJ_E_OVERFLOW: slots [0, capacity) hold the first `capacity` pairs of the defined order, nothing at or
+ * past capacity is written, and the three CSR outputs are complete, so a caller can finish with rhj_range_expand_dev or slice R.
+ * Every result is bit-identical from run to run.
+ * Empty tables: nR == 0: RHJ_OK, total 0, offsets[0] = 0 if given, nothing else written.  nS == 0 with nR > 0: total 0, offsets all 0
+ * and first all 0 (one fill launch).
+ * RHJ_E_INVALID, before any launch, with a message naming the argument: unknown flag bits; NULL d_loR with nR > 0; NULL d_onS with nS
+ * > 0; NULL d_hiR without RHJ_RANGE_BAND and nR > 0; non-NULL d_hiR under RHJ_RANGE_BAND; the one-sided `by`; NULL d_out with a
+ * non-zero out_capacity.  *out_count and the outputs are then untouched.
+ * Inputs are neither modified nor retained; outputs must not overlap inputs; pointers need 8-byte alignment.  The call synchronises;
+ * it honours rhj_set_stream and rhj_set_profiling (the inner sorts' spans; RHJ_K_AUX: concatenation, gathers, fill, validation; per
+ * scan RHJ_K_HIST, RHJ_K_SCAN, RHJ_K_SCATTER; RHJ_K_TASKS: the searches; RHJ_K_JOIN: the expansion).
+ * How: one launch concatenates R's lower bounds (under BAND the saturated x - below, computed in the view) and S's `on` words into one
+ * column of n = nR + nS words, [R ; S], under RHJ_RANGE_LO_OPEN [S ; R], and the `by` words alike; the side of a concatenated position
+ * follows from its index.  The order (by, word, concatenated position) comes from the stable sort as in the as-of entry -- two sorts
+ * with a gather between them, one sort without `by` --, so among equal words a row of S stands behind a row of R exactly when
+ * equality qualifies at the lower end.  The rank scan -- a reduce per unit, a one-workgroup carry over the at most 2048 unit sums, an
+ * apply per unit, on the sort's units ("sort.max_units" caps them here too; the result never depends on it) -- gives srank[p], the rows
+ * of S before sorted position p, and stores rowsS[srank[p]] at the positions of S.  One flat launch then searches, from every
+ * position p of R, the first position q at which "the same `by` word and word <= hi" (< hi under RHJ_RANGE_HI_OPEN) fails -- the test is
+ * monotone from p on, a galloping search of about 2 log2(q - p) dependent loads -- and stores first[i] = srank[p], cnt[i] = srank[q] -
+ * srank[p].  The same scan over cnt in row order gives offsets; the host reads the total.  The expansion runs one workgroup per
+ * "range_join.expand_tile" output slots: it finds the rows that cover its slots by binary search in offsets, every thread its slot's row
+ * among them, and writes the pair with one 16-byte store: work is balanced over pairs, not rows.  No workgroup waits on another inside
+ * a kernel, and no position, count or value comes from an atomic.
+ * Costs in bytes: per row of nR + nS the concatenation 16 (32 with `by`), the sorts (see there) plus 24 for the gather between two of
+ * them and 24 for the order words after them, the rank scan 8 + 8 + 8, the search 8 + 8 and per row of R a gathered 8 (hi), the
+ * dependent loads of its search and two scattered 8-byte stores; per row of R the offsets scan 8 + 8 + 8; per pair one 16-byte store, a
+ * gathered 8-byte load and log2(rows per tile) cached loads.
+ * rhj_get_info: "last.range_join_units" the units the rank scan was cut into, "last.range_join_sorts" the inner sorts that ran (1
+ * without `by`, else 2; 0 with an empty table), "last.range_join_pairs" the total, "last.range_join_expand_tiles" the workgroups of
+ * the expansion; all four are 0 after every other call.  After a range call "last.join_kernel" is -1 and "last.sort_*" / "last.topk_*"
+ * / "last.window_*" / "last.asof_*" / "last.frame*" are 0.  "range_join.tile_rows": the positions one workgroup scans at once,
+ * "range_join.expand_tile": the pairs one workgroup of the expansion writes; constants of the build.
+ * Memory: a workspace buffer of its own (the inner sorts regrow the sort's), kept until rhj_release_workspace: 4 x 8 bytes per row of
+ * nR + nS, 6 x 8 with `by`, 8 per row of R, and 8 per word of every CSR output that is NULL.
+ * rhj_range_expand_dev is the second half on its own, so a caller sizes the pair buffer after one set of sorts: count with d_out ==
+ * NULL, allocate *out_count pairs, expand.  d_offsets (nR + 1 words), d_first (nR words) and d_rowsS (nS words) are the CSR result of a
+ * range call, or any arrays of that shape.  One flat validation launch over the rows checks offsets[0] == 0, offsets[i] <=
+ * offsets[i + 1], and first[i] + cnt[i] <= nS wherever cnt[i] > 0, and reduces to one flag, which the host reads together with
+ * offsets[nR] before the expansion is launched: a violation is RHJ_E_INVALID with nothing written -- an error code, never an address.
+ * NULL d_offsets, NULL d_first with nR > 0, NULL d_rowsS with nS > 0 and NULL d_out with a non-zero capacity are RHJ_E_INVALID before
+ * any launch.  Capacity, overflow, the first-`capacity` rule and *out_count are as above.  No sort runs in it: it leaves
+ * "last.range_join_units" and "last.range_join_sorts" as the call before it left them -- behind a range call they still speak of the
+ * call that made the arrays --, the other two names speak of it.
+ * Out of scope: interval-overlap joins with intervals on both sides, inequality joins on two different columns, float order columns,
+ * a sharded form, the query layer.  There is no 16-byte tuple form. */
+#define RHJ_RANGE_I64      1u   /* order lo / hi / on as two's-complement int64 (default: unsigned), as RHJ_SORT_I64 */
+#define RHJ_RANGE_LO_OPEN  2u   /* on >  lo instead of on >= lo */
+#define RHJ_RANGE_HI_OPEN  4u   /* on <  hi instead of on <= hi */
+#define RHJ_RANGE_BAND     8u   /* d_loR holds R's own order word x, d_hiR must be NULL: the interval is [x - below, x + above] */
+int rhj_range_join_cols_dev(rhj_ctx *ctx, const uint64_t *d_byR, const uint64_t *d_loR, const uint64_t *d_hiR, uint64_t nR,
+                            const uint64_t *d_byS, const uint64_t *d_onS, uint64_t nS, uint32_t flags, uint64_t below, uint64_t above,
+                            uint64_t *d_out_offsets, uint64_t *d_out_first, uint64_t *d_out_rowsS,
+                            rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count);
+int rhj_range_expand_dev(rhj_ctx *ctx, const uint64_t *d_offsets, const uint64_t *d_first, uint64_t nR,
+                         const uint64_t *d_rowsS, uint64_t nS, rhj_pair *d_out, uint64_t out_capacity, uint64_t *out_count);
 
 /* ---- composite keys: up to four key columns per relation packed into ONE 64-bit key column (JOIN .. ON r.a = s.a AND r.b = s.b; GROUP
  * BY a, b; torch.unique(dim=0); merge(on=[..])).  Every operator above compares 64-bit values by bit pattern, so what it needs is an

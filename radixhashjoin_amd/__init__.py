@@ -49,6 +49,11 @@ min / max and the frame's first / last row, a sliding min / max at the same cost
 ``Engine(0).ntile_columns(k, t, 4)`` is NTILE(4).
 RANGE frames: ``Engine(0).frame_range_columns(sym, t, [x, None], ["sum", "count"], 5_000_000_000)`` is the sum and the count of the same
 symbol's rows of the last 5 seconds -- the frame a value distance on the order key, peers always inside (``rhj_frame_range_cols_dev``).
+Range join: ``idx_R, idx_S = Engine(0).range_join_columns(lo_R, hi_R, t_S, by_R=sym_R, by_S=sym_S)`` is every pair with the same ``by``
+and ``lo_R[i] <= t_S[j] <= hi_R[i]``, ordered by i and then by (t_S[j], j) -- a defined order, bit-identical from run to run;
+``offsets, first, rows_S, total = Engine(0).range_join_csr_columns(..)`` the same as runs of S in sorted order, 16 bytes per row of R
+and 8 per row of S however many pairs there are; ``Engine(0).band_join_columns(t_R, t_S, below, above, ..)`` the band join
+``t_R[i] - below <= t_S[j] <= t_R[i] + above`` with saturating ends (``rhj_range_join_cols_dev``, ``rhj_range_expand_dev``).
 """
 from .binding import (  # noqa: F401
     AGG_MAX_I64,
@@ -69,6 +74,10 @@ from .binding import (  # noqa: F401
     ASOF_STRICT,
     ASOF_TOLERANCE,
     PAIR,
+    RANGE_BAND,
+    RANGE_HI_OPEN,
+    RANGE_I64,
+    RANGE_LO_OPEN,
     TUPLE,
     DeviceBuffer,
     Engine,
@@ -125,5 +134,5 @@ from .binding import (  # noqa: F401
     unmix64,
 )
 
-__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS", "SORT_I64", "SORT_DESC", "WINDOW_MAX_OPS", "WIN_ROW_NUMBER", "WIN_RANK", "WIN_DENSE_RANK", "WIN_LAG_ROW", "WIN_LEAD_ROW", "WIN_CUMSUM", "WIN_CUMMIN_U64", "WIN_CUMMAX_U64", "WIN_CUMMIN_I64", "WIN_CUMMAX_I64", "ASOF_I64", "ASOF_FORWARD", "ASOF_STRICT", "ASOF_TOLERANCE", "FRAME_MAX_OPS", "FRAME_UNBOUNDED", "FRAME_COUNT", "FRAME_SUM", "FRAME_MIN_U64", "FRAME_MAX_U64", "FRAME_MIN_I64", "FRAME_MAX_I64", "FRAME_FIRST_ROW", "FRAME_LAST_ROW"]
+__all__ = ["Engine", "Opts", "Timings", "DeviceBuffer", "RhjError", "TUPLE", "PAIR", "lib_path", "load_library", "mix64", "unmix64", "SEMI", "ANTI", "OUTER_LEFT", "OUTER_RIGHT", "OUTER_FULL", "NO_ROW", "SUM_MAX_COLS", "GROUP_MAX_COLS", "GROUP_JOIN_MAX_COLS", "GJ_INNER", "GJ_LEFT", "AGG_SUM", "AGG_MIN_U64", "AGG_MAX_U64", "AGG_MIN_I64", "AGG_MAX_I64", "KeyPlan", "KeysLayout", "keys_layout", "KEYS_MAX_COLS", "KEYS_NO_UNPACK", "KEYS_RANGE", "KEYS_DICT", "LOOKUP_FIRST", "LOOKUP_LAST", "LOOKUP_MAX_COLS", "ARG_MIN_U64", "ARG_MAX_U64", "ARG_MIN_I64", "ARG_MAX_I64", "ARG_ROW", "ARG_TIE_FIRST", "ARG_TIE_LAST", "GROUP_ARG_MAX_COLS", "SORT_I64", "SORT_DESC", "WINDOW_MAX_OPS", "WIN_ROW_NUMBER", "WIN_RANK", "WIN_DENSE_RANK", "WIN_LAG_ROW", "WIN_LEAD_ROW", "WIN_CUMSUM", "WIN_CUMMIN_U64", "WIN_CUMMAX_U64", "WIN_CUMMIN_I64", "WIN_CUMMAX_I64", "ASOF_I64", "ASOF_FORWARD", "ASOF_STRICT", "ASOF_TOLERANCE", "FRAME_MAX_OPS", "FRAME_UNBOUNDED", "FRAME_COUNT", "FRAME_SUM", "FRAME_MIN_U64", "FRAME_MAX_U64", "FRAME_MIN_I64", "FRAME_MAX_I64", "FRAME_FIRST_ROW", "FRAME_LAST_ROW", "RANGE_I64", "RANGE_LO_OPEN", "RANGE_HI_OPEN", "RANGE_BAND"]
 __version__ = "0.1.0"

@@ -146,6 +146,8 @@ SYMBOLS = {
     "rhj_window_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
     "rhj_frame_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
     "rhj_frame_range_cols_dev": (C.c_int, [_vp, _vp, _vp, _u64, C.c_uint32, _P(C.c_uint32), _P(_u64), _P(_u64), _P(_vp), C.c_uint32, _P(_vp), _P(_u64)]),
+    "rhj_range_join_cols_dev": (C.c_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _P(_u64)]),
+    "rhj_range_expand_dev": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _P(_u64)]),
     "rhj_histogram": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "rhj_prefix": (C.c_int, [_vp, _vp, _u64, _vp]),
     "rhj_partition": (C.c_int, [_vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
@@ -395,6 +397,35 @@ def _asof_args(by_R, by_S, values_S, direction, allow_exact_matches, tolerance, 
     return flags, tolerance or 0, values_S, fills
 
 
+# include/rhj.h RHJ_RANGE_*: flags of a range_join_cols_dev call -- the int64 view, the open ends, the band form
+RANGE_I64, RANGE_LO_OPEN, RANGE_HI_OPEN, RANGE_BAND = 1, 2, 4, 8
+_RANGE_CLOSED = {"both": 0, "left": RANGE_HI_OPEN, "right": RANGE_LO_OPEN, "neither": RANGE_LO_OPEN | RANGE_HI_OPEN}
+
+
+def _range_args(by_R, by_S, closed, unsigned, below=0, above=0, lo_R=None, hi_R=None):
+    """the flags of a range_join_columns / band_join_columns call (without RANGE_BAND); ValueError on a wrong `closed`, flag, distance,
+    `by`, number of tensors or length -- nothing here touches a device"""
+    if not isinstance(closed, str) or closed not in _RANGE_CLOSED:
+        raise ValueError(f"closed: 'both', 'left', 'right' or 'neither' is needed, not {closed!r}")
+    if not isinstance(unsigned, bool):
+        raise ValueError(f"unsigned: a bool is needed, not {unsigned!r}")
+    for name, d in (("below", below), ("above", above)):
+        if isinstance(d, bool) or not isinstance(d, int) or not 0 <= d <= NO_ROW:
+            raise ValueError(f"{name}: an int >= 0 (below 2^64) is needed, not {d!r}")
+    if (by_R is None) != (by_S is None):
+        raise ValueError(f"{'by_S' if by_S is None else 'by_R'}: None, but the other side has a `by`: both sides or neither")
+    if by_R is not None:
+        counts = [len(b) if isinstance(b, (list, tuple)) else 1 for b in (by_R, by_S)]
+        for name, k in zip(("by_R", "by_S"), counts):
+            if not 1 <= k <= KEYS_MAX_COLS:
+                raise ValueError(f"{name}: 1 to {KEYS_MAX_COLS} tensors are needed, not {k}")
+        if counts[0] != counts[1]:
+            raise ValueError(f"by_S: {counts[1]} tensors, by_R has {counts[0]}")
+    if hasattr(lo_R, "numel") and hasattr(hi_R, "numel") and lo_R.numel() != hi_R.numel():
+        raise ValueError(f"hi_R: {hi_R.numel()} elements, lo_R has {lo_R.numel()}")
+    return (0 if unsigned else RANGE_I64) | _RANGE_CLOSED[closed]
+
+
 # include/rhj.h RHJ_FRAME_*: the ops of a frame_cols_dev call, how many one call takes, and "to the partition's edge"
 FRAME_MAX_OPS = 4
 FRAME_UNBOUNDED = 0xFFFFFFFFFFFFFFFF
@@ -612,8 +643,9 @@ class Engine:
         "last.sort_bits", "last.sort_passes", "last.sort_units", "last.topk_bits", "last.topk_passes", "last.topk_candidates",
         "last.topk_sorted_rows", "last.window_units", "last.window_sorts", "last.window_partitions", "last.asof_units", "last.asof_sorts",
         "last.asof_matched", "last.frame_units", "last.frame_sorts", "last.frame_scans", "last.frame_partitions", "last.frame_range_units", "last.frame_range_sorts",
-        "last.frame_range_scans", "last.frame_range_levels", "last.frame_range_partitions"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows",
-        "asof.tile_rows")"""
+        "last.frame_range_scans", "last.frame_range_levels", "last.frame_range_partitions", "last.range_join_units", "last.range_join_sorts",
+        "last.range_join_pairs", "last.range_join_expand_tiles"; include/rhj.h) and constants of the build ("sort.tile_rows", "topk.auto_candidates", "window.tile_rows",
+        "asof.tile_rows", "range_join.tile_rows", "range_join.expand_tile")"""
         v = C.c_int64(0)
         self._chk(self.lib.rhj_get_info(self.ctx, name.encode(), C.byref(v)))
         return v.value
@@ -1835,6 +1867,96 @@ class Engine:
             if values and nR:
                 self.gather_cols_fill(values_S, nS, idx_S, nR, fills, values)
         return idx_S, matched, values
+
+    def range_join_cols_dev(self, d_byR, d_loR, d_hiR, nR, d_byS, d_onS, nS, flags=0, below=0, above=0, d_out_offsets=None, d_out_first=None,
+                            d_out_rowsS=None, d_out=None, out_capacity=0, allow_overflow=False):
+        """rhj_range_join_cols_dev: the rows of S with a bit-equal `by` word (d_byR and d_byS None: one partition) whose `on` word lies
+        in [lo[i], hi[i]] -- flags: RANGE_I64 (the words as int64), RANGE_LO_OPEN / RANGE_HI_OPEN (that end excluded), RANGE_BAND (d_loR
+        holds x, d_hiR is None, the interval is [x - below, x + above], saturating) -- as d_out_rowsS (uint64[nS]: the rows of S ordered
+        by (by, on, row)), d_out_first (uint64[nR]) and d_out_offsets (uint64[nR + 1]): the partners of row i are rowsS[first[i] ..
+        first[i] + offsets[i + 1] - offsets[i]); and as d_out, out_capacity pairs {rowR, rowS} ordered by rowR, then as rowsS.  Each
+        output may be None.  Returns the exact number of pairs; with allow_overflow a capacity below it is not an error (the first
+        out_capacity pairs are written, the CSR outputs are complete)."""
+        count = _u64()
+        rc = self.lib.rhj_range_join_cols_dev(self.ctx, _addr(d_byR), _addr(d_loR), _addr(d_hiR), nR, _addr(d_byS), _addr(d_onS), nS, flags, below,
+                                              above, _addr(d_out_offsets), _addr(d_out_first), _addr(d_out_rowsS), _addr(d_out), out_capacity,
+                                              C.byref(count))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return count.value
+
+    def range_expand_dev(self, d_offsets, d_first, nR, d_rowsS, nS, d_out=None, out_capacity=0, allow_overflow=False):
+        """rhj_range_expand_dev: the pairs of a CSR result (range_join_cols_dev's three arrays, validated on the device first: RhjError
+        for arrays that are none) into d_out, out_capacity pairs.  Returns the exact number of pairs; allow_overflow as there."""
+        count = _u64()
+        rc = self.lib.rhj_range_expand_dev(self.ctx, _addr(d_offsets), _addr(d_first), nR, _addr(d_rowsS), nS, _addr(d_out), out_capacity,
+                                           C.byref(count))
+        self._chk(rc, allow=(RHJ_E_OVERFLOW,) if allow_overflow else ())
+        return count.value
+
+    def _range_csr(self, lo_R, hi_R, on_S, by_R, by_S, flags, below=0, above=0):
+        """one rhj_range_join_cols_dev call without pairs: (offsets, first, rows_S, total, device)"""
+        import torch
+        if isinstance(by_R, (list, tuple)) or isinstance(by_S, (list, tuple)):
+            by_R, by_S, plan = self.pack_keys(by_R if isinstance(by_R, (list, tuple)) else [by_R],
+                                              by_S if isinstance(by_S, (list, tuple)) else [by_S], keep_dictionaries=False)
+            plan.close()                           # (a join needs no dictionary: the plan holds nothing)
+        with self._on_torch_stream(lo_R, on_S, tuple(t for t in (hi_R, by_R) if t is not None), weights_S=() if by_S is None else (by_S,)) as dev:
+            nR, nS = lo_R.numel(), on_S.numel()
+            offsets = torch.zeros(nR + 1, dtype=torch.int64, device=dev)
+            first = torch.zeros(nR, dtype=torch.int64, device=dev)
+            rows_S = torch.empty(nS, dtype=torch.int64, device=dev)
+            total = 0
+            if nR and nS:
+                total = self.range_join_cols_dev(by_R, lo_R, hi_R, nR, by_S, on_S, nS, flags, below, above, offsets, first, rows_S)
+            elif nS:
+                rows_S = torch.empty(0, dtype=torch.int64, device=dev)     # no row of R: S is not sorted, nothing refers to it
+        return offsets, first, rows_S, total, dev
+
+    def _range_pairs(self, csr):
+        """(idx_R, idx_S) of a CSR result: one rhj_range_expand_dev and one rhj_pairs_split -- no second set of sorts"""
+        import torch
+        offsets, first, rows_S, total, dev = csr
+        idx_R = torch.empty(total, dtype=torch.int64, device=dev)
+        idx_S = torch.empty(total, dtype=torch.int64, device=dev)
+        if total:
+            with self._on_torch_stream(offsets, rows_S, weights_S=()):
+                pairs = torch.empty((total, 2), dtype=torch.int64, device=dev)
+                got = self.range_expand_dev(offsets, first, first.numel(), rows_S, rows_S.numel(), pairs, total)
+                assert got == total, (got, total)
+                self.pairs_split(pairs, total, idx_R, idx_S)
+        return idx_R, idx_S
+
+    def range_join_csr_columns(self, lo_R, hi_R, on_S, by_R=None, by_S=None, closed="both", unsigned=False):
+        """(offsets, first, rows_S, total): the range join SELECT .. FROM R JOIN S ON r.by = s.by AND s.on BETWEEN r.lo AND r.hi in its
+        compact form -- rows_S the indices of S ordered by (by, on, index), and for row i of R its partners rows_S[first[i] : first[i] +
+        offsets[i + 1] - offsets[i]]; offsets the exclusive prefix of the counts (len(lo_R) + 1 words, offsets[-1] == total); total a
+        Python int.  int64 tensors on the tensors' device: 16 bytes per row of R and 8 per row of S however many pairs there are.
+        lo_R / hi_R / on_S: contiguous 1-D 64-bit integer tensors on the engine's device, ordered as int64 (unsigned=True: the words as
+        uint64); NEITHER table needs to be sorted.  closed: "both" (lo <= on <= hi), "left" (on < hi), "right" (lo < on) or "neither".
+        An interval with lo > hi has no partner.  by_R / by_S: None (one partition), a tensor per side, or a list of 1 to KEYS_MAX_COLS
+        tensors per side (packed first, pack_keys; rows_S is then ordered by the packed word first -- the runs hold the same rows in
+        the same order for any packing).  With no row of R rows_S is empty.  A wrong closed, a non-bool unsigned, `by` on
+        one side only, a different number of `by` tensors per side, hi_R of another length than lo_R: ValueError before any device
+        use.  One rhj_range_join_cols_dev call.  Streams and completion as join_columns."""
+        flags = _range_args(by_R, by_S, closed, unsigned, lo_R=lo_R, hi_R=hi_R)
+        return self._range_csr(lo_R, hi_R, on_S, by_R, by_S, flags)[:4]
+
+    def range_join_columns(self, lo_R, hi_R, on_S, by_R=None, by_S=None, closed="both", unsigned=False):
+        """(idx_R, idx_S): the range join as index pairs -- every (i, j) with by_R[i] == by_S[j] and lo_R[i] <= on_S[j] <= hi_R[i]
+        exactly once, ordered by i and within one i by (on_S[j], j): a defined order, bit-identical from run to run.  Arguments and
+        errors as range_join_csr_columns.  One csr call, then total pairs are allocated and filled by one rhj_range_expand_dev and one
+        rhj_pairs_split: the sorts run once."""
+        flags = _range_args(by_R, by_S, closed, unsigned, lo_R=lo_R, hi_R=hi_R)
+        return self._range_pairs(self._range_csr(lo_R, hi_R, on_S, by_R, by_S, flags))
+
+    def band_join_columns(self, on_R, on_S, below, above, by_R=None, by_S=None, closed="both", unsigned=False):
+        """(idx_R, idx_S): the band join on_R[i] - below <= on_S[j] <= on_R[i] + above (and by_R[i] == by_S[j]) as index pairs, ordered
+        as range_join_columns' -- "every quote within 5 s around each trade".  below / above: ints >= 0, exact distances: both ends
+        saturate at the view's minimum and maximum, nothing wraps, and 2^64 - 1 is "to the end of the view".  closed applies to the
+        saturated ends.  A negative, bool or float below / above: ValueError before any device use; the other arguments and errors as
+        range_join_csr_columns.  RANGE_BAND: no bound tensor is materialised."""
+        flags = _range_args(by_R, by_S, closed, unsigned, below, above) | RANGE_BAND
+        return self._range_pairs(self._range_csr(on_R, None, on_S, by_R, by_S, flags, below, above))
 
     def factorize_columns(self, keys):
         """(codes, uniques): pandas.factorize without the ordering promise -- uniques the distinct values of keys in no particular

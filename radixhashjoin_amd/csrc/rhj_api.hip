@@ -288,6 +288,9 @@ struct rhj_ctx {
     int last_frange_units = 0, last_frange_sorts = 0, last_frange_scans = 0, last_frange_levels = 0;   // "last.frame_range_units" / "_sorts" / "_scans" / "_levels": the same of the last RANGE frame call, and the sparse-table levels it built (0: another call)
     u64 last_frange_parts = 0;         // "last.frame_range_partitions": the partitions it found
     DevBuf frame_ws;                   // the frame entry's permutation, sorted words, flags, bounds, by-position scans and unit tables (rhj_frame.hip): not sort_ws, which the inner sorts regrow
+    int last_range_units = 0, last_range_sorts = 0;     // "last.range_join_units" / "last.range_join_sorts": the units the last range join's rank scan was cut into, its inner sorts (0: another call)
+    u64 last_range_pairs = 0, last_range_tiles = 0;     // "last.range_join_pairs" / "last.range_join_expand_tiles": the pairs of the last range join or expansion, the workgroups that wrote them
+    DevBuf range_ws;                   // the range join's concatenation, permutation, order words, ranks, counts and unit tables (rhj_range.hip): not sort_ws, which the inner sorts regrow
     DevBuf asof_ws;                    // the as-of entry's concatenation, permutation, flags and unit tables (rhj_asof.hip): not sort_ws, which the inner sorts regrow
     DevBuf window_ws;                  // the window entry's permutation, sorted words, flags, starts and unit tables (rhj_window.hip): not sort_ws, which the inner sorts regrow
     CallArgs call;                     // the operator arguments of the entry in progress (CallScope)
@@ -534,6 +537,8 @@ void prof_reset(rhj_ctx *ctx)
     ctx->last_frame_parts = 0;
     ctx->last_frange_units = ctx->last_frange_sorts = ctx->last_frange_scans = ctx->last_frange_levels = 0;   // "last.frame_range_*": ... and the RANGE frame entry these
     ctx->last_frange_parts = 0;
+    ctx->last_range_units = ctx->last_range_sorts = 0;                        // "last.range_join_*": ... and the range join entries these
+    ctx->last_range_pairs = ctx->last_range_tiles = 0;
 }
 
 int check_launch(rhj_ctx *ctx, const char *what)
@@ -2169,6 +2174,25 @@ int rhj_internal_asof_workspace(rhj_ctx *ctx, size_t bytes, void **out)
     *out = ctx->asof_ws.p;
     return RHJ_OK;
 }
+// ... and for rhj_range.hip
+void rhj_internal_range_report(rhj_ctx *ctx, int units, int sorts, u64 pairs, u64 tiles)
+{
+    ctx->last_range_units = units;
+    ctx->last_range_sorts = sorts;
+    ctx->last_range_pairs = pairs;
+    ctx->last_range_tiles = tiles;
+}
+void rhj_internal_range_last(rhj_ctx *ctx, int *units, int *sorts)
+{
+    *units = ctx->last_range_units;
+    *sorts = ctx->last_range_sorts;
+}
+int rhj_internal_range_workspace(rhj_ctx *ctx, size_t bytes, void **out)
+{
+    RHJCHK(ensure(ctx, ctx->range_ws, bytes));
+    *out = ctx->range_ws.p;
+    return RHJ_OK;
+}
 // ... and for rhj_frame.hip
 void rhj_internal_frame_report(rhj_ctx *ctx, int units, int sorts, int scans, u64 partitions)
 {
@@ -2282,7 +2306,7 @@ int rhj_release_workspace(rhj_ctx *ctx)
                      &ctx->grp_rng, &ctx->unit_start2, &ctx->narrow_flag, &ctx->agg_out, &ctx->seg_rng, &ctx->tag_base,
                      &ctx->shard_ps[0], &ctx->shard_ps[1], &ctx->shard_mm, &ctx->shard_wide, &ctx->shard_peer_tab, &ctx->fuse_ctl, &ctx->sniff_tab, &ctx->hist2_b, &ctx->grp_rng_b,
                      &ctx->unit_start2_b, &ctx->ps_1_b, &ctx->part_tmp_b, &ctx->cf_cnt1, &ctx->cf_pre, &ctx->cf_tot, &ctx->cf2_end[0], &ctx->cf2_end[1], &ctx->cols_aos[0], &ctx->cols_aos[1], &ctx->b_in[0], &ctx->b_out[0], &ctx->b_cnt[0],
-                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws, &ctx->window_ws, &ctx->asof_ws, &ctx->frame_ws};
+                     &ctx->b_in[1], &ctx->b_out[1], &ctx->b_cnt[1], &ctx->sort_ws, &ctx->topk_ws, &ctx->window_ws, &ctx->asof_ws, &ctx->frame_ws, &ctx->range_ws};
     ctx->fuse_clean = false;
     for (DevBuf *b : all) release(*b);
     ctx->small_hdr_clean = false;
@@ -2406,6 +2430,12 @@ int rhj_get_info(rhj_ctx *ctx, const char *name, int64_t *value)
     if (n == "last.frame_range_scans") { *value = ctx->last_frange_scans; return RHJ_OK; }
     if (n == "last.frame_range_levels") { *value = ctx->last_frange_levels; return RHJ_OK; }
     if (n == "last.frame_range_partitions") { *value = (int64_t)ctx->last_frange_parts; return RHJ_OK; }
+    if (n == "last.range_join_units") { *value = ctx->last_range_units; return RHJ_OK; }
+    if (n == "last.range_join_sorts") { *value = ctx->last_range_sorts; return RHJ_OK; }
+    if (n == "last.range_join_pairs") { *value = (int64_t)ctx->last_range_pairs; return RHJ_OK; }
+    if (n == "last.range_join_expand_tiles") { *value = (int64_t)ctx->last_range_tiles; return RHJ_OK; }
+    if (n == "range_join.tile_rows") { *value = RANGE_TILE; return RHJ_OK; }
+    if (n == "range_join.expand_tile") { *value = RANGE_EXPAND_TILE; return RHJ_OK; }
     if (n == "partition.mix") { *value = join_mix(ctx) != MIX_NONE; return RHJ_OK; }
     return fail(ctx, RHJ_E_INVALID, "rhj_get_info: unknown name: " + n);
 }

@@ -484,3 +484,7 @@ constexpr int TOPK_AUTO_CANDIDATES = 1 << 16;
 constexpr int WINDOW_TILE = SORT_TILE;
 // ... and so does the as-of scan (rhj_asof.hip; "asof.tile_rows")
 constexpr int ASOF_TILE = SORT_TILE;
+// ... and the range join's two scans (rhj_range.hip; "range_join.tile_rows"); its expansion writes this many pairs per
+// workgroup ("range_join.expand_tile")
+constexpr int RANGE_TILE = SORT_TILE;
+constexpr int RANGE_EXPAND_TILE = 2048;

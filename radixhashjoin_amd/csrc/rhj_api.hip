@@ -2127,12 +2127,6 @@ void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units)
     ctx->last_sort_passes = passes;
     ctx->last_sort_units = units;
 }
-int rhj_internal_sort_workspace(rhj_ctx *ctx, size_t bytes, void **out)
-{
-    RHJCHK(ensure(ctx, ctx->sort_ws, bytes));
-    *out = ctx->sort_ws.p;
-    return RHJ_OK;
-}
 int rhj_internal_sort_max_units(rhj_ctx *ctx) { return ctx->opt_sort_units; }
 void rhj_internal_topk_report(rhj_ctx *ctx, int bits, int passes, u64 candidates, u64 sorted_rows)
 {
@@ -2140,12 +2134,6 @@ void rhj_internal_topk_report(rhj_ctx *ctx, int bits, int passes, u64 candidates
     ctx->last_topk_passes = passes;
     ctx->last_topk_cand = candidates;
     ctx->last_topk_sorted = sorted_rows;
-}
-int rhj_internal_topk_workspace(rhj_ctx *ctx, size_t bytes, void **out)
-{
-    RHJCHK(ensure(ctx, ctx->topk_ws, bytes));
-    *out = ctx->topk_ws.p;
-    return RHJ_OK;
 }
 int64_t rhj_internal_topk_max_candidates(rhj_ctx *ctx) { return ctx->opt_topk_cand; }
 // ... and for rhj_window.hip
@@ -2155,24 +2143,12 @@ void rhj_internal_window_report(rhj_ctx *ctx, int units, int sorts, u64 partitio
     ctx->last_window_sorts = sorts;
     ctx->last_window_parts = partitions;
 }
-int rhj_internal_window_workspace(rhj_ctx *ctx, size_t bytes, void **out)
-{
-    RHJCHK(ensure(ctx, ctx->window_ws, bytes));
-    *out = ctx->window_ws.p;
-    return RHJ_OK;
-}
 // ... and for rhj_asof.hip
 void rhj_internal_asof_report(rhj_ctx *ctx, int units, int sorts, u64 matched)
 {
     ctx->last_asof_units = units;
     ctx->last_asof_sorts = sorts;
     ctx->last_asof_matched = matched;
-}
-int rhj_internal_asof_workspace(rhj_ctx *ctx, size_t bytes, void **out)
-{
-    RHJCHK(ensure(ctx, ctx->asof_ws, bytes));
-    *out = ctx->asof_ws.p;
-    return RHJ_OK;
 }
 // ... and for rhj_range.hip
 void rhj_internal_range_report(rhj_ctx *ctx, int units, int sorts, u64 pairs, u64 tiles)
@@ -2186,12 +2162,6 @@ void rhj_internal_range_last(rhj_ctx *ctx, int *units, int *sorts)
 {
     *units = ctx->last_range_units;
     *sorts = ctx->last_range_sorts;
-}
-int rhj_internal_range_workspace(rhj_ctx *ctx, size_t bytes, void **out)
-{
-    RHJCHK(ensure(ctx, ctx->range_ws, bytes));
-    *out = ctx->range_ws.p;
-    return RHJ_OK;
 }
 // ... and for rhj_frame.hip
 void rhj_internal_frame_report(rhj_ctx *ctx, int units, int sorts, int scans, u64 partitions)
@@ -2209,10 +2179,12 @@ void rhj_internal_frame_range_report(rhj_ctx *ctx, int units, int sorts, int sca
     ctx->last_frange_levels = levels;
     ctx->last_frange_parts = partitions;
 }
-int rhj_internal_frame_workspace(rhj_ctx *ctx, size_t bytes, void **out)
+// one accessor for the six entries' buffers (RHJ_WS_*): separate buffers, so that an outer entry's survives the inner sorts regrowing theirs
+int rhj_internal_workspace(rhj_ctx *ctx, int which, size_t bytes, void **out)
 {
-    RHJCHK(ensure(ctx, ctx->frame_ws, bytes));
-    *out = ctx->frame_ws.p;
+    DevBuf *const ws[RHJ_WS_COUNT] = {&ctx->sort_ws, &ctx->topk_ws, &ctx->window_ws, &ctx->asof_ws, &ctx->frame_ws, &ctx->range_ws};
+    RHJCHK(ensure(ctx, *ws[which], bytes));
+    *out = ws[which]->p;
     return RHJ_OK;
 }
 void *rhj_internal_span_open(rhj_ctx *ctx, int kind) { return new Span(ctx, kind); }

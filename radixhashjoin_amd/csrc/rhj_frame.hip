@@ -9,64 +9,18 @@
 // atomic.
 // The RANGE entry (include/rhj.h, "RANGE frames") stands behind it in this file and runs on the same kernels: its frames
 // are value distances on the order key, found by two searches per row in the order words by sorted position.
-#include "../../include/rhj.h"
-#include "rhj_internal.h"
-
-#include <string>
-#include <vector>
-
-// provided by rhj_api.hip
-int rhj_internal_use_device(rhj_ctx *ctx);
-hipStream_t rhj_internal_stream(rhj_ctx *ctx);
-int rhj_internal_fail(rhj_ctx *ctx, int code, const char *msg);
-void rhj_internal_sort_begin(rhj_ctx *ctx);     // the start of a call: timings and "last.*" as prof_reset leaves them, "last.join_kernel" -1
-void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units);
-int rhj_internal_frame_workspace(rhj_ctx *ctx, size_t bytes, void **out);       // the frame entry's own buffer (the inner sorts regrow the sort's), grown to >= bytes
-void rhj_internal_frame_report(rhj_ctx *ctx, int units, int sorts, int scans, u64 partitions);   // "last.frame_units" / "last.frame_sorts" / "last.frame_scans" / "last.frame_partitions"
-void rhj_internal_frame_range_report(rhj_ctx *ctx, int units, int sorts, int scans, int levels, u64 partitions);   // "last.frame_range_*", as above and "last.frame_range_levels"
-void *rhj_internal_span_open(rhj_ctx *ctx, int kind);
-void rhj_internal_span_close(void *span);
-// provided by rhj_sort.hip
-int rhj_internal_sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, const u64 *rows, u64 n, u32 flags, u64 *okeys, u64 *orows);
-void rhj_internal_sort_units(rhj_ctx *ctx, u64 n, u64 *L, u32 *U);              // units of L rows, a whole number of tiles, under "sort.max_units"
+#include "rhj_ordered.h"
 
 namespace {
 
-constexpr u64 BIAS = 1ull << 63;
-constexpr int ST = SORT_THREADS, TPT = SORT_TPT, TILE = WINDOW_TILE, NW = ST / 64;
-constexpr u32 FRM_MAX_UNITS = 2048;              // the sort's: what one carry workgroup scans
-constexpr int RED_UNROLL = 4;
-constexpr int FLAT_THREADS = 256;
-constexpr u32 FLAT_MAX_GRID = 4096;
-static_assert(TILE == ST * TPT && ST % 64 == 0 && TILE % (NW * 64 * RED_UNROLL) == 0, "k_frm_reduce's and k_frm_apply's geometry");
+constexpr int TILE = WINDOW_TILE;
+static_assert(TILE == SORT_TILE, "k_frm_reduce's and k_frm_apply's geometry is the sort's (rhj_ordered.h)");
 
 // ---- the scan's algebra ------------------------------------------------------------------------------------------------------------
-// An element is (f, v): f -- a head stands here, v -- its value.  (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2), the later
-// element on the right, + the op.  It is associative wherever the heads stand, so heads at block starts beside the
+// rhj_ordered.h's (f, v) fold.  It is associative wherever the heads stand, so heads at block starts beside the
 // partition heads change nothing in the argument, and neither does the direction: a backward scan is this fold over the index
 // m = n - 1 - p, in which a partition's tail and a block's end are the heads.
-enum { OP_SUM = 0, OP_MIN = 1, OP_MAX = 2 };
 enum { VS_COL = 0, VS_POS = 1 };                 // the value: a column word through the permutation; head ? position : the identity
-
-template <int OP> __device__ __forceinline__ u64 ident() { return OP == OP_MIN ? ~0ull : 0ull; }
-template <int OP> __device__ __forceinline__ u64 comb(u64 a, u64 b)
-{
-    return OP == OP_SUM ? a + b : OP == OP_MIN ? (b < a ? b : a) : (b > a ? b : a);
-}
-
-// inclusive scan of (f, v) over the wave's lanes: __shfl_up with the head flag carried along
-template <int OP> __device__ __forceinline__ void wave_seg_scan(u32 &f, u64 &v, u32 lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u64 ov = __shfl_up(v, off, 64);
-        const u32 of = __shfl_up(f, off, 64);
-        if (lane >= (u32)off) {
-            v = f ? v : comb<OP>(ov, v);
-            f |= of;
-        }
-    }
-}
 
 struct FrmScan {
     const unsigned char *flags;                  // n bytes, by sorted position: non-zero where a partition starts
@@ -141,16 +95,6 @@ k_frm_heads(const u64 *__restrict__ sp, u64 n, u64 L, unsigned char *__restrict_
     ucnt[u] = s;
 }
 
-// ---- k_frm_gather: dst[i] = src[idx[i]] -- the partition column in the order of the first inner sort ------------------------------
-__global__ void __launch_bounds__(FLAT_THREADS)
-k_frm_gather(const u64 *__restrict__ src, const u64 *__restrict__ idx, u64 n, u64 *__restrict__ dst)
-{
-    for (u64 i = (u64)blockIdx.x * FLAT_THREADS + threadIdx.x; i < n; i += (u64)gridDim.x * FLAT_THREADS) {
-        const u64 r = idx[i];
-        dst[i] = r < n ? src[r] : 0;                                  // (r < n always: idx is a permutation of 0 .. n - 1)
-    }
-}
-
 // ---- k_frm_reduce<OP, VS, BACK, BLK>: per unit "has a head" and the aggregate since the unit's last head --------------------------
 // One workgroup per unit of the index m.  Wave w walks the w-th eighth of the unit 64 indices at a time, RED_UNROLL rounds of loads
 // in flight.  A round with a head keeps only the lanes from its last head on and replaces the wave's running aggregate; one without
@@ -211,49 +155,10 @@ k_frm_reduce(FrmScan a)
     a.usum_f[u] = f;
 }
 
-// ---- k_frm_carry<OP>: one workgroup -- the exclusive scan of at most 2048 unit summaries -------------------------------------------
-// Thread t folds its run of ceil(U / 512) consecutive units, the runs are scanned over the workgroup (wave scan, per-wave totals
-// through LDS), and the thread walks its run again from its carry-in.
-template <int OP>
-__global__ void __launch_bounds__(ST)
-k_frm_carry(const u64 *__restrict__ usum_v, const u32 *__restrict__ usum_f, u32 U, u64 *__restrict__ carry)
-{
-    __shared__ u64 wv[NW];
-    __shared__ u32 wf[NW];
-    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 per = (U + ST - 1) / ST;
-    const u32 b = tid * per < U ? tid * per : U, e = b + per < U ? b + per : U;
-    u32 sf = 0;
-    u64 sv = ident<OP>();
-    for (u32 u = b; u < e; u++) {
-        const u32 fu = usum_f[u];
-        const u64 vu = usum_v[u];
-        sv = fu ? vu : comb<OP>(sv, vu);
-        sf |= fu;
-    }
-    wave_seg_scan<OP>(sf, sv, lane);
-    if (lane == 63) { wv[wave] = sv; wf[wave] = sf; }
-    __syncthreads();
-    u64 pv = ident<OP>();
-#pragma unroll
-    for (int w = 0; w < NW; w++)
-        if ((u32)w < wave) pv = wf[w] ? wv[w] : comb<OP>(pv, wv[w]);
-    u64 ev = __shfl_up(sv, 1, 64);
-    u32 ef = __shfl_up(sf, 1, 64);
-    if (lane == 0) { ev = ident<OP>(); ef = 0; }
-    u64 cur = ef ? ev : comb<OP>(pv, ev);
-    for (u32 u = b; u < e; u++) {
-        carry[u] = cur;
-        const u32 fu = usum_f[u];
-        const u64 vu = usum_v[u];
-        cur = fu ? vu : comb<OP>(cur, vu);
-    }
-}
-
 // ---- k_frm_apply<OP, VS, BACK, BLK>: the scan itself, stored by position -------------------------------------------------------------
 // One workgroup per unit, tile by tile, in the order (wave, round, lane): wave w of a tile owns the indices [w * 64 * TPT, (w + 1) *
 // 64 * TPT) of it.  Per round a wave scan, continued from the wave's running aggregate (lane 63 of the round before); per tile the
-// waves' totals through LDS, folded onto the tile's carry-in -- the unit's from k_frm_carry, then the running one.  An index behind a
+// waves' totals through LDS, folded onto the tile's carry-in -- the unit's from k_ord_carry, then the running one.  An index behind a
 // head of its own wave is final after the wave's rounds; any other takes the fold of the carry and the waves before.
 template <int OP, int VS, bool BACK, bool BLK>
 __global__ void __launch_bounds__(ST)
@@ -399,53 +304,14 @@ k_frm_emit(const u64 *__restrict__ pstart, const u64 *__restrict__ pend, const u
     }
 }
 
-int hip_fail(rhj_ctx *ctx, const char *what, hipError_t e)
-{
-    (void)hipGetLastError();
-    return rhj_internal_fail(ctx, e == hipErrorOutOfMemory ? RHJ_E_NOMEM : RHJ_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
-int check(rhj_ctx *ctx, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RHJ_OK : hip_fail(ctx, what, e);
-}
-
-struct Span {
-    void *s;
-    Span(rhj_ctx *ctx, int kind) : s(rhj_internal_span_open(ctx, kind)) {}
-    ~Span() { rhj_internal_span_close(s); }
-};
-
-unsigned flat_grid(u64 n)
-{
-    u64 g = (n + FLAT_THREADS - 1) / FLAT_THREADS;
-    if (g > FLAT_MAX_GRID) g = FLAT_MAX_GRID;
-    return (unsigned)(g ? g : 1);
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // one scan: reduce, carry, apply, ordered by the stream
 template <int OP, int VS, bool BACK, bool BLK>
 int scan_t(rhj_ctx *ctx, hipStream_t st, const FrmScan &a)
 {
     int rc;
-    {
-        Span s(ctx, RHJ_K_HIST);
-        hipLaunchKernelGGL((k_frm_reduce<OP, VS, BACK, BLK>), dim3(a.U), dim3(ST), 0, st, a);
-    }
-    if ((rc = check(ctx, "k_frm_reduce")) != RHJ_OK) return rc;
-    {
-        Span s(ctx, RHJ_K_SCAN);
-        hipLaunchKernelGGL(k_frm_carry<OP>, dim3(1), dim3(ST), 0, st, (const u64 *)a.usum_v, (const u32 *)a.usum_f, a.U, a.carry);
-    }
-    if ((rc = check(ctx, "k_frm_carry")) != RHJ_OK) return rc;
-    {
-        Span s(ctx, RHJ_K_SCATTER);
-        hipLaunchKernelGGL((k_frm_apply<OP, VS, BACK, BLK>), dim3(a.U), dim3(ST), 0, st, a);
-    }
-    return check(ctx, "k_frm_apply");
+    if ((rc = launch(ctx, RHJ_K_HIST, "k_frm_reduce", k_frm_reduce<OP, VS, BACK, BLK>, a.U, ST, st, a)) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_SCAN, "k_ord_carry", k_ord_carry<OP>, 1, ST, st, a.usum_v, a.usum_f, a.U, a.carry)) != RHJ_OK) return rc;
+    return launch(ctx, RHJ_K_SCATTER, "k_frm_apply", k_frm_apply<OP, VS, BACK, BLK>, a.U, ST, st, a);
 }
 
 template <int OP>
@@ -458,32 +324,42 @@ int scan_col(rhj_ctx *ctx, hipStream_t st, const FrmScan &a, bool back, bool blk
 bool is_col_op(u32 op) { return op >= RHJ_FRAME_SUM && op <= RHJ_FRAME_MAX_I64; }
 bool is_minmax(u32 op) { return op >= RHJ_FRAME_MIN_U64 && op <= RHJ_FRAME_MAX_I64; }
 
-int frame_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 flags, const u32 *ops, const u64 *preceding,
-              const u64 *following, const u64 *const *d_cols, u32 nops, u64 *const *d_outs, u64 *out_partitions)
+// what both entries ask of their flags and op lists, in this order; order_err: the entry's own complaint about d_order (null: none),
+// max_nops / last_op: the entry's bounds on nops and ops[j] (both entries pass RHJ_FRAME_MAX_OPS and RHJ_FRAME_LAST_ROW, which the
+// two texts name: an entry with other bounds needs its own words there)
+int check_ops(rhj_ctx *ctx, const std::string &me, u32 flags, const char *order_err, u32 max_nops, u32 last_op, const u32 *ops,
+              const u64 *const *d_cols, u32 nops, u64 *const *d_outs, u64 n)
 {
-    const std::string me("rhj_frame_cols_dev");
     if (flags & ~(RHJ_SORT_I64 | RHJ_SORT_DESC)) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": unknown flags").c_str());
-    if (flags && !d_order) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": flags without d_order: they say how the order column is read").c_str());
-    if (nops == 0 || nops > RHJ_FRAME_MAX_OPS) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": nops must be 1 .. RHJ_FRAME_MAX_OPS").c_str());
+    if (order_err) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + order_err).c_str());
+    if (nops == 0 || nops > max_nops) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": nops must be 1 .. RHJ_FRAME_MAX_OPS").c_str());
     if (!ops) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops is null").c_str());
     if (!d_outs) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_outs is null").c_str());
     for (u32 j = 0; j < nops; j++) {
         const std::string at = "[" + std::to_string(j) + "]";
-        if (ops[j] > RHJ_FRAME_LAST_ROW) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops" + at + " is not an RHJ_FRAME_* op").c_str());
+        if (ops[j] > last_op) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops" + at + " is not an RHJ_FRAME_* op").c_str());
         if (!d_outs[j]) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_outs" + at + " is null").c_str());
         if (is_col_op(ops[j]) && n > 0 && (!d_cols || !d_cols[j]))
             return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_cols" + at + " is null for a column op with a non-zero row count").c_str());
     }
+    return RHJ_OK;
+}
+
+int frame_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 flags, const u32 *ops, const u64 *preceding,
+              const u64 *following, const u64 *const *d_cols, u32 nops, u64 *const *d_outs, u64 *out_partitions)
+{
+    const std::string me("rhj_frame_cols_dev");
+    int rc = check_ops(ctx, me, flags, flags && !d_order ? ": flags without d_order: they say how the order column is read" : nullptr, RHJ_FRAME_MAX_OPS,
+                       RHJ_FRAME_LAST_ROW, ops, d_cols, nops, d_outs, n);
+    if (rc != RHJ_OK) return rc;
     if (out_partitions) *out_partitions = 0;
     if (n == 0) return RHJ_OK;
 
     hipStream_t st = rhj_internal_stream(ctx);
-    hipError_t e;
-    int rc;
     u64 L;
     u32 U;
     rhj_internal_sort_units(ctx, n, &L, &U);
-    if (U == 0 || U > FRM_MAX_UNITS) return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
+    if (U == 0 || U > ORD_MAX_UNITS) return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
 
     // 1. the plan of every op: its frame, and for MIN / MAX which scans it needs.  A side that reaches n - 1 positions reaches every
     //    partition's edge from every row: it is unbounded.  With preceding unbounded lo is the partition's start and F alone answers;
@@ -526,7 +402,7 @@ int frame_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
     const bool need_ab = sorts == 2 || need_ps || need_pe;
     const size_t bytes = (need_ab ? 2 * nb : 0) + (sorts ? 2 * nb : 0) + (size_t)arrays * nb + up256((size_t)n) + 4 * ub;
     void *ws = nullptr;
-    if ((rc = rhj_internal_frame_workspace(ctx, bytes, &ws)) != RHJ_OK) return rc;
+    if ((rc = rhj_internal_workspace(ctx, RHJ_WS_FRAME, bytes, &ws)) != RHJ_OK) return rc;
     unsigned char *p = (unsigned char *)ws;
     u64 *bufA = nullptr, *bufB = nullptr, *skey = nullptr, *perm = nullptr;
     if (need_ab) { bufA = (u64 *)p; p += nb; bufB = (u64 *)p; p += nb; }
@@ -538,31 +414,12 @@ int frame_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
     u64 *d_carry = (u64 *)p; p += ub;
     u64 *d_ucnt = (u64 *)p; p += ub;
 
-    // 3. the order (partition, order key, input position), exactly as the window entry's
-    const u64 *sp = nullptr;
-    if (sorts == 2) {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, nullptr, bufA)) != RHJ_OK) return rc;
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_frm_gather, dim3(flat_grid(n)), dim3(FLAT_THREADS), 0, st, d_part, (const u64 *)bufA, n, bufB);
-        }
-        if ((rc = check(ctx, "k_frm_gather")) != RHJ_OK) return rc;
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), bufB, bufA, n, 0, skey, perm)) != RHJ_OK) return rc;
-        sp = skey;
-    } else if (d_part) {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_part, nullptr, n, 0, skey, perm)) != RHJ_OK) return rc;
-        sp = skey;
-    } else if (d_order) {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, skey, perm)) != RHJ_OK) return rc;
-    }
-    rhj_internal_sort_report(ctx, 0, 0, 0);                              // "last.sort_*" speak of the sort entries only
+    // 3. the order (partition, order key, input position)
+    Ordered o;
+    if ((rc = order_rows(ctx, st, me.c_str(), d_part, d_order, n, flags, bufA, bufB, skey, skey, perm, &o)) != RHJ_OK) return rc;
 
     // 4. heads
-    {
-        Span s(ctx, RHJ_K_AUX);
-        hipLaunchKernelGGL(k_frm_heads, dim3(U), dim3(ST), 0, st, sp, n, L, d_flags, d_ucnt);
-    }
-    if ((rc = check(ctx, "k_frm_heads")) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_AUX, "k_frm_heads", k_frm_heads, U, ST, st, o.sp, n, L, d_flags, d_ucnt)) != RHJ_OK) return rc;
 
     FrmScan a = {};
     a.flags = d_flags; a.perm = perm; a.n = n; a.L = L; a.U = U; a.usum_v = d_usum_v; a.usum_f = d_usum_f; a.carry = d_carry;
@@ -607,20 +464,12 @@ int frame_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
     }
 
     // 7. every op's answer, by row
-    {
-        Span s(ctx, RHJ_K_AUX);
-        hipLaunchKernelGGL(k_frm_emit, dim3(eg), dim3(FLAT_THREADS), 0, st, (const u64 *)(need_ps ? bufA : nullptr),
-                           (const u64 *)(need_pe ? bufB : nullptr), (const u64 *)perm, n, em);
-    }
-    if ((rc = check(ctx, "k_frm_emit")) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_AUX, "k_frm_emit", k_frm_emit, eg, FLAT_THREADS, st, need_ps ? bufA : nullptr, need_pe ? bufB : nullptr, perm, n, em)) != RHJ_OK)
+        return rc;
 
     // 8. the partitions: the heads' per-unit counts, summed on the host
-    std::vector<u64> cnt(U);
-    e = hipMemcpyAsync(cnt.data(), d_ucnt, (size_t)U * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(ctx, "rhj_frame_cols_dev", e);
     u64 parts = 0;
-    for (u32 u = 0; u < U; u++) parts += cnt[u];
+    if ((rc = unit_total(ctx, st, me.c_str(), d_ucnt, U, &parts)) != RHJ_OK) return rc;
     if (out_partitions) *out_partitions = parts;
     rhj_internal_frame_report(ctx, (int)U, sorts, scans, parts);
     return RHJ_OK;
@@ -821,28 +670,17 @@ int range_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
               const u64 *following, const u64 *const *d_cols, u32 nops, u64 *const *d_outs, u64 *out_partitions)
 {
     const std::string me("rhj_frame_range_cols_dev");
-    if (flags & ~(RHJ_SORT_I64 | RHJ_SORT_DESC)) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": unknown flags").c_str());
-    if (!d_order && (n > 0 || flags)) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_order is null: a value distance needs a value").c_str());
-    if (nops == 0 || nops > RHJ_FRAME_MAX_OPS) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": nops must be 1 .. RHJ_FRAME_MAX_OPS").c_str());
-    if (!ops) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops is null").c_str());
-    if (!d_outs) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_outs is null").c_str());
-    for (u32 j = 0; j < nops; j++) {
-        const std::string at = "[" + std::to_string(j) + "]";
-        if (ops[j] > RHJ_FRAME_LAST_ROW) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": ops" + at + " is not an RHJ_FRAME_* op").c_str());
-        if (!d_outs[j]) return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_outs" + at + " is null").c_str());
-        if (is_col_op(ops[j]) && n > 0 && (!d_cols || !d_cols[j]))
-            return rhj_internal_fail(ctx, RHJ_E_INVALID, (me + ": d_cols" + at + " is null for a column op with a non-zero row count").c_str());
-    }
+    int rc = check_ops(ctx, me, flags, !d_order && (n > 0 || flags) ? ": d_order is null: a value distance needs a value" : nullptr, RHJ_FRAME_MAX_OPS,
+                       RHJ_FRAME_LAST_ROW, ops, d_cols, nops, d_outs, n);
+    if (rc != RHJ_OK) return rc;
     if (out_partitions) *out_partitions = 0;
     if (n == 0) return RHJ_OK;
 
     hipStream_t st = rhj_internal_stream(ctx);
-    hipError_t e;
-    int rc;
     u64 L;
     u32 U;
     rhj_internal_sort_units(ctx, n, &L, &U);
-    if (U == 0 || U > FRM_MAX_UNITS) return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
+    if (U == 0 || U > ORD_MAX_UNITS) return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
 
     // 1. the plan: the distinct frames (one pair of searches each), the distinct columns (one gather each), and per MIN / MAX the
     //    scans: an all-ones preceding makes lo the partition's start and F alone answers, an all-ones following B alone; else both, in
@@ -884,7 +722,7 @@ int range_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
     const size_t nb = up256((size_t)n * 8), ub = up256((size_t)U * 8), tb = up256((size_t)nblk * 8);
     const size_t bytes = 4 * nb + (sorts == 2 ? nb : 0) + (size_t)(ncols + arrays) * nb + (size_t)nboth * levels * tb + up256((size_t)n) + 4 * ub;
     void *ws = nullptr;
-    if ((rc = rhj_internal_frame_workspace(ctx, bytes, &ws)) != RHJ_OK) return rc;
+    if ((rc = rhj_internal_workspace(ctx, RHJ_WS_FRAME, bytes, &ws)) != RHJ_OK) return rc;
     unsigned char *p = (unsigned char *)ws;
     u64 *bufA = (u64 *)p; p += nb;
     u64 *bufB = (u64 *)p; p += nb;
@@ -905,33 +743,13 @@ int range_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
     em.levels = (u32)levels;
 
     // 3. the order (partition, order key, input position), and the order words by sorted position
-    const u64 *sp = nullptr;
     const unsigned fg = flat_grid(n);
-    if (sorts == 2) {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, nullptr, bufA)) != RHJ_OK) return rc;
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_frm_gather, dim3(fg), dim3(FLAT_THREADS), 0, st, d_part, (const u64 *)bufA, n, bufB);
-        }
-        if ((rc = check(ctx, "k_frm_gather")) != RHJ_OK) return rc;
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), bufB, bufA, n, 0, skey, perm)) != RHJ_OK) return rc;
-        sp = skey;
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_frm_gather, dim3(fg), dim3(FLAT_THREADS), 0, st, d_order, (const u64 *)perm, n, vs);
-        }
-        if ((rc = check(ctx, "k_frm_gather")) != RHJ_OK) return rc;
-    } else {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, skey, perm)) != RHJ_OK) return rc;
-    }
-    rhj_internal_sort_report(ctx, 0, 0, 0);                              // "last.sort_*" speak of the sort entries only
+    Ordered o;
+    if ((rc = order_rows(ctx, st, me.c_str(), d_part, d_order, n, flags, bufA, bufB, skey, skey, perm, &o)) != RHJ_OK) return rc;
+    if (sorts == 2 && (rc = launch(ctx, RHJ_K_AUX, "k_ord_gather", k_ord_gather<u64>, fg, FLAT_THREADS, st, d_order, perm, n, vs)) != RHJ_OK) return rc;
 
     // 4. heads, and the two bounds
-    {
-        Span s(ctx, RHJ_K_AUX);
-        hipLaunchKernelGGL(k_frm_heads, dim3(U), dim3(ST), 0, st, sp, n, L, d_flags, d_ucnt);
-    }
-    if ((rc = check(ctx, "k_frm_heads")) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_AUX, "k_frm_heads", k_frm_heads, U, ST, st, o.sp, n, L, d_flags, d_ucnt)) != RHJ_OK) return rc;
     FrmScan a = {};
     a.flags = d_flags; a.n = n; a.L = L; a.U = U; a.usum_v = d_usum_v; a.usum_f = d_usum_f; a.carry = d_carry;
     {
@@ -944,11 +762,7 @@ int range_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
 
     // 5. every distinct column by sorted position: the scans below and the walk read it in place (a.perm stays null)
     for (int c = 0; c < ncols; c++) {
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_frm_gather, dim3(fg), dim3(FLAT_THREADS), 0, st, ucol[c], (const u64 *)perm, n, d_V + (size_t)c * (nb / 8));
-        }
-        if ((rc = check(ctx, "k_frm_gather")) != RHJ_OK) return rc;
+        if ((rc = launch(ctx, RHJ_K_AUX, "k_ord_gather", k_ord_gather<u64>, fg, FLAT_THREADS, st, ucol[c], perm, n, d_V + (size_t)c * (nb / 8))) != RHJ_OK) return rc;
     }
 
     // 6. the value scans, and the tables
@@ -983,30 +797,19 @@ int range_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 fl
             const u64 half = l ? 1ull << (l - 1) : 0, cnt = nblk - (1ull << l) + 1;
             const u64 *src = l ? tnext + (size_t)(l - 1) * em.tstride : em.F[j];
             const u64 src_n = l ? nblk - half + 1 : n;
-            {
-                Span s(ctx, RHJ_K_TASKS);
-                hipLaunchKernelGGL(k_frr_level, dim3(flat_grid(cnt)), dim3(FLAT_THREADS), 0, st, src, src_n, cnt, half, (u32)(mn ? 1 : 0),
-                                   tnext + (size_t)l * em.tstride);
-            }
-            if ((rc = check(ctx, "k_frr_level")) != RHJ_OK) return rc;
+            if ((rc = launch(ctx, RHJ_K_TASKS, "k_frr_level", k_frr_level, flat_grid(cnt), FLAT_THREADS, st, src, src_n, cnt, half, (u32)(mn ? 1 : 0),
+                             tnext + (size_t)l * em.tstride)) != RHJ_OK)
+                return rc;
         }
         tnext += (size_t)levels * em.tstride;
     }
 
     // 7. the searches and every op's answer, by row
-    {
-        Span s(ctx, RHJ_K_JOIN);
-        hipLaunchKernelGGL(k_frr_emit, dim3(fg), dim3(FLAT_THREADS), 0, st, (const u64 *)bufA, (const u64 *)bufB, (const u64 *)perm, (const u64 *)vs, n, em);
-    }
-    if ((rc = check(ctx, "k_frr_emit")) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_JOIN, "k_frr_emit", k_frr_emit, fg, FLAT_THREADS, st, bufA, bufB, perm, vs, n, em)) != RHJ_OK) return rc;
 
     // 8. the partitions: the heads' per-unit counts, summed on the host
-    std::vector<u64> cnt(U);
-    e = hipMemcpyAsync(cnt.data(), d_ucnt, (size_t)U * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(ctx, "rhj_frame_range_cols_dev", e);
     u64 parts = 0;
-    for (u32 u = 0; u < U; u++) parts += cnt[u];
+    if ((rc = unit_total(ctx, st, me.c_str(), d_ucnt, U, &parts)) != RHJ_OK) return rc;
     if (out_partitions) *out_partitions = parts;
     rhj_internal_frame_range_report(ctx, (int)U, sorts, scans, levels, parts);
     return RHJ_OK;

@@ -488,3 +488,29 @@ constexpr int ASOF_TILE = SORT_TILE;
 // workgroup ("range_join.expand_tile")
 constexpr int RANGE_TILE = SORT_TILE;
 constexpr int RANGE_EXPAND_TILE = 2048;
+
+// ---- rhj_api.hip's hooks for the other translation units of the library (rhj_query.hip, rhj_keys.hip and the sort-based files) -----
+typedef struct rhj_ctx rhj_ctx;                 // (include/rhj.h's)
+int rhj_internal_use_device(rhj_ctx *ctx);
+hipStream_t rhj_internal_stream(rhj_ctx *ctx);
+int rhj_internal_fail(rhj_ctx *ctx, int code, const char *msg);
+void *rhj_internal_counters(rhj_ctx *ctx);      // >= 64 bytes of zeroable device scratch, or nullptr on failure
+void *rhj_internal_span_open(rhj_ctx *ctx, int kind);                           // a profiling span (RHJ_K_*) around the launches that follow
+void rhj_internal_span_close(void *span);
+// one buffer per entry, grown to >= bytes: an outer entry's own buffer survives the inner sorts, which regrow the sort's
+enum { RHJ_WS_SORT = 0, RHJ_WS_TOPK, RHJ_WS_WINDOW, RHJ_WS_ASOF, RHJ_WS_FRAME, RHJ_WS_RANGE, RHJ_WS_COUNT };
+int rhj_internal_workspace(rhj_ctx *ctx, int which, size_t bytes, void **out);
+void rhj_internal_sort_begin(rhj_ctx *ctx);     // the start of a call: timings and "last.*" as prof_reset leaves them, "last.join_kernel" -1
+void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units);   // "last.sort_bits" / "last.sort_passes" / "last.sort_units"
+int rhj_internal_sort_max_units(rhj_ctx *ctx);                                  // "sort.max_units": -1 automatic, else 1 .. SORT_MAX_UNITS
+void rhj_internal_topk_report(rhj_ctx *ctx, int bits, int passes, u64 candidates, u64 sorted_rows);   // "last.topk_*"
+int64_t rhj_internal_topk_max_candidates(rhj_ctx *ctx);                         // "topk.max_candidates": -1 automatic, else 1 .. 2^31 - 1
+void rhj_internal_window_report(rhj_ctx *ctx, int units, int sorts, u64 partitions);   // "last.window_units" / "last.window_sorts" / "last.window_partitions"
+void rhj_internal_asof_report(rhj_ctx *ctx, int units, int sorts, u64 matched);   // "last.asof_units" / "last.asof_sorts" / "last.asof_matched"
+void rhj_internal_frame_report(rhj_ctx *ctx, int units, int sorts, int scans, u64 partitions);   // "last.frame_units" / "last.frame_sorts" / "last.frame_scans" / "last.frame_partitions"
+void rhj_internal_frame_range_report(rhj_ctx *ctx, int units, int sorts, int scans, int levels, u64 partitions);   // "last.frame_range_*", as above and "last.frame_range_levels"
+void rhj_internal_range_report(rhj_ctx *ctx, int units, int sorts, u64 pairs, u64 tiles);   // "last.range_join_units" / "_sorts" / "_pairs" / "_expand_tiles"
+void rhj_internal_range_last(rhj_ctx *ctx, int *units, int *sorts);             // ... the first two as they stand
+// ... and rhj_sort.hip's, for the entries that order their rows with it
+int rhj_internal_sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, const u64 *rows, u64 n, u32 flags, u64 *okeys, u64 *orows);
+void rhj_internal_sort_units(rhj_ctx *ctx, u64 n, u64 *L, u32 *U);              // units of L rows, a whole number of tiles, under "sort.max_units"

@@ -7,12 +7,6 @@
 #include <string>
 #include <vector>
 
-// provided by rhj_api.hip
-int rhj_internal_use_device(rhj_ctx *ctx);
-hipStream_t rhj_internal_stream(rhj_ctx *ctx);
-int rhj_internal_fail(rhj_ctx *ctx, int code, const char *msg);
-void *rhj_internal_counters(rhj_ctx *ctx);      // >= 64 bytes of zeroable device scratch, or nullptr on failure
-
 static_assert(RHJ_KEYS_MAX_COLS == 4 && RHJ_KEYS_MAX_FOLDS == 2 && RHJ_KEYS_FOLD0 == RHJ_KEYS_MAX_COLS, "the fold shapes below");
 
 // the plan: the layout, and what the layout's fields need to be read back

@@ -6,12 +6,6 @@
 
 #include <string>
 
-// provided by rhj_api.hip
-int rhj_internal_use_device(rhj_ctx *ctx);
-hipStream_t rhj_internal_stream(rhj_ctx *ctx);
-int rhj_internal_fail(rhj_ctx *ctx, int code, const char *msg);
-void *rhj_internal_counters(rhj_ctx *ctx);      // >= 64 bytes of zeroable device scratch, or nullptr on failure
-
 namespace {
 
 struct __align__(16) Tup { u64 key; u64 payload; };

@@ -8,35 +8,13 @@
 // an apply per unit --, the galloping search for q, the same scan over the counts in row order, and the expansion of the CSR result
 // into pairs, balanced over pairs and not over rows.  No workgroup ever waits on another, and no position, count or value comes from
 // an atomic.
-#include "../../include/rhj.h"
-#include "rhj_internal.h"
-
-#include <string>
-
-// provided by rhj_api.hip
-int rhj_internal_use_device(rhj_ctx *ctx);
-hipStream_t rhj_internal_stream(rhj_ctx *ctx);
-int rhj_internal_fail(rhj_ctx *ctx, int code, const char *msg);
-void rhj_internal_sort_begin(rhj_ctx *ctx);     // the start of a call: timings and "last.*" as prof_reset leaves them, "last.join_kernel" -1
-void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units);
-int rhj_internal_range_workspace(rhj_ctx *ctx, size_t bytes, void **out);       // the range entries' own buffer (the inner sorts regrow the sort's), grown to >= bytes
-void rhj_internal_range_report(rhj_ctx *ctx, int units, int sorts, u64 pairs, u64 tiles);   // "last.range_join_units" / "_sorts" / "_pairs" / "_expand_tiles"
-void rhj_internal_range_last(rhj_ctx *ctx, int *units, int *sorts);             // ... the first two as they stand
-void *rhj_internal_span_open(rhj_ctx *ctx, int kind);
-void rhj_internal_span_close(void *span);
-// provided by rhj_sort.hip
-int rhj_internal_sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, const u64 *rows, u64 n, u32 flags, u64 *okeys, u64 *orows);
-void rhj_internal_sort_units(rhj_ctx *ctx, u64 n, u64 *L, u32 *U);              // units of L rows, a whole number of tiles, under "sort.max_units"
+#include "rhj_ordered.h"
 
 namespace {
 
-constexpr u64 BIAS = 1ull << 63;
-constexpr int ST = SORT_THREADS, TPT = SORT_TPT, TILE = RANGE_TILE, NW = ST / 64;
-constexpr u32 RJ_MAX_UNITS = 2048;               // the sort's: what one carry workgroup scans
-constexpr int FLAT_THREADS = 256;
-constexpr u32 FLAT_MAX_GRID = 4096;
+constexpr int TILE = RANGE_TILE;
 constexpr int EX_THREADS = 256, EX_SPT = RANGE_EXPAND_TILE / EX_THREADS;   // the expansion: slots per thread
-static_assert(TILE == ST * TPT && ST % 64 == 0, "k_rj_apply's geometry");
+static_assert(TILE == SORT_TILE, "k_rj_apply's geometry is the sort's (rhj_ordered.h)");
 static_assert(RANGE_EXPAND_TILE == EX_THREADS * EX_SPT && EX_THREADS >= 128, "k_rj_expand's geometry");
 
 // The concatenation is [first ; second]: [R ; S], under RHJ_RANGE_LO_OPEN [S ; R].  Concatenated index c belongs to R when
@@ -83,16 +61,6 @@ k_rj_concat(const u64 *__restrict__ loR, const u64 *__restrict__ onS, const u64 
         }
         con[c] = w;
         if (cby) cby[c] = isR ? byR[row] : byS[row];
-    }
-}
-
-// ---- k_rj_gather: dst[i] = src[idx[i]] -- the `by` words in the order of the first inner sort, the order words in the final order ---
-__global__ void __launch_bounds__(FLAT_THREADS)
-k_rj_gather(const u64 *__restrict__ src, const u64 *__restrict__ idx, u64 n, u64 *__restrict__ dst)
-{
-    for (u64 i = (u64)blockIdx.x * FLAT_THREADS + threadIdx.x; i < n; i += (u64)gridDim.x * FLAT_THREADS) {
-        const u64 r = idx[i];
-        dst[i] = r < n ? src[r] : 0;                                  // (r < n always: idx is a permutation of 0 .. n - 1)
     }
 }
 
@@ -337,54 +305,15 @@ k_rj_expand(const u64 *__restrict__ offsets, const u64 *__restrict__ first, cons
     }
 }
 
-int hip_fail(rhj_ctx *ctx, const char *what, hipError_t e)
-{
-    (void)hipGetLastError();
-    return rhj_internal_fail(ctx, e == hipErrorOutOfMemory ? RHJ_E_NOMEM : RHJ_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
-int check(rhj_ctx *ctx, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RHJ_OK : hip_fail(ctx, what, e);
-}
-
-struct Span {
-    void *s;
-    Span(rhj_ctx *ctx, int kind) : s(rhj_internal_span_open(ctx, kind)) {}
-    ~Span() { rhj_internal_span_close(s); }
-};
-
-unsigned flat_grid(u64 n)
-{
-    u64 g = (n + FLAT_THREADS - 1) / FLAT_THREADS;
-    if (g > FLAT_MAX_GRID) g = FLAT_MAX_GRID;
-    return (unsigned)(g ? g : 1);
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the exclusive sum over n words in three launches: a.src, a.out, a.rows and the sides are the caller's
 template <int MODE>
 int scan(rhj_ctx *ctx, hipStream_t st, RjScan a, u64 L, u32 U, const char *what)
 {
     int rc;
     a.L = L;
-    {
-        Span s(ctx, RHJ_K_HIST);
-        hipLaunchKernelGGL(k_rj_reduce<MODE>, dim3(U), dim3(ST), 0, st, a);
-    }
-    if ((rc = check(ctx, what)) != RHJ_OK) return rc;
-    {
-        Span s(ctx, RHJ_K_SCAN);
-        hipLaunchKernelGGL(k_rj_carry, dim3(1), dim3(ST), 0, st, (const u64 *)a.usum, U, a.carry);
-    }
-    if ((rc = check(ctx, what)) != RHJ_OK) return rc;
-    {
-        Span s(ctx, RHJ_K_SCATTER);
-        hipLaunchKernelGGL(k_rj_apply<MODE>, dim3(U), dim3(ST), 0, st, a);
-    }
-    return check(ctx, what);
+    if ((rc = launch(ctx, RHJ_K_HIST, what, k_rj_reduce<MODE>, U, ST, st, a)) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_SCAN, what, k_rj_carry, 1, ST, st, a.usum, U, a.carry)) != RHJ_OK) return rc;
+    return launch(ctx, RHJ_K_SCATTER, what, k_rj_apply<MODE>, U, ST, st, a);
 }
 
 // step 6 of both entries: the first min(total, capacity) pairs; tiles: the workgroups it took
@@ -396,12 +325,8 @@ int expand(rhj_ctx *ctx, hipStream_t st, const u64 *offsets, const u64 *first, c
     if (limit == 0 || !d_out) return RHJ_OK;
     const u64 g = (limit + RANGE_EXPAND_TILE - 1) / RANGE_EXPAND_TILE;
     if (g > 0x7FFFFFFFull) return rhj_internal_fail(ctx, RHJ_E_INVALID, "range join: more than 2^31 - 1 expansion tiles in one call -- slice R");
-    {
-        Span s(ctx, RHJ_K_JOIN);
-        hipLaunchKernelGGL(k_rj_expand, dim3((unsigned)g), dim3(EX_THREADS), 0, st, offsets, first, rowsS, nR, nS, limit, (ulonglong2 *)d_out);
-    }
     *tiles = g;
-    return check(ctx, "k_rj_expand");
+    return launch(ctx, RHJ_K_JOIN, "k_rj_expand", k_rj_expand, (unsigned)g, EX_THREADS, st, offsets, first, rowsS, nR, nS, limit, (ulonglong2 *)d_out);
 }
 
 int range_run(rhj_ctx *ctx, const u64 *d_byR, const u64 *d_loR, const u64 *d_hiR, u64 nR, const u64 *d_byS, const u64 *d_onS, u64 nS, u32 flags,
@@ -433,11 +358,9 @@ int range_run(rhj_ctx *ctx, const u64 *d_byR, const u64 *d_loR, const u64 *d_hiR
     }
     if (nS == 0) {
         if (d_offsets || d_first) {
-            {
-                Span s(ctx, RHJ_K_AUX);
-                hipLaunchKernelGGL(k_rj_fill, dim3(flat_grid(nR + 1)), dim3(FLAT_THREADS), 0, st, d_offsets, d_offsets ? nR + 1 : 0, d_first, d_first ? nR : 0);
-            }
-            if ((rc = check(ctx, "k_rj_fill")) != RHJ_OK) return rc;
+            if ((rc = launch(ctx, RHJ_K_AUX, "k_rj_fill", k_rj_fill, flat_grid(nR + 1), FLAT_THREADS, st, d_offsets, d_offsets ? nR + 1 : 0, d_first,
+                             d_first ? nR : 0)) != RHJ_OK)
+                return rc;
             if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, "k_rj_fill", e);
         }
         if (out_count) *out_count = 0;
@@ -451,7 +374,7 @@ int range_run(rhj_ctx *ctx, const u64 *d_byR, const u64 *d_loR, const u64 *d_hiR
     u32 U, UR;
     rhj_internal_sort_units(ctx, n, &L, &U);
     rhj_internal_sort_units(ctx, nR, &LR, &UR);
-    if (U == 0 || U > RJ_MAX_UNITS || UR == 0 || UR > RJ_MAX_UNITS)
+    if (U == 0 || U > ORD_MAX_UNITS || UR == 0 || UR > ORD_MAX_UNITS)
         return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
 
     // 1. the workspace: the concatenation, the permutation, the order words by position (with `by`: the sorted `by` words and the two
@@ -460,7 +383,7 @@ int range_run(rhj_ctx *ctx, const u64 *d_byR, const u64 *d_loR, const u64 *d_hiR
     const size_t nb = up256((size_t)n * 8), rb = up256((size_t)(nR + 1) * 8), sb = up256((size_t)nS * 8), ub = up256((size_t)(U > UR ? U : UR) * 8);
     const size_t bytes = (by ? 6 : 4) * nb + rb + (d_offsets ? 0 : rb) + (d_first ? 0 : rb) + (d_rowsS ? 0 : sb) + 2 * ub + 256;
     void *ws = nullptr;
-    if ((rc = rhj_internal_range_workspace(ctx, bytes, &ws)) != RHJ_OK) return rc;
+    if ((rc = rhj_internal_workspace(ctx, RHJ_WS_RANGE, bytes, &ws)) != RHJ_OK) return rc;
     unsigned char *p = (unsigned char *)ws;
     u64 *con = (u64 *)p; p += nb;
     u64 *perm = (u64 *)p; p += nb;
@@ -481,35 +404,17 @@ int range_run(rhj_ctx *ctx, const u64 *d_byR, const u64 *d_loR, const u64 *d_hiR
     const u32 r_first = lo_open ? 0u : 1u;
     const u64 nfirst = r_first ? nR : nS;
     const unsigned fg = flat_grid(n);
-    {
-        Span s(ctx, RHJ_K_AUX);
-        hipLaunchKernelGGL(k_rj_concat, dim3(fg), dim3(FLAT_THREADS), 0, st, d_loR, d_onS, d_byR, d_byS, nR, nS, r_first, band ? 1u : 0u, bias, below, con, cby);
-    }
-    if ((rc = check(ctx, "k_rj_concat")) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_AUX, "k_rj_concat", k_rj_concat, fg, FLAT_THREADS, st, d_loR, d_onS, d_byR, d_byS, nR, nS, r_first, band ? 1u : 0u, bias, below,
+                     con, cby)) != RHJ_OK)
+        return rc;
 
     // 3. the order (by, word, concatenated position), as the as-of entry's: the words argsorted in the view, then `by` gathered through
     //    that permutation and stable-sorted with the permutation as its rows; the order words by sorted position are the sorted keys
     //    after one sort, one gather after two
     const u32 sflags = (flags & RHJ_RANGE_I64) ? RHJ_SORT_I64 : 0;
-    const u64 *sp = nullptr;
-    if (by) {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), con, nullptr, n, sflags, nullptr, bufA)) != RHJ_OK) return rc;
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_rj_gather, dim3(fg), dim3(FLAT_THREADS), 0, st, (const u64 *)cby, (const u64 *)bufA, n, vs);
-        }
-        if ((rc = check(ctx, "k_rj_gather")) != RHJ_OK) return rc;
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), vs, bufA, n, 0, cby, perm)) != RHJ_OK) return rc;
-        sp = cby;
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_rj_gather, dim3(fg), dim3(FLAT_THREADS), 0, st, (const u64 *)con, (const u64 *)perm, n, vs);
-        }
-        if ((rc = check(ctx, "k_rj_gather")) != RHJ_OK) return rc;
-    } else {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), con, nullptr, n, sflags, vs, perm)) != RHJ_OK) return rc;
-    }
-    rhj_internal_sort_report(ctx, 0, 0, 0);                              // "last.sort_*" speak of the sort entries only
+    Ordered ord;
+    if ((rc = order_rows(ctx, st, me.c_str(), cby, con, n, sflags, bufA, vs, cby, vs, perm, &ord)) != RHJ_OK) return rc;
+    if (by && (rc = launch(ctx, RHJ_K_AUX, "k_ord_gather", k_ord_gather<u64>, fg, FLAT_THREADS, st, con, perm, n, vs)) != RHJ_OK) return rc;
 
     // 4. the rank scan: srank[p] = the rows of S before sorted position p, and rowsS
     RjScan a = {};
@@ -518,14 +423,10 @@ int range_run(rhj_ctx *ctx, const u64 *d_byR, const u64 *d_loR, const u64 *d_hiR
 
     // 5. the searches: first and cnt by row of R
     RjSearch s = {};
-    s.perm = perm; s.vs = vs; s.sp = sp; s.srank = srank; s.loR = d_loR; s.hiR = d_hiR; s.first = first; s.cnt = cnt;
+    s.perm = perm; s.vs = vs; s.sp = ord.sp; s.srank = srank; s.loR = d_loR; s.hiR = d_hiR; s.first = first; s.cnt = cnt;
     s.n = n; s.nfirst = nfirst; s.nR = nR; s.nS = nS; s.bias = bias; s.above = above;
     s.r_first = r_first; s.band = band ? 1 : 0; s.hi_open = (flags & RHJ_RANGE_HI_OPEN) ? 1 : 0;
-    {
-        Span sp_(ctx, RHJ_K_TASKS);
-        hipLaunchKernelGGL(k_rj_search, dim3(fg), dim3(FLAT_THREADS), 0, st, s);
-    }
-    if ((rc = check(ctx, "k_rj_search")) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_TASKS, "k_rj_search", k_rj_search, fg, FLAT_THREADS, st, s)) != RHJ_OK) return rc;
 
     // 6. the offsets: the same scan over the counts in row order; the host reads the total
     RjScan o = {};
@@ -560,16 +461,12 @@ int expand_run(rhj_ctx *ctx, const u64 *d_offsets, const u64 *d_first, u64 nR, c
     hipError_t e;
     int rc;
     void *ws = nullptr;
-    if ((rc = rhj_internal_range_workspace(ctx, 256, &ws)) != RHJ_OK) return rc;
+    if ((rc = rhj_internal_workspace(ctx, RHJ_WS_RANGE, 256, &ws)) != RHJ_OK) return rc;
     u64 *d_res = (u64 *)ws;
     u64 res[2] = {0, 0};
     if ((e = hipMemsetAsync(d_res, 0, 16, st)) != hipSuccess) return hip_fail(ctx, me.c_str(), e);
     if (nR > 0) {
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_rj_validate, dim3(flat_grid(nR)), dim3(FLAT_THREADS), 0, st, d_offsets, d_first, nR, nS, d_res);
-        }
-        if ((rc = check(ctx, "k_rj_validate")) != RHJ_OK) return rc;
+        if ((rc = launch(ctx, RHJ_K_AUX, "k_rj_validate", k_rj_validate, flat_grid(nR), FLAT_THREADS, st, d_offsets, d_first, nR, nS, d_res)) != RHJ_OK) return rc;
         e = hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, st);
     } else {
         e = hipMemcpyAsync(res, d_offsets, 8, hipMemcpyDeviceToHost, st);   // offsets[0], which must be 0

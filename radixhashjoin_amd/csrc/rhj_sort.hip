@@ -3,31 +3,13 @@
 // digit, scan, stable scatter -- the launch shape of the exact-cursor partition passes.  No workgroup ever waits on another.
 // Behind it the top-k entries (include/rhj.h, "top-k"): a most-significant-digit radix select on the same sort key, a
 // stable compaction, and the sort above over what is left.
-#include "../../include/rhj.h"
-#include "rhj_internal.h"
+#include "rhj_ordered.h"
 
 #include <atomic>
-#include <string>
-
-// provided by rhj_api.hip
-int rhj_internal_use_device(rhj_ctx *ctx);
-hipStream_t rhj_internal_stream(rhj_ctx *ctx);
-int rhj_internal_fail(rhj_ctx *ctx, int code, const char *msg);
-void *rhj_internal_counters(rhj_ctx *ctx);      // >= 64 bytes of zeroable device scratch, or nullptr on failure
-void rhj_internal_sort_begin(rhj_ctx *ctx);     // the start of a call: timings and "last.*" as prof_reset leaves them, "last.join_kernel" -1
-void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units);   // "last.sort_bits" / "last.sort_passes" / "last.sort_units"
-int rhj_internal_sort_workspace(rhj_ctx *ctx, size_t bytes, void **out);        // the context's sort buffer, grown to >= bytes
-int rhj_internal_sort_max_units(rhj_ctx *ctx);                                  // "sort.max_units": -1 automatic, else 1 .. SORT_MAX_UNITS
-void rhj_internal_topk_report(rhj_ctx *ctx, int bits, int passes, u64 candidates, u64 sorted_rows);   // "last.topk_*"
-int rhj_internal_topk_workspace(rhj_ctx *ctx, size_t bytes, void **out);        // top-k's own buffer (the inner sort regrows the sort's), grown to >= bytes
-int64_t rhj_internal_topk_max_candidates(rhj_ctx *ctx);                         // "topk.max_candidates": -1 automatic, else 1 .. 2^31 - 1
-void *rhj_internal_span_open(rhj_ctx *ctx, int kind);                           // a profiling span (RHJ_K_*) around the launches that follow
-void rhj_internal_span_close(void *span);
 
 namespace {
 
-constexpr u64 BIAS = 1ull << 63;
-constexpr int ST = SORT_THREADS, TPT = SORT_TPT, TILE = SORT_TILE, NW = ST / 64, BINS = 1 << SORT_DIGIT_BITS;
+constexpr int TILE = SORT_TILE, BINS = 1 << SORT_DIGIT_BITS;
 constexpr u32 DMASK = BINS - 1;
 constexpr u32 SORT_MAX_UNITS = 2048;             // ~8 units per CU, as PART_TARGET_UNITS ("sort.max_units": fewer)
 constexpr int PROBE_THREADS = 256;
@@ -358,24 +340,6 @@ k_sort_scatter(SortPass a)
     }
 }
 
-int hip_fail(rhj_ctx *ctx, const char *what, hipError_t e)
-{
-    (void)hipGetLastError();
-    return rhj_internal_fail(ctx, e == hipErrorOutOfMemory ? RHJ_E_NOMEM : RHJ_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
-int check(rhj_ctx *ctx, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RHJ_OK : hip_fail(ctx, what, e);
-}
-
-struct Span {
-    void *s;
-    Span(rhj_ctx *ctx, int kind) : s(rhj_internal_span_open(ctx, kind)) {}
-    ~Span() { rhj_internal_span_close(s); }
-};
-
 u32 bits_of(u64 x) { u32 b = 0; while (x) { b++; x >>= 1; } return b; }          // 64 - clz(x), 0 for 0
 
 unsigned probe_grid(u64 n)
@@ -414,8 +378,6 @@ hipError_t launch_scatter(hipStream_t st, int form, const SortPass &a, bool firs
     return form == 0 ? launch_scatter_f<0>(st, a, first, last) : form == 1 ? launch_scatter_f<1>(st, a, first, last) : launch_scatter_f<2>(st, a, first, last);
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the range probe, one launch and one 32-byte read-back: h_w[0] / h_w[2] = the minimum / maximum of v ^ bias over the column
 int probe_range(rhj_ctx *ctx, hipStream_t st, const std::string &me, const u64 *keys, u64 kstride, u64 n, const KeyXf &xf, u64 *d_w, u64 *h_w)
 {
@@ -423,11 +385,7 @@ int probe_range(rhj_ctx *ctx, hipStream_t st, const std::string &me, const u64 *
     hipError_t e = hipMemsetAsync(d_w, 0xFF, 16, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_w + 2, 0, 16, st);
     if (e != hipSuccess) return hip_fail(ctx, (me + ": probe words").c_str(), e);
-    {
-        Span s(ctx, RHJ_K_AUX);
-        hipLaunchKernelGGL(k_sort_probe<0>, dim3(probe_grid(n)), dim3(PROBE_THREADS), 0, st, keys, kstride, n, xf, d_w);
-    }
-    if ((rc = check(ctx, "k_sort_probe")) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_AUX, "k_sort_probe", k_sort_probe<0>, probe_grid(n), PROBE_THREADS, st, keys, kstride, n, xf, d_w)) != RHJ_OK) return rc;
     e = hipMemcpyAsync(h_w, d_w, 4 * sizeof(u64), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return hip_fail(ctx, "k_sort_probe", e);
@@ -471,12 +429,9 @@ int sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
 
     // 2. width 0: the outputs are copies
     if (w == 0) {
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_sort_copy, dim3(probe_grid(n)), dim3(PROBE_THREADS), 0, st, keys, kstride, rows, rstride, n, okeys, okstride,
-                               orows, orstride);
-        }
-        if ((rc = check(ctx, "k_sort_copy")) != RHJ_OK) return rc;
+        if ((rc = launch(ctx, RHJ_K_AUX, "k_sort_copy", k_sort_copy, probe_grid(n), PROBE_THREADS, st, keys, kstride, rows, rstride, n, okeys, okstride, orows,
+                         orstride)) != RHJ_OK)
+            return rc;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, "k_sort_copy", e);
         rhj_internal_sort_report(ctx, 0, 0, 0);
         return RHJ_OK;
@@ -487,11 +442,7 @@ int sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
     if (w <= SORT_DIGIT_BITS) {
         shifts[np++] = 0;
     } else {
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_sort_probe<1>, dim3(probe_grid(n)), dim3(PROBE_THREADS), 0, st, keys, kstride, n, xf, d_w);
-        }
-        if ((rc = check(ctx, "k_sort_probe")) != RHJ_OK) return rc;
+        if ((rc = launch(ctx, RHJ_K_AUX, "k_sort_probe", k_sort_probe<1>, probe_grid(n), PROBE_THREADS, st, keys, kstride, n, xf, d_w)) != RHJ_OK) return rc;
         e = hipMemcpyAsync(h_w, d_w, sizeof h_w, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return hip_fail(ctx, "k_sort_probe", e);
@@ -514,7 +465,7 @@ int sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
     const bool k1_ws = need1 && !(okeys && okstride == 1), r1_ws = need1 && form != 0 && !(orows && orstride == 1);
     const size_t bytes = hist_b + rel_b + tot_b + (need0 ? kb + rb : 0) + (k1_ws ? kb : 0) + (r1_ws ? rb : 0);
     void *ws = nullptr;
-    if ((rc = rhj_internal_sort_workspace(ctx, bytes, &ws)) != RHJ_OK) return rc;
+    if ((rc = rhj_internal_workspace(ctx, RHJ_WS_SORT, bytes, &ws)) != RHJ_OK) return rc;
     unsigned char *p = (unsigned char *)ws;
     u32 *d_hist = (u32 *)p; p += hist_b;
     u64 *d_rel = (u64 *)p; p += rel_b;
@@ -535,17 +486,10 @@ int sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
         else { const int src = (np - 1 - i) & 1; a.in_keys = tk[src]; a.in_kstride = 1; a.in_rows = tr[src]; a.in_rstride = 1; }
         if (last) { a.out_keys = okeys; a.out_kstride = okstride; a.out_rows = orows; a.out_rstride = orstride; }
         else { const int dst = (np - 2 - i) & 1; a.out_keys = tk[dst]; a.out_kstride = 1; a.out_rows = tr[dst]; a.out_rstride = 1; }
-        {
-            Span s(ctx, RHJ_K_HIST);
-            if (first) hipLaunchKernelGGL(k_sort_hist<true>, dim3(U), dim3(ST), 0, st, a.in_keys, a.in_kstride, n, L, U, a.shift, xf, d_hist);
-            else hipLaunchKernelGGL(k_sort_hist<false>, dim3(U), dim3(ST), 0, st, a.in_keys, a.in_kstride, n, L, U, a.shift, xf, d_hist);
-        }
-        if ((rc = check(ctx, "k_sort_hist")) != RHJ_OK) return rc;
-        {
-            Span s(ctx, RHJ_K_SCAN);
-            hipLaunchKernelGGL(k_sort_scan, dim3(BINS), dim3(ST), 0, st, (const u32 *)d_hist, U, d_rel, d_tot);
-        }
-        if ((rc = check(ctx, "k_sort_scan")) != RHJ_OK) return rc;
+        rc = first ? launch(ctx, RHJ_K_HIST, "k_sort_hist", k_sort_hist<true>, U, ST, st, a.in_keys, a.in_kstride, n, L, U, a.shift, xf, d_hist)
+                   : launch(ctx, RHJ_K_HIST, "k_sort_hist", k_sort_hist<false>, U, ST, st, a.in_keys, a.in_kstride, n, L, U, a.shift, xf, d_hist);
+        if (rc != RHJ_OK) return rc;
+        if ((rc = launch(ctx, RHJ_K_SCAN, "k_sort_scan", k_sort_scan, BINS, ST, st, d_hist, U, d_rel, d_tot)) != RHJ_OK) return rc;
         {
             Span s(ctx, RHJ_K_SCATTER);
             e = launch_scatter(st, form, a, first, last);
@@ -810,12 +754,9 @@ int topk_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
     // width 0: every key is the same word, the first m rows of the input are the answer
     if (w == 0) {
         if (!pure) {
-            {
-                Span s(ctx, RHJ_K_AUX);
-                hipLaunchKernelGGL(k_sort_copy, dim3(probe_grid(m)), dim3(PROBE_THREADS), 0, st, keys, kstride, rows, rstride, m, okeys, okstride,
-                                   orows, orstride);
-            }
-            if ((rc = check(ctx, "k_sort_copy")) != RHJ_OK) return rc;
+            if ((rc = launch(ctx, RHJ_K_AUX, "k_sort_copy", k_sort_copy, probe_grid(m), PROBE_THREADS, st, keys, kstride, rows, rstride, m, okeys, okstride,
+                             orows, orstride)) != RHJ_OK)
+                return rc;
             if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, "k_sort_copy", e);
         }
         rhj_internal_topk_report(ctx, 0, 0, n, 0);
@@ -834,23 +775,15 @@ int topk_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
     int passes = 0, shift = 0;
     if (sel[TS_CAND] > max_cand) {
         void *ws = nullptr;
-        if ((rc = rhj_internal_topk_workspace(ctx, head_b, &ws)) != RHJ_OK) return rc;
+        if ((rc = rhj_internal_workspace(ctx, RHJ_WS_TOPK, head_b, &ws)) != RHJ_OK) return rc;
         u64 *d_state = (u64 *)ws;
         unsigned long long *d_ghist = (unsigned long long *)((unsigned char *)ws + state_b);
         e = hipMemcpyAsync(d_state, sel, sizeof sel, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemsetAsync(d_ghist, 0, (size_t)BINS * 8, st);
         if (e != hipSuccess) return hip_fail(ctx, (me + ": select state").c_str(), e);
         for (shift = (int)((w - 1) / SORT_DIGIT_BITS) * SORT_DIGIT_BITS;; shift -= SORT_DIGIT_BITS) {
-            {
-                Span s(ctx, RHJ_K_HIST);
-                hipLaunchKernelGGL(k_topk_hist, dim3(U), dim3(ST), 0, st, keys, kstride, n, L, shift, xf, (const u64 *)d_state, d_ghist);
-            }
-            if ((rc = check(ctx, "k_topk_hist")) != RHJ_OK) return rc;
-            {
-                Span s(ctx, RHJ_K_SCAN);
-                hipLaunchKernelGGL(k_topk_pick, dim3(1), dim3(ST), 0, st, d_ghist, d_state, shift);
-            }
-            if ((rc = check(ctx, "k_topk_pick")) != RHJ_OK) return rc;
+            if ((rc = launch(ctx, RHJ_K_HIST, "k_topk_hist", k_topk_hist, U, ST, st, keys, kstride, n, L, shift, xf, d_state, d_ghist)) != RHJ_OK) return rc;
+            if ((rc = launch(ctx, RHJ_K_SCAN, "k_topk_pick", k_topk_pick, 1, ST, st, d_ghist, d_state, shift)) != RHJ_OK) return rc;
             if ((rc = read_words(ctx, st, "k_topk_pick", sel, d_state, TS_WORDS)) != RHJ_OK) return rc;
             passes++;
             if (sel[TS_CAND] <= max_cand || shift == 0) break;
@@ -874,7 +807,7 @@ int topk_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
     u64 in_ks = kstride, in_rs = rstride, *out_k = nullptr, *out_r = nullptr;
     void *ws = nullptr;
     const size_t bytes = head_b + (passes ? kb + (need_rows ? kb : 0) : 0) + (direct ? 0 : (need_keys ? kb : 0) + (need_rows ? kb : 0));
-    if ((rc = rhj_internal_topk_workspace(ctx, bytes, &ws)) != RHJ_OK) return rc;
+    if ((rc = rhj_internal_workspace(ctx, RHJ_WS_TOPK, bytes, &ws)) != RHJ_OK) return rc;
     {
         unsigned char *p = (unsigned char *)ws + state_b + ghist_b;
         u32 *d_cnt = (u32 *)p; p += cnt_b;
@@ -887,21 +820,9 @@ int topk_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
             TopkKeep a = {};
             a.keys = keys; a.kstride = kstride; a.n = n; a.L = L; a.U = U; a.shift = shift; a.xf = xf; a.want = sel[TS_PREFIX] >> shift;
             a.keep_sure = keep_sure; a.lo = lo; a.hi = hi;
-            {
-                Span s(ctx, RHJ_K_HIST);
-                hipLaunchKernelGGL(k_topk_count, dim3(U), dim3(ST), 0, st, a, d_cnt);
-            }
-            if ((rc = check(ctx, "k_topk_count")) != RHJ_OK) return rc;
-            {
-                Span s(ctx, RHJ_K_SCAN);
-                hipLaunchKernelGGL(k_sort_scan, dim3(2), dim3(ST), 0, st, (const u32 *)d_cnt, U, d_rel, d_tot);
-            }
-            if ((rc = check(ctx, "k_sort_scan")) != RHJ_OK) return rc;
-            {
-                Span s(ctx, RHJ_K_SCATTER);
-                hipLaunchKernelGGL(k_topk_compact, dim3(U), dim3(ST), 0, st, a, rows, rstride, (const u64 *)d_rel, kk, kr, kept);
-            }
-            if ((rc = check(ctx, "k_topk_compact")) != RHJ_OK) return rc;
+            if ((rc = launch(ctx, RHJ_K_HIST, "k_topk_count", k_topk_count, U, ST, st, a, d_cnt)) != RHJ_OK) return rc;
+            if ((rc = launch(ctx, RHJ_K_SCAN, "k_sort_scan", k_sort_scan, 2, ST, st, d_cnt, U, d_rel, d_tot)) != RHJ_OK) return rc;
+            if ((rc = launch(ctx, RHJ_K_SCATTER, "k_topk_compact", k_topk_compact, U, ST, st, a, rows, rstride, d_rel, kk, kr, kept)) != RHJ_OK) return rc;
             in_k = kk; in_r = kr; in_ks = in_rs = 1;
         }
         if (!direct) {
@@ -917,12 +838,9 @@ int topk_run(rhj_ctx *ctx, const char *who, const u64 *keys, u64 kstride, const 
     rhj_internal_sort_report(ctx, 0, 0, 0);                              // "last.sort_*" speak of the sort entries only
     rhj_internal_topk_report(ctx, (int)w, passes, c, kept);
     if (!direct && !pure) {
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_sort_copy, dim3(probe_grid(m)), dim3(PROBE_THREADS), 0, st, (const u64 *)out_k, (u64)1, (const u64 *)out_r, (u64)1, m,
-                               okeys, okstride, orows, orstride);
-        }
-        if ((rc = check(ctx, "k_sort_copy")) != RHJ_OK) return rc;
+        if ((rc = launch(ctx, RHJ_K_AUX, "k_sort_copy", k_sort_copy, probe_grid(m), PROBE_THREADS, st, out_k, (u64)1, out_r, (u64)1, m, okeys, okstride, orows,
+                         orstride)) != RHJ_OK)
+            return rc;
         if (!out_kth && (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, "k_sort_copy", e);
     }
     if (!out_kth) return RHJ_OK;

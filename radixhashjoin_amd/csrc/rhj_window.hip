@@ -4,63 +4,16 @@
 // that order which restarts at every partition head.  Per scan three launches ordered on the context's stream -- a reduce per unit,
 // a one-workgroup carry over the unit summaries, an apply per unit -- on the sort's unit geometry.  No workgroup ever waits on
 // another, and no position or value comes from an atomic.
-#include "../../include/rhj.h"
-#include "rhj_internal.h"
-
-#include <string>
-#include <vector>
-
-// provided by rhj_api.hip
-int rhj_internal_use_device(rhj_ctx *ctx);
-hipStream_t rhj_internal_stream(rhj_ctx *ctx);
-int rhj_internal_fail(rhj_ctx *ctx, int code, const char *msg);
-void rhj_internal_sort_begin(rhj_ctx *ctx);     // the start of a call: timings and "last.*" as prof_reset leaves them, "last.join_kernel" -1
-void rhj_internal_sort_report(rhj_ctx *ctx, int bits, int passes, int units);
-int rhj_internal_window_workspace(rhj_ctx *ctx, size_t bytes, void **out);      // the window entry's own buffer (the inner sorts regrow the sort's), grown to >= bytes
-void rhj_internal_window_report(rhj_ctx *ctx, int units, int sorts, u64 partitions);   // "last.window_units" / "last.window_sorts" / "last.window_partitions"
-void *rhj_internal_span_open(rhj_ctx *ctx, int kind);
-void rhj_internal_span_close(void *span);
-// provided by rhj_sort.hip
-int rhj_internal_sort_run(rhj_ctx *ctx, const char *who, const u64 *keys, const u64 *rows, u64 n, u32 flags, u64 *okeys, u64 *orows);
-void rhj_internal_sort_units(rhj_ctx *ctx, u64 n, u64 *L, u32 *U);              // units of L rows, a whole number of tiles, under "sort.max_units"
+#include "rhj_ordered.h"
 
 namespace {
 
-constexpr u64 BIAS = 1ull << 63;
-constexpr int ST = SORT_THREADS, TPT = SORT_TPT, TILE = WINDOW_TILE, NW = ST / 64;
-constexpr u32 WIN_MAX_UNITS = 2048;              // the sort's: what one carry workgroup scans
-constexpr int RED_UNROLL = 4;
-constexpr int FLAT_THREADS = 256;
-constexpr u32 FLAT_MAX_GRID = 4096;
+constexpr int TILE = WINDOW_TILE;
 constexpr u32 F_PART = 1, F_PEER = 2;            // the flag byte of a sorted position: it heads a partition / a run of peers
-static_assert(TILE == ST * TPT && ST % 64 == 0 && TILE % (NW * 64 * RED_UNROLL) == 0, "k_win_reduce's and k_win_apply's geometry");
+static_assert(TILE == SORT_TILE, "k_win_reduce's and k_win_apply's geometry is the sort's (rhj_ordered.h)");
 
-// ---- the scan's algebra ------------------------------------------------------------------------------------------------------------
-// An element is (f, v): f -- a head stands here, v -- its value.  (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 + v2), the later
-// element on the right, + the op.  It is associative, so the aggregate "since the last head" of a range is the fold of its pieces in
-// order, whatever the pieces: lanes, rounds, waves, tiles, units.
-enum { OP_SUM = 0, OP_MIN = 1, OP_MAX = 2 };
+// The scans fold rhj_ordered.h's (f, v) algebra; what makes v:
 enum { VS_COL = 0, VS_PEER = 1, VS_POS = 2 };    // the value: a column word through the permutation; the peer-head bit; head ? position : 0
-
-template <int OP> __device__ __forceinline__ u64 ident() { return OP == OP_MIN ? ~0ull : 0ull; }
-template <int OP> __device__ __forceinline__ u64 comb(u64 a, u64 b)
-{
-    return OP == OP_SUM ? a + b : OP == OP_MIN ? (b < a ? b : a) : (b > a ? b : a);
-}
-
-// inclusive scan of (f, v) over the wave's lanes: __shfl_up with the head flag carried along
-template <int OP> __device__ __forceinline__ void wave_seg_scan(u32 &f, u64 &v, u32 lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u64 ov = __shfl_up(v, off, 64);
-        const u32 of = __shfl_up(f, off, 64);
-        if (lane >= (u32)off) {
-            v = f ? v : comb<OP>(ov, v);
-            f |= of;
-        }
-    }
-}
 
 struct WinScan {
     const unsigned char *flags;                  // n flag bytes, by sorted position
@@ -130,16 +83,6 @@ k_win_heads(const u64 *__restrict__ sp, const u64 *__restrict__ so, const u64 *_
     ucnt[u] = s;
 }
 
-// ---- k_win_gather: dst[i] = src[idx[i]] -- the partition column in the order of the first inner sort ------------------------------
-__global__ void __launch_bounds__(FLAT_THREADS)
-k_win_gather(const u64 *__restrict__ src, const u64 *__restrict__ idx, u64 n, u64 *__restrict__ dst)
-{
-    for (u64 i = (u64)blockIdx.x * FLAT_THREADS + threadIdx.x; i < n; i += (u64)gridDim.x * FLAT_THREADS) {
-        const u64 r = idx[i];
-        dst[i] = r < n ? src[r] : 0;                                  // (r < n always: idx is a permutation of 0 .. n - 1)
-    }
-}
-
 // ---- k_win_reduce<OP, VS>: per unit "has a head" and the aggregate since the unit's last head -------------------------------------
 // One workgroup per unit.  Wave w walks the w-th eighth of the unit (L is a whole number of tiles, so an eighth is a whole number of
 // rounds) 64 positions at a time, RED_UNROLL rounds of loads in flight.  A round with a head keeps only the lanes from its last head
@@ -197,49 +140,10 @@ k_win_reduce(WinScan a)
     a.usum_f[u] = f;
 }
 
-// ---- k_win_carry<OP>: one workgroup -- the exclusive scan of at most 2048 unit summaries -------------------------------------------
-// Thread t folds its run of ceil(U / 512) consecutive units, the runs are scanned over the workgroup (wave scan, per-wave totals
-// through LDS: block_excl_scan's shape with the flag carried along), and the thread walks its run again from its carry-in.
-template <int OP>
-__global__ void __launch_bounds__(ST)
-k_win_carry(const u64 *__restrict__ usum_v, const u32 *__restrict__ usum_f, u32 U, u64 *__restrict__ carry)
-{
-    __shared__ u64 wv[NW];
-    __shared__ u32 wf[NW];
-    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 per = (U + ST - 1) / ST;
-    const u32 b = tid * per < U ? tid * per : U, e = b + per < U ? b + per : U;
-    u32 sf = 0;
-    u64 sv = ident<OP>();
-    for (u32 u = b; u < e; u++) {
-        const u32 fu = usum_f[u];
-        const u64 vu = usum_v[u];
-        sv = fu ? vu : comb<OP>(sv, vu);
-        sf |= fu;
-    }
-    wave_seg_scan<OP>(sf, sv, lane);
-    if (lane == 63) { wv[wave] = sv; wf[wave] = sf; }
-    __syncthreads();
-    u64 pv = ident<OP>();
-#pragma unroll
-    for (int w = 0; w < NW; w++)
-        if ((u32)w < wave) pv = wf[w] ? wv[w] : comb<OP>(pv, wv[w]);
-    u64 ev = __shfl_up(sv, 1, 64);
-    u32 ef = __shfl_up(sf, 1, 64);
-    if (lane == 0) { ev = ident<OP>(); ef = 0; }
-    u64 cur = ef ? ev : comb<OP>(pv, ev);
-    for (u32 u = b; u < e; u++) {
-        carry[u] = cur;
-        const u32 fu = usum_f[u];
-        const u64 vu = usum_v[u];
-        cur = fu ? vu : comb<OP>(cur, vu);
-    }
-}
-
 // ---- k_win_apply<OP, VS>: the scan itself, and out[perm[p]] ------------------------------------------------------------------------
 // One workgroup per unit, tile by tile, in the sort's position order (wave, round, lane): wave w of a tile owns positions [w * 64 *
 // TPT, (w + 1) * 64 * TPT) of it.  Per round a wave scan, continued from the wave's running aggregate (lane 63 of the round before);
-// per tile the waves' totals through LDS, folded onto the tile's carry-in -- the unit's from k_win_carry, then the running one.  A
+// per tile the waves' totals through LDS, folded onto the tile's carry-in -- the unit's from k_ord_carry, then the running one.  A
 // position behind a head of its own wave is final after the wave's rounds; any other takes the fold of the carry and the waves before.
 template <int OP, int VS>
 __global__ void __launch_bounds__(ST)
@@ -337,53 +241,14 @@ k_win_rows(const u64 *__restrict__ pstart, const u64 *__restrict__ qstart, const
     }
 }
 
-int hip_fail(rhj_ctx *ctx, const char *what, hipError_t e)
-{
-    (void)hipGetLastError();
-    return rhj_internal_fail(ctx, e == hipErrorOutOfMemory ? RHJ_E_NOMEM : RHJ_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
-int check(rhj_ctx *ctx, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RHJ_OK : hip_fail(ctx, what, e);
-}
-
-struct Span {
-    void *s;
-    Span(rhj_ctx *ctx, int kind) : s(rhj_internal_span_open(ctx, kind)) {}
-    ~Span() { rhj_internal_span_close(s); }
-};
-
-unsigned flat_grid(u64 n)
-{
-    u64 g = (n + FLAT_THREADS - 1) / FLAT_THREADS;
-    if (g > FLAT_MAX_GRID) g = FLAT_MAX_GRID;
-    return (unsigned)(g ? g : 1);
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // one scan: reduce, carry, apply, ordered by the stream
 template <int OP, int VS>
 int scan_t(rhj_ctx *ctx, hipStream_t st, const WinScan &a)
 {
     int rc;
-    {
-        Span s(ctx, RHJ_K_HIST);
-        hipLaunchKernelGGL((k_win_reduce<OP, VS>), dim3(a.U), dim3(ST), 0, st, a);
-    }
-    if ((rc = check(ctx, "k_win_reduce")) != RHJ_OK) return rc;
-    {
-        Span s(ctx, RHJ_K_SCAN);
-        hipLaunchKernelGGL(k_win_carry<OP>, dim3(1), dim3(ST), 0, st, (const u64 *)a.usum_v, (const u32 *)a.usum_f, a.U, a.carry);
-    }
-    if ((rc = check(ctx, "k_win_carry")) != RHJ_OK) return rc;
-    {
-        Span s(ctx, RHJ_K_SCATTER);
-        hipLaunchKernelGGL((k_win_apply<OP, VS>), dim3(a.U), dim3(ST), 0, st, a);
-    }
-    return check(ctx, "k_win_apply");
+    if ((rc = launch(ctx, RHJ_K_HIST, "k_win_reduce", k_win_reduce<OP, VS>, a.U, ST, st, a)) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_SCAN, "k_ord_carry", k_ord_carry<OP>, 1, ST, st, a.usum_v, a.usum_f, a.U, a.carry)) != RHJ_OK) return rc;
+    return launch(ctx, RHJ_K_SCATTER, "k_win_apply", k_win_apply<OP, VS>, a.U, ST, st, a);
 }
 
 bool is_row_op(u32 op) { return op == RHJ_WIN_ROW_NUMBER || op == RHJ_WIN_RANK || op == RHJ_WIN_LAG_ROW || op == RHJ_WIN_LEAD_ROW; }
@@ -414,12 +279,11 @@ int window_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 f
     if (n == 0) return RHJ_OK;
 
     hipStream_t st = rhj_internal_stream(ctx);
-    hipError_t e;
     int rc;
     u64 L;
     u32 U;
     rhj_internal_sort_units(ctx, n, &L, &U);
-    if (U == 0 || U > WIN_MAX_UNITS) return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
+    if (U == 0 || U > ORD_MAX_UNITS) return rhj_internal_fail(ctx, RHJ_E_HIP, (me + ": unit geometry").c_str());   // (never: the sort's own bound)
 
     // 1. the workspace: four n-word arrays at most, the flag bytes, the unit tables
     const int sorts = (d_part ? 1 : 0) + (d_order ? 1 : 0);
@@ -427,7 +291,7 @@ int window_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 f
     const bool need_ab = sorts == 2 || any_row;                          // A, B: the first sort's outputs, then the two starts
     const size_t bytes = (need_ab ? 2 * nb : 0) + (sorts ? 2 * nb : 0) + up256((size_t)n) + 4 * ub;
     void *ws = nullptr;
-    if ((rc = rhj_internal_window_workspace(ctx, bytes, &ws)) != RHJ_OK) return rc;
+    if ((rc = rhj_internal_workspace(ctx, RHJ_WS_WINDOW, bytes, &ws)) != RHJ_OK) return rc;
     unsigned char *p = (unsigned char *)ws;
     u64 *bufA = nullptr, *bufB = nullptr, *skey = nullptr, *perm = nullptr;
     if (need_ab) { bufA = (u64 *)p; p += nb; bufB = (u64 *)p; p += nb; }
@@ -438,34 +302,13 @@ int window_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 f
     u64 *d_carry = (u64 *)p; p += ub;
     u64 *d_ucnt = (u64 *)p; p += ub;
 
-    // 2. the order (partition, order key, input position): the order column argsorted under flags, then the partition column gathered
-    //    through that permutation and stable-sorted with the permutation as its rows
-    const u64 *sp = nullptr, *so = nullptr, *ord = nullptr;
-    if (sorts == 2) {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, nullptr, bufA)) != RHJ_OK) return rc;
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_win_gather, dim3(flat_grid(n)), dim3(FLAT_THREADS), 0, st, d_part, (const u64 *)bufA, n, bufB);
-        }
-        if ((rc = check(ctx, "k_win_gather")) != RHJ_OK) return rc;
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), bufB, bufA, n, 0, skey, perm)) != RHJ_OK) return rc;
-        sp = skey;
-        ord = d_order;
-    } else if (d_part) {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_part, nullptr, n, 0, skey, perm)) != RHJ_OK) return rc;
-        sp = skey;
-    } else if (d_order) {
-        if ((rc = rhj_internal_sort_run(ctx, me.c_str(), d_order, nullptr, n, flags, skey, perm)) != RHJ_OK) return rc;
-        so = skey;
-    }
-    rhj_internal_sort_report(ctx, 0, 0, 0);                              // "last.sort_*" speak of the sort entries only
+    // 2. the order (partition, order key, input position); after two sorts the order words are read through the permutation
+    Ordered o;
+    if ((rc = order_rows(ctx, st, me.c_str(), d_part, d_order, n, flags, bufA, bufB, skey, skey, perm, &o)) != RHJ_OK) return rc;
+    const u64 *ord = sorts == 2 ? d_order : nullptr;
 
     // 3. heads
-    {
-        Span s(ctx, RHJ_K_AUX);
-        hipLaunchKernelGGL(k_win_heads, dim3(U), dim3(ST), 0, st, sp, so, ord, (const u64 *)perm, n, L, d_flags, d_ucnt);
-    }
-    if ((rc = check(ctx, "k_win_heads")) != RHJ_OK) return rc;
+    if ((rc = launch(ctx, RHJ_K_AUX, "k_win_heads", k_win_heads, U, ST, st, o.sp, o.so, ord, perm, n, L, d_flags, d_ucnt)) != RHJ_OK) return rc;
 
     WinScan a = {};
     a.flags = d_flags; a.perm = perm; a.n = n; a.L = L; a.U = U; a.usum_v = d_usum_v; a.usum_f = d_usum_f; a.carry = d_carry;
@@ -487,11 +330,7 @@ int window_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 f
             w.out[w.nops] = d_outs[j];
             w.nops++;
         }
-        {
-            Span s(ctx, RHJ_K_AUX);
-            hipLaunchKernelGGL(k_win_rows, dim3(flat_grid(n)), dim3(FLAT_THREADS), 0, st, (const u64 *)bufA, (const u64 *)bufB, (const u64 *)perm, n, w);
-        }
-        if ((rc = check(ctx, "k_win_rows")) != RHJ_OK) return rc;
+        if ((rc = launch(ctx, RHJ_K_AUX, "k_win_rows", k_win_rows, flat_grid(n), FLAT_THREADS, st, bufA, bufB, perm, n, w)) != RHJ_OK) return rc;
     }
 
     // 5. one scan per remaining op
@@ -514,12 +353,8 @@ int window_run(rhj_ctx *ctx, const u64 *d_part, const u64 *d_order, u64 n, u32 f
     }
 
     // 6. the partitions: the heads' per-unit counts, summed on the host
-    std::vector<u64> cnt(U);
-    e = hipMemcpyAsync(cnt.data(), d_ucnt, (size_t)U * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(ctx, "rhj_window_cols_dev", e);
     u64 parts = 0;
-    for (u32 u = 0; u < U; u++) parts += cnt[u];
+    if ((rc = unit_total(ctx, st, me.c_str(), d_ucnt, U, &parts)) != RHJ_OK) return rc;
     if (out_partitions) *out_partitions = parts;
     rhj_internal_window_report(ctx, (int)U, sorts, parts);
     return RHJ_OK;
